@@ -2,11 +2,15 @@
 MI355X (BASELINE.json configs[1]); the reference's own measurement loop is `legged_gym/tests/test_env_simstep_time.py:10-17`
 (random-normal actions, mean wall time of env.step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One process per GPU; envs shard by rank (weak scaling: 4096 envs per GPU) with no data-path collective; after the timed
 region every rank contributes its episode statistics to one RCCL all-gather.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes what the last timed `env.step` returned (observations, privileged observations, rewards, resets,
+the `extras` tensors) as DIR/<name>.npy (float32 / float64), so that two builds can be compared output for output: with the
+same arguments the terrain, the env randomisation and the action pool are the same seeded draws on every run.
 """
 import argparse
 import json
@@ -187,6 +191,41 @@ def pmc_traffic(N):
         return {"traffic": None}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(ret):
+    """Host float copies of what one `env.step` returned: (obs, privileged_obs, rew, reset, extras), extras flattened."""
+    obs, priv, rew, reset, extras = ret
+    out = {"obs": obs, "privileged_obs": priv, "rew": rew, "reset": reset}
+
+    def flat(prefix, d):
+        for k, v in d.items():
+            if isinstance(v, dict):
+                flat(f"{prefix}_{k}", v)
+            else:
+                out[f"{prefix}_{k}"] = v
+    flat("extras", extras)
+    arrays = {}
+    for name, v in out.items():
+        if v is None:
+            continue
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        arrays[name] = a
+    return arrays
+
+
+def dump_outputs(arrays, dirname, rank, world):
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values()) * world
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -196,7 +235,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pd-control", action="store_true", help="diagnostic: PD actuators instead of the LSTM net")
     ap.add_argument("--solver", choices=["tgs", "pgs"], default="tgs", help="diagnostic: pgs = round 2's solver instead of the configured TGS")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed env.step returned as DIR/<name>.npy (float32 / float64)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: this process has not touched the GPU yet, so it may start the N ranks as
@@ -256,12 +299,14 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for i in range(a.steps):
-        env.step(pool[i % len(pool)])
+        last = env.step(pool[i % len(pool)])
     torch.cuda.synchronize(dev)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    # the returned tensors are views of buffers the passes below overwrite: copy them to the host now
+    outputs = step_outputs(last) if a.dump_outputs else None
 
     # a separate, untimed pass for the per-kernel durations of the roofline block: HIP events on the stream the kernels
     # run on, every 4th step sampled, at least 64 samples whatever --steps was
@@ -335,6 +380,11 @@ def main():
             out["rehearsal"] = True          # ranks shared one GPU over gloo: a functional run of the N > 1 path, not a measurement
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(env, pool)
+        if outputs is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": sorted(outputs)}
+    if outputs is not None:
+        dump_outputs(outputs, a.dump_outputs, rank, world)
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

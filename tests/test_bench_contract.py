@@ -105,3 +105,44 @@ def test_sharded_main_rollout_driver_rehearsed_on_one_gpu():
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["rehearsal"] is True and out["first_global_main"] == 0
     assert out["episode_stats"]["ranks"] == 2 and out["episode_stats"]["env_steps"] > 0
     assert out["rollout_env_steps_per_s"] > 0 and out["rollout_batch_H16_ms"] > 0
+
+
+def test_dump_outputs_writes_float_arrays_of_the_step_return(tmp_path):
+    """`--dump-outputs`: the 5-tuple of `env.step` as float32 / float64 .npy files, `extras` flattened, None left out."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 8
+    ret = (torch.randn(n, 5), None, torch.randn(n, dtype=torch.float64), torch.tensor([True, False] * 4),
+           {"episode": {"rew_a": torch.tensor(0.5), "reward_stage": 2.0}, "time_outs": torch.zeros(n, dtype=torch.bool)})
+    arrays = bench.step_outputs(ret)
+    assert sorted(arrays) == ["extras_episode_rew_a", "extras_episode_reward_stage", "extras_time_outs", "obs", "reset", "rew"]
+    assert arrays["obs"].dtype == np.float32 and arrays["rew"].dtype == np.float64 and arrays["reset"].dtype == np.float32
+    np.testing.assert_array_equal(arrays["reset"], [1, 0] * 4)
+    bench.dump_outputs(arrays, str(tmp_path / "d"), 0, 1)
+    for name, a in arrays.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "d" / f"{name}.npy"), a)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs({"big": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)}, str(tmp_path / "e"), 0, 1)
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    import numpy as np
+    out_dir = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--envs-per-gpu", "512",
+           "--no-cpu-baseline", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _last_json_line(r.stdout)
+    assert out["steps"] == 7 and out["ms_per_step"] > 0 and out["finite"] is True
+    names = out["dumped_outputs"]["arrays"]
+    assert {"obs", "rew", "reset"} <= set(names)
+    total = 0
+    for name in names:
+        a = np.load(out_dir / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert np.load(out_dir / "obs.npy").shape == (512, 235) and np.load(out_dir / "rew.npy").shape == (512,)
+    assert total <= 64 << 20
