@@ -710,9 +710,10 @@ LG_DEV bool closest_point_lattice_row16(const LatticeView& L, V3 p, float R, int
     closest_grid_triangle(p, a, b, cc, best2, found, bestabs, bestp, bestn);
   };
   // a lane whose own best is not within the band of the group's minimum forgets it (its face cannot decide anything) and prunes with the group's bound
-  auto share_bound = [&]() {
+  auto share_bound = [&]() -> float {
     const float gm = row16_min(found ? best2 : R * R);
     if (!(found && best2 <= gm * (1.f + 1e-5f) + 1e-12f)) { found = false; bestabs = -1.f; best2 = gm; }
+    return gm;
   };
   // 1. the cell under the point: its faces dealt over the lanes
   const int ci = max(i0, min((int)floorf(fx), i1)), cj = max(j0, min((int)floorf(fy), j1));
@@ -720,9 +721,12 @@ LG_DEV bool closest_point_lattice_row16(const LatticeView& L, V3 p, float R, int
     const u2v r = RUN[(size_t)cj * L.nx + ci];
     const int cnt = (int)(r.y & 0xffffu) + (int)(r.y >> 16);
     for (int f = k; f < cnt; f += 16) face((int)r.x + f);
-    share_bound();
+    const float gm = share_bound();
     if (row16_min(found ? 1 : 2) == 1) {                                      // something found: the window shrinks to what can be closer
-      const float rr = sqrtf(best2) * (1.f + 1e-4f);
+      // The window must be the same on all 16 lanes: cell c belongs to lane c % 16 of ONE window, and share_bound's shuffles in the loop below want
+      // every lane.  A lane's own best2 is not group-uniform (lanes within the tie band keep theirs, which differ in the last bits), the group's
+      // minimum is; widened by the band, it still reaches every face that can decide the answer.
+      const float rr = sqrtf(gm * (1.f + 1e-5f) + 1e-12f) * (1.f + 1e-4f);
       grx = rr * ihx + 2.f * LATTICE_TOL; gry = rr * ihy + 2.f * LATTICE_TOL;
       i0 = max(i0, (int)floorf(fx - grx)); i1 = min(i1, (int)floorf(fx + grx)); j0 = max(j0, (int)floorf(fy - gry)); j1 = min(j1, (int)floorf(fy + gry));
     }

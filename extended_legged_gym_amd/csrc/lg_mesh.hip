@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void raycaster_kernel(MeshView M, RayGrid G, c
 // Round 6: on a lattice mesh (the OBJ meshes of the confined-space / heightfield converters: lg_mesh.d_gcz) a query with a cached bound is answered from the
 // cells around the body by a group of 16 lanes (closest_point_lattice_row16, lg_bvh.h) instead of one lane's tree walk -- the walk paid ~30 dependent
 // 128-byte node fetches per query and re-fetched 14 x its algorithmic bytes.  Same per-face arithmetic and tie rule: the same answer to rounding
-// (tests/test_hip_config3.py).  A query whose bound is wider than LATTICE_SDF_CELLS cell widths (no cache entry yet; a body far above the surface) keeps the
+// (tests/test_hip_config3.py; against a float64 brute force: tests/test_hip_mesh_sdf_reference.py).  A query whose bound is wider than LATTICE_SDF_CELLS cell widths (no cache entry yet; a body far above the surface) keeps the
 // tree, walked by the group's first lane.  LG_SDF_LATTICE=0: always the tree (the A/B switch and the tests' checker).
 #define LATTICE_SDF_CELLS 12.f
 __global__ __launch_bounds__(256) void sdf_bodies_kernel(MeshView M, LatticeView L, const float* __restrict__ rb /* (N,B,13) */, int B,
