@@ -188,6 +188,8 @@ def declare_product(lib):
     lib.lg_set_reward_terms.restype = C.c_int
     lib.lg_set_async_gait.argtypes = [vp, C.POINTER(f32), f32, vp]
     lib.lg_set_async_gait.restype = C.c_int
+    lib.lg_set_lattice_capsules.argtypes = [vp, i32]
+    lib.lg_set_lattice_capsules.restype = C.c_int
     lib.lg_step_subset_physics.argtypes = [vp, vp, vp, i32, vp]
     lib.lg_step_subset_physics.restype = C.c_int
     lib.lg_post_physics_subset.argtypes = [vp, vp, i32, i32, vp]
@@ -306,4 +308,4 @@ PRODUCT_SYMBOLS = ["lg_abi_sizes", "lg_arena_bytes", "lg_create", "lg_get_tensor
                    "lg_simulate", "lg_post_physics_step", "lg_reset_idx", "lg_profile_begin", "lg_profile_end", "lg_last_error",
                    "lg_destroy", "lg_set_extra_obs", "lg_mesh_create", "lg_mesh_destroy", "lg_mesh_info", "lg_mesh_ray_lattice", "lg_mesh_contact_lattice", "lg_mesh_last_error",
                    "lg_raycast_mesh", "lg_mesh_query_sdf", "lg_raycaster_update", "lg_depth_camera_update",
-                   "lg_terrain_generate", "lg_heightfield_to_trimesh", "lg_pose_layer_step", "lg_set_reward_terms", "lg_set_async_gait", "lg_step_subset_physics", "lg_post_physics_subset", "lg_raycaster_update_subset", "lg_sdf_bodies_update", "lg_set_state_indexed", "lg_gather_step_rows", "lg_step_subset_rows", "lg_step_rollout", "lg_set_extra_termination", "lg_foottrack_stray", "lg_foottrack_layer_step"]
+                   "lg_terrain_generate", "lg_heightfield_to_trimesh", "lg_pose_layer_step", "lg_set_reward_terms", "lg_set_async_gait", "lg_set_lattice_capsules", "lg_step_subset_physics", "lg_post_physics_subset", "lg_raycaster_update_subset", "lg_sdf_bodies_update", "lg_set_state_indexed", "lg_gather_step_rows", "lg_step_subset_rows", "lg_step_rollout", "lg_set_extra_termination", "lg_foottrack_stray", "lg_foottrack_layer_step"]

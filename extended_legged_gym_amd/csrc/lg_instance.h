@@ -35,6 +35,7 @@
     (c, actions, env_ids, n, rollout_mode, stream))                                                                                                   \
   X(int, lg_set_reward_terms, (lg_ctx * c, int32_t num_terms, const int32_t* term_ids, const float* scales, void* stream), (c, num_terms, term_ids, scales, stream)) \
   X(int, lg_set_async_gait, (lg_ctx * c, const float weights[3], float foot_z_align, void* stream), (c, weights, foot_z_align, stream))               \
+  X(int, lg_set_lattice_capsules, (lg_ctx * c, int32_t on), (c, on))                                                                               \
   X(int, lg_step_subset_physics, (lg_ctx * c, const float* actions, const int32_t* env_ids, int32_t n, void* stream), (c, actions, env_ids, n, stream)) \
   X(int, lg_post_physics_subset, (lg_ctx * c, const int32_t* env_ids, int32_t n, int32_t rollout_mode, void* stream), (c, env_ids, n, rollout_mode, stream)) \
   X(int, lg_sync_main_to_rollout, (lg_ctx * c, int32_t rollouts_per_main, float pos_drift, void* stream), (c, rollouts_per_main, pos_drift, stream))   \
@@ -69,6 +70,7 @@
 #define lg_step_subset LG_ENTRY(lg_step_subset)
 #define lg_set_reward_terms LG_ENTRY(lg_set_reward_terms)
 #define lg_set_async_gait LG_ENTRY(lg_set_async_gait)
+#define lg_set_lattice_capsules LG_ENTRY(lg_set_lattice_capsules)
 #define lg_step_subset_physics LG_ENTRY(lg_step_subset_physics)
 #define lg_post_physics_subset LG_ENTRY(lg_post_physics_subset)
 #define lg_sync_main_to_rollout LG_ENTRY(lg_sync_main_to_rollout)

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <string>
 #include <vector>
+#include <unordered_map>
 
 #include "lg_device.h"
 #include "../../include/lgstep.h"
@@ -580,6 +581,41 @@ lg_mesh* lg_mesh_create(const float* vertices, int64_t n_vertices, const int32_t
         m->gmaxrun = std::max(m->gmaxrun, cnt);
       }
       if (ok) {
+        // crease flags (capsule segments on lattice meshes, lattice_caps_edges): w of a face's first vertex = bit e set when its edge (v_e, v_e+1) is owned by a
+        // face that is not coplanar with it -- where the surface bends.  Edges are keyed by their two end points, bit for bit (the faces share vertices).
+        struct EKey { uint32_t u[6]; bool operator==(const EKey& o) const { return memcmp(u, o.u, sizeof(u)) == 0; } };
+        struct EHash { size_t operator()(const EKey& k) const { uint64_t h = 1469598103934665603ull; for (uint32_t x : k.u) { h ^= x; h *= 1099511628211ull; } return (size_t)h; } };
+        struct EVal { float n[3]; bool crease; };
+        auto key = [](const float4& p, const float4& q) {
+          EKey k; uint32_t a[3], b[3]; memcpy(&a[0], &p.x, 4); memcpy(&a[1], &p.y, 4); memcpy(&a[2], &p.z, 4); memcpy(&b[0], &q.x, 4); memcpy(&b[1], &q.y, 4); memcpy(&b[2], &q.z, 4);
+          const bool sw = std::lexicographical_compare(b, b + 3, a, a + 3);
+          for (int i = 0; i < 3; ++i) { k.u[i] = sw ? b[i] : a[i]; k.u[3 + i] = sw ? a[i] : b[i]; }
+          return k;
+        };
+        auto normal = [](const float4* v, float n[3]) {
+          const double e1[3] = {(double)v[1].x - v[0].x, (double)v[1].y - v[0].y, (double)v[1].z - v[0].z}, e2[3] = {(double)v[2].x - v[0].x, (double)v[2].y - v[0].y, (double)v[2].z - v[0].z};
+          n[0] = (float)(e1[1] * e2[2] - e1[2] * e2[1]); n[1] = (float)(e1[2] * e2[0] - e1[0] * e2[2]); n[2] = (float)(e1[0] * e2[1] - e1[1] * e2[0]);
+        };
+        auto parallel = [](const float* a, const float* b) {
+          const double c0 = (double)a[1] * b[2] - (double)a[2] * b[1], c1 = (double)a[2] * b[0] - (double)a[0] * b[2], c2 = (double)a[0] * b[1] - (double)a[1] * b[0];
+          const double aa = (double)a[0] * a[0] + (double)a[1] * a[1] + (double)a[2] * a[2], bb = (double)b[0] * b[0] + (double)b[1] * b[1] + (double)b[2] * b[2];
+          return c0 * c0 + c1 * c1 + c2 * c2 <= 1e-6 * aa * bb;
+        };
+        std::unordered_map<EKey, EVal, EHash> edges; edges.reserve(G.tris.size());
+        const size_t nf = G.tris.size() / 3;
+        for (size_t f = 0; f < nf; ++f) {
+          const float4* v = &G.tris[3 * f]; float n[3]; normal(v, n);
+          for (int e = 0; e < 3; ++e) {
+            auto it = edges.find(key(v[e], v[(e + 1) % 3]));
+            if (it == edges.end()) { EVal x; x.n[0] = n[0]; x.n[1] = n[1]; x.n[2] = n[2]; x.crease = false; edges.emplace(key(v[e], v[(e + 1) % 3]), x); }
+            else if (!parallel(it->second.n, n)) it->second.crease = true;
+          }
+        }
+        for (size_t f = 0; f < nf; ++f) {
+          float4* v = &G.tris[3 * f]; unsigned fl = 0u;
+          for (int e = 0; e < 3; ++e) if (edges.find(key(v[e], v[(e + 1) % 3]))->second.crease) fl |= 1u << e;
+          v[0].w = (float)fl;
+        }
         if (hipMalloc((void**)&m->d_gcz, cz.size() * sizeof(float4)) != hipSuccess || hipMalloc((void**)&m->d_gcr, cr.size() * sizeof(uint2)) != hipSuccess ||
             hipMemcpy(m->d_gcz, cz.data(), cz.size() * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(m->d_gcr, cr.data(), cr.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess ||

@@ -1048,7 +1048,98 @@ LG_DEV void closest_point_lattice_pair(const LatticeView& L, ClosestQuery& QA, C
   wave_lds_sync();                                                     // (the records are the caller's again)
 }
 
-template <bool MCAPS = false>
+// Capsule segments on a LATTICE mesh (TerrainView::L: OBJ / confined terrains; contact_detect_mesh<MCAPS, true>, opt-in: lg_set_lattice_capsules).  The grid
+// rule's shape (contact_detect_*_caps, and the grid-mesh block of contact_detect_mesh) with the lattice's own lines: per axis the first lattice line the
+// segment's ground track crosses; the faces of the two cells on either side of the crossing, in every layer (ground and ceiling) whose height group meets the
+// capsule's z band; of each face the edges that
+// lie ON that line, longer in xy than half a cell (an edge stood upright or collapsed is no crease) and inside the capsule's z band; an exact segment-edge
+// closest-point pair each.  A candidate takes the slot when it is deeper than what the sphere found by more than 10 um (phi, n, xc in and out).
+// Which side is outside: the faces that own the edge say, not the sign of z (under a ceiling "above the edge" is inside).  The point is outside when it is in
+// front of ANY face that owns the edge (exact for a convex crease; at a concave one it errs towards outside, where a candidate is never deeper than the faces
+// the spheres answer).  An edge counts only where the surface bends: some owner is not coplanar with the face listing it (on a plane a segment is never
+// deeper than its end spheres; the diagonal inside a vertical face on the line is no crease) -- lg_mesh_create flags those edges once per face (w of its first
+// vertex).  A face that has the point behind it asks every face of the two cells whether it owns the same edge (both end points, bit for bit: a mesh's faces
+// share their vertices) and has the point in front of it -- the quadratic pass runs only for such claims, which also need the axis within the radius of the
+// edge ("below the edge by more than the radius is the spheres' business", as on grid meshes).  A vertical face is listed in the
+// cells on both sides of its line: its duplicate gives the same candidate bit for bit, which never beats the first by 10 um.  Face loops run to the wave's
+// maximum (at most 2 x 255 faces) with predicated bodies; everything is read from global memory; no private arrays.
+LG_DEV void lattice_caps_edges(const LatticeView& L, bool on, V3 x, V3 gv, float rad, float cofs, float& phi, V3& n, V3& xc) {
+  typedef unsigned u2v __attribute__((ext_vector_type(2))); typedef float f4v __attribute__((ext_vector_type(4)));
+  typedef const u2v __attribute__((address_space(1)))* gu2; typedef const f4v __attribute__((address_space(1)))* gf4;
+  const gf4 CELL = (gf4)L.cell; const gu2 RUN = (gu2)L.run; const gf4 TRI = (gf4)L.tris;
+  const float ihx = frcp(L.hx), ihy = frcp(L.hy);
+  const float zlow = fminf(x.z, x.z + gv.z) - rad - cofs, zhigh = fmaxf(x.z, x.z + gv.z) + rad + cofs;    // the capsule's z band
+  const float fx0 = (x.x - L.x0) * ihx, fy0 = (x.y - L.y0) * ihy, dfx = gv.x * ihx, dfy = gv.y * ihy;
+#pragma unroll 1
+  for (int ax = 0; ax < 2; ++ax) {
+    // axis 0: a line of constant x (line pc.L of nx + 1, the crossing in row pc.j); axis 1: constant y
+    const int nacross = ax == 0 ? L.nx : L.ny;
+    const EdgePiece pc = ax == 0 ? caps_edge_piece(fx0, dfx, fy0, dfy, L.nx + 1, L.ny + 1) : caps_edge_piece(fy0, dfy, fx0, dfx, L.ny + 1, L.nx + 1);
+    const int ia = max(pc.L - 1, 0), ib = min(pc.L, nacross - 1);
+    const size_t ca = ax == 0 ? (size_t)pc.j * L.nx + ia : (size_t)ia * L.nx + pc.j, cb = ax == 0 ? (size_t)pc.j * L.nx + ib : (size_t)ib * L.nx + pc.j;
+    const f4v za = CELL[ca], zb = CELL[cb]; const u2v ra = RUN[ca], rb = RUN[cb];
+    // of each cell the height groups (closest_point_lattice_pair: lower = ground, upper = ceiling / wall tops, one run in that order) whose z range meets the band
+    const bool va = on && pc.on && pc.L >= 1, vb = on && pc.on && pc.L <= nacross - 1;      // (an empty group: +1e30, -1e30, never meets)
+    const bool a0 = va && za.x <= zhigh && za.y >= zlow, a1 = va && za.z <= zhigh && za.w >= zlow, b0 = vb && zb.x <= zhigh && zb.y >= zlow, b1 = vb && zb.z <= zhigh && zb.w >= zlow;
+    const unsigned fa = ra.x + (a0 ? 0u : (ra.y & 0xffffu)), fb = rb.x + (b0 ? 0u : (rb.y & 0xffffu));
+    const int na = (a0 ? (int)(ra.y & 0xffffu) : 0) + (a1 ? (int)(ra.y >> 16) : 0), nt = na + (b0 ? (int)(rb.y & 0xffffu) : 0) + (b1 ? (int)(rb.y >> 16) : 0);
+    if (!__any(nt > 0)) continue;                                          // most substeps no lane of the wave has a candidate
+    const float line = ax == 0 ? L.x0 + (float)pc.L * L.hx : L.y0 + (float)pc.L * L.hy, tol = LATTICE_TOL * (ax == 0 ? L.hx : L.hy);
+    const float hal = ax == 0 ? L.hy : L.hx, minlen2 = 0.25f * hal * hal;
+    auto face = [&](int kf, V3& p0, V3& p1, V3& p2) -> unsigned {     // returns the face's crease flags (lg_mesh_create: bit e = edge (v_e, v_e+1) is a crease)
+      const unsigned fi = kf < na ? fa + (unsigned)kf : fb + (unsigned)(kf - na);
+      const f4v t0 = TRI[3 * (size_t)fi], t1 = TRI[3 * (size_t)fi + 1], t2 = TRI[3 * (size_t)fi + 2];
+      p0 = v3(t0.x, t0.y, t0.z); p1 = v3(t1.x, t1.y, t1.z); p2 = v3(t2.x, t2.y, t2.z);
+      return (unsigned)t0.w;
+    };
+#pragma unroll 1
+    for (int kf = 0; __any(kf < nt); ++kf) {
+      if (kf < nt) {
+        V3 a, b, c; unsigned fl = face(kf, a, b, c);
+#pragma unroll 1
+        for (int e = 0; e < 3; ++e) {                                      // edge (a, b); then the vertices rotate (no indexed private array) -- on EVERY pass
+          const float aa = ax == 0 ? a.x : a.y, ba = ax == 0 ? b.x : b.y, al = ax == 0 ? a.y : a.x, bl = ax == 0 ? b.y : b.x;
+          const float lx = b.x - a.x, ly = b.y - a.y;
+          const bool ok = (fl & 1u) && fabsf(aa - line) <= tol && fabsf(ba - line) <= tol && lx * lx + ly * ly > minlen2 && fminf(a.z, b.z) <= zhigh && fmaxf(a.z, b.z) >= zlow;
+          fl >>= 1;
+          if (__any(ok)) {
+            // the edge in one orientation whichever face lists it (from its lower end along the line): the same closest points for every owner
+            const bool fwd = al < bl;
+            const V3 E0 = sel3(fwd, a, b), E1 = sel3(fwd, b, a);
+            V3 A, E; seg_seg_closest(x, gv, E0, ok ? E1 - E0 : v3(hal, hal, 0.f), &A, &E);
+            const V3 d = A - E; const float dist = norm(d);
+            const bool out = dot(d, cross(b - a, c - a)) >= 0.f;           // (the face's normal: the same for every rotation of its vertices)
+            const float pe = out ? dist - rad : -dist - rad;
+            bool better = ok && pe < phi - 1e-5f && (out || dist <= rad);
+            if (__any(better)) {
+              const bool ask = better && !out;
+              if (__any(ask)) {                                            // behind this face: does another owner of the edge have the point in front of it?
+                bool veto = false;
+#pragma unroll 1
+                for (int kg = 0; __any(ask && kg < nt); ++kg) {
+                  if (ask && kg < nt) {
+                    V3 q0, q1, q2; (void)face(kg, q0, q1, q2);
+                    const bool h0 = (q0.x == E0.x && q0.y == E0.y && q0.z == E0.z) || (q1.x == E0.x && q1.y == E0.y && q1.z == E0.z) || (q2.x == E0.x && q2.y == E0.y && q2.z == E0.z);
+                    const bool h1 = (q0.x == E1.x && q0.y == E1.y && q0.z == E1.z) || (q1.x == E1.x && q1.y == E1.y && q1.z == E1.z) || (q2.x == E1.x && q2.y == E1.y && q2.z == E1.z);
+                    veto = veto || (h0 && h1 && dot(d, cross(q1 - q0, q2 - q0)) >= 0.f);
+                  }
+                }
+                better = better && !veto;
+              }
+              const V3 fn = cross(b - a, c - a);
+              const float sg = out ? 1.f : -1.f;
+              const V3 ne = dist > 1e-9f ? (sg * frcp(dist)) * d : __builtin_amdgcn_rsqf(fmaxf(dot(fn, fn), 1e-30f)) * fn;
+              phi = better ? pe : phi; n = sel3(better, ne, n); xc = sel3(better, A, xc);
+            }
+          }
+          const V3 t = a; a = b; b = c; c = t;
+        }
+      }
+    }
+  }
+}
+
+template <bool MCAPS = false, bool LCAPS = false>
 LG_DEV void contact_detect_mesh(int s0, int s1, const LegModel& lm_, const TerrainView& T, const PhysParams& P, const LegKin& k,
                                 const M3& Rb, V3 pb, float* cst, int lane, float* cq = nullptr, unsigned long long* dbg = nullptr) {
   const int ncp = lm_.i(LM_CP_COUNT);
@@ -1137,7 +1228,7 @@ LG_DEV void contact_detect_mesh(int s0, int s1, const LegModel& lm_, const Terra
         }
       }
       V3 xc = x;
-      if (MCAPS && sl < ncp && ((P.slide_mask >> sl) & 1u)) {                     // (kernel-uniform)
+      if (MCAPS && (!LCAPS || T.SEG4) && sl < ncp && ((P.slide_mask >> sl) & 1u)) {                     // (kernel-uniform)
         // Capsule segments on a GRID mesh (round 6; T.SEG4 = lg_terrain.grid_vertices): the height grid's rule (contact_detect_*_caps) with the mesh's own
         // edges -- the segment [x, x + gv] against the mesh edge (L, j)-(L, j + 1) of the first lattice line of each axis its ground track crosses; the edge's
         // end points are the mesh's vertices, wherever the slope correction put them.  The candidate takes the slot when it is
@@ -1177,6 +1268,31 @@ LG_DEV void contact_detect_mesh(int s0, int s1, const LegModel& lm_, const Terra
       CS4(sl, 2) = make_float4(0.f, 0.f, 0.f, 0.f);
       const unsigned long long am = __ballot(active);
       if (lane == 0) AMASK(sl) = am;
+    }
+    if (LCAPS) {
+      // Capsule segments on a LATTICE mesh (lattice_caps_edges), behind both spheres' results: the queries' state is dead here (register room for the face
+      // loops), the sphere's result is read back from its record and rewritten where a segment candidate took the slot.  The same acceptance as above,
+      // evaluated whatever the sphere's distance cache said -- the cache speaks for the sphere's centre, not for the far end of its segment.
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int ps = sp0 + h, sl = (int)((P.slot_perm >> (4 * ps)) & 7u);
+        if (ps >= s1 || !((P.slide_mask >> sl) & 1u) || (MCAPS && T.SEG4)) continue;      // (kernel-uniform; slide_mask: a lattice mesh only)
+        const float4 c0 = CS4(sl, 0);
+        const V3 x = sel3(h == 0, xs[0], xs[1]); const float rad = h == 0 ? rads[0] : rads[1];      // (a rolled loop: no indexed private array)
+        float phi = c0.w; V3 n = v3(c0.x, c0.y, c0.z), xc = x;
+        const int link = lm_.i(LM_CP_LINK + sl);
+        const V3 ls = lm_.v(LM_CP_SLIDE + 3 * sl);
+        const V3 gv = sel3(link < 0, mul(Rb, ls), sel3(link == 0, mul(k.R[0], ls), sel3(link == 1, mul(k.R[1], ls), mul(k.R[2], ls))));
+        lattice_caps_edges(T.L, sl < ncp, x, gv, rad, P.contact_offset, phi, n, xc);      // (every lane: the ballot below)
+        const bool took = phi != c0.w, active = took ? phi < P.contact_offset : CS4(sl, 1).w != 0.f;
+        if (took) {
+          const V3 r = (xc - rad * n) - pb;
+          CS4(sl, 0) = make_float4(n.x, n.y, n.z, phi);
+          CS4(sl, 1) = make_float4(r.x, r.y, r.z, active ? 1.f : 0.f);
+        }
+        const unsigned long long am = __ballot(active);
+        if (lane == 0) AMASK(sl) = am;
+      }
     }
   }
 }
@@ -1498,8 +1614,8 @@ LG_DEV V3 sc_sphere(const float* cst, const LegModel& lm_, int gb, int leg, int 
 // [0, MAIN_DETECT) before the rendezvous (0: the helpers, or the inline path, detect everything).
 // SPEC = 1: the instance of the reference's own solver settings (sim.physx.solver_type = 1: TGS, PhysX's pyramid friction rows) with both
 // choices fixed at compile time; SPEC = 0 reads them from the parameters (the unified step evaluates both friction forms and selects).
-// FEAT: bit 0 = capsule parts (sliding spheres, contact_detect_*_caps), bit 1 = the self-collision pass -- compile-time, so that the instance without
-// them is the kernel it was before they existed.
+// FEAT: bit 0 = capsule parts (sliding spheres, contact_detect_*_caps), bit 1 = the self-collision pass, bit 2 = capsule segments against a lattice
+// mesh's edges (triangle-mesh instances: lattice_caps_edges) -- compile-time, so that the instance without them is the kernel it was before they existed.
 template <bool TMESH, int MAIN_DETECT, bool ALLOW_INLINE, int SPEC = 0, int FEAT = 0, class TauFn, class PrepFn, class ShareFn>
 LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel& lm_, const TerrainView& T, const PhysParams& P,
                             int lane, float* cst, QuadState& s, TauFn tau_fn, PrepFn prep_fn, ShareFn share_fn, SlotShare share,
@@ -1518,9 +1634,9 @@ LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel
   // mass matrix and its factors it sat in the middle of ~500 live registers and the inlined closest-point scan spilled them
   // (~800 scratch loads in the substep of the main wave)
 #if defined(LG_STAMPS) && defined(LG_STAMP_MAIN_MESH)
-  if (TMESH && MAIN_DETECT > 0 && share.n > 1) contact_detect_mesh<(FEAT & 1) != 0>(MAIN_DETECT - 100, MAIN_DETECT - 98, lm_, T, P, k, Rb, pb, cst, lane, cq, stamps);   // diagnostic: the query counters watch this wave
+  if (TMESH && MAIN_DETECT > 0 && share.n > 1) contact_detect_mesh<(FEAT & 1) != 0, TMESH && (FEAT & 4) != 0>(MAIN_DETECT - 100, MAIN_DETECT - 98, lm_, T, P, k, Rb, pb, cst, lane, cq, stamps);   // diagnostic: the query counters watch this wave
 #else
-  if (TMESH && MAIN_DETECT > 0 && share.n > 1) contact_detect_mesh<(FEAT & 1) != 0>(MAIN_DETECT - 100, MAIN_DETECT - 98, lm_, T, P, k, Rb, pb, cst, lane, cq);   // (triangle-mesh instances: MAIN_DETECT = 100 + the first slot of this wave's pair)
+  if (TMESH && MAIN_DETECT > 0 && share.n > 1) contact_detect_mesh<(FEAT & 1) != 0, TMESH && (FEAT & 4) != 0>(MAIN_DETECT - 100, MAIN_DETECT - 98, lm_, T, P, k, Rb, pb, cst, lane, cq);   // (triangle-mesh instances: MAIN_DETECT = 100 + the first slot of this wave's pair)
 #endif
   // ---------------------------------------------------------------- bias forces (RNEA, zero generalised acceleration)
   const float m0 = m->base_mass + madd, iscale = m0 * frcp(m->base_mass);
@@ -1603,7 +1719,7 @@ LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel
     //  registers and code)
     if (ALLOW_INLINE) {
       leg_bias(lm_, k, pb, wb, s.qd, P.grav, bk, Fs, Ns);
-      if (TMESH) contact_detect_mesh<(FEAT & 1) != 0>(0, LG_MAX_CP, lm_, T, P, k, Rb, pb, cst, lane);
+      if (TMESH) contact_detect_mesh<(FEAT & 1) != 0, TMESH && (FEAT & 4) != 0>(0, LG_MAX_CP, lm_, T, P, k, Rb, pb, cst, lane);
       else if (FEAT & 1) contact_detect_caps<0, LG_MAX_CP>(lm_, T, P, k, Rb, pb, cst, lane);
       else contact_detect<0, LG_MAX_CP>(lm_, T, P, k, Rb, pb, cst, lane);
     }

@@ -121,6 +121,8 @@ struct lg_ctx {
   void* grid_verts = nullptr;   // device copy of lg_terrain.grid_vertices
   void* hmin = nullptr;         // TerrainView::Hmin
   int grid_mesh = 1;           // LG_GRID_MESH=0: walk the BVH for grid meshes too (diagnostic / A-B)
+  int lat_caps = 0;            // lg_set_lattice_capsules: capsule segments against a lattice mesh's edges (off by default; LG_LATTICE_CAPS=1|0 overrides it at lg_create)
+  int lat_caps_env = -1;       // LG_LATTICE_CAPS at lg_create (-1: unset)
   TensorInfo t[LG_T_COUNT];
   int device = 0;
   unsigned long sync_calls = 0;
@@ -559,7 +561,7 @@ LG_DEV bool fused_needs_feet_rows(const DevCtx* __restrict__ C);
 // headline runs does not carry the single-wave fallback (the whole LSTM inlined in the main wave, inline leg bias and contact
 // detection): that dead code accounted for most of the register spills the compiler reported for the kernel.
 // SPEC & 3: 1 = TGS + pyramid friction rows fixed at compile time (A/B build 13 only, see physics_substep); 2 = the fused tail in its rollout variant.
-// SPEC >> 2 = FEAT of physics_substep: bit 0 capsule parts (sliding spheres), bit 1 the self-collision pass.  Launches with helper waves pick the
+// SPEC >> 2 = FEAT of physics_substep: bit 0 capsule parts (sliding spheres), bit 1 the self-collision pass, bit 2 capsule segments on a lattice mesh (lg_set_lattice_capsules).  Launches with helper waves pick the
 // instance the model / config needs (launch_physics); the single-wave instances always carry both (FEAT_ALL: a model without sliding spheres or
 // pairs takes the same paths with an empty mask / list), so the kernel of a robot of fixed spheres without self-collision is what it was.
 #define FEAT_ALL 12
@@ -642,6 +644,7 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
   constexpr int FEAT = SPEC >> 2;
   constexpr bool CAPS = !TMESH && (FEAT & 1);
   constexpr bool MCAPS = TMESH && (FEAT & 1);               // capsule segments against the edges of a GRID mesh (contact_detect_mesh<true>; launch_physics picks the instance when the terrain has TerrainView::SEG4)
+  constexpr bool LCAPS = TMESH && (FEAT & 4);               // ... and of a LATTICE mesh (lattice_caps_edges; opt-in: lg_set_lattice_capsules, launch_physics picks the instance then)
   const int32_t* const fids = ro ? ids : nullptr;           // the tail's row -> env map: a literal null (rows = envs) in the full step's instance
   int64_t fstep = ro ? C->counters[3] + 1 : C->counters[0] + 1;         // LR:123 (the statistics step of the previous launch stored it)
   const int64_t gstep_f = C->counters[0] + 1;             // what the gait term's "has a scheduler step run yet" test sees (post_instance: gstep)
@@ -750,7 +753,7 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
     PhysParams P;
     P.dt = g.sim_dt; P.grav = v3(g.gravity[0], g.gravity[1], g.gravity[2]); P.iters = g.solver_iterations;
     P.contact_offset = g.contact_offset; P.max_depen = g.max_depenetration_velocity; P.erp = g.erp; P.cfm = g.cfm; P.solver = g.solver_type; P.fric = g.friction_model;
-    P.terrain_mu = C->terrain_mu; P.slide_mask = (CAPS || (MCAPS && C->ter.SEG4)) ? C->slide_mask : 0u; P.slot_perm = CAPS ? C->slot_perm : (TMESH ? C->mesh_perm : 0x76543210u); P.cache_reach = TMESH ? C->mesh_reach : 0.f;
+    P.terrain_mu = C->terrain_mu; P.slide_mask = (CAPS || (MCAPS && C->ter.SEG4) || (LCAPS && C->ter.L.cell)) ? C->slide_mask : 0u; P.slot_perm = CAPS ? C->slot_perm : (TMESH ? C->mesh_perm : 0x76543210u); P.cache_reach = TMESH ? C->mesh_reach : 0.f;
 #if LG_AB == 21
     P.slide_mask = 0u;
 #endif
@@ -798,17 +801,17 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
           pb4[0] = make_float4(bk[0], bk[1], bk[2], Fs.x); pb4[1] = make_float4(Fs.y, Fs.z, Ns.x, Ns.y); pb4[2] = make_float4(Ns.z, 0.f, 0.f, 0.f);
         }
         if (!TMESH) { if (DS0 < DS1) { if (CAPS) contact_detect_begin_caps<DS0, DS1P>(lm_, T, k, Rb, pb, P.slide_mask, pc1, P.slot_perm); else contact_detect_begin<DS0, DS1P>(lm_, T, k, Rb, pb, pr1); } }
-        else contact_detect_mesh<MCAPS>(MESH_PAIR0(1), MESH_PAIR0(1) + 2, lm_, T, P, k, Rb, pb, cst, lane, cqc);
+        else contact_detect_mesh<MCAPS, LCAPS>(MESH_PAIR0(1), MESH_PAIR0(1) + 2, lm_, T, P, k, Rb, pb, cst, lane, cqc);
       } else if (TMESH) {
 #ifdef LG_STAMPS
-        contact_detect_mesh<MCAPS>(MESH_PAIR0(wv), MESH_PAIR0(wv) + 2, lm_, T, P, k, Rb, pb, cst, lane, cqc,
+        contact_detect_mesh<MCAPS, LCAPS>(MESH_PAIR0(wv), MESH_PAIR0(wv) + 2, lm_, T, P, k, Rb, pb, cst, lane, cqc,
 #ifdef LG_STAMP_MAIN_MESH
                             nullptr);
 #else
                             (blockIdx.x == 0 && wv == 2) ? C->stamps : nullptr);
 #endif
 #else
-        contact_detect_mesh<MCAPS>(MESH_PAIR0(wv), MESH_PAIR0(wv) + 2, lm_, T, P, k, Rb, pb, cst, lane, cqc);
+        contact_detect_mesh<MCAPS, LCAPS>(MESH_PAIR0(wv), MESH_PAIR0(wv) + 2, lm_, T, P, k, Rb, pb, cst, lane, cqc);
 #endif
       } else if (wv == 2) {
         if (CAPS) contact_detect_begin_caps<DS1, DS2>(lm_, T, k, Rb, pb, P.slide_mask, pc2, P.slot_perm); else contact_detect_begin<DS1, DS2>(lm_, T, k, Rb, pb, pr2);
@@ -1005,7 +1008,7 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
   PhysParams P;
   P.dt = g.sim_dt; P.grav = v3(g.gravity[0], g.gravity[1], g.gravity[2]); P.iters = g.solver_iterations;
   P.contact_offset = g.contact_offset; P.max_depen = g.max_depenetration_velocity; P.erp = g.erp; P.cfm = g.cfm; P.solver = g.solver_type; P.fric = g.friction_model;
-  P.terrain_mu = C->terrain_mu; P.slide_mask = (CAPS || (MCAPS && C->ter.SEG4)) ? C->slide_mask : 0u; P.slot_perm = CAPS ? C->slot_perm : (TMESH ? C->mesh_perm : 0x76543210u); P.cache_reach = TMESH ? C->mesh_reach : 0.f;
+  P.terrain_mu = C->terrain_mu; P.slide_mask = (CAPS || (MCAPS && C->ter.SEG4) || (LCAPS && C->ter.L.cell)) ? C->slide_mask : 0u; P.slot_perm = CAPS ? C->slot_perm : (TMESH ? C->mesh_perm : 0x76543210u); P.cache_reach = TMESH ? C->mesh_reach : 0.f;
 #if LG_AB == 21
   P.slide_mask = 0u;
 #endif
@@ -2834,6 +2837,7 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
   h.ter.L = LatticeView{nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 1.f, 1.f, LATP_CAP};
   h.ter.M = MeshView{nullptr, nullptr}; h.ter.GV = nullptr; h.ter.GV4 = nullptr; h.ter.GM = nullptr; h.ter.mcols = 0; h.ter.SEG4 = nullptr;
   if (const char* ev = getenv("LG_GRID_MESH")) c->grid_mesh = atoi(ev) != 0;
+  if (const char* ev = getenv("LG_LATTICE_CAPS")) { c->lat_caps_env = atoi(ev) != 0 ? 1 : 0; c->lat_caps = c->lat_caps_env; }   // (lg_set_lattice_capsules; A/B: tools/ab_env_var.sh)
   bool mesh_caps = true;                                   // LG_MESH_CAPS=0: the spheres alone on grid meshes (A/B, the tests' checker)
   if (const char* ev = getenv("LG_MESH_CAPS")) mesh_caps = atoi(ev) != 0;
   if (ter->mesh_type == LG_MESH_TRIMESH && ter->grid_vertices && (c->grid_mesh || mesh_caps)) {      // grid mesh: contact queries by cell index, capsule segments against its edges
@@ -2998,6 +3002,10 @@ static int chain_epb(int n) {
   if (const char* ev = getenv("LG_CHAIN_EPB")) { const int v = atoi(ev); if (v >= 1 && v <= EPW) epb = v; }
   return epb;
 }
+// capsule segments against a lattice mesh's edges (FEAT bit 2): switched on, a lattice mesh without the grid rule's vertices (TerrainView::SEG4 answers grid meshes), a robot with segments
+static bool lattice_caps_on(const lg_ctx* c) {
+  return NJ == 3 && c->lat_caps && c->h.ter.mesh_type == LG_MESH_TRIMESH && c->h.ter.L.cell && !c->h.ter.SEG4 && c->h.slide_mask != 0u;
+}
 static void launch_physics(lg_ctx* c, hipStream_t st, const float* actions, const int32_t* ids, int n, int act_stride = NDOF, int fuse = 0,
                            PostSink sink = PostSink{nullptr, nullptr, nullptr, nullptr, 0.f}) {
 #if NJ != 3
@@ -3025,6 +3033,7 @@ static void launch_physics(lg_ctx* c, hipStream_t st, const float* actions, cons
   const bool tm = c->h.ter.mesh_type == LG_MESH_TRIMESH;
   const bool caps = c->h.ter.mesh_type == LG_MESH_HEIGHTFIELD && c->h.slide_mask != 0u, selfc = c->h.n_sc > 0;       // (a plane has no grid lines: the plain instance)
   const bool mcaps = tm && c->h.ter.SEG4 && c->h.slide_mask != 0u;      // grid meshes: the segments against the mesh's edges (other meshes: spheres alone)
+  const bool lcaps = lattice_caps_on(c);                              // lattice meshes, when switched on (lg_set_lattice_capsules): the segments against the lattice's edges
 #define LG_LAUNCH_PK(TM, HELP, SPEC_, THREADS) \
   hipLaunchKernelGGL((physics_kernel<0, TM, HELP, SPEC_>), dim3(nb), dim3(THREADS), 0, st, c->d, actions, c->h.cfg.decimation, nact, ids, n, act_stride, fuse, sink)
 #if LG_LEGS == 4
@@ -3035,14 +3044,16 @@ static void launch_physics(lg_ctx* c, hipStream_t st, const float* actions, cons
     return;
   }
   if (fuse == 2) {                                       // (can_fuse() held: helper waves are present)
-    if (tm) { if (selfc) { if (mcaps) LG_LAUNCH_PK(true, true, 2 + 12, 256); else LG_LAUNCH_PK(true, true, 2 + 8, 256); } else if (mcaps) LG_LAUNCH_PK(true, true, 2 + 4, 256); else LG_LAUNCH_PK(true, true, 2, 256); }
+    if (lcaps) { if (selfc) LG_LAUNCH_PK(true, true, 2 + 8 + 16, 256); else LG_LAUNCH_PK(true, true, 2 + 16, 256); }
+    else if (tm) { if (selfc) { if (mcaps) LG_LAUNCH_PK(true, true, 2 + 12, 256); else LG_LAUNCH_PK(true, true, 2 + 8, 256); } else if (mcaps) LG_LAUNCH_PK(true, true, 2 + 4, 256); else LG_LAUNCH_PK(true, true, 2, 256); }
     else if (selfc) LG_LAUNCH_PK(false, true, 2 + 12, 256);
     else if (caps) LG_LAUNCH_PK(false, true, 2 + 4, 256);
     else LG_LAUNCH_PK(false, true, 2, 256);
     return;
   }
 #endif
-  if (tm) { if (selfc) { if (mcaps) LG_LAUNCH_PK(true, true, 12, 256); else LG_LAUNCH_PK(true, true, 8, 256); } else if (mcaps) LG_LAUNCH_PK(true, true, 4, 256); else LG_LAUNCH_PK(true, true, 0, 256); }
+  if (lcaps) { if (selfc) LG_LAUNCH_PK(true, true, 8 + 16, 256); else LG_LAUNCH_PK(true, true, 16, 256); }
+  else if (tm) { if (selfc) { if (mcaps) LG_LAUNCH_PK(true, true, 12, 256); else LG_LAUNCH_PK(true, true, 8, 256); } else if (mcaps) LG_LAUNCH_PK(true, true, 4, 256); else LG_LAUNCH_PK(true, true, 0, 256); }
   else
 #if LG_AB == 13
     if (nact == 3 && c->h.cfg.solver_type == LG_SOLVER_TGS && c->h.cfg.friction_model == LG_FRICTION_PYRAMID && c->spec && !caps && !selfc)
@@ -3129,6 +3140,18 @@ int lg_set_reward_terms(lg_ctx* c, int32_t num_terms, const int32_t* term_ids, c
   hot_config(c->h);
   HIP_TRY(c, hipMemcpyAsync((char*)c->d + ((char*)&c->h.rew_term_mask - base), &c->h.rew_term_mask, 4 * sizeof(int) + sizeof(c->h.hot), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemsetAsync(c->h.ep_sums, 0, (size_t)LG_MAX_REWARD_TERMS * c->h.N * sizeof(float), st));
+  return LG_OK;
+}
+
+int lg_set_lattice_capsules(lg_ctx* c, int32_t on) {
+  if (!c) return LG_ERR_INVALID;
+  if (NJ != 3) { c->err = "lg_set_lattice_capsules: the two-legged (six joints per leg) instance has no lattice-mesh contact path"; return LG_ERR_INVALID; }
+  const TerrainView& T = c->h.ter;
+  if (T.mesh_type != LG_MESH_TRIMESH || (!T.L.cell && !T.GV && !T.SEG4)) {
+    c->err = "lg_set_lattice_capsules: the terrain is not a lattice mesh (a plane, a height grid, or a triangle mesh whose contact queries walk the BVH)"; return LG_ERR_INVALID;
+  }
+  // (a grid mesh: its segments run against its own edges already -- TerrainView::SEG4 --, a robot without sliding spheres has none: accepted, nothing changes)
+  c->lat_caps = c->lat_caps_env >= 0 ? c->lat_caps_env : (on != 0);      // LG_LATTICE_CAPS, when set, overrides the switch (same-session A/B)
   return LG_OK;
 }
 
@@ -3378,7 +3401,9 @@ int lg_simulate(lg_ctx* c, void* stream) {
   if (c->h.ter.mesh_type == LG_MESH_TRIMESH) hipLaunchKernelGGL((physics_kernel_chain<1, true>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, (const int32_t*)nullptr, c->h.N, NDOF, EPW);
   else hipLaunchKernelGGL((physics_kernel_chain<1, false>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, (const int32_t*)nullptr, c->h.N, NDOF, EPW);
 #else
-  if (c->h.ter.mesh_type == LG_MESH_TRIMESH)
+  if (lattice_caps_on(c))
+    hipLaunchKernelGGL((physics_kernel<1, true, false, FEAT_ALL + 16>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
+  else if (c->h.ter.mesh_type == LG_MESH_TRIMESH)
     hipLaunchKernelGGL((physics_kernel<1, true, false, FEAT_ALL>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
   else
     hipLaunchKernelGGL((physics_kernel<1, false, false, FEAT_ALL>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});

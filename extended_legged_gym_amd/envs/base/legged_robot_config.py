@@ -55,6 +55,10 @@ class LeggedRobotCfg(BaseConfig):
         origins_x_range = [-20.0, 20.0]
         origins_y_range = [-20.0, 20.0]
         height_clearance_factor = 2.0
+        # (extension, like `collide_height_grid`) capsule segments against the edges of a LATTICE mesh -- TerrainObj OBJ files and
+        # TerrainConfined (`confined_trimesh`), whose cylinders the reference loads as capsules too (asset.replace_cylinder_with_capsule):
+        # off by default, the spheres alone (lg_set_lattice_capsules; grid meshes of a procedural Terrain always carry their segments)
+        lattice_mesh_capsules = False
 
     class raycaster:
         enable_raycast = False

@@ -196,6 +196,13 @@ class NativeSetup:
                  custom_origins=None, terminate_on_flip=False, reward_term_variants=None, reward_class="base", noise_layout_dof=None,
                  keep_small_commands=False, feet_air_time_ungated=False):
         self.model_dict = model
+        # terrain.lattice_mesh_capsules (lg_set_lattice_capsules, applied by NativeCore): refused here, before anything is built, where it cannot act
+        self.lattice_mesh_capsules = bool(getattr(cfg.terrain, "lattice_mesh_capsules", False))
+        if self.lattice_mesh_capsules:
+            if int(model.get("num_legs", len(model["cp_count"]))) == 2:
+                raise ValueError("terrain.lattice_mesh_capsules: the biped (Cassie) kernel instance has no lattice-mesh contact path")
+            if not getattr(cfg.asset, "replace_cylinder_with_capsule", True):
+                raise ValueError("terrain.lattice_mesh_capsules needs asset.replace_cylinder_with_capsule = True: without capsules there are no segments")
         if not getattr(cfg.asset, "replace_cylinder_with_capsule", True) and "cp_slide" in model:
             # (legged_robot_config.py:171; every task of the reference leaves it True.)  Without the option the cylinders stay cylinders in PhysX;
             # here their spheres then stay where they are
@@ -405,3 +412,5 @@ class NativeSetup:
             t.mesh_type = abi.LG_MESH_PLANE
             self.height_samples, self.terrain_origins = None, None
         self.terrain = t
+        if self.lattice_mesh_capsules and t.mesh_type != abi.LG_MESH_TRIMESH:
+            raise ValueError("terrain.lattice_mesh_capsules needs a triangle-mesh terrain (TerrainObj / TerrainConfined): a plane or height grid has no lattice mesh")

@@ -55,6 +55,9 @@ class NativeCore:
             from extended_legged_gym_amd.utils.mesh import DeviceMesh
             self.collision_mesh = DeviceMesh(setup.collision_vertices, setup.collision_triangles, device=dev)
             setup.terrain.collision_mesh = self.collision_mesh.handle
+            if getattr(setup, "lattice_mesh_capsules", False) and self.collision_mesh.contact_lattice == (0, 0):
+                self.collision_mesh.close()
+                raise ValueError("terrain.lattice_mesh_capsules: the collision mesh is not a lattice mesh (contact_lattice (0, 0): its contact queries walk the BVH)")
         nbytes = self.lib.lg_arena_bytes(C.byref(setup.cfg), C.byref(setup.model), C.byref(setup.terrain))
         if nbytes == 0:
             raise ValueError("lg_arena_bytes rejected the configuration: " + self._err(None))
@@ -64,6 +67,8 @@ class NativeCore:
                                       self.device_index, C.c_void_p(self.arena.data_ptr()))
         if not self.ctx:
             raise RuntimeError("lg_create failed: " + self._err(None))
+        if getattr(setup, "lattice_mesh_capsules", False):
+            self._check(self.lib.lg_set_lattice_capsules(self.ctx, 1))     # capsule segments against the lattice mesh's edges
         self.t = {}
         base = self.arena.data_ptr()
         for name, tid in abi.TENSOR_ID.items():

@@ -387,6 +387,17 @@ int lg_set_reward_terms(lg_ctx* ctx, int32_t num_terms, const int32_t* term_ids,
  * anymal_c_batch_rollout.py:212-216) and the foot_z_align constant of the spawn pose (see lg_config.async_*).  Stream-ordered. */
 int lg_set_async_gait(lg_ctx* ctx, const float weights[3], float foot_z_align, void* stream);
 
+/* Capsule segments against a LATTICE mesh's edges (TerrainObj OBJ files, TerrainConfined): the reference loads every collision cylinder as a capsule
+ * (asset.replace_cylinder_with_capsule = True, legged_robot_config.py:171, handed to PhysX at legged_robot.py:741) on every terrain.  on = 1: a sphere
+ * with a successor on its capsule (lg_robot_model.cp_slide) also tests the segment to it against the mesh edges that lie on the first lattice line of
+ * each axis its ground track crosses (both cells beside the crossing, every layer: ground and ceiling); an edge candidate deeper than the sphere by more
+ * than 10 um takes the slot -- the rule grid meshes run (lg_terrain.grid_vertices), with the outside side taken from the faces that own the edge.
+ * Off by default (0: spheres alone, the kernels of before); LG_LATTICE_CAPS=1|0 at lg_create overrides the switch.  LG_ERR_INVALID (lg_last_error
+ * says why) when the terrain is not a lattice mesh (lg_mesh_contact_lattice (0, 0), a plane, a height grid) or the instance has no lattice-mesh path
+ * (the two-legged robot).  A grid mesh (its own edges answer already) and a robot without sliding spheres are accepted and change nothing.
+ * Host-side: selects the kernel instances of later launches. */
+int lg_set_lattice_capsules(lg_ctx* ctx, int32_t on);
+
 /* The two halves of lg_step_subset, so that sensor kernels (ray caster, body SDF) can run on the post-physics, pre-reset state
  * in between (RobotBatchRolloutPercept._post_physics_step_callback, robot_batch_rollout_percept.py:301-331). */
 int lg_step_subset_physics(lg_ctx* ctx, const float* actions, const int32_t* env_ids, int32_t n, void* stream);

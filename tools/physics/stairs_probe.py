@@ -11,6 +11,8 @@ segments' edge contacts when the model carries them; `LG_CAPS=0` in the environm
 
 Round 6: `trimesh` as a second argument runs the terrain as `anymal_c_rough` registers it (the slope-corrected triangle mesh; the surface under a sample is then found by
 a downward ray on the collision mesh itself), where the segments meet the mesh's own edges (`contact_detect_mesh<true>`); `LG_MESH_CAPS=0` runs the spheres alone there.
+The same mesh through the LATTICE path (what an OBJ / confined mesh takes): `LG_GRID_MESH=0 LG_MESH_CAPS=0` (cells of the lattice, no grid rule), with
+`LG_LATTICE_CAPS=1` the lattice mesh's capsule segments (`lattice_caps_edges`), `=0` the spheres alone.
 
     python tools/physics/stairs_probe.py [steps] [heightfield|trimesh]        (prints one JSON object)
 """
@@ -111,7 +113,8 @@ def main(steps=400, n=1024, mesh_type="heightfield"):
                depth_mm_median=float(d.median() * 1e3) if len(d) else 0.0, depth_mm_p95=float(d.quantile(0.95) * 1e3) if len(d) else 0.0,
                depth_mm_max=float(d.max() * 1e3) if len(d) else 0.0, envs=n, steps=steps,
                resets_per_env_step=float(env.reset_buf.float().mean()), mean_forward_speed=float(env.base_lin_vel[:, 0].mean()), mesh_type=mesh_type,
-               segments=os.environ.get("LG_MESH_CAPS" if mesh_type == "trimesh" else "LG_CAPS", "1") != "0")
+               segments=os.environ.get("LG_MESH_CAPS" if mesh_type == "trimesh" else "LG_CAPS", "1") != "0",
+               lattice_path=os.environ.get("LG_GRID_MESH") == "0", lattice_segments=os.environ.get("LG_LATTICE_CAPS", "0") != "0")
     print(json.dumps(out))
 
 
