@@ -25,6 +25,7 @@
 #include "../../include/lgstep.h"
 
 #include "lg_bvh.h"
+#include "lg_switches.h"
 
 
 static thread_local std::string g_mesh_err;
@@ -485,6 +486,8 @@ void lg_mesh_destroy(lg_mesh* m) {
 
 lg_mesh* lg_mesh_create(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, int device_id) {
   if (!vertices || !triangles || n_vertices <= 0 || n_triangles <= 0) { g_mesh_err = "empty mesh"; return nullptr; }
+  int ray_grid = 1, lattice_cp = 1;                // LG_RAY_GRID, LG_LATTICE_CP (lg_switches.h)
+  if (!lg_switch_flag("LG_RAY_GRID", ray_grid, g_mesh_err) || !lg_switch_flag("LG_LATTICE_CP", lattice_cp, g_mesh_err)) return nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_mesh_err = "no HIP device: mesh queries have no CPU path"; return nullptr; }
   if (device_id < 0 || device_id >= ndev) { g_mesh_err = "bad device"; return nullptr; }
@@ -519,9 +522,8 @@ lg_mesh* lg_mesh_create(const float* vertices, int64_t n_vertices, const int32_t
     g_mesh_err = "device allocation / upload of the BVH failed"; lg_mesh_destroy(m); return nullptr;
   }
   // rays over a lattice mesh walk its cells instead of the tree (LG_RAY_GRID=0: always the tree -- the A/B switch, and how the tests compare the two)
-  const char* rg = getenv("LG_RAY_GRID");
   RayGridHost G;
-  if (!(rg && rg[0] == '0') && G.build(t)) {
+  if (ray_grid && G.build(t)) {
     if (hipMalloc((void**)&m->d_gxb, G.xb.size() * 4) != hipSuccess || hipMalloc((void**)&m->d_gyb, G.yb.size() * 4) != hipSuccess ||
         hipMalloc((void**)&m->d_gcells, G.cells.size() * sizeof(int2)) != hipSuccess || hipMalloc((void**)&m->d_gzr, G.zr.size() * sizeof(float2)) != hipSuccess ||
         hipMemcpy(m->d_gzr, G.zr.data(), G.zr.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess || hipMalloc((void**)&m->d_gtris, G.tris.size() * sizeof(float4)) != hipSuccess ||
@@ -544,9 +546,8 @@ lg_mesh* lg_mesh_create(const float* vertices, int64_t n_vertices, const int32_t
       }
     }
     // evenly spaced boundaries: the cell table of the closest-point queries (LG_LATTICE_CP=0: none -- contact queries walk the tree; the A/B switch and the tests' checker)
-    const char* lc = getenv("LG_LATTICE_CP");
     const float hx = (G.xb.back() - G.xb.front()) / (float)m->gnx, hy = (G.yb.back() - G.yb.front()) / (float)m->gny;
-    bool even = !(lc && lc[0] == '0') && hx > 0.f && hy > 0.f;
+    bool even = lattice_cp && hx > 0.f && hy > 0.f;
     for (int i = 0; even && i <= m->gnx; ++i) even = std::fabs(G.xb[i] - (G.xb[0] + (float)i * hx)) <= 0.5f * LATTICE_TOL * hx;
     for (int i = 0; even && i <= m->gny; ++i) even = std::fabs(G.yb[i] - (G.yb[0] + (float)i * hy)) <= 0.5f * LATTICE_TOL * hy;
     if (even) {
@@ -689,6 +690,12 @@ int lg_sdf_bodies_update(lg_mesh* m, const float* rigid_body_state, int32_t num_
   if (!m || !rigid_body_state || !body_indices || !sdf_values || num_bodies <= 0 || num_query_bodies <= 0 || n <= 0 ||
       sdf_stride < num_query_bodies)
     return LG_ERR_INVALID;
+  // (round 6, measured on config 3, three rounds: 256 threads + one env's five bodies side by side 0.3435 ms per step; 128 threads + the same body of eight envs per
+  //  workgroup 0.3373: a wave no longer waits for the one trunk among its four queries.  LG_SDF_BLOCK / LG_SDF_ORDER: A/B)
+  int sdf_lattice = 1, sdf_order = 1, sdf_block = 128;
+  if (!lg_switch_flag("LG_SDF_LATTICE", sdf_lattice, m->err) || !lg_switch_flag("LG_SDF_ORDER", sdf_order, m->err) ||
+      !lg_switch_int_in("LG_SDF_BLOCK", {64, 128, 256}, sdf_block, m->err))
+    return LG_ERR_INVALID;
   DeviceScope ds_(m->device);
   MeshView M{m->d_nodes, m->d_tris};
   int64_t tot = (int64_t)n * num_query_bodies;
@@ -699,14 +706,8 @@ int lg_sdf_bodies_update(lg_mesh* m, const float* rigid_body_state, int32_t num_
     m->sdf_cache_n = tot;
     MESH_TRY(m, hipMemsetAsync(m->d_sdf_cache, 0, (size_t)tot * sizeof(float4), (hipStream_t)stream));
   }
-  const char* sl = getenv("LG_SDF_LATTICE");
   LatticeView L{nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 1.f, 1.f, LATP_CAP};
-  if (m->d_gcz && m->d_gcr && !(sl && sl[0] == '0')) L = LatticeView{m->d_gcz, m->d_gcr, m->d_gtris, m->gnx, m->gny, m->gx0, m->gy0, m->ghx, m->ghy, LATP_CAP};
-  // (round 6, measured on config 3, three rounds: 256 threads + one env's five bodies side by side 0.3435 ms per step; 128 threads + the same body of eight envs per
-  //  workgroup 0.3373: a wave no longer waits for the one trunk among its four queries.  LG_SDF_BLOCK / LG_SDF_ORDER: A/B)
-  int sdf_block = 128, sdf_order = 1;
-  if (const char* ev = getenv("LG_SDF_BLOCK")) { const int v = atoi(ev); if (v == 64 || v == 128 || v == 256) sdf_block = v; }
-  if (const char* ev = getenv("LG_SDF_ORDER")) sdf_order = atoi(ev) != 0;
+  if (m->d_gcz && m->d_gcr && sdf_lattice) L = LatticeView{m->d_gcz, m->d_gcr, m->d_gtris, m->gnx, m->gny, m->gx0, m->gy0, m->ghx, m->ghy, LATP_CAP};
   const int qpb = sdf_block / 16;
   hipLaunchKernelGGL(sdf_bodies_kernel, dim3((unsigned)((tot + qpb - 1) / qpb)), dim3(sdf_block), 0, (hipStream_t)stream, M, L, rigid_body_state, num_bodies,
                      body_indices, sphere_offsets, num_query_bodies, env_ids, n, max_dist, sdf_values, sdf_stride, sdf_gradients, nearest_points, m->d_sdf_cache, sdf_order);
@@ -723,7 +724,8 @@ int lg_depth_camera_update(lg_mesh* m, const lg_depth_params* p, const float* ro
   size_t lds = (size_t)p->width * p->height * sizeof(float);
   if (lds > 64 * 1024) { m->err = "depth image too large for the LDS-staged resize"; return LG_ERR_UNSUPPORTED; }
   // the lattice instance keeps its boundary tables in LDS next to the image; together they must stay within the 64 KB a launch gets without opting in
-  const char* rs_ = getenv("LG_RAY_SKIP"); const int skip = rs_ ? atoi(rs_) : 1;      // (A/B switch; 0: every ray walks from the camera, 2: also the coarse walk over blocks -- measured: +-1 %)
+  int skip = 1;      // LG_RAY_SKIP (A/B switch; 0: every ray walks from the camera, 2: also the coarse walk over blocks -- measured: +-1 %; 9: timing probe)
+  if (!lg_switch_int_in("LG_RAY_SKIP", {0, 1, 2, 9}, skip, m->err)) return LG_ERR_INVALID;
   int mode = 0;
   const size_t rs_lds = (size_t)5 * (p->resized_width + p->resized_height) * sizeof(float);      // the resize's per-column / per-row weights (depth_kernel)
   if (m->d_gcells && m->gnx >= 1 && m->gny >= 1 && lds + ray_grid_lds(m) + rs_lds <= 64 * 1024) { mode = 1; lds += ray_grid_lds(m); }

@@ -241,47 +241,6 @@ LG_DEV void spd6_inverse_from_chol(const float* L, float* Si) {
       Si[LT(a, b)] = sacc;
     }
 }
-// Inverse of an SPD 6 x 6 (packed lower) by 3 x 3 blocks: S = [A B^T; B D] (A: rows 0..2, D: rows 3..5, B = rows 3..5 x cols 0..2),
-//   A^-1 and the Schur complement's inverse C^-1 = (D - B A^-1 B^T)^-1 in closed form (cofactors, one reciprocal each),
-//   S^-1 = [A^-1 + E^T C^-1 E, -E^T C^-1; -C^-1 E, C^-1] with E = B A^-1.
-// Against the Cholesky route (six dependent rsqrt / row chains, then a triangular inverse) this is two short chains of independent products: what a wave
-// that is alone on its SIMD is short of is not arithmetic but dependent latency.
-LG_DEV void spd6_inverse_blocks(const float* S, float* Si) {
-  const float A[6] = {S[LT(0, 0)], S[LT(1, 0)], S[LT(2, 0)], S[LT(1, 1)], S[LT(2, 1)], S[LT(2, 2)]};      // 00 01 02 11 12 22
-  const float D[6] = {S[LT(3, 3)], S[LT(4, 3)], S[LT(5, 3)], S[LT(4, 4)], S[LT(5, 4)], S[LT(5, 5)]};
-  float B[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) B[i][j] = S[LT(3 + i, j)];
-  float Ai[6]; sym3_inverse(A, Ai);
-  float E[3][3];                      // E = B A^-1
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { const float bi[3] = {B[i][0], B[i][1], B[i][2]}; sym3_mul(Ai, bi, E[i]); }
-  float C[6];                         // D - E B^T (symmetric)
-  C[0] = D[0] - (E[0][0] * B[0][0] + E[0][1] * B[0][1] + E[0][2] * B[0][2]);
-  C[1] = D[1] - (E[0][0] * B[1][0] + E[0][1] * B[1][1] + E[0][2] * B[1][2]);
-  C[2] = D[2] - (E[0][0] * B[2][0] + E[0][1] * B[2][1] + E[0][2] * B[2][2]);
-  C[3] = D[3] - (E[1][0] * B[1][0] + E[1][1] * B[1][1] + E[1][2] * B[1][2]);
-  C[4] = D[4] - (E[1][0] * B[2][0] + E[1][1] * B[2][1] + E[1][2] * B[2][2]);
-  C[5] = D[5] - (E[2][0] * B[2][0] + E[2][1] * B[2][1] + E[2][2] * B[2][2]);
-  float Ci[6]; sym3_inverse(C, Ci);
-  float G[3][3];                      // G = C^-1 E  (rows 3..5 x cols 0..2 of -S^-1)
-#pragma unroll
-  for (int j = 0; j < 3; ++j) { const float ej[3] = {E[0][j], E[1][j], E[2][j]}; float g[3]; sym3_mul(Ci, ej, g); G[0][j] = g[0]; G[1][j] = g[1]; G[2][j] = g[2]; }
-  // lower-right block
-  Si[LT(3, 3)] = Ci[0]; Si[LT(4, 3)] = Ci[1]; Si[LT(5, 3)] = Ci[2]; Si[LT(4, 4)] = Ci[3]; Si[LT(5, 4)] = Ci[4]; Si[LT(5, 5)] = Ci[5];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Si[LT(3 + i, j)] = -G[i][j];
-  // upper-left block: A^-1 + E^T G
-  const int ai[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b <= a; ++b) Si[LT(a, b)] = Ai[ai[a][b]] + E[0][a] * G[0][b] + E[1][a] * G[1][b] + E[2][a] * G[2][b];
-}
 LG_DEV void symv6(const float* Si, const float* x, float* y) {
 #pragma unroll
   for (int a = 0; a < 6; ++a) {
@@ -637,9 +596,6 @@ LG_DEV void closest_point_grid(const TerrainView& T, ClosestQuery& A, int* visit
 #define GSTAMP(k)
 #endif
   if (!A.on) return;
-#if LG_AB == 1      // timing probe: no query at all (nothing is ever found)
-  A.found = false; A.cp = A.p; A.fn = v3(0, 0, 1); return;
-#endif
   // pointers read out of a struct are generic to the compiler (flat_load: counted on both wait counters, drained with vmcnt(0) and
   // lgkmcnt(0) together); these three are device-global by construction
   typedef float f4v __attribute__((ext_vector_type(4)));
@@ -733,9 +689,6 @@ LG_DEV void closest_point_grid(const TerrainView& T, ClosestQuery& A, int* visit
     ci = max(i0, min((int)floorf(gx), i1)); cj = max(j0, min((int)floorf(gy), j1));
     exact(ci, cj);
     GSTAMP(23);
-#if LG_AB == 2      // timing probe: the cell under the sphere only
-    A.found = found; A.cp = bestp; A.fn = bestn; return;
-#endif
     if (found) {
       gr = sqrtf(best2) * ihs * (1.f + 1e-4f) + 1e-3f;
       i0 = max(i0, (int)floorf(gx - gr) - margin); i1 = min(i1, (int)floorf(gx + gr) + margin);
@@ -1569,9 +1522,6 @@ struct SelfRow { bool on; float phi, iA, lam; V3 n; float f[3], Wb[6], Wk[3]; in
 // squared distance against the entry's threshold (radius a + radius b + contact_offset)^2 (1 + 1e-4) -- no root, conservative; three pairs per round, loads
 // batched.  Robots walk with their links decimetres apart: the mask is zero nearly always, and the exact pass behind it then does not run.
 LG_DEV unsigned sc_prefilter(const float* cst, const uint4* tab, int n, int lane, int share, int nshare) {
-#if LG_AB == 41      // (timing probe: no filter work at all; the rows' code stays)
-  return 0u;
-#endif
   const int gb = lane & ~(GRP - 1), lgi = lane & (GRP - 1);
   const float4* rec = reinterpret_cast<const float4*>(cst);
   const unsigned gb4 = (unsigned)gb * (CF_FIELDS / 4);
@@ -1612,11 +1562,11 @@ LG_DEV V3 sc_sphere(const float* cst, const LegModel& lm_, int gb, int leg, int 
 // holds the rendezvous and fills the three outputs); false means this wave computes them itself.
 // With helper waves on a heightfield the contact detection is dealt two slots per wave; this wave takes slots
 // [0, MAIN_DETECT) before the rendezvous (0: the helpers, or the inline path, detect everything).
-// SPEC = 1: the instance of the reference's own solver settings (sim.physx.solver_type = 1: TGS, PhysX's pyramid friction rows) with both
-// choices fixed at compile time; SPEC = 0 reads them from the parameters (the unified step evaluates both friction forms and selects).
+// The solver and friction model are read from the parameters (the unified step evaluates both friction forms and selects; a compile-time TGS + pyramid
+// instance measured 1.2 % slower in round 5).
 // FEAT: bit 0 = capsule parts (sliding spheres, contact_detect_*_caps), bit 1 = the self-collision pass, bit 2 = capsule segments against a lattice
 // mesh's edges (triangle-mesh instances: lattice_caps_edges) -- compile-time, so that the instance without them is the kernel it was before they existed.
-template <bool TMESH, int MAIN_DETECT, bool ALLOW_INLINE, int SPEC = 0, int FEAT = 0, class TauFn, class PrepFn, class ShareFn>
+template <bool TMESH, int MAIN_DETECT, bool ALLOW_INLINE, int FEAT = 0, class TauFn, class PrepFn, class ShareFn>
 LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel& lm_, const TerrainView& T, const PhysParams& P,
                             int lane, float* cst, QuadState& s, TauFn tau_fn, PrepFn prep_fn, ShareFn share_fn, SlotShare share,
                             float* xs, float mu_robot, float madd, V3* fbody, unsigned long long* stamps = nullptr,
@@ -1690,18 +1640,10 @@ LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel
     L[LT(5, 0)] += -ht.y; L[LT(5, 1)] += ht.x;
     L[LT(3, 3)] += It.xx; L[LT(4, 3)] += It.xy; L[LT(5, 3)] += It.xz;
     L[LT(4, 4)] += It.yy; L[LT(5, 4)] += It.yz; L[LT(5, 5)] += It.zz;
-#if LG_AB != 32
     chol6(L);
-#endif
   }
   float Si[21];
-#if LG_AB == 32      // measured and dropped (round 5, four same-session pairs): the inverse by 3 x 3 blocks -- two short chains instead of six dependent
-                     // rsqrt rows -- leaves the step where it was (0.0806 vs 0.0808 ms; 0.0752 vs 0.0752 on the plain instance): the main wave has slack in front
-                     // of rendezvous (A2), the helper waves arrive last
-  spd6_inverse_blocks(L, Si);
-#else
-  spd6_inverse_from_chol(L, Si);
-#endif
+  spd6_inverse_from_chol(L, Si);     // (3 x 3 block inverse: measured in round 5, no gain -- the main wave has slack in front of (A2))
   if (share.n > 1) { if (TMESH) publish_mass_factors(xs, lane, Mi, Mbk, Y, Si); else publish_mass_factors_pk(xs, lane, Mi, Mbk, Y, Si); }
 
   STAMP(3);
@@ -1922,7 +1864,7 @@ LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel
 
   // the step's generalised displacement: dq = sum over the sub-intervals of h * v (TGS), dt * v of the last sweep (PGS)
   pk2 dqB[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}}; pk2 dqK01 = {0.f, 0.f}; float dqK2 = 0.f;
-  const bool tgs = SPEC == 1 ? true : P.solver == LG_SOLVER_TGS;
+  const bool tgs = P.solver == LG_SOLVER_TGS;
   const int iters = P.iters > 0 ? P.iters : 1;
   const float h = tgs ? dt * frcp((float)iters) : dt, ih = frcp(h);
   const float tgsf = tgs ? 1.f : 0.f;
@@ -1934,7 +1876,7 @@ LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel
     pk2 Y01[6];
 #pragma unroll
     for (int a = 0; a < 6; ++a) { Y01[a].x = Y[0][a]; Y01[a].y = Y[1][a]; }
-    const bool pyr = SPEC == 1 ? true : P.fric != LG_FRICTION_CONE;
+    const bool pyr = P.fric != LG_FRICTION_CONE;
     const float erp_ih = P.erp * ih;
     // A lane with nothing to relax at a step still reads a record (and multiplies it by zero impulses): it must be one the
     // set-up has written in THIS launch for every lane -- any slot of the wave's mask -- not a slot nobody uses, whose LDS
@@ -1977,14 +1919,11 @@ LG_DEV void physics_substep(const lg_robot_model* __restrict__ m, const LegModel
       const pk2 w12 = pk_fma(an12, pk_splat(dn), u12);
       const float lim = mu * ln;
       // cone: exact 2x2 tangential block, projected on the disc
-      pk2 c12 = {0.f, 0.f};
-      if (SPEC != 1) {
-        pk2 t12 = b_r0 * pk_splat(w12.x);
-        t12 = pk_fma(b_r1, pk_splat(w12.y), t12);
-        c12 = l12 - t12;
-        const float m2 = c12.x * c12.x + c12.y * c12.y;
-        if (m2 > lim * lim) { const float sc = m2 > 0.f ? lim * __builtin_amdgcn_rsqf(m2) : 0.f; c12 = c12 * pk_splat(sc); }
-      }
+      pk2 t12 = b_r0 * pk_splat(w12.x);
+      t12 = pk_fma(b_r1, pk_splat(w12.y), t12);
+      pk2 c12 = l12 - t12;
+      const float m2 = c12.x * c12.x + c12.y * c12.y;
+      if (m2 > lim * lim) { const float sc = m2 > 0.f ? lim * __builtin_amdgcn_rsqf(m2) : 0.f; c12 = c12 * pk_splat(sc); }
       // pyramid: two scalar rows, each clamped on its own (b_r0 = (1/A11, A12), b_r1 = (A12, 1/A22))
       const float p1 = fminf(fmaxf(l12.x - w12.x * b_r0.x, -lim), lim);
       const float p2 = fminf(fmaxf(l12.y - fmaf(b_r0.y, p1 - l12.x, w12.y) * b_r1.y, -lim), lim);

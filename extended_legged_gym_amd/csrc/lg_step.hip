@@ -23,6 +23,7 @@
 
 #include "lg_device.h"
 #include "lg_bvh.h"
+#include "lg_switches.h"
 #define LG_INSTANCE_TU
 #include "lg_instance.h"          // LG_LEGS -> this instance's namespace and the names of its entry points (lg4_* / lg6_*)
 
@@ -110,6 +111,23 @@ struct DevCtx {
 
 struct TensorInfo { size_t off; int64_t shape[4]; int ndim; int dtype; };
 
+// The environment switches a context reads at lg_create; what each one changes: lg_switches.h.  The defaults are what ships.
+struct CtxSwitches {
+  int split = 1, fuse = 1, persist = 1, gfuse = 0, caps = 1, mesh_caps = 1, grid_mesh = 1;   // LG_SPLIT, LG_FUSE, LG_PERSIST, LG_GFUSE, LG_CAPS, LG_MESH_CAPS, LG_GRID_MESH
+  int lat_caps_env = -1, lattice_cap = LATP_CAP;                 // LG_LATTICE_CAPS (-1: unset), LG_LATTICE_CAP
+  unsigned deal_perm = 0u, mesh_deal_perm = 0u;                  // LG_DEAL, LG_MESH_DEAL (0: unset; set, they replace the computed deals)
+  float mesh_reach = LG_MESH_CACHE_REACH;                        // LG_MESH_REACH
+};
+static bool read_ctx_switches(CtxSwitches& w, std::string& err) {
+  return lg_switch_flag("LG_SPLIT", w.split, err) && lg_switch_flag("LG_FUSE", w.fuse, err) && lg_switch_flag("LG_PERSIST", w.persist, err) &&
+         lg_switch_flag("LG_GFUSE", w.gfuse, err) && lg_switch_flag("LG_CAPS", w.caps, err) && lg_switch_flag("LG_MESH_CAPS", w.mesh_caps, err) &&
+         lg_switch_flag("LG_GRID_MESH", w.grid_mesh, err) && lg_switch_flag("LG_LATTICE_CAPS", w.lat_caps_env, err) &&
+         lg_switch_int("LG_LATTICE_CAP", 1, LATP_CAP, w.lattice_cap, err) &&
+         lg_switch_perm8("LG_DEAL", w.deal_perm, err) && lg_switch_perm8("LG_MESH_DEAL", w.mesh_deal_perm, err) &&
+         lg_switch_float("LG_MESH_REACH", 0.f, 1.f, w.mesh_reach, err);
+}
+enum { FEAT_CAPS = 1, FEAT_SELF = 2, FEAT_LCAPS = 4 };   // physics_kernel's FEAT: capsule segments (height grid lines, grid mesh edges), self-collision, lattice segments
+
 struct lg_ctx {
   int32_t legs = NLEG; // first member: how the library's entry points (lg_dispatch.cpp) find the instance a context belongs to
   DevCtx h;            // host copy
@@ -120,24 +138,26 @@ struct lg_ctx {
   void* mesh_cache = nullptr;
   void* grid_verts = nullptr;   // device copy of lg_terrain.grid_vertices
   void* hmin = nullptr;         // TerrainView::Hmin
-  int grid_mesh = 1;           // LG_GRID_MESH=0: walk the BVH for grid meshes too (diagnostic / A-B)
-  int lat_caps = 0;            // lg_set_lattice_capsules: capsule segments against a lattice mesh's edges (off by default; LG_LATTICE_CAPS=1|0 overrides it at lg_create)
-  int lat_caps_env = -1;       // LG_LATTICE_CAPS at lg_create (-1: unset)
+  CtxSwitches sw;
+  unsigned feat = 0u;          // FEAT_* of this context's physics launches (physics_feat: lg_create, lg_set_lattice_capsules)
   TensorInfo t[LG_T_COUNT];
   int device = 0;
   unsigned long sync_calls = 0;
-  int split = 1;       // fused step: run the LSTM actuators on three extra waves (LG_SPLIT=0 disables, diagnostic)
-  int fuse = 1;        // lg_step ends inside the physics kernel (LG_FUSE=0: separate post kernel, diagnostic / A-B)
-  int persist = 1;     // lg_rollout_batch is one launch per horizon (LG_PERSIST=0: one launch per step, the checker of that path)
-  int gfuse = 0;       // LG_GFUSE=1: the six-legged instance's lg_step in one launch (can_gfuse)
-  int spec = 1;        // A/B build 13 only: TGS + pyramid steps run a compile-time instance of that solver.  Measured (one session, three
-                       // rounds each): 0.0792 ms per step against 0.0782 for the generic instance -- 20 instructions fewer per relaxation, a
-                       // different schedule of the same dependent chain, 1.2 % slower; not instantiated in the product library
   std::string err;
   // optional per-kernel timing (lg_profile_begin / lg_profile_end)
   std::vector<hipEvent_t> ev; int prof_max = 0, prof_stride = 1, prof_n = 0; long prof_calls = 0;
 };
 
+// lat_caps: lg_set_lattice_capsules (off by default; LG_LATTICE_CAPS overrides it).  Lattice segments need a lattice mesh without the grid rule's vertices
+// (TerrainView::SEG4 answers grid meshes) and a robot with segments.
+static unsigned physics_feat(const lg_ctx* c, bool lat_caps) {
+  const TerrainView& T = c->h.ter;
+  const bool tm = T.mesh_type == LG_MESH_TRIMESH, segs = c->h.slide_mask != 0u;
+  unsigned f = c->h.n_sc > 0 ? FEAT_SELF : 0u;
+  if (segs && (T.mesh_type == LG_MESH_HEIGHTFIELD || (tm && T.SEG4))) f |= FEAT_CAPS;      // (a plane has no grid lines; other meshes: spheres alone)
+  if (NJ == 3 && segs && lat_caps && tm && T.L.cell && !T.SEG4) f |= FEAT_LCAPS;
+  return f;
+}
 static_assert(offsetof(lg_ctx, legs) == 0, "lg_dispatch.cpp finds a context's kernel instance in its first four bytes");
 static thread_local std::string g_err;
 
@@ -289,9 +309,6 @@ LG_DEV float lstm_actuator1(const float* __restrict__ W, float x0, float x1, flo
 // wave runs its Gauss-Seidel sweeps (the actuator waves have nothing else to do then); what stays on the critical path
 // in front of the rendezvous is the input part: 2 of 10 columns of layer 0 and 8 of 16 of layer 1, plus the gates.
 struct LstmPre { v4f a0[8], a1[8]; };
-#ifndef LG_LSTM_LDS
-#define LG_LSTM_LDS (LG_AB == 7)     // A/B build 7: the actuator waves read the LSTM weights from LDS instead of through scalar loads
-#endif
 LG_DEV void lstm_recurrent_part(const float* __restrict__ W, const float* h0, const float* h1, LstmPre& pre) {
   const v4f* B0 = (const v4f*)(W + LW_B0); const v4f* H0 = (const v4f*)(W + LW_H0);
   const v4f* B1 = (const v4f*)(W + LW_B1); const v4f* H1 = (const v4f*)(W + LW_H1);
@@ -560,21 +577,12 @@ LG_DEV bool fused_needs_feet_rows(const DevCtx* __restrict__ C);
 // HELPERS: the launch has the three helper waves (every policy step unless LG_SPLIT=0).  A separate instance, so that the kernel the
 // headline runs does not carry the single-wave fallback (the whole LSTM inlined in the main wave, inline leg bias and contact
 // detection): that dead code accounted for most of the register spills the compiler reported for the kernel.
-// SPEC & 3: 1 = TGS + pyramid friction rows fixed at compile time (A/B build 13 only, see physics_substep); 2 = the fused tail in its rollout variant.
+// SPEC & 3: 2 = the fused tail in its rollout variant, 3 = ... and the persistent horizon.  (A compile-time TGS + pyramid instance measured 1.2 % slower: dropped.)
 // SPEC >> 2 = FEAT of physics_substep: bit 0 capsule parts (sliding spheres), bit 1 the self-collision pass, bit 2 capsule segments on a lattice mesh (lg_set_lattice_capsules).  Launches with helper waves pick the
 // instance the model / config needs (launch_physics); the single-wave instances always carry both (FEAT_ALL: a model without sliding spheres or
 // pairs takes the same paths with an empty mask / list), so the kernel of a robot of fixed spheres without self-collision is what it was.
 #define FEAT_ALL 12
-#ifndef LG_LSTM_WARM
-#define LG_LSTM_WARM 1       // helper waves warm the scalar cache with the LSTM weights at kernel entry (0: A/B)
-#endif
-#ifndef LG_CAPS_DEAL
-#define LG_CAPS_DEAL (LG_LEGS == 4)      // the capsule-segment instance deals the contact slots 2 / 1 / 3 / 2 over main / waves 1-3 (0: 3 / 1 / 2 / 2 like the plain instance; A/B)
-#endif
 template <int MODE, bool TMESH, bool HELPERS = false, int SPEC = 0>
-#if LG_AB == 9      // timing probe: cap the kernel at the 256 registers per wave that two workgroups per CU would leave (spills go to scratch)
-__attribute__((amdgpu_num_vgpr(120)))
-#endif
 __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__ C, const float* __restrict__ actions_in, int nsub, int nact,
                                                       const int32_t* __restrict__ ids, int n, int act_stride, int fuse_arg, PostSink sink) {
   // fuse_arg != 0: the launch ends the policy step itself -- through the hand-tuned tail of lg_fused_post.h (four-legged instance: `fuse`), or, for an
@@ -589,15 +597,11 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
   // Triangle-mesh steps: every wave takes one PAIR of slots (one traversal serves two neighbouring spheres).  The feet and the lowest shank spheres
   // (slots 0, 1: always near the ground, never skipped by the distance cache) are the expensive pair: they go to a helper wave -- wave 2, wave 1 has
   // the leg bias as well --, the main wave takes the cheapest pair (6, 7: trunk spheres, skipped by the cache in nearly every substep).  Round 4 had the
-  // main wave on (0, 1): its queries were 76 % of the kernel on config 3 while the helper waves of a PD robot idled (A/B build 31 = that deal).
-#if LG_AB == 31
-#define MESH_PAIR0(wv_) (2 * (wv_))
-#else
+  // main wave on (0, 1): its queries were 76 % of the kernel on config 3 while the helper waves of a PD robot idled.
 #define MESH_PAIR0(wv_) ((wv_) == 0 ? 6 : ((wv_) == 1 ? 2 : ((wv_) == 2 ? 0 : 4)))
-#endif
   // (round 6, capsule-segment instance of the quadruped: 2 / 1 / 3 / 2 -- with a segment slot on it the main wave was the LAST at (A2): per-wave stamps,
   //  profiles/r06_schedule_experiments.txt, r06_phase_stamps_wave{1,2,3}.txt: helper waves 1 / 2 / 3 waited 1.5 / 2.8 / 1.4 k cycles for it there; one plain slot moved to wave 2)
-  constexpr bool CAPS_DEAL = LG_CAPS_DEAL && ((SPEC >> 2) & 1) && !TMESH;
+  constexpr bool CAPS_DEAL = LG_LEGS == 4 && ((SPEC >> 2) & 1) && !TMESH;     // (the six-legged capsule instance keeps the plain deal)
   constexpr int DS0 = CAPS_DEAL ? 2 : 3, DS1 = CAPS_DEAL ? 3 : 4, DS2 = 6;   // main 3 / wave 1 (which also has the leg bias) 1 / 2 / 2: the helpers are the last to arrive at (A2), the main wave has ~3 k cycles of slack there (A/B in one session: 2/2/2/2 +1.4 us, 4/0/2/2 +0.3 us; 1/2/2/3 and 0/2/3/3: worse still; the capsule-segment instance, round 5: 4/0/2/2 +3.5 us, 2/1/2/3 +0.3 us against this deal)
   // Workgroup = 16 envs.  Wave 0 ("main") runs the dynamics, one leg per lane.  With nact == 3 (fused step with the
   // LSTM actuator) waves 1..3 are actuator waves: wave w evaluates joint w-1 of every leg, concurrently with the main
@@ -618,12 +622,7 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
   __shared__ int s_last_f;                                 // fused step: this workgroup is the last of the launch to arrive
   constexpr bool FUSABLE = LG_LEGS == 4;                    // (can_fuse: the fused tail exists for the four-legged instance only; the others keep the LDS)
   __shared__ __attribute__((aligned(16))) float hot[FUSABLE ? ((HC_COUNT + 3) & ~3) : 4];             // fused step: the scalars of the post-physics tail (HC_*)
-  // A/B build 7 only: an LDS copy of the 905 gate-interleaved LSTM weights for the actuator waves (one ds_read_b128 at a wave-uniform
-  // address = four weights).  Measured against the scalar loads (s_load_dwordx16 -> SGPR pairs feeding the packed FMAs) in one session:
-  // 0.0897 ms per step from LDS, 0.0818 ms through SGPRs -- the scalar unit fetches the weights beside the vector ALU, while LDS
-  // reads take issue slots of the wave whose chain of gate evaluations is the critical path in front of rendezvous (A2).
-  constexpr bool LSTM_LDS = !TMESH && LG_LSTM_LDS;
-  __shared__ __attribute__((aligned(16))) float wlds[LSTM_LDS ? LW_COUNT + 3 : 4];
+  // (the LSTM weights stay scalar loads: an LDS copy measured 0.0897 ms per step against 0.0818 -- LDS reads take issue slots of the gate chain in front of (A2))
   // fused ROLLOUT step of an env subset (lg_step_subset rollout_mode = 1, lg_rollout_batch): its own instance (SPEC = 2), so that the
   // full step's tail carries none of the variant's selects (as run-time branches they cost the headline step 1.3 %: A/B in one session)
   // SPEC & 3 == 3: the same tail, and the launch runs sink.nsteps rollout steps of its envs back to back (lg_rollout_batch: one launch per horizon).  A
@@ -692,24 +691,21 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
     pre_act = actions_in[(size_t)krow * act_stride + 3 * l + (wv - 1)];
   }
   fill_leg_model(lmod, C->lmod, threadIdx.x, blockDim.x);
-#if LG_LSTM_WARM
   // (round 6) The scalar cache is invalidated at every launch, and the helper waves' first recurrent half fetches 2 KB of LSTM weights through it in six
   // dependent batches of s_load_dwordx16 -- the main wave waited ~6 k cycles at the first barrier (A) for that.  A helper wave touches every 64-byte line
   // of the weight block now, while its state rows are still on their way from HBM: one round of independent scalar loads, and the recurrent half hits.
-  if (helper_wave && net && !LSTM_LDS) {
+  if (helper_wave && net) {
     float warm = 0.f;
 #pragma unroll
     for (int i = 0; i < LW_COUNT; i += 16) warm += wlstm[i];
     asm volatile("" :: "s"(warm));
   }
-#endif
   if (SC_LDS) for (int i = threadIdx.x; i < C->n_sc; i += blockDim.x) sctab[i] = C->sc_tab[i];      // (first read by the main wave behind (A2) of the first substep)
   if (FUSABLE && fuse && wv == 1) for (int i = lane; i < HC_COUNT; i += 64) hot[i] = C->hot[i];
-  if (LSTM_LDS && MODE == 0 && net && wv >= 2) for (int i = (wv - 2) * 64 + lane; i < LW_COUNT; i += 128) wlds[i] = wlstm[i];
   // With helper waves nobody reads these tables before rendezvous (A) of the first substep (every wave's first use is the kinematics behind it), and
   // every wave has filled its share before it gets there: (A) stands in for a barrier here, and the helper waves start their first recurrent half
   // as soon as their own rows have landed instead of waiting for every wave's (A/B: -0.7 % on the step)
-  if (!(MODE == 0 && HELPERS && !LSTM_LDS)) lds_barrier();
+  if (!(MODE == 0 && HELPERS)) lds_barrier();
 #ifdef LG_STAMPS
   const unsigned long long t_bar0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -754,9 +750,6 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
     P.dt = g.sim_dt; P.grav = v3(g.gravity[0], g.gravity[1], g.gravity[2]); P.iters = g.solver_iterations;
     P.contact_offset = g.contact_offset; P.max_depen = g.max_depenetration_velocity; P.erp = g.erp; P.cfm = g.cfm; P.solver = g.solver_type; P.fric = g.friction_model;
     P.terrain_mu = C->terrain_mu; P.slide_mask = (CAPS || (MCAPS && C->ter.SEG4) || (LCAPS && C->ter.L.cell)) ? C->slide_mask : 0u; P.slot_perm = CAPS ? C->slot_perm : (TMESH ? C->mesh_perm : 0x76543210u); P.cache_reach = TMESH ? C->mesh_reach : 0.f;
-#if LG_AB == 21
-    P.slide_mask = 0u;
-#endif
     const TerrainView T = C->ter;
     if (TMESH && st == 0) mesh_cache_io<true>(C, cqc, e, l, lane, MESH_PAIR0(wv));   // this wave's two slots of the persisted query cache -> LDS
 #ifdef LG_STAMPS
@@ -768,8 +761,7 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
 #endif
     LstmPre lpre;
     if (net) {
-      if (LSTM_LDS) lstm_recurrent_part(wlds, h0, h1, lpre);
-      else { int zero; asm volatile("s_mov_b32 %0, 0" : "=s"(zero)); lstm_recurrent_part(wlstm + zero, h0, h1, lpre); }
+      int zero; asm volatile("s_mov_b32 %0, 0" : "=s"(zero)); lstm_recurrent_part(wlstm + zero, h0, h1, lpre);
     }
 #pragma unroll 1
     for (int sub = 0; sub < nsub; ++sub) {
@@ -824,11 +816,8 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
         const float x0 = (tgt - qq[j]) * g.actuator_in_scale[0], x1 = qdd[j] * g.actuator_in_scale[1];
         // an opaque zero keeps the ~60 weight addresses from being hoisted out of the substep loop as loop invariants
         // (they would fill the SGPR file and spill): inside the loop they fold into the s_load immediate offsets
-        if (LSTM_LDS) xtau[j][lane] = lstm_input_part(wlds, x0, x1, lpre, h0, c0, h1, c1, g.actuator_out_scale);
-        else {
-          int zero; asm volatile("s_mov_b32 %0, 0" : "=s"(zero));
-          xtau[j][lane] = lstm_input_part(wlstm + zero, x0, x1, lpre, h0, c0, h1, c1, g.actuator_out_scale);
-        }
+        int zero; asm volatile("s_mov_b32 %0, 0" : "=s"(zero));
+        xtau[j][lane] = lstm_input_part(wlstm + zero, x0, x1, lpre, h0, c0, h1, c1, g.actuator_out_scale);
       }
       if (!TMESH && wv == 1) { if (DS0 < DS1) { if (CAPS) contact_detect_finish_caps<DS0, DS1P>(lm_, T, P, pb, P.slide_mask, pc1, cst, lane, P.slot_perm); else contact_detect_finish<DS0, DS1P>(lm_, T, P, pb, pr1, cst, lane); } }
       else if (!TMESH && wv == 2) { if (CAPS) contact_detect_finish_caps<DS1, DS2>(lm_, T, P, pb, P.slide_mask, pc2, cst, lane, P.slot_perm); else contact_detect_finish<DS1, DS2>(lm_, T, P, pb, pr2, cst, lane); }
@@ -860,8 +849,7 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
       lds_barrier();                                   // (A3) slot table complete
       STAMP(22);                                       // (diagnostic)
       if (net && sub + 1 < nsub) {                     // while the main wave sweeps: recurrent half of the next substep's network
-        if (LSTM_LDS) lstm_recurrent_part(wlds, h0, h1, lpre);
-        else { int zero; asm volatile("s_mov_b32 %0, 0" : "=s"(zero)); lstm_recurrent_part(wlstm + zero, h0, h1, lpre); }
+        int zero; asm volatile("s_mov_b32 %0, 0" : "=s"(zero)); lstm_recurrent_part(wlstm + zero, h0, h1, lpre);
       }
       STAMP(23);                                       // (diagnostic)
       if (fuse && sub + 1 == nsub) {                   // ... in the last substep: what the post-physics tail needs from HBM
@@ -1009,9 +997,6 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
   P.dt = g.sim_dt; P.grav = v3(g.gravity[0], g.gravity[1], g.gravity[2]); P.iters = g.solver_iterations;
   P.contact_offset = g.contact_offset; P.max_depen = g.max_depenetration_velocity; P.erp = g.erp; P.cfm = g.cfm; P.solver = g.solver_type; P.fric = g.friction_model;
   P.terrain_mu = C->terrain_mu; P.slide_mask = (CAPS || (MCAPS && C->ter.SEG4) || (LCAPS && C->ter.L.cell)) ? C->slide_mask : 0u; P.slot_perm = CAPS ? C->slot_perm : (TMESH ? C->mesh_perm : 0x76543210u); P.cache_reach = TMESH ? C->mesh_reach : 0.f;
-#if LG_AB == 21
-  P.slide_mask = 0u;
-#endif
   const TerrainView T = C->ter;
   const SelfCol scol{C->sc_pairs, (FEAT & 2) ? C->n_sc : 0, SC_LDS ? sctab : C->sc_tab, ((FEAT & 2) && helpers) ? reinterpret_cast<unsigned*>(&xst[0][0]) : nullptr};
   const float mu_robot = pre_mu, madd = pre_madd;
@@ -1089,7 +1074,7 @@ __global__ __launch_bounds__(256) void physics_kernel(const DevCtx* __restrict__
     };
     auto share_fn = [&]() { if (helpers) lds_barrier(); };   // (A3) every wave has finished its slots
     const SlotShare share{helpers ? 4 : 1, helpers ? 3 : 0, helpers};     // set-up order: wave 1, 2, 3, then this wave
-    physics_substep<TMESH, TMESH ? MESH_PAIR0(0) + 100 : DS0, !(MODE == 0 && HELPERS), (SPEC & 3) == 1 ? 1 : 0, FEAT>(m, lm_, T, P, lane, cst, s, tau_fn, prep_fn, share_fn, share, xs, mu_robot, madd,
+    physics_substep<TMESH, TMESH ? MESH_PAIR0(0) + 100 : DS0, !(MODE == 0 && HELPERS), FEAT>(m, lm_, T, P, lane, cst, s, tau_fn, prep_fn, share_fn, share, xs, mu_robot, madd,
                               sub == nsub - 1 ? fbody : nullptr, stamps, (TMESH && helpers) ? cqc : nullptr, scol);
 #ifdef LG_STAMPS
     stamp_t = __builtin_amdgcn_s_memtime();
@@ -1269,7 +1254,7 @@ LG_DEV void write_rigid_body_state(const DevCtx* __restrict__ C, const LegModel&
 template <int MODE, bool TMESH, bool HELP = false>
 __global__ __launch_bounds__(HELP ? 256 : 64) void physics_kernel_chain(const DevCtx* __restrict__ C, const float* __restrict__ actions_in, int nsub, const int32_t* __restrict__ ids, int n, int act_stride,
                                                            int epb) {
-  // epb: envs this workgroup steps (<= EPW; chain_epb).  The kernel is a chain of dependent latencies, one workgroup per CU (86 KB of LDS): a launch of few
+  // epb: envs this workgroup steps (<= EPW; launch_physics).  The kernel is a chain of dependent latencies, one workgroup per CU (86 KB of LDS): a launch of few
   // workgroups leaves CUs idle, so the host deals the envs over up to 256 of them and the lanes past epb groups compute on a copy and store nothing.
   __shared__ __attribute__((aligned(16))) float cst[CH_CST_FLOATS];
   __shared__ float lmod[LM_FIELDS * GRP];
@@ -2709,13 +2694,15 @@ void lg_destroy(lg_ctx* c) {
 
 lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_terrain* ter, int device_id, void* arena) {
   if (const char* why = validate(cfg, model, ter)) { g_err = why; return nullptr; }
+  CtxSwitches sw;
+  if (!read_ctx_switches(sw, g_err)) return nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the env step has no CPU path"; return nullptr; }
   if (device_id < 0 || device_id >= ndev) { g_err = "device_id out of range"; return nullptr; }
   DeviceScope ds_(device_id);                      // (restores the caller's current device on every return path)
   if (!ds_.ok) { g_err = "hipSetDevice failed"; return nullptr; }
   lg_ctx* c = new lg_ctx();
-  c->device = device_id;
+  c->device = device_id; c->sw = sw;
   c->arena_bytes = build_layout(cfg, model, ter, c->t);
   auto fail = [&](const std::string& why) { g_err = why; lg_destroy(c); return (lg_ctx*)nullptr; };
   if (arena) c->arena = arena;
@@ -2735,11 +2722,11 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
   for (int l = 0; l < NLEG; ++l)
     for (int sl = 0; sl < model->cp_count[l]; ++sl)
       if (model->cp_slide[l][sl][0] != 0.f || model->cp_slide[l][sl][1] != 0.f || model->cp_slide[l][sl][2] != 0.f) h.slide_mask |= 1u << sl;
-  if (const char* ev = getenv("LG_CAPS")) { if (atoi(ev) == 0) h.slide_mask = 0u; }      // (diagnostic / A-B: every sphere stays in the middle of its part)
+  if (!c->sw.caps) h.slide_mask = 0u;
   if (ter->mesh_type == LG_MESH_PLANE) h.slide_mask = 0u;       // a plane has no edges: the self-collision instances (which carry the capsule code) skip it at run time (config 5: -2 %)
   // Who detects which slot (capsule instances on a height grid).  A slot with a segment costs about twice a plain one (two edge pieces), an empty slot
   // nothing; the waves take positions 0-2 (main) / 3 (wave 1, which also has the leg bias) / 4-5 / 6-7 -- the quadruped's capsule instance since round 6:
-  // 0-1 / 2 / 3-5 / 6-7 (LG_CAPS_DEAL).  Segment slots go to wave 3's first position, then the main wave's last, then wave 2's; slots no leg has fill up
+  // 0-1 / 2 / 3-5 / 6-7.  Segment slots go to wave 3's first position, then the main wave's last, then wave 2's; slots no leg has fill up
   // behind them (wave 3's second position first); plain slots take what is left in ascending order.  ANYmal-C (foot, three shank spheres of which two carry
   // segments, two thigh-drive spheres, a trunk sphere): {0, 3 | 1 | 4, 5, 6 | 2, -}.  LG_DEAL=0: the identity (A/B).
   {
@@ -2747,7 +2734,7 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
     for (int l = 0; l < NLEG; ++l) max_cp = model->cp_count[l] > max_cp ? model->cp_count[l] : max_cp;
     int at[LG_MAX_CP]; bool used[LG_MAX_CP] = {false};
     for (int p = 0; p < LG_MAX_CP; ++p) at[p] = -1;
-#if LG_CAPS_DEAL      // positions 0-1 main / 2 wave 1 / 3-5 wave 2 / 6-7 wave 3: ANYmal-C {0, 3 | 1 | 4, 5, 6 | 2, -}
+#if LG_LEGS == 4      // positions 0-1 main / 2 wave 1 / 3-5 wave 2 / 6-7 wave 3 (physics_kernel's CAPS_DEAL): ANYmal-C {0, 3 | 1 | 4, 5, 6 | 2, -}
     const int seg_pos[LG_MAX_CP] = {6, 1, 3, 4, 7, 0, 5, 2}, empty_pos[LG_MAX_CP] = {7, 5, 2, 4, 3, 6, 1, 0};
 #else
     const int seg_pos[LG_MAX_CP] = {6, 2, 4, 5, 7, 0, 1, 3}, empty_pos[LG_MAX_CP] = {7, 3, 5, 1, 6, 4, 2, 0};
@@ -2761,10 +2748,7 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
     h.slot_perm = 0u;
     for (int p = 0; p < LG_MAX_CP; ++p) h.slot_perm |= (unsigned)at[p] << (4 * p);
     if (h.slide_mask == 0u) h.slot_perm = 0x76543210u;
-    if (const char* ev = getenv("LG_DEAL")) {            // (A/B: "0" = the identity; eight digits = the slots at positions 0..7)
-      if (strlen(ev) == 8) { h.slot_perm = 0u; for (int p = 0; p < 8; ++p) h.slot_perm |= (unsigned)((ev[p] - '0') & 7) << (4 * p); }
-      else if (atoi(ev) == 0) h.slot_perm = 0x76543210u;
-    }
+    if (c->sw.deal_perm) h.slot_perm = c->sw.deal_perm;
   }
   // Triangle-mesh terrains: every wave answers the closest-point queries of a PAIR of positions per substep, and the step waits for the slowest pair at
   // rendezvous (A2).  LG_MESH_DEAL: eight digits = the slots at positions 0..7 (wave 2 takes positions 0-1, wave 1 2-3, wave 3 4-5, the main wave 6-7: MESH_PAIR0).
@@ -2789,12 +2773,8 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
     h.mesh_perm = 0u;
     for (int i = 0; i < 4; ++i) h.mesh_perm |= (unsigned)rk[i] << (4 * (2 * i)) | (unsigned)rk[4 + i] << (4 * (2 * i + 1));
   }
-  if (const char* ev = getenv("LG_MESH_DEAL")) {
-    if (strlen(ev) == 8) { h.mesh_perm = 0u; for (int p = 0; p < 8; ++p) h.mesh_perm |= (unsigned)((ev[p] - '0') & 7) << (4 * p); }
-    else if (atoi(ev) == 0) h.mesh_perm = 0x76543210u;
-  }
-  h.mesh_reach = LG_MESH_CACHE_REACH;
-  if (const char* ev = getenv("LG_MESH_REACH")) { const float v = (float)atof(ev); if (v >= 0.f && v <= 1.f) h.mesh_reach = v; }
+  if (c->sw.mesh_deal_perm) h.mesh_perm = c->sw.mesh_deal_perm;
+  h.mesh_reach = c->sw.mesh_reach;
   h.n_sc = cfg->self_collisions ? model->num_sc_pairs : 0;
   for (int i = 0; i < h.n_sc; ++i) {
     const int32_t* q = model->sc_pairs[i];
@@ -2836,11 +2816,7 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
   h.ter.H = (const int16_t LG_G*)P(LG_T_HEIGHT_SAMPLES);
   h.ter.L = LatticeView{nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 1.f, 1.f, LATP_CAP};
   h.ter.M = MeshView{nullptr, nullptr}; h.ter.GV = nullptr; h.ter.GV4 = nullptr; h.ter.GM = nullptr; h.ter.mcols = 0; h.ter.SEG4 = nullptr;
-  if (const char* ev = getenv("LG_GRID_MESH")) c->grid_mesh = atoi(ev) != 0;
-  if (const char* ev = getenv("LG_LATTICE_CAPS")) { c->lat_caps_env = atoi(ev) != 0 ? 1 : 0; c->lat_caps = c->lat_caps_env; }   // (lg_set_lattice_capsules; A/B: tools/ab_env_var.sh)
-  bool mesh_caps = true;                                   // LG_MESH_CAPS=0: the spheres alone on grid meshes (A/B, the tests' checker)
-  if (const char* ev = getenv("LG_MESH_CAPS")) mesh_caps = atoi(ev) != 0;
-  if (ter->mesh_type == LG_MESH_TRIMESH && ter->grid_vertices && (c->grid_mesh || mesh_caps)) {      // grid mesh: contact queries by cell index, capsule segments against its edges
+  if (ter->mesh_type == LG_MESH_TRIMESH && ter->grid_vertices && (c->sw.grid_mesh || c->sw.mesh_caps)) {      // grid mesh: contact queries by cell index, capsule segments against its edges
     // vertices as (x, y, z, 0) -- one 16-byte load each --, then the max z of every 2 x 2 block of vertices (the clearance test in closest_point_grid)
     const size_t nvert = (size_t)ter->rows * ter->cols, nv = nvert * 4;
     const int mr = (ter->rows + 1) / 2, mc = (ter->cols + 1) / 2;
@@ -2864,16 +2840,15 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
         hipMemcpy(c->grid_verts, v4.data(), nv * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy((float*)c->grid_verts + nv, top.data(), top.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       return fail("grid-mesh vertex upload failed");
-    if (c->grid_mesh) { h.ter.GV = (const float*)c->grid_verts; h.ter.GV4 = (const float4*)c->grid_verts; h.ter.GM = (const float*)c->grid_verts + nv; h.ter.mcols = mc; }
-    if (mesh_caps && ter->rows <= 65535 && ter->cols <= 32767) h.ter.SEG4 = (const float4*)c->grid_verts;      // (caps_edge_piece's packed indices; larger grids: spheres alone)
+    if (c->sw.grid_mesh) { h.ter.GV = (const float*)c->grid_verts; h.ter.GV4 = (const float4*)c->grid_verts; h.ter.GM = (const float*)c->grid_verts + nv; h.ter.mcols = mc; }
+    if (c->sw.mesh_caps && ter->rows <= 65535 && ter->cols <= 32767) h.ter.SEG4 = (const float4*)c->grid_verts;      // (caps_edge_piece's packed indices; larger grids: spheres alone)
   }
   if (ter->mesh_type == LG_MESH_TRIMESH) {
     if (ter->collision_mesh->device != device_id) return fail("collision mesh lives on another device");
     h.ter.M = MeshView{ter->collision_mesh->d_nodes, ter->collision_mesh->d_tris};
     if (const lg_mesh* cm = ter->collision_mesh; cm->d_gcz && cm->d_gcr && !h.ter.GV)      // a lattice mesh: contact queries by cell (closest_point_lattice)
     {
-      int cap = LATP_CAP;                                  // LG_LATTICE_CAP: a smaller query table (never below the longest run of faces: a run must fit an empty table)
-      if (const char* ev = getenv("LG_LATTICE_CAP")) cap = std::min(LATP_CAP, std::max(atoi(ev), std::max(cm->gmaxrun, 1)));
+      const int cap = std::min(LATP_CAP, std::max(c->sw.lattice_cap, std::max(cm->gmaxrun, 1)));     // LG_LATTICE_CAP: never below the longest run of faces (a run must fit an empty table)
       h.ter.L = LatticeView{cm->d_gcz, cm->d_gcr, cm->d_gtris, cm->gnx, cm->gny, cm->gx0, cm->gy0, cm->ghx, cm->ghy, cap};
     }
     for (int k = 0; k < 3; ++k) { h.mesh_lo[k] = ter->collision_mesh->bmin[k]; h.mesh_hi[k] = ter->collision_mesh->bmax[k]; }
@@ -2943,11 +2918,7 @@ lg_ctx* lg_create(const lg_config* cfg, const lg_robot_model* model, const lg_te
   if (hipMalloc((void**)&c->d, sizeof(DevCtx)) != hipSuccess) return fail("hipMalloc(ctx) failed");
   if (hipMemcpy(c->d, &h, sizeof(DevCtx), hipMemcpyHostToDevice) != hipSuccess) return fail("copy ctx failed");
   if (hipDeviceSynchronize() != hipSuccess) return fail("device sync failed");
-  if (const char* ev = getenv("LG_SPLIT")) c->split = atoi(ev) != 0;
-  if (const char* ev = getenv("LG_FUSE")) c->fuse = atoi(ev) != 0;
-  if (const char* ev = getenv("LG_PERSIST")) c->persist = atoi(ev) != 0;
-  if (const char* ev = getenv("LG_GFUSE")) c->gfuse = atoi(ev) != 0;
-  if (const char* ev = getenv("LG_SPEC")) c->spec = atoi(ev) != 0;
+  c->feat = physics_feat(c, c->sw.lat_caps_env == 1);
   return c;
 }
 
@@ -2988,85 +2959,135 @@ static int launch_post(lg_ctx* c, hipStream_t st, hipEvent_t* ev, const int32_t*
 
 // fuse: the post-physics step runs as the tail of the physics kernel (full steps of all envs with helper waves; LG_FUSE=0 keeps
 // the two-launch path, which every split / subset / rollout entry point uses anyway)
-static bool can_fuse(const lg_ctx* c) { return LG_LEGS == 4 && c->fuse && !c->h.extra_term && !c->h.cfg.keep_small_commands && !c->h.cfg.feet_air_time_ungated && (c->split || c->h.ter.mesh_type == LG_MESH_TRIMESH) && c->h.P <= MAX_P; }
+static bool can_fuse(const lg_ctx* c) { return LG_LEGS == 4 && c->sw.fuse && !c->h.extra_term && !c->h.cfg.keep_small_commands && !c->h.cfg.feet_air_time_ungated && (c->sw.split || c->h.ter.mesh_type == LG_MESH_TRIMESH) && c->h.P <= MAX_P; }
 // The six-legged instance can end lg_step / lg_step_transition in the physics launch too, through the post kernel's own code (generic_fused_tail): OFF unless
 // LG_GFUSE=1.  Measured (round 5, 4096 envs, same session): 0.159 / 0.162 ms in one launch against 0.158 / 0.153 ms in two -- the post-physics chain is latency-bound,
 // and on one wave per SIMD it takes as long as the separate kernel (eight workgroups per CU) plus its launch gap; round 1 found the same for the quadruped.  The
 // path stays as the bit-exact checker of a future hand-tuned tail (tests/test_elspider.py).
-static bool can_gfuse(const lg_ctx* c) { return LG_LEGS == 6 && NJ == 3 && c->gfuse && c->fuse && c->split && c->h.ter.mesh_type != LG_MESH_TRIMESH && !c->h.cfg.inject_sim_state; }
-// fuse: 0 = physics only (a post kernel follows), 1 = full policy step with the fused tail, 2 = fused ROLLOUT step of the listed envs, 3 = sink.nsteps of them in one launch
-// envs per workgroup of the chain instance's physics kernel: EPW, halved while the launch would have fewer workgroups than the chip has CUs (LG_CHAIN_EPB sets it)
-static int chain_epb(int n) {
-  int epb = EPW;
-  while (epb > 4 && (n + epb - 1) / epb < 256) epb >>= 1;
-  if (const char* ev = getenv("LG_CHAIN_EPB")) { const int v = atoi(ev); if (v >= 1 && v <= EPW) epb = v; }
-  return epb;
+static bool can_gfuse(const lg_ctx* c) { return LG_LEGS == 6 && NJ == 3 && c->sw.gfuse && c->sw.fuse && c->sw.split && c->h.ter.mesh_type != LG_MESH_TRIMESH && !c->h.cfg.inject_sim_state; }
+
+// How a step request runs (physics_kernel's fuse argument): 0 = physics, then post_kernel; 1 = full policy step with the fused tail; 2 = fused ROLLOUT step of
+// the listed envs; 3 = a whole horizon of them in one launch.  full: a step of all envs (lg_step, lg_step_transition); otherwise an env subset, `rollout`: its
+// rollout step, `horizon`: steps this request runs back to back.
+enum { STEP_TWO_LAUNCH = 0, STEP_FUSED = 1, STEP_FUSED_ROLLOUT = 2, STEP_PERSIST = 3 };
+static int step_shape(const lg_ctx* c, bool full, bool rollout, int horizon) {
+  if (full) return can_fuse(c) || can_gfuse(c) ? STEP_FUSED : STEP_TWO_LAUNCH;
+  if (!rollout || !can_fuse(c)) return STEP_TWO_LAUNCH;
+  // One launch for the whole horizon (round 5): the workgroup that owns an env keeps its state on chip from step to step.  Not with the clock-driven gait
+  // term (lg_config.gait_enabled: the two forms are not compared with it; the env class goes step by step anyway), not on mesh terrains (no persistent
+  // instance), LG_PERSIST=0 = the A/B switch.
+  return horizon > 1 && c->sw.persist && !c->h.cfg.gait_enabled && c->h.ter.mesh_type != LG_MESH_TRIMESH ? STEP_PERSIST : STEP_FUSED_ROLLOUT;
 }
-// capsule segments against a lattice mesh's edges (FEAT bit 2): switched on, a lattice mesh without the grid rule's vertices (TerrainView::SEG4 answers grid meshes), a robot with segments
-static bool lattice_caps_on(const lg_ctx* c) {
-  return NJ == 3 && c->lat_caps && c->h.ter.mesh_type == LG_MESH_TRIMESH && c->h.ter.L.cell && !c->h.ter.SEG4 && c->h.slide_mask != 0u;
+
+// ------------------------------------------------------------------------------------------------ physics kernel instances
+// Every instance of the physics kernel this library launches, in the order the device compiler emits them, and the one place that picks among them.
+struct PhysicsKey { int mode; bool tmesh, helpers; int spec;
+                    bool operator==(const PhysicsKey& o) const { return mode == o.mode && tmesh == o.tmesh && helpers == o.helpers && spec == o.spec; } };
+#if NJ == 3
+using PhysicsFn = void (*)(const DevCtx*, const float*, int, int, const int32_t*, int, int, int, PostSink);
+#define LG_PK(MODE, TM, HELP, SPEC) {{MODE, TM, HELP, SPEC}, (HELP) ? 256 : 64, physics_kernel<MODE, TM, HELP, SPEC>}
+#else
+using PhysicsFn = void (*)(const DevCtx*, const float*, int, const int32_t*, int, int, int);
+#define LG_PK(MODE, TM, HELP) {{MODE, TM, HELP, 0}, (HELP) ? 256 : 64, physics_kernel_chain<MODE, TM, HELP>}
+#endif
+struct PhysicsInstance { PhysicsKey key; int threads; PhysicsFn fn; };
+static const PhysicsInstance physics_instances[] = {
+#if NJ == 3
+#if LG_LEGS == 4
+  // the persistent horizon (height grids and planes), then the fused rollout step
+  LG_PK(0, false, true, 3 + 12), LG_PK(0, false, true, 3 + 4), LG_PK(0, false, true, 3),
+  LG_PK(0, true, true, 2 + 24), LG_PK(0, true, true, 2 + 16), LG_PK(0, true, true, 2 + 12), LG_PK(0, true, true, 2 + 8), LG_PK(0, true, true, 2 + 4), LG_PK(0, true, true, 2),
+  LG_PK(0, false, true, 2 + 12), LG_PK(0, false, true, 2 + 4), LG_PK(0, false, true, 2),
+#endif
+  // policy steps (fused or not): triangle meshes, height grids and planes with helper waves, the single-wave launch
+  LG_PK(0, true, true, 24), LG_PK(0, true, true, 16), LG_PK(0, true, true, 12), LG_PK(0, true, true, 8), LG_PK(0, true, true, 4), LG_PK(0, true, true, 0),
+  LG_PK(0, false, true, 12), LG_PK(0, false, true, 4), LG_PK(0, false, true, 0), LG_PK(0, false, false, FEAT_ALL),
+  LG_PK(2, false, false, 0),                                                                               // lg_compute_torques
+  LG_PK(1, true, false, FEAT_ALL + 16), LG_PK(1, true, false, FEAT_ALL), LG_PK(1, false, false, FEAT_ALL),   // lg_simulate
+#else
+  LG_PK(0, true, true), LG_PK(0, false, true), LG_PK(0, true, false), LG_PK(0, false, false),
+  LG_PK(2, false, false),
+  LG_PK(1, true, false), LG_PK(1, false, false),
+#endif
+};
+#undef LG_PK
+
+// The instance a launch needs.  mode: 0 policy step, 1 lg_simulate, 2 lg_compute_torques; fuse: step_shape; helpers: the launch has helper waves; feat: FEAT_*.
+// physics_kernel's SPEC = FEAT << 2 | the rollout tail (2, 3).  With helper waves a triangle mesh gets the features it needs; on a height grid or a plane the
+// self-collision instance carries the capsule code too, and a robot of fixed spheres without self-collision runs the plain instance.  The single-wave
+// instances carry both (FEAT_ALL), plus the lattice segments when they are on.  The chain instances have no features or tails of their own.
+static PhysicsKey physics_key(int mode, int fuse, bool tm, bool helpers, unsigned feat) {
+  if (mode == 2) return {2, false, false, 0};
+  if (NJ != 3) return {mode, tm, helpers, 0};
+  unsigned f;
+  if (mode == 1 || !helpers) f = FEAT_CAPS | FEAT_SELF | (feat & FEAT_LCAPS);
+  else if (tm) f = feat;
+  else f = (feat & FEAT_SELF) ? FEAT_CAPS | FEAT_SELF : feat & FEAT_CAPS;
+  return {mode, tm, helpers, (int)(f << 2) | (fuse >= STEP_FUSED_ROLLOUT ? fuse : 0)};
 }
-static void launch_physics(lg_ctx* c, hipStream_t st, const float* actions, const int32_t* ids, int n, int act_stride = NDOF, int fuse = 0,
-                           PostSink sink = PostSink{nullptr, nullptr, nullptr, nullptr, 0.f}) {
+// launches the instance of key k; a key without one is an error, never a different instance
+extern "C++" template <class... A>      // (inside the ABI's extern "C" block)
+static int launch_instance(lg_ctx* c, hipStream_t st, const PhysicsKey& k, int nb, A... args) {
+  for (const PhysicsInstance& p : physics_instances)
+    if (p.key == k) { hipLaunchKernelGGL(p.fn, dim3(nb), dim3(p.threads), 0, st, args...); return LG_OK; }
+  c->err = "no physics kernel instance for <" + std::to_string(k.mode) + ", " + std::to_string(k.tmesh) + ", " + std::to_string(k.helpers) + ", " + std::to_string(k.spec) + ">";
+  return LG_ERR_UNSUPPORTED;
+}
+
+static int launch_physics(lg_ctx* c, hipStream_t st, const float* actions, const int32_t* ids, int n, int act_stride = NDOF, int fuse = STEP_TWO_LAUNCH,
+                          PostSink sink = PostSink{nullptr, nullptr, nullptr, nullptr, 0.f}) {
+  const bool tm = c->h.ter.mesh_type == LG_MESH_TRIMESH;
 #if NJ != 3
   (void)fuse; (void)sink;
-  const int epb = chain_epb(n), nb = (n + epb - 1) / epb;
+  int epb = EPW;         // envs per workgroup: EPW, halved while the launch would have fewer workgroups than the chip has CUs (LG_CHAIN_EPB sets it)
+  while (epb > 4 && (n + epb - 1) / epb < 256) epb >>= 1;
+  if (!lg_switch_int("LG_CHAIN_EPB", 1, EPW, epb, c->err)) return LG_ERR_INVALID;
+  const int nb = (n + epb - 1) / epb;
   if (n != c->h.n_stepped) { c->h.n_stepped = n; hipLaunchKernelGGL(set_n_stepped, dim3(1), dim3(1), 0, st, c->d, n); }
   // (helper waves for the contact detection: LG_SPLIT=0 keeps the single-wave launch, the checker of that path)
-  if (c->split) {
-    if (c->h.ter.mesh_type == LG_MESH_TRIMESH) hipLaunchKernelGGL((physics_kernel_chain<0, true, true>), dim3(nb), dim3(256), 0, st, c->d, actions, c->h.cfg.decimation, ids, n, act_stride, epb);
-    else hipLaunchKernelGGL((physics_kernel_chain<0, false, true>), dim3(nb), dim3(256), 0, st, c->d, actions, c->h.cfg.decimation, ids, n, act_stride, epb);
-  } else if (c->h.ter.mesh_type == LG_MESH_TRIMESH) hipLaunchKernelGGL((physics_kernel_chain<0, true>), dim3(nb), dim3(64), 0, st, c->d, actions, c->h.cfg.decimation, ids, n, act_stride, epb);
-  else hipLaunchKernelGGL((physics_kernel_chain<0, false>), dim3(nb), dim3(64), 0, st, c->d, actions, c->h.cfg.decimation, ids, n, act_stride, epb);
-  return;
+  return launch_instance(c, st, physics_key(0, 0, tm, c->sw.split, 0u), nb, c->d, actions, c->h.cfg.decimation, ids, n, act_stride, epb);
 #else
   const int nb = (n + EPB - 1) / EPB;
   // helper waves (leg bias, contact detection, a share of the contact set-up; with the actuator network also its three
   // joints per leg): always, unless LG_SPLIT=0 (diagnostic) -- and even then on triangle-mesh terrains, whose contact
   // detection is a BVH traversal per collision sphere that should not sit on the main wave.  PD-controlled robots gain
   // as well: the main wave alone took 0.134 ms per rollout step of 4096 envs on the plane
-  const int nact = (c->split || c->h.ter.mesh_type == LG_MESH_TRIMESH) ? 3 : 0;
+  const int nact = (c->sw.split || tm) ? 3 : 0;
   if (n != c->h.n_stepped) { c->h.n_stepped = n; hipLaunchKernelGGL(set_n_stepped, dim3(1), dim3(1), 0, st, c->d, n); }
-  // Which instance (physics_kernel's SPEC): rollout tail or not, and the model features the launch needs -- capsule segments (height grids against their grid lines, grid meshes against their own edges; other meshes and planes: spheres alone)
-  // and the self-collision pass.  A robot of fixed spheres without self-collision runs
-  // the plain instance.
-  const bool tm = c->h.ter.mesh_type == LG_MESH_TRIMESH;
-  const bool caps = c->h.ter.mesh_type == LG_MESH_HEIGHTFIELD && c->h.slide_mask != 0u, selfc = c->h.n_sc > 0;       // (a plane has no grid lines: the plain instance)
-  const bool mcaps = tm && c->h.ter.SEG4 && c->h.slide_mask != 0u;      // grid meshes: the segments against the mesh's edges (other meshes: spheres alone)
-  const bool lcaps = lattice_caps_on(c);                              // lattice meshes, when switched on (lg_set_lattice_capsules): the segments against the lattice's edges
-#define LG_LAUNCH_PK(TM, HELP, SPEC_, THREADS) \
-  hipLaunchKernelGGL((physics_kernel<0, TM, HELP, SPEC_>), dim3(nb), dim3(THREADS), 0, st, c->d, actions, c->h.cfg.decimation, nact, ids, n, act_stride, fuse, sink)
-#if LG_LEGS == 4
-  if (fuse == 3 && !tm) {                                // persistent rollout launch: sink.nsteps steps (heightfield / plane terrains; mesh terrains go step by step)
-    if (selfc) LG_LAUNCH_PK(false, true, 3 + 12, 256);
-    else if (caps) LG_LAUNCH_PK(false, true, 3 + 4, 256);
-    else LG_LAUNCH_PK(false, true, 3, 256);
-    return;
+  return launch_instance(c, st, physics_key(0, fuse, tm, nact == 3, c->feat), nb, c->d, actions, c->h.cfg.decimation, nact, ids, n, act_stride, fuse, sink);
+#endif
+}
+
+// lg_compute_torques (mode 2: the torques of `actions`) and lg_simulate (mode 1: one dt with the torques of LG_T_TORQUES): every env, single-wave instances
+static int launch_all_envs(lg_ctx* c, hipStream_t st, int mode, const float* actions) {
+  const int nb = (c->h.N + EPB - 1) / EPB, nsub = mode == 1 ? 1 : 0;
+  const PhysicsKey k = physics_key(mode, STEP_TWO_LAUNCH, c->h.ter.mesh_type == LG_MESH_TRIMESH, false, c->feat);
+#if NJ != 3
+  const int rc = launch_instance(c, st, k, nb, c->d, actions, nsub, (const int32_t*)nullptr, c->h.N, NDOF, EPW);
+#else
+  const int rc = launch_instance(c, st, k, nb, c->d, actions, nsub, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
+#endif
+  if (rc != LG_OK) return rc;
+  HIP_TRY(c, hipGetLastError());
+  return LG_OK;
+}
+
+// One step request in the shape step_shape chose: the physics launch, then -- unless its tail ended the step -- the post kernel.  k: the fused tail's sink; the
+// two-launch path hands its reward column (rew_out, rew_stride) to post_kernel as arguments of their own.  ev: lg_step's profiling events.
+static int launch_step(lg_ctx* c, hipStream_t st, int shape, const float* actions, const int32_t* ids, int n, int act_stride, int post_mode, PostSink k,
+                       hipEvent_t* ev = nullptr) {
+  if (ev) (void)hipEventRecord(ev[0], st);
+  int rc = launch_physics(c, st, actions, ids, n, act_stride, shape, shape != STEP_TWO_LAUNCH ? k : PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
+  if (rc != LG_OK) return rc;
+  if (ev) (void)hipEventRecord(ev[1], st);
+  if (shape != STEP_TWO_LAUNCH) {
+    if (ev) { (void)hipEventRecord(ev[2], st); (void)hipEventRecord(ev[3], st); }
+    HIP_TRY(c, hipGetLastError());
+    return LG_OK;
   }
-  if (fuse == 2) {                                       // (can_fuse() held: helper waves are present)
-    if (lcaps) { if (selfc) LG_LAUNCH_PK(true, true, 2 + 8 + 16, 256); else LG_LAUNCH_PK(true, true, 2 + 16, 256); }
-    else if (tm) { if (selfc) { if (mcaps) LG_LAUNCH_PK(true, true, 2 + 12, 256); else LG_LAUNCH_PK(true, true, 2 + 8, 256); } else if (mcaps) LG_LAUNCH_PK(true, true, 2 + 4, 256); else LG_LAUNCH_PK(true, true, 2, 256); }
-    else if (selfc) LG_LAUNCH_PK(false, true, 2 + 12, 256);
-    else if (caps) LG_LAUNCH_PK(false, true, 2 + 4, 256);
-    else LG_LAUNCH_PK(false, true, 2, 256);
-    return;
-  }
-#endif
-  if (lcaps) { if (selfc) LG_LAUNCH_PK(true, true, 8 + 16, 256); else LG_LAUNCH_PK(true, true, 16, 256); }
-  else if (tm) { if (selfc) { if (mcaps) LG_LAUNCH_PK(true, true, 12, 256); else LG_LAUNCH_PK(true, true, 8, 256); } else if (mcaps) LG_LAUNCH_PK(true, true, 4, 256); else LG_LAUNCH_PK(true, true, 0, 256); }
-  else
-#if LG_AB == 13
-    if (nact == 3 && c->h.cfg.solver_type == LG_SOLVER_TGS && c->h.cfg.friction_model == LG_FRICTION_PYRAMID && c->spec && !caps && !selfc)
-      LG_LAUNCH_PK(false, true, 1, 256);
-    else
-#endif
-    if (nact == 3) {
-      if (selfc) LG_LAUNCH_PK(false, true, 12, 256);
-      else if (caps) LG_LAUNCH_PK(false, true, 4, 256);
-      else LG_LAUNCH_PK(false, true, 0, 256);
-    } else LG_LAUNCH_PK(false, false, FEAT_ALL, 64);
-#undef LG_LAUNCH_PK
-#endif
+  float* rew_out = k.rew_out; const int rew_stride = k.rew_stride;
+  k.rew_out = nullptr; k.rew_stride = 0;
+  return launch_post(c, st, ev, ids, n, post_mode, rew_out, rew_stride, k);
 }
 
 int lg_step(lg_ctx* c, const float* actions, void* stream) {
@@ -3079,16 +3100,7 @@ int lg_step(lg_ctx* c, const float* actions, void* stream) {
     if (c->prof_n < c->prof_max && (c->prof_calls % c->prof_stride) == 0) ev = &c->ev[(size_t)4 * c->prof_n++];
     c->prof_calls++;
   }
-  if (ev) (void)hipEventRecord(ev[0], st);
-  const bool fuse = can_fuse(c) || can_gfuse(c);
-  launch_physics(c, st, actions, nullptr, c->h.N, NDOF, fuse ? 1 : 0);
-  if (ev) (void)hipEventRecord(ev[1], st);
-  if (fuse) {                                            // one launch per policy step
-    if (ev) { (void)hipEventRecord(ev[2], st); (void)hipEventRecord(ev[3], st); }
-    HIP_TRY(c, hipGetLastError());
-    return LG_OK;
-  }
-  return launch_post(c, st, ev, nullptr, c->h.N, 0);
+  return launch_step(c, st, step_shape(c, true, false, 1), actions, nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f}, ev);
 }
 
 // lg_step whose post-physics kernel also fills one transition of a rollout storage (see PostSink): what
@@ -3098,29 +3110,15 @@ int lg_step_transition(lg_ctx* c, const float* actions, float* next_observations
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);
   if (!actions || !values || !rewards || !dones) { c->err = "lg_step_transition: null row"; return LG_ERR_INVALID; }
-  hipStream_t st = (hipStream_t)stream;
-  const PostSink sink{next_observations, values, rewards, dones, gamma};
-  if (can_fuse(c) || can_gfuse(c)) {
-    launch_physics(c, st, actions, nullptr, c->h.N, NDOF, 1, sink);
-    HIP_TRY(c, hipGetLastError());
-    return LG_OK;
-  }
-  launch_physics(c, st, actions, nullptr, c->h.N);
-  return launch_post(c, st, nullptr, nullptr, c->h.N, 0, nullptr, 0, sink);
+  return launch_step(c, (hipStream_t)stream, step_shape(c, true, false, 1), actions, nullptr, c->h.N, NDOF, 0, PostSink{next_observations, values, rewards, dones, gamma});
 }
 
 int lg_step_subset(lg_ctx* c, const float* actions, const int32_t* env_ids, int32_t n, int32_t rollout_mode, void* stream) {
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);
   if (!actions || !env_ids || n <= 0 || n > c->h.N) { c->err = "bad subset step arguments"; return LG_ERR_INVALID; }
-  hipStream_t st = (hipStream_t)stream;
-  if (rollout_mode && can_fuse(c)) {                     // rollout steps end inside the physics kernel as well (LG_FUSE=0: two launches)
-    launch_physics(c, st, actions, env_ids, n, NDOF, 2);
-    HIP_TRY(c, hipGetLastError());
-    return LG_OK;
-  }
-  launch_physics(c, st, actions, env_ids, n);
-  return launch_post(c, st, nullptr, env_ids, n, rollout_mode ? 1 : 0);
+  return launch_step(c, (hipStream_t)stream, step_shape(c, false, rollout_mode, 1), actions, env_ids, n, NDOF, rollout_mode ? 1 : 0,
+                     PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
 }
 
 int lg_set_reward_terms(lg_ctx* c, int32_t num_terms, const int32_t* term_ids, const float* scales, void* stream) {
@@ -3151,7 +3149,7 @@ int lg_set_lattice_capsules(lg_ctx* c, int32_t on) {
     c->err = "lg_set_lattice_capsules: the terrain is not a lattice mesh (a plane, a height grid, or a triangle mesh whose contact queries walk the BVH)"; return LG_ERR_INVALID;
   }
   // (a grid mesh: its segments run against its own edges already -- TerrainView::SEG4 --, a robot without sliding spheres has none: accepted, nothing changes)
-  c->lat_caps = c->lat_caps_env >= 0 ? c->lat_caps_env : (on != 0);      // LG_LATTICE_CAPS, when set, overrides the switch (same-session A/B)
+  c->feat = physics_feat(c, c->sw.lat_caps_env >= 0 ? c->sw.lat_caps_env : on != 0);      // LG_LATTICE_CAPS, when set, overrides the switch (same-session A/B)
   return LG_OK;
 }
 
@@ -3170,7 +3168,8 @@ int lg_step_subset_physics(lg_ctx* c, const float* actions, const int32_t* env_i
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);
   if (!actions || !env_ids || n <= 0 || n > c->h.N) { c->err = "bad subset step arguments"; return LG_ERR_INVALID; }
-  launch_physics(c, (hipStream_t)stream, actions, env_ids, n);
+  const int rc = launch_physics(c, (hipStream_t)stream, actions, env_ids, n);
+  if (rc != LG_OK) return rc;
   HIP_TRY(c, hipGetLastError());
   return LG_OK;
 }
@@ -3186,7 +3185,8 @@ int lg_step_physics(lg_ctx* c, const float* actions, void* stream) {
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);
   if (!actions) { c->err = "actions is null"; return LG_ERR_INVALID; }
-  launch_physics(c, (hipStream_t)stream, actions, nullptr, c->h.N);
+  const int rc = launch_physics(c, (hipStream_t)stream, actions, nullptr, c->h.N);
+  if (rc != LG_OK) return rc;
   HIP_TRY(c, hipGetLastError());
   return LG_OK;
 }
@@ -3277,24 +3277,12 @@ int lg_rollout_batch(lg_ctx* c, const float* all_us, int32_t horizon, const int3
   hipStream_t st = (hipStream_t)stream;
   int rc = lg_sync_main_to_rollout(c, rollouts_per_main, pos_drift, stream);
   if (rc != LG_OK) return rc;
-  const bool fuse = can_fuse(c);
-  // One launch for the whole horizon (round 5): the workgroup that owns an env keeps its state on chip from step to step.  Not with the clock-driven gait
-  // term (lg_config.gait_enabled: the two forms are not compared with it; the env class goes step by step anyway), not on mesh terrains (no persistent
-  // instance), LG_PERSIST=0 = the A/B switch.
-  if (fuse && horizon > 1 && c->persist && !c->h.cfg.gait_enabled && c->h.ter.mesh_type != LG_MESH_TRIMESH) {
-    PostSink sk{nullptr, nullptr, nullptr, nullptr, 0.f, rewards, horizon};
-    sk.nsteps = horizon;
-    launch_physics(c, st, all_us, env_ids, n, horizon * NDOF, 3, sk);
-    HIP_TRY(c, hipGetLastError());
-    return lg_sync_main_to_rollout(c, rollouts_per_main, pos_drift, stream);
-  }
-  for (int i = 0; i < horizon; ++i) {
-    if (fuse) {                                          // one launch per rollout step: the reward column is written by the kernel's tail
-      launch_physics(c, st, all_us + (size_t)i * NDOF, env_ids, n, horizon * NDOF, 2, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f, rewards + i, horizon});
-      continue;
-    }
-    launch_physics(c, st, all_us + (size_t)i * NDOF, env_ids, n, horizon * NDOF);
-    rc = launch_post(c, st, nullptr, env_ids, n, 1, rewards + i, horizon);
+  // one launch per rollout step (the reward column i is written by the kernel's tail, or by post_kernel), or one for the whole horizon (sink.nsteps)
+  const int shape = step_shape(c, false, true, horizon);
+  for (int i = 0; i < (shape == STEP_PERSIST ? 1 : horizon); ++i) {
+    PostSink sk{nullptr, nullptr, nullptr, nullptr, 0.f, rewards + i, horizon};
+    if (shape == STEP_PERSIST) sk.nsteps = horizon;
+    rc = launch_step(c, st, shape, all_us + (size_t)i * NDOF, env_ids, n, horizon * NDOF, 1, sk);
     if (rc != LG_OK) return rc;
   }
   HIP_TRY(c, hipGetLastError());
@@ -3308,11 +3296,8 @@ int lg_step_subset_rows(lg_ctx* c, const float* actions, const int32_t* env_ids,
   DeviceScope ds_(c->device);
   if (!actions || !env_ids || n <= 0 || n > c->h.N) { c->err = "bad subset step arguments"; return LG_ERR_INVALID; }
   if (!obs_out || !rew_out || !reset_out || !time_out_out) { c->err = "lg_step_subset_rows: null output row"; return LG_ERR_INVALID; }
-  if (rollout_mode && can_fuse(c)) {                     // the rows leave the tail of the one launch of a rollout step
-    launch_physics(c, (hipStream_t)stream, actions, env_ids, n, NDOF, 2, PostSink{obs_out, nullptr, nullptr, nullptr, 0.f, rew_out, 1, reset_out, time_out_out, 1});
-    HIP_TRY(c, hipGetLastError());
-    return LG_OK;
-  }
+  if (const int shape = step_shape(c, false, rollout_mode, 1))         // the rows leave the tail of the one launch of a rollout step
+    return launch_step(c, (hipStream_t)stream, shape, actions, env_ids, n, NDOF, 1, PostSink{obs_out, nullptr, nullptr, nullptr, 0.f, rew_out, 1, reset_out, time_out_out, 1});
   const int rc = lg_step_subset(c, actions, env_ids, n, rollout_mode, stream);
   return rc != LG_OK ? rc : lg_gather_step_rows(c, env_ids, n, obs_out, rew_out, reset_out, time_out_out, stream);
 }
@@ -3383,33 +3368,13 @@ int lg_profile_end(lg_ctx* c, float mean_ms[3], int32_t* nsamples) {
 int lg_compute_torques(lg_ctx* c, const float* actions, void* stream) {
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);
-  const int nb = (c->h.N + EPB - 1) / EPB;
-#if NJ != 3
-  hipLaunchKernelGGL((physics_kernel_chain<2, false>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, actions, 0, (const int32_t*)nullptr, c->h.N, NDOF, EPW);
-#else
-  hipLaunchKernelGGL((physics_kernel<2, false>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, actions, 0, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
-#endif
-  HIP_TRY(c, hipGetLastError());
-  return LG_OK;
+  return launch_all_envs(c, (hipStream_t)stream, 2, actions);
 }
 
 int lg_simulate(lg_ctx* c, void* stream) {
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);
-  const int nb = (c->h.N + EPB - 1) / EPB;
-#if NJ != 3
-  if (c->h.ter.mesh_type == LG_MESH_TRIMESH) hipLaunchKernelGGL((physics_kernel_chain<1, true>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, (const int32_t*)nullptr, c->h.N, NDOF, EPW);
-  else hipLaunchKernelGGL((physics_kernel_chain<1, false>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, (const int32_t*)nullptr, c->h.N, NDOF, EPW);
-#else
-  if (lattice_caps_on(c))
-    hipLaunchKernelGGL((physics_kernel<1, true, false, FEAT_ALL + 16>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
-  else if (c->h.ter.mesh_type == LG_MESH_TRIMESH)
-    hipLaunchKernelGGL((physics_kernel<1, true, false, FEAT_ALL>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
-  else
-    hipLaunchKernelGGL((physics_kernel<1, false, false, FEAT_ALL>), dim3(nb), dim3(64), 0, (hipStream_t)stream, c->d, (const float*)nullptr, 1, 0, (const int32_t*)nullptr, c->h.N, NDOF, 0, PostSink{nullptr, nullptr, nullptr, nullptr, 0.f});
-#endif
-  HIP_TRY(c, hipGetLastError());
-  return LG_OK;
+  return launch_all_envs(c, (hipStream_t)stream, 1, nullptr);
 }
 
 int lg_post_physics_step(lg_ctx* c, void* stream) {
