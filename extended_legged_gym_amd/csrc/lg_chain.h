@@ -4,10 +4,10 @@
 //
 // Same model and the same solver as the tuned three-joint kernels of lg_physics.h -- floating base replicated on the lanes of an env's group, one leg per
 // lane, legs coupled through the 6x6 base Schur complement reduced with DPP adds; composite-rigid-body mass matrix + recursive Newton-Euler bias; sphere
-// (+ capsule-segment edge) contacts against plane / height grid / grid mesh; TGS or PGS over contact, self-collision and joint-limit rows with pyramid or
-// cone friction -- written once over NJ in plain loops: a leg's joint block Mkk is NJ x NJ (packed, inverted through its Cholesky factor), every
-// "three" of lg_physics.h is a loop bound.  One wave per workgroup, no helper waves, no fused tail: this instance is about coverage, its
-// step is physics_kernel_chain + post_kernel.  The oracle (run-time joint count) is the checker, as for the others.
+// (+ capsule-segment edge) contacts against plane / height grid / any triangle mesh (the grid mesh's cells or the BVH walk: CH_MESH_* below); TGS or PGS
+// over contact, self-collision and joint-limit rows with pyramid or cone friction -- written once over NJ in plain loops: a leg's joint block Mkk is NJ x NJ
+// (packed, inverted through its Cholesky factor), every "three" of lg_physics.h is a loop bound.  One wave per workgroup, no helper waves, no fused tail:
+// this instance is about coverage, its step is physics_kernel_chain + post_kernel.  The oracle (run-time joint count) is the checker, as for the others.
 #pragma once
 static_assert(NJ == 6, "lg_chain.h inverts the leg block with the 6 x 6 routines of lg_physics.h");
 
@@ -53,8 +53,16 @@ LG_DEV void ch_wave_sync() {          // LDS writes of one half of the wave visi
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// contact detection of slot sl: plane / height grid (sphere + the capsule segment's edge candidates) or grid mesh (closest point + the segment against the mesh's own edges)
-template <bool TMESH>
+// How a triangle-mesh instance answers its closest-point queries (physics_key picks the instance from the terrain view): CH_MESH_GRID the grid mesh's cells
+// (TerrainView::GV; also the value of the plane / height-grid instances, which never query), CH_MESH_TREE the BVH walk (TerrainView::M) on every other mesh --
+// OBJ and confined meshes, and a grid mesh under LG_GRID_MESH=0.  Same per-face arithmetic and order-free tie rule as the oracle's scan.  The walk's
+// traversal stack is private memory (scratch).  Measured and dropped: the lattice cells lane by lane (closest_point_lattice) on the confined OBJ mesh of
+// tools/bench_configs.py cassie-confined, 0.515 ms per step against the walk's 0.370 -- a wave waits for its widest window.
+enum { CH_MESH_GRID = 0, CH_MESH_TREE = 1 };
+
+// contact detection of slot sl: plane / height grid (sphere + the capsule segment's edge candidates) or triangle mesh (closest point; on a grid mesh -- SEG4 --
+// plus the segment against the mesh's own edges; on other meshes the spheres stand alone)
+template <bool TMESH, int MQ = CH_MESH_GRID>
 LG_DEV void ch_detect_slot(int sl, const LegModel& lm_, const TerrainView& T, const PhysParams& P, const LegKin& k, const M3& Rb, V3 pb, float* cst, int lane) {
   const int ncp = lm_.i(LM_CP_COUNT);
   const int link = lm_.i(LM_CP_LINK + sl);
@@ -64,11 +72,12 @@ LG_DEV void ch_detect_slot(int sl, const LegModel& lm_, const TerrainView& T, co
   const V3 gv = mul(Rl, lm_.v(LM_CP_SLIDE + 3 * sl));
   const bool seg = gv.x != 0.f || gv.y != 0.f || gv.z != 0.f;
   V3 x = x0, n = v3(0, 0, 1); float phi = 1.f; bool hit = true;
-  if (TMESH) {                                         // (grid meshes only: validate())
+  if (TMESH) {
     ClosestQuery Q;
     Q.p = x; Q.max_dist = rad + P.contact_offset + LG_MESH_CONTACT_MARGIN; Q.on = sl < ncp; Q.found = false; Q.cp = x; Q.fn = v3(0, 0, 1);
     Q.range = rad + P.contact_offset; Q.lb = Q.max_dist;
-    closest_point_grid(T, Q);
+    if (MQ == CH_MESH_GRID) closest_point_grid(T, Q);
+    else if (Q.on) Q.found = closest_point(T.M, Q.p, Q.max_dist, &Q.cp, &Q.fn);
     hit = false;
     if (Q.on && Q.found) {
       const V3 diff = x - Q.cp; const float dist = norm(diff);
@@ -147,7 +156,7 @@ struct ChSelfRow { bool on; float phi, iA, lam; V3 n; float f[NJ], Wb[6], Wk[NJ]
 // fbody[NJ + 2] (optional): net contact force on {base (group-summed), link 0 .. NJ-1, foot body}.
 // EXT_DETECT: helper waves of the workgroup detect the contact slots while this wave builds the bias and the mass matrix (physics_kernel_chain<.., HELP = true>);
 // the rendezvous with them stands in front of the first read of a slot record.
-template <bool TMESH, bool EXT_DETECT = false>
+template <bool TMESH, bool EXT_DETECT = false, int MQ = CH_MESH_GRID>
 LG_DEV void chain_substep(const lg_robot_model* __restrict__ m, const LegModel& lm_, const TerrainView& T, const PhysParams& P, int lane, float* cst, QuadState& s,
                           const float tau[NJ], float mu_robot, float madd, V3* fbody, SelfCol scol, int half = -1) {
   // half >= 0: this lane and lane + 32 of the wave are mirrors (same env and leg, `lane` = their common row): slot `sl` is set up by the half sl & 1
@@ -163,7 +172,7 @@ LG_DEV void chain_substep(const lg_robot_model* __restrict__ m, const LegModel& 
   // ---- contact detection (reads only the kinematics): before the mass matrix is live
   if (!EXT_DETECT) {
 #pragma unroll 1
-    for (int sl = 0; sl < CH_NCP; ++sl) ch_detect_slot<TMESH>(sl, lm_, T, P, k, Rb, pb, cst, lane);
+    for (int sl = 0; sl < CH_NCP; ++sl) ch_detect_slot<TMESH, MQ>(sl, lm_, T, P, k, Rb, pb, cst, lane);
   }
   // ---- leg bias (RNEA, zero generalised acceleration, moments about the base origin)
   float bk[NJ]; V3 Fs = v3(0, 0, 0), Ns = v3(0, 0, 0);

@@ -1248,9 +1248,12 @@ LG_DEV void write_rigid_body_state(const DevCtx* __restrict__ C, const LegModel&
 
 // The physics of a policy step (MODE 0: clip actions, nsub x (PD torques + one dt)), one dt with the torques of LG_T_TORQUES (MODE 1: lg_simulate), or the
 // torques alone (MODE 2: lg_compute_torques) for the chain instance: ONE wave per workgroup, a lane per leg, EPW envs per wave; post_kernel ends the step.
-// TMESH: contacts against a grid mesh (closest-point queries by cell index; the instance has no BVH walk).
+// TMESH: contacts against a triangle mesh; MQ (CH_MESH_*, lg_chain.h): how its closest-point queries go -- the cells of a grid mesh (physics_kernel_chain) or
+// the BVH walk (physics_kernel_chain_bvh).
 // HELP (round 5): a 256-thread launch whose waves 1-3 detect the contact slots -- kinematics of the published state, then their slots' queries, on a grid mesh
 // ~10 k cycles each -- while the main wave runs the bias, the mass matrix and its factorisation (Cassie, 4096 envs, trimesh: 0.281 -> ms per step, see the A/B log).
+// The two templates share their body (lg_chain_body.h, included in each).
+// plane, height grid, grid mesh
 template <int MODE, bool TMESH, bool HELP = false>
 __global__ __launch_bounds__(HELP ? 256 : 64) void physics_kernel_chain(const DevCtx* __restrict__ C, const float* __restrict__ actions_in, int nsub, const int32_t* __restrict__ ids, int n, int act_stride,
                                                            int epb) {
@@ -1260,170 +1263,20 @@ __global__ __launch_bounds__(HELP ? 256 : 64) void physics_kernel_chain(const De
   __shared__ float lmod[LM_FIELDS * GRP];
   constexpr int XST = 13 + 2 * NJ;                       // state a helper wave needs, per lane: root 13 | q NJ | qd NJ (an odd stride: conflict-free)
   __shared__ float xst[HELP ? 64 * XST : 1];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  // HALVES (the helper-wave instance at <= 16 envs per workgroup, i.e. N <= 4096): the upper 32 lanes of every wave would be idle copies; instead they MIRROR
-  // the lower 32 -- same env, same leg, same arithmetic, same slot-record rows -- and the work that is per contact slot is split between the halves:
-  // a helper wave detects two slots at once, the main wave sets up the even slots on its lower and the odd slots on its upper half.
-  const bool halves = HELP && epb * GRP <= 32;
-  const int le = halves ? (lane & 31) : lane;              // the lane's row in the slot records and in the published state
-  const int half = halves ? (lane >> 5) : -1;
-  const int kq = blockIdx.x * epb + le / GRP;
-  const int l = lane % GRP;
-  const bool live = kq < n && le / GRP < epb;
-  const bool valid = live && half <= 0;                   // (the lower half stores)
-  const int krow = live ? kq : n - 1;
-  const int e = ids ? ids[krow] : krow;
-  const lg_robot_model* __restrict__ m = &C->model;
-  const lg_config& g = C->cfg;
-  fill_leg_model(lmod, C->lmod, threadIdx.x, blockDim.x);
-  lds_barrier();
-  const LegModel lm_{lmod, l};
-  if (HELP && wv > 0) {
-    // ---- helper wave: per substep, the kinematics of the state the main wave published and the detection of this wave's slots
-    PhysParams P;
-    P.dt = g.sim_dt; P.grav = v3(g.gravity[0], g.gravity[1], g.gravity[2]); P.iters = g.solver_iterations;
-    P.contact_offset = g.contact_offset; P.max_depen = g.max_depenetration_velocity; P.erp = g.erp; P.cfm = g.cfm; P.solver = g.solver_type; P.fric = g.friction_model;
-    P.terrain_mu = C->terrain_mu; P.slide_mask = C->slide_mask; P.slot_perm = 0x76543210u; P.cache_reach = LG_MESH_CACHE_REACH;
-    const TerrainView T = C->ter;
-#pragma unroll 1
-    for (int sub = 0; sub < nsub; ++sub) {
-      lds_barrier();                                     // (A) the main wave has published root, q, qd of this substep
-      float r13[13], qq[NJ], qdd[NJ];
-      // (halves: a helper wave's two halves detect two slots of the same 32 rows at once -- the four slots take ONE slot's time on three waves instead of two)
-      const float* x = xst + le * XST;
-#pragma unroll
-      for (int i = 0; i < 13; ++i) r13[i] = x[i];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) { qq[j] = x[13 + j]; qdd[j] = x[13 + NJ + j]; }
-      const M3 Rb = quat_to_mat(r13 + 3);
-      const V3 pb = v3(r13[0], r13[1], r13[2]), vb = v3(r13[7], r13[8], r13[9]), wb = v3(r13[10], r13[11], r13[12]);
-      LegKin k;
-      leg_kinematics(lm_, Rb, pb, vb, wb, qq, qdd, k);
-      // slots dealt round-robin over the three helper waves (CH_NCP = 4: wave 1 takes slots 0 and 3)
-      if (halves) {
-        const int sl = lane < 32 ? wv - 1 : wv + 2;
-        if (sl < CH_NCP) ch_detect_slot<TMESH>(sl, lm_, T, P, k, Rb, pb, cst, le);
-      } else {
-#pragma unroll 1
-        for (int sl = wv - 1; sl < CH_NCP; sl += 3) ch_detect_slot<TMESH>(sl, lm_, T, P, k, Rb, pb, cst, lane);
-      }
-      lds_barrier();                                     // (A2) detection blocks complete
-    }
-    return;
-  }
-  QuadState s;
-#pragma unroll
-  for (int i = 0; i < 13; ++i) s.root[i] = C->root[(size_t)e * 13 + i];
-  float last_qd[NJ], act[NJ], tau[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    s.q[j] = C->dof[((size_t)e * NDOF + NJ * l + j) * 2]; s.qd[j] = C->dof[((size_t)e * NDOF + NJ * l + j) * 2 + 1];
-    last_qd[j] = C->last_dof_vel[(size_t)e * NDOF + NJ * l + j];
-    act[j] = 0.f; tau[j] = 0.f;
-  }
-  if (MODE != 1) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      float a = actions_in ? actions_in[(size_t)krow * act_stride + NJ * l + j] : C->actions[(size_t)e * NDOF + NJ * l + j];
-      a = fminf(fmaxf(a, -g.clip_actions), g.clip_actions);        // LR:93-94
-      act[j] = a;
-      if (valid && actions_in) C->actions[(size_t)e * NDOF + NJ * l + j] = a;
-    }
-  }
-  if (MODE == 2) {
-    ch_leg_torques(g, lm_, act, s.q, s.qd, last_qd, tau);
-    if (valid) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) C->torques[(size_t)e * NDOF + NJ * l + j] = tau[j];
-    }
-    return;
-  }
-  PhysParams P;
-  P.dt = g.sim_dt; P.grav = v3(g.gravity[0], g.gravity[1], g.gravity[2]); P.iters = g.solver_iterations;
-  P.contact_offset = g.contact_offset; P.max_depen = g.max_depenetration_velocity; P.erp = g.erp; P.cfm = g.cfm; P.solver = g.solver_type; P.fric = g.friction_model;
-  P.terrain_mu = C->terrain_mu; P.slide_mask = C->slide_mask; P.slot_perm = 0x76543210u; P.cache_reach = LG_MESH_CACHE_REACH;
-  const TerrainView T = C->ter;
-  const SelfCol scol{C->sc_pairs, C->n_sc, nullptr, nullptr};
-  const float mu_robot = C->friction[e], madd = C->mass_added[e];
-  V3 fbody[NJ + 2];
-#pragma unroll
-  for (int b = 0; b < NJ + 2; ++b) fbody[b] = v3(0, 0, 0);
-  bool fault = false;
-#pragma unroll 1
-  for (int sub = 0; sub < nsub; ++sub) {
-    if (MODE == 0) ch_leg_torques(g, lm_, act, s.q, s.qd, last_qd, tau);
-    else {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) tau[j] = C->torques[(size_t)e * NDOF + NJ * l + j];
-    }
-    float root0[7], q0[NJ];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) root0[i] = s.root[i];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) q0[j] = s.q[j];
-    if (HELP) {
-      float* x = xst + le * XST;                           // (halves: both mirrors write the same values)
-#pragma unroll
-      for (int i = 0; i < 13; ++i) x[i] = s.root[i];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) { x[13 + j] = s.q[j]; x[13 + NJ + j] = s.qd[j]; }
-      lds_barrier();                                     // (A)
-    }
-    chain_substep<TMESH, HELP>(m, lm_, T, P, le, cst, s, tau, mu_robot, madd, sub == nsub - 1 ? fbody : nullptr, scol, half);
-    // fault guard: a non-finite or diverged state is rolled back to the pre-step pose at rest and flagged for termination
-    float acc = 0.f, acc0 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 13; ++i) acc += s.root[i] * 0.f;
-#pragma unroll
-    for (int i = 7; i < 13; ++i) acc += fabsf(s.root[i]) < 1e3f ? 0.f : 1.f;
-    if (TMESH) {
-      acc += (s.root[0] < C->mesh_lo[0] - LG_MESH_OOB_MARGIN || s.root[0] > C->mesh_hi[0] + LG_MESH_OOB_MARGIN ||
-              s.root[1] < C->mesh_lo[1] - LG_MESH_OOB_MARGIN || s.root[1] > C->mesh_hi[1] + LG_MESH_OOB_MARGIN ||
-              s.root[2] < C->mesh_lo[2] - LG_MESH_OOB_MARGIN) ? 1.f : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { acc += s.q[j] * 0.f + s.qd[j] * 0.f; acc0 += q0[j] * 0.f; }
-#pragma unroll
-    for (int i = 0; i < 7; ++i) acc0 += root0[i] * 0.f;
-    acc = grp_sum(acc); acc0 = grp_sum(acc0);
-    if (!(acc == 0.f)) {
-      const bool ok0 = acc0 == 0.f;
-      fault = true;
-#pragma unroll
-      for (int i = 0; i < 13; ++i)
-        s.root[i] = ok0 ? (i < 7 ? root0[i] : 0.f) : g.base_init_state[i] + (i < 3 ? C->origins[(size_t)e * 3 + i] : 0.f);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) { s.q[j] = ok0 ? q0[j] : lm_.f(LM_DEFAULT_POS + j); s.qd[j] = 0.f; }
-#pragma unroll
-      for (int b = 0; b < NJ + 2; ++b) fbody[b] = v3(0, 0, 0);
-    }
-  }
-  if (!valid) return;
-  if (fault && l == 0) C->reset_buf[e] = 2;
-  if (l == 0) {
-#pragma unroll
-    for (int i = 0; i < 13; ++i) C->root[(size_t)e * 13 + i] = s.root[i];
-  }
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    C->dof[((size_t)e * NDOF + NJ * l + j) * 2] = s.q[j];
-    C->dof[((size_t)e * NDOF + NJ * l + j) * 2 + 1] = s.qd[j];
-    if (MODE == 0) C->torques[(size_t)e * NDOF + NJ * l + j] = tau[j];
-  }
-  const int per_leg = C->per_leg, B = C->B;
-  {
-    float* cf = C->cforce + (size_t)e * B * 3;
-    if (l == 0) { cf[0] = fbody[0].x; cf[1] = fbody[0].y; cf[2] = fbody[0].z; }
-    float* cl = cf + (size_t)(1 + per_leg * l) * 3;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      V3 f = fbody[1 + j];
-      if (j == NJ - 1 && per_leg == NJ) f = f + fbody[NJ + 1];      // no separate foot body: its spheres report on the last link
-      cl[3 * j] = f.x; cl[3 * j + 1] = f.y; cl[3 * j + 2] = f.z;
-    }
-    if (per_leg == NJ + 1) { cl[3 * NJ] = fbody[NJ + 1].x; cl[3 * NJ + 1] = fbody[NJ + 1].y; cl[3 * NJ + 2] = fbody[NJ + 1].z; }
-  }
-  write_rigid_body_state(C, lm_, e, l, s.root, s.q, s.qd);
+  constexpr int MQ = CH_MESH_GRID;
+#include "lg_chain_body.h"
+}
+// triangle meshes without the grid rule's vertices (OBJ, confined, or a grid mesh under LG_GRID_MESH=0): the BVH walk
+template <int MODE, bool HELP = false>
+__global__ __launch_bounds__(HELP ? 256 : 64) void physics_kernel_chain_bvh(const DevCtx* __restrict__ C, const float* __restrict__ actions_in, int nsub, const int32_t* __restrict__ ids, int n,
+                                                               int act_stride, int epb) {
+  __shared__ __attribute__((aligned(16))) float cst[CH_CST_FLOATS];
+  __shared__ float lmod[LM_FIELDS * GRP];
+  constexpr int XST = 13 + 2 * NJ;
+  __shared__ float xst[HELP ? 64 * XST : 1];
+  constexpr bool TMESH = true;
+  constexpr int MQ = CH_MESH_TREE;
+#include "lg_chain_body.h"
 }
 #endif           // NJ == 3
 
@@ -2619,7 +2472,6 @@ static const char* validate(const lg_config* cfg, const lg_robot_model* model, c
   if (model->num_joints_per_leg != NJ) return "num_joints_per_leg does not match this kernel instance (4 x 3, 6 x 3, 2 x 6)";
 #if NJ != 3
   if (cfg->control_type == LG_CTRL_ACTUATOR_NET) return "the 2 x 6 instance has no actuator network (cassie_config.py: PD control)";
-  if (ter->mesh_type == LG_MESH_TRIMESH && !ter->grid_vertices) return "the 2 x 6 instance collides with grid meshes (lg_terrain.grid_vertices) only: it has no BVH walk";
   for (int l = 0; l < NLEG; ++l) if (model->cp_count[l] > CH_NCP) return "the 2 x 6 instance holds four collision spheres per leg";
 #endif
   if (cfg->num_obs != NPROP + (cfg->measure_heights ? cfg->num_height_points : 0) + cfg->num_extra_obs) return "num_obs does not match the observation layout";
@@ -2988,7 +2840,8 @@ using PhysicsFn = void (*)(const DevCtx*, const float*, int, int, const int32_t*
 #define LG_PK(MODE, TM, HELP, SPEC) {{MODE, TM, HELP, SPEC}, (HELP) ? 256 : 64, physics_kernel<MODE, TM, HELP, SPEC>}
 #else
 using PhysicsFn = void (*)(const DevCtx*, const float*, int, const int32_t*, int, int, int);
-#define LG_PK(MODE, TM, HELP) {{MODE, TM, HELP, 0}, (HELP) ? 256 : 64, physics_kernel_chain<MODE, TM, HELP>}
+#define LG_PK(MODE, TM, HELP) {{MODE, TM, HELP, CH_MESH_GRID}, (HELP) ? 256 : 64, physics_kernel_chain<MODE, TM, HELP>}
+#define LG_PKB(MODE, HELP) {{MODE, true, HELP, CH_MESH_TREE}, (HELP) ? 256 : 64, physics_kernel_chain_bvh<MODE, HELP>}
 #endif
 struct PhysicsInstance { PhysicsKey key; int threads; PhysicsFn fn; };
 static const PhysicsInstance physics_instances[] = {
@@ -3008,22 +2861,31 @@ static const PhysicsInstance physics_instances[] = {
   LG_PK(0, true, true), LG_PK(0, false, true), LG_PK(0, true, false), LG_PK(0, false, false),
   LG_PK(2, false, false),
   LG_PK(1, true, false), LG_PK(1, false, false),
+  // triangle meshes without grid vertices, the BVH walk: policy steps with and without helper waves, lg_simulate
+  LG_PKB(0, true), LG_PKB(0, false), LG_PKB(1, false),
 #endif
 };
 #undef LG_PK
+#undef LG_PKB
 
 // The instance a launch needs.  mode: 0 policy step, 1 lg_simulate, 2 lg_compute_torques; fuse: step_shape; helpers: the launch has helper waves; feat: FEAT_*.
 // physics_kernel's SPEC = FEAT << 2 | the rollout tail (2, 3).  With helper waves a triangle mesh gets the features it needs; on a height grid or a plane the
 // self-collision instance carries the capsule code too, and a robot of fixed spheres without self-collision runs the plain instance.  The single-wave
-// instances carry both (FEAT_ALL), plus the lattice segments when they are on.  The chain instances have no features or tails of their own.
-static PhysicsKey physics_key(int mode, int fuse, bool tm, bool helpers, unsigned feat) {
+// instances carry both (FEAT_ALL), plus the lattice segments when they are on.  The chain instances have no features or tails of their own: their SPEC is
+// the way the terrain's closest-point queries go (CH_MESH_*, lg_chain.h) -- the grid mesh's cells (and every plane or height grid), else the BVH walk.
+static PhysicsKey physics_key(int mode, int fuse, const TerrainView& T, bool helpers, unsigned feat) {
+  const bool tm = T.mesh_type == LG_MESH_TRIMESH;
   if (mode == 2) return {2, false, false, 0};
-  if (NJ != 3) return {mode, tm, helpers, 0};
+#if NJ != 3
+  (void)fuse; (void)feat;
+  return {mode, tm, helpers, !tm || T.GV ? CH_MESH_GRID : CH_MESH_TREE};
+#else
   unsigned f;
   if (mode == 1 || !helpers) f = FEAT_CAPS | FEAT_SELF | (feat & FEAT_LCAPS);
   else if (tm) f = feat;
   else f = (feat & FEAT_SELF) ? FEAT_CAPS | FEAT_SELF : feat & FEAT_CAPS;
   return {mode, tm, helpers, (int)(f << 2) | (fuse >= STEP_FUSED_ROLLOUT ? fuse : 0)};
+#endif
 }
 // launches the instance of key k; a key without one is an error, never a different instance
 extern "C++" template <class... A>      // (inside the ABI's extern "C" block)
@@ -3038,14 +2900,14 @@ static int launch_physics(lg_ctx* c, hipStream_t st, const float* actions, const
                           PostSink sink = PostSink{nullptr, nullptr, nullptr, nullptr, 0.f}) {
   const bool tm = c->h.ter.mesh_type == LG_MESH_TRIMESH;
 #if NJ != 3
-  (void)fuse; (void)sink;
+  (void)fuse; (void)sink; (void)tm;
   int epb = EPW;         // envs per workgroup: EPW, halved while the launch would have fewer workgroups than the chip has CUs (LG_CHAIN_EPB sets it)
   while (epb > 4 && (n + epb - 1) / epb < 256) epb >>= 1;
   if (!lg_switch_int("LG_CHAIN_EPB", 1, EPW, epb, c->err)) return LG_ERR_INVALID;
   const int nb = (n + epb - 1) / epb;
   if (n != c->h.n_stepped) { c->h.n_stepped = n; hipLaunchKernelGGL(set_n_stepped, dim3(1), dim3(1), 0, st, c->d, n); }
   // (helper waves for the contact detection: LG_SPLIT=0 keeps the single-wave launch, the checker of that path)
-  return launch_instance(c, st, physics_key(0, 0, tm, c->sw.split, 0u), nb, c->d, actions, c->h.cfg.decimation, ids, n, act_stride, epb);
+  return launch_instance(c, st, physics_key(0, 0, c->h.ter, c->sw.split, 0u), nb, c->d, actions, c->h.cfg.decimation, ids, n, act_stride, epb);
 #else
   const int nb = (n + EPB - 1) / EPB;
   // helper waves (leg bias, contact detection, a share of the contact set-up; with the actuator network also its three
@@ -3054,14 +2916,14 @@ static int launch_physics(lg_ctx* c, hipStream_t st, const float* actions, const
   // as well: the main wave alone took 0.134 ms per rollout step of 4096 envs on the plane
   const int nact = (c->sw.split || tm) ? 3 : 0;
   if (n != c->h.n_stepped) { c->h.n_stepped = n; hipLaunchKernelGGL(set_n_stepped, dim3(1), dim3(1), 0, st, c->d, n); }
-  return launch_instance(c, st, physics_key(0, fuse, tm, nact == 3, c->feat), nb, c->d, actions, c->h.cfg.decimation, nact, ids, n, act_stride, fuse, sink);
+  return launch_instance(c, st, physics_key(0, fuse, c->h.ter, nact == 3, c->feat), nb, c->d, actions, c->h.cfg.decimation, nact, ids, n, act_stride, fuse, sink);
 #endif
 }
 
 // lg_compute_torques (mode 2: the torques of `actions`) and lg_simulate (mode 1: one dt with the torques of LG_T_TORQUES): every env, single-wave instances
 static int launch_all_envs(lg_ctx* c, hipStream_t st, int mode, const float* actions) {
   const int nb = (c->h.N + EPB - 1) / EPB, nsub = mode == 1 ? 1 : 0;
-  const PhysicsKey k = physics_key(mode, STEP_TWO_LAUNCH, c->h.ter.mesh_type == LG_MESH_TRIMESH, false, c->feat);
+  const PhysicsKey k = physics_key(mode, STEP_TWO_LAUNCH, c->h.ter, false, c->feat);
 #if NJ != 3
   const int rc = launch_instance(c, st, k, nb, c->d, actions, nsub, (const int32_t*)nullptr, c->h.N, NDOF, EPW);
 #else

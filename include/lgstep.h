@@ -34,7 +34,8 @@ extern "C" {
  * each.  The library holds one instance of its kernels per supported topology -- 4 x 3 (ANYmal-B/C, A1, Go2), 6 x 3 (ElSpider Air, el_mini.urdf)
  * and 2 x 6 (Cassie, cassie.urdf: an open chain, the knee-spring joints are commented out in the reference's file) -- chosen by lg_create from the
  * model; the structs below are sized for the largest, and every (N, dof) / (N, legs) / (N, bodies) tensor has the model's own extents (12 / 4 / 17
- * for a quadruped with FOOT bodies, 18 / 6 / 25 for the hexapod, 12 / 2 / 13 for the biped). */
+ * for a quadruped with FOOT bodies, 18 / 6 / 25 for the hexapod, 12 / 2 / 13 for the biped).  Every instance collides with every terrain kind: plane,
+ * height grid, grid mesh, and any other triangle mesh (the 2 x 6 instance walks the BVH there). */
 #define LG_MAX_LEGS 6
 #define LG_JOINTS_PER_LEG 3    /* the three-joint instances */
 #define LG_MAX_JOINTS_PER_LEG 6

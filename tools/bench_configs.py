@@ -6,6 +6,7 @@ public Python API, synthetic N(0,1) actions, after a warm-up.  Informational; on
             TerrainObj), contacts by closest-point (SDF) queries on the mesh BVH inside the physics kernel, 4096 envs
   config 4  ANYmal-C rough + 60x30 ray-cast depth camera, 4096 envs on this GPU (of 8192 over 2 GPUs)
   config 5  ANYmal-C main-rollout sampler: 128 main x 32 rollouts on this GPU (of 1024 x 32 over 8 GPUs): step_rollout
+  cassie-confined (named only, not in the default list)  Cassie on a confined two-layer OBJ mesh (TerrainObj), contacts by the BVH walk, 4096 envs
 
 Multi-GPU compositions of configs 4 and 5 (BASELINE.json: 8192 envs over 2 GPUs env-sharded; 1024 mains x 32 over 8 GPUs sharded by main):
     python tools/bench_configs.py --gpus N 4|5
@@ -239,6 +240,44 @@ def config_cassie():
     return out
 
 
+def config_cassie_confined():
+    """Cassie (PD, the lg2 chain instance) on a confined two-layer mesh loaded through TerrainObj, in the style of config 3: timber piles, gaps and columns
+    (tiles a standing biped fits under), 4096 envs.  The chain instance's contact queries walk the BVH.  Not in the default list."""
+    import copy
+    import tempfile
+    from extended_legged_gym_amd.envs import task_registry
+    from extended_legged_gym_amd.utils.helpers import get_args
+    from extended_legged_gym_amd.utils.obj_io import save_obj
+    from extended_legged_gym_amd.utils.terrain_confine import TerrainConfined, convert_2layer_heightfield_to_trimesh
+    cfg = copy.deepcopy(task_registry.get_cfgs("cassie")[0])
+    gen = copy.deepcopy(cfg.terrain)
+    gen.mesh_type, gen.curriculum, gen.border_size = "confined_trimesh", True, 5.0
+    gen.num_rows, gen.num_cols, gen.terrain_length, gen.terrain_width = 4, 4, 8.0, 8.0
+    gen.confined_terrain_proportions = [0.0, 0.0, 0.4, 0.3, 0.3, 0.0]
+    np.random.seed(2)
+    tc = TerrainConfined(gen, 4096)
+    v, tri = convert_2layer_heightfield_to_trimesh(tc.ground_height_field_raw, tc.ceiling_height_field_raw, gen.horizontal_scale,
+                                                   gen.vertical_scale, gen.slope_treshold, enable_ceiling=True)
+    path = os.path.join(tempfile.mkdtemp(), "confined.obj")
+    save_obj(path, v, tri)
+    t = cfg.terrain
+    t.mesh_type, t.use_terrain_obj, t.terrain_file, t.curriculum = "trimesh", True, path, False
+    t.random_origins, t.origins_x_range, t.origins_y_range = True, [-15.0, 15.0], [-15.0, 15.0]
+    t.height_clearance_factor = 1.2
+    torch.manual_seed(1)
+    env = task_registry.make_env("cassie", args=get_args(["--headless", "--sim_device", "cuda:0", "--num_envs", "4096"]), env_cfg=cfg)[0]
+    env.reset()
+    a = 0.3 * torch.randn(4096, 12, device="cuda")
+    dt = timeit(lambda: env.step(a), 200, 500)
+    mesh = env.core.collision_mesh
+    out = dict(config="cassie-confined: Cassie 2 x 6 (PD) on a confined two-layer OBJ mesh (TerrainObj: timber piles, gaps, columns), 4096 envs on 1 GPU",
+               env_steps_per_s=4096 / dt, ms_per_step=dt * 1e3, contact_lattice=list(mesh.contact_lattice), mesh_triangles=mesh.num_triangles,
+               finite=bool(torch.isfinite(env.root_states).all()), base_z_min=float(env.root_states[:, 2].min()),
+               mean_episode_len=float(env.episode_length_buf.float().mean()))
+    env.core.close()
+    return out
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
     gpus = 1
@@ -258,7 +297,7 @@ if __name__ == "__main__":
                "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(gpus)] + which
         sys.exit(subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")))
     for w in which:
-        line = {"1": config1, "3": config3, "4": config4, "5": config5, "hexapod": config_hexapod, "cassie": config_cassie}[w]()
+        line = {"1": config1, "3": config3, "4": config4, "5": config5, "hexapod": config_hexapod, "cassie": config_cassie, "cassie-confined": config_cassie_confined}[w]()
         if REHEARSE:
             line["rehearsal"] = True
         if RANK == 0:
