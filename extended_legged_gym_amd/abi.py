@@ -271,6 +271,11 @@ class lg_rollout(C.Structure):
                                           "last_values", "returns", "advantages")]
 
 
+class lg_rollout_hidden(C.Structure):
+    """include/lgpolicy.h: device pointers to the (T, L, n, H) hidden-state rows of one collected rollout (state before each step's act)."""
+    _fields_ = [(k, C.c_void_p) for k in ("h_a", "c_a", "h_c", "c_c")]
+
+
 def declare_policy(lib):
     """Prototypes of the rollout-collection entry points (include/lgpolicy.h), same library."""
     vp = C.c_void_p
@@ -297,11 +302,30 @@ def declare_policy(lib):
     lib.lg_mppi_sample_plans.restype = C.c_int
     lib.lg_planner_diffuse.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, i32, f32, vp, vp, vp, vp, vp]
     lib.lg_planner_diffuse.restype = C.c_int
+    fpp = C.POINTER(C.POINTER(f32))
+    lib.lg_rnn_create.argtypes = [i32, i32, i32, i32, fpp, fpp, fpp, fpp, C.c_int]
+    lib.lg_rnn_create.restype = vp
+    lib.lg_rnn_destroy.argtypes = [vp]
+    lib.lg_rnn_destroy.restype = None
+    lib.lg_rnn_tile_weights.argtypes = [i32, i32, i32, vp, vp, vp]
+    lib.lg_rnn_tile_weights.restype = C.c_int64
+    lib.lg_rnn_step.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.lg_rnn_step.restype = C.c_int
+    lib.lg_rnn_reset_rows.argtypes = [vp, vp, vp, vp, C.c_int64, vp]
+    lib.lg_rnn_reset_rows.restype = C.c_int
+    lib.lg_policy_act_recurrent.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, vp, u64, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lg_policy_act_recurrent.restype = C.c_int
+    lib.lg_collect_rollout_recurrent.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, f32, f32, i32, C.POINTER(lg_rollout), C.POINTER(lg_rollout_hidden),
+                                                 vp, vp, vp, vp, vp]
+    lib.lg_collect_rollout_recurrent.restype = C.c_int
     return lib
 
 
 POLICY_SYMBOLS = ["lg_mlp_create", "lg_mlp_destroy", "lg_mlp_last_error", "lg_mlp_forward", "lg_policy_act", "lg_compute_returns",
-                  "lg_collect_rollout", "lg_plan_from_nodes", "lg_mppi_update", "lg_mppi_sample_plans", "lg_planner_diffuse"]
+                  "lg_collect_rollout", "lg_plan_from_nodes", "lg_mppi_update", "lg_mppi_sample_plans", "lg_planner_diffuse",
+                  "lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",
+                  "lg_collect_rollout_recurrent"]
+RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2, "lrelu": 3, "selu": 4}
 
 PRODUCT_SYMBOLS = ["lg_abi_sizes", "lg_arena_bytes", "lg_create", "lg_get_tensor", "lg_step", "lg_step_physics", "lg_step_subset", "lg_step_transition", "lg_sync_main_to_rollout", "lg_rollout_batch", "lg_compute_torques",

@@ -1,5 +1,6 @@
 // lg_policy.hip — gfx950 kernels for the rollout-collection side of PPO (include/lgpolicy.h): fused MLP forward on the
-// fp32 matrix cores, PPO.act (both networks + Gaussian sampling + log-prob) in one launch, GAE returns.
+// fp32 matrix cores, PPO.act (both networks + Gaussian sampling + log-prob) in one launch, GAE returns; further down the planner's
+// arithmetic and the LSTM / GRU memory of the recurrent actor-critic (one launch per memory layer).
 //
 // MLP kernel.  Workgroup = 8 waves = 32 rows of the batch through ALL layers.  The activations of the current layer live in LDS
 // in an image a lane reads with ONE ds_read_b128 per four k-steps: [k/16][row][k%4][(k/4)%4] -- the four values a lane feeds to
@@ -541,3 +542,406 @@ int lg_planner_diffuse(lg_ctx* ctx, float* mean, const float* sigma_nodes, const
   }
   return LG_OK;
 }
+
+
+// ============================================================================================ recurrent memory (lgpolicy.h: lg_rnn_*)
+// One step of one nn.LSTM / nn.GRU layer (rsl_rl networks/memory.py:27-33, inference mode) for 32 rows per workgroup; ONE launch per
+// memory layer, the actor's and the critic's memory side by side on blockIdx.y when both step together (lg_policy_act_recurrent).
+//
+// The two products W_ih x + W_hh h are one k-chain over the concatenated row [x (padded to 16) ; h (padded to 16)], staged in LDS in the
+// MLP kernel's activation image (IMG above: one ds_read_b128 feeds four k-steps).  A wave owns 16 hidden units at a time and keeps ALL
+// gate accumulators of those units for both row halves (LSTM: i f g o; GRU: r z n_x n_h -- the n gate's x part and h part apart, because
+// r multiplies the h part only): 8 independent 16x16 tiles, 32 MFMAs per pair of LDS reads, and the gate non-linearities + state update are
+// a register epilogue with no second pass through LDS or HBM.  Weights are re-tiled on the host (rnn_tile_weights) so that a wave loads the
+// fragments of one gate for a block of 16 inputs with one coalesced dwordx4; the fragments of the next block are requested before
+// the MFMAs of the current one.
+// LDS: 32 rows x 1024 floats = 128 KB (input 512 + hidden 512, the widest allowed), static; nothing else is staged.
+#define RNN_KMAX 1024        // widest concatenated row: 512 inputs + 512 hidden, each padded to 16
+#define RNN_MAX_LAYERS 4
+
+struct RnnLayerDev {
+  int gru, I, H, Ip, nbx, nb, nch;   // Ip: x padded to 16; nbx = Ip / 16 blocks of x, nb blocks of [x ; h]; nch chunks of 16 hidden units
+  const float* w;                    // tiled [chunk][block][gate][lane][4]
+  const float* b;                    // [4][16 * nch]: LSTM b_ih + b_hh of i f g o; GRU (b_ir + b_hr), (b_iz + b_hz), b_in, b_hn
+};
+
+struct RnnStepArgs {                 // one memory's operands of a layer step (device pointers)
+  RnnLayerDev L;
+  const float* x;                    // (n, I): the observation, or the h' of the layer below
+  float* h;                          // (n, H) of this layer, updated in place
+  float* c;                          // (n, H) or null (GRU)
+  const float* reset;                // (n) or null
+  float* out;                        // (n, H) or null: a copy of h'
+};
+
+struct lg_rnn {
+  int type = 0, num_layers = 0, input = 0, hidden = 0, device = 0;
+  RnnLayerDev layer[RNN_MAX_LAYERS];
+  std::vector<void*> allocs;
+};
+
+LG_DEV float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+
+// blocks [kb0, kb1) of a chunk: G gate fragments per block; gate 2 of a GRU accumulates into acc[NSLOT] (2: x part, 3: h part).
+// Two fragment sets: the loads of the next block are issued before the 8 G MFMAs of the current one (sched_barrier pins that order, as in
+// MLP_BLOCK), so the wait in front of a block's first MFMA is for loads issued a whole block earlier.
+template <int G>
+struct RnnFrag { float4 w[G], a0, a1; };
+template <int G>
+LG_DEV void rnn_load(RnnFrag<G>& f, const float4* __restrict__ wc, const float4* ap, int kb) {
+#pragma unroll
+  for (int g = 0; g < G; ++g) f.w[g] = wc[((size_t)kb * G + g) * 64];
+  f.a0 = ap[kb * 128]; f.a1 = ap[kb * 128 + 64];
+}
+template <int G, int NSLOT>
+LG_DEV void rnn_mfma(f32x4 (&acc)[4][2], const RnnFrag<G>& f) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const float x0 = s == 0 ? f.a0.x : s == 1 ? f.a0.y : s == 2 ? f.a0.z : f.a0.w;
+    const float x1 = s == 0 ? f.a1.x : s == 1 ? f.a1.y : s == 2 ? f.a1.z : f.a1.w;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float wv = s == 0 ? f.w[g].x : s == 1 ? f.w[g].y : s == 2 ? f.w[g].z : f.w[g].w;
+      const int slot = (G == 3 && g == 2) ? NSLOT : g;
+      acc[slot][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0, wv, acc[slot][0], 0, 0, 0);
+      acc[slot][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1, wv, acc[slot][1], 0, 0, 0);
+    }
+  }
+}
+template <int G, int NSLOT>
+LG_DEV void rnn_blocks(f32x4 (&acc)[4][2], const float4* __restrict__ wc, const float4* ap, int kb0, int kb1, int kzero) {
+  if (kb0 >= kb1) return;
+  RnnFrag<G> f0, f1;
+  rnn_load<G>(f0, wc, ap, kb0);
+  for (int kb = kb0; kb < kb1; kb += 2) {
+    // an odd count's second half multiplies the chunk's all-zero weight block (kzero): no branch around the MFMAs, so the loads stay where they are
+    const bool two = kb + 1 < kb1, more = kb + 2 < kb1;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int g = 0; g < G; ++g) f1.w[g] = wc[((size_t)(two ? kb + 1 : kzero) * G + g) * 64];
+    f1.a0 = ap[(two ? kb + 1 : kb) * 128]; f1.a1 = ap[(two ? kb + 1 : kb) * 128 + 64];
+    __builtin_amdgcn_sched_barrier(0);
+    rnn_mfma<G, NSLOT>(acc, f0);
+    __builtin_amdgcn_sched_barrier(0);
+    rnn_load<G>(f0, wc, ap, more ? kb + 2 : kb);             // past the end: an in-bounds block, unused
+    __builtin_amdgcn_sched_barrier(0);
+    rnn_mfma<G, NSLOT>(acc, f1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <bool GRU>
+LG_DEV void rnn_tile(const RnnStepArgs& S, int64_t row0, int64_t n, float* img) {
+  const RnnLayerDev& R = S.L;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int I = R.I, H = R.H, Ip = R.Ip, Kp = R.nb * 16;
+  // stage [x ; h] of this workgroup's 32 rows.  The workgroup owns WHOLE rows and reads every h it will need here, before the barrier; h'
+  // (and c') are stored only after it, and no other workgroup touches these rows: the state is updated in place without a second buffer.
+  // A row whose reset flag is set enters with h = 0 (and c = 0 in the epilogue): Memory.reset(dones), memory.py:35-51, folded into the step.
+  for (int base = 0; base < MLP_ROWS * Kp; base += 8 * MLP_THREADS) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = base + u * MLP_THREADS + tid, r = idx / Kp, k = idx - r * Kp;
+      const int64_t row = row0 + r;
+      float val = 0.f;
+      if (idx < MLP_ROWS * Kp && row < n) {
+        if (k < I) val = S.x[row * I + k];
+        else if (k >= Ip && k < Ip + H) val = (S.reset && S.reset[row] != 0.f) ? 0.f : S.h[row * H + (k - Ip)];
+      }
+      v[u] = val;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = base + u * MLP_THREADS + tid, r = idx / Kp, k = idx - r * Kp;
+      if (idx < MLP_ROWS * Kp) img[IMG(r, k)] = v[u];
+    }
+  }
+  lds_barrier();
+  constexpr int G = GRU ? 3 : 4;
+  const float4* ap = reinterpret_cast<const float4*>(img) + (lane & 15) * 4 + (lane >> 4);
+  const int Hp = 16 * R.nch;
+  for (int c = wv; c < R.nch; c += MLP_THREADS / 64) {
+    f32x4 acc[4][2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) { acc[g][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[g][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    const float4* wc = reinterpret_cast<const float4*>(R.w) + (size_t)c * (R.nb + 1) * G * 64 + lane;
+    if (GRU) {
+      rnn_blocks<G, 2>(acc, wc, ap, 0, R.nbx, R.nb);
+      rnn_blocks<G, 3>(acc, wc, ap, R.nbx, R.nb, R.nb);
+    } else {
+      rnn_blocks<G, 2>(acc, wc, ap, 0, R.nb, R.nb);
+    }
+    const int col = c * 16 + (lane & 15);
+    const float b0 = R.b[col], b1 = R.b[Hp + col], b2 = R.b[2 * Hp + col], b3 = R.b[3 * Hp + col];
+    // epilogue: C[m = 4 * (lane >> 4) + i (+ 16)][col]
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = 4 * (lane >> 4) + i + 16 * hf;
+        const int64_t row = row0 + m;
+        if (col >= H || row >= n) continue;
+        float hn;
+        if (GRU) {
+          const float r = sigmoidf_(acc[0][hf][i] + b0), z = sigmoidf_(acc[1][hf][i] + b1);
+          const float ng = tanhf((acc[2][hf][i] + b2) + r * (acc[3][hf][i] + b3));
+          const float hold = img[IMG(m, Ip + col)];                 // the h this step used (after the reset mask)
+          hn = (1.f - z) * ng + z * hold;
+        } else {
+          const float ig = sigmoidf_(acc[0][hf][i] + b0), fg = sigmoidf_(acc[1][hf][i] + b1);
+          const float gg = tanhf(acc[2][hf][i] + b2), og = sigmoidf_(acc[3][hf][i] + b3);
+          const float cold = (S.reset && S.reset[row] != 0.f) ? 0.f : S.c[row * H + col];
+          const float cn = fg * cold + ig * gg;
+          S.c[row * H + col] = cn;
+          hn = og * tanhf(cn);
+        }
+        S.h[row * H + col] = hn;
+        if (S.out) S.out[row * H + col] = hn;
+      }
+  }
+}
+
+// blockIdx.y picks the memory (0: the actor's or the only one, 1: the critic's)
+__global__ __launch_bounds__(MLP_THREADS) void rnn_layer_kernel(RnnStepArgs S0, RnnStepArgs S1, int64_t n) {
+  __shared__ __attribute__((aligned(16))) float img[MLP_ROWS * RNN_KMAX];
+  const RnnStepArgs& S = blockIdx.y == 0 ? S0 : S1;
+  const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
+  if (S.L.gru) rnn_tile<true>(S, row0, n, img); else rnn_tile<false>(S, row0, n, img);
+}
+
+// Memory.reset(dones) (memory.py:45-51): hidden_state[..., dones == 1, :] = 0 on every layer
+__global__ __launch_bounds__(256) void rnn_reset_rows_kernel(float* __restrict__ h, float* __restrict__ c, const float* __restrict__ dones, int64_t n, int H, int L) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)L * n * H) return;
+  const int64_t row = (idx / H) % n;
+  if (dones[row] != 0.f) { h[idx] = 0.f; if (c) c[idx] = 0.f; }
+}
+
+// [x ; h] weights of one layer in MFMA B-fragment order: tiled[((c * (nb + 1) + b) * G + g) * 64 + lane][s] = Wcat[g * H + 16 c + (lane & 15)][16 b + 4 s + (lane >> 4)],
+// Wcat[:, 0 .. I) = w_ih, Wcat[:, Ip .. Ip + H) = w_hh, zero elsewhere (Ip = I rounded up to 16); block nb of every chunk is all zero (what the second half
+// of an odd block count multiplies).  A pure function of its arguments.
+static size_t rnn_tiled_count(int G, int I, int H) {
+  const int Ip = (I + 15) & ~15, nb = (Ip + ((H + 15) & ~15)) / 16, nch = (H + 15) / 16;
+  return (size_t)nch * (nb + 1) * G * 64 * 4;
+}
+static void rnn_tile_weights(int G, int I, int H, const float* w_ih, const float* w_hh, float* tiled) {
+  const int Ip = (I + 15) & ~15, nb = (Ip + ((H + 15) & ~15)) / 16, nch = (H + 15) / 16;
+  for (int c = 0; c < nch; ++c)
+    for (int b = 0; b <= nb; ++b)
+      for (int g = 0; g < G; ++g)
+        for (int ln = 0; ln < 64; ++ln)
+          for (int s = 0; s < 4; ++s) {
+            const int u = c * 16 + (ln & 15), k = b * 16 + s * 4 + (ln >> 4);
+            float v = 0.f;
+            if (u < H) {
+              if (k < I) v = w_ih[(size_t)(g * H + u) * I + k];
+              else if (k >= Ip && k < Ip + H) v = w_hh[(size_t)(g * H + u) * H + (k - Ip)];
+            }
+            tiled[((((size_t)c * (nb + 1) + b) * G + g) * 64 + ln) * 4 + s] = v;
+          }
+}
+
+static int rnn_check(const lg_rnn* m, const float* h, const float* c, int64_t n) {
+  if (!m || !h || n < 0) return LG_ERR_INVALID;
+  if (m->type == LG_RNN_LSTM && !c) { g_pol_err = "lg_rnn: an LSTM needs its cell state"; return LG_ERR_INVALID; }
+  return LG_OK;
+}
+
+static RnnStepArgs rnn_args(const lg_rnn* m, int l, const float* x, int64_t n, float* h, float* c, const float* reset, float* out) {
+  RnnStepArgs a;
+  const size_t slab = (size_t)n * m->hidden;
+  a.L = m->layer[l];
+  a.x = l == 0 ? x : h + (size_t)(l - 1) * slab;
+  a.h = h + (size_t)l * slab;
+  a.c = m->type == LG_RNN_LSTM ? c + (size_t)l * slab : nullptr;
+  a.reset = reset;
+  a.out = l == m->num_layers - 1 ? out : nullptr;
+  return a;
+}
+
+extern "C" {
+
+int64_t lg_rnn_tile_weights(int32_t type, int32_t input, int32_t hidden, const float* w_ih, const float* w_hh, float* tiled) {
+  if ((type != LG_RNN_LSTM && type != LG_RNN_GRU) || input < 1 || input > 512 || hidden < 1 || hidden > 512) return LG_ERR_INVALID;
+  const int G = type == LG_RNN_GRU ? 3 : 4;
+  if (tiled) {
+    if (!w_ih || !w_hh) return LG_ERR_INVALID;
+    rnn_tile_weights(G, input, hidden, w_ih, w_hh, tiled);
+  }
+  return (int64_t)rnn_tiled_count(G, input, hidden);
+}
+
+void lg_rnn_destroy(lg_rnn* m) {
+  if (!m) return;
+  DeviceScope ds_(m->device);
+  for (void* p : m->allocs) (void)hipFree(p);
+  delete m;
+}
+
+lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t hidden, const float* const* w_ih, const float* const* w_hh,
+                      const float* const* b_ih, const float* const* b_hh, int device_id) {
+  if (type != LG_RNN_LSTM && type != LG_RNN_GRU) { g_pol_err = "lg_rnn_create: unknown memory type (lstm | gru)"; return nullptr; }
+  if (num_layers < 1 || num_layers > RNN_MAX_LAYERS) { g_pol_err = "lg_rnn_create: number of layers out of range (1..4)"; return nullptr; }
+  if (input < 1 || input > 512) { g_pol_err = "lg_rnn_create: input width out of range (1..512)"; return nullptr; }
+  if (hidden < 1 || hidden > 512) { g_pol_err = "lg_rnn_create: hidden width out of range (1..512)"; return nullptr; }
+  if (!w_ih || !w_hh || !b_ih || !b_hh) { g_pol_err = "lg_rnn_create: null weight list"; return nullptr; }
+  for (int l = 0; l < num_layers; ++l)
+    if (!w_ih[l] || !w_hh[l] || !b_ih[l] || !b_hh[l]) { g_pol_err = "lg_rnn_create: null weight"; return nullptr; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_pol_err = "no HIP device: the policy kernels have no CPU path"; return nullptr; }
+  if (device_id < 0 || device_id >= ndev) { g_pol_err = "bad device"; return nullptr; }
+  DeviceScope ds_(device_id);
+  if (!ds_.ok) { g_pol_err = "bad device"; return nullptr; }
+  lg_rnn* m = new lg_rnn();
+  m->type = type; m->num_layers = num_layers; m->input = input; m->hidden = hidden; m->device = device_id;
+  const int G = type == LG_RNN_GRU ? 3 : 4, H = hidden;
+  for (int l = 0; l < num_layers; ++l) {
+    const int I = l == 0 ? input : hidden, Ip = (I + 15) & ~15, nch = (H + 15) / 16, Hp = 16 * nch;
+    RnnLayerDev& R = m->layer[l];
+    R.gru = type == LG_RNN_GRU; R.I = I; R.H = H; R.Ip = Ip; R.nbx = Ip / 16; R.nb = (Ip + Hp) / 16; R.nch = nch;
+    std::vector<float> tw(rnn_tiled_count(G, I, H)), tb((size_t)4 * Hp, 0.f);
+    rnn_tile_weights(G, I, H, w_ih[l], w_hh[l], tw.data());
+    for (int u = 0; u < H; ++u) {
+      if (type == LG_RNN_LSTM) {
+        for (int g = 0; g < 4; ++g) tb[(size_t)g * Hp + u] = b_ih[l][g * H + u] + b_hh[l][g * H + u];
+      } else {
+        tb[u] = b_ih[l][u] + b_hh[l][u];
+        tb[(size_t)Hp + u] = b_ih[l][H + u] + b_hh[l][H + u];
+        tb[(size_t)2 * Hp + u] = b_ih[l][2 * H + u];
+        tb[(size_t)3 * Hp + u] = b_hh[l][2 * H + u];
+      }
+    }
+    void *dw = nullptr, *db = nullptr;
+    if (hipMalloc(&dw, tw.size() * 4) != hipSuccess || hipMalloc(&db, tb.size() * 4) != hipSuccess ||
+        hipMemcpy(dw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(db, tb.data(), tb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      if (dw) m->allocs.push_back(dw);
+      if (db) m->allocs.push_back(db);
+      g_pol_err = "lg_rnn_create: weight upload failed"; lg_rnn_destroy(m); return nullptr;
+    }
+    m->allocs.push_back(dw); m->allocs.push_back(db);
+    R.w = (const float*)dw; R.b = (const float*)db;
+  }
+  return m;
+}
+
+#define RNN_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_pol_err = std::string(#expr) + ": " + hipGetErrorString(_e); return LG_ERR_HIP; } } while (0)
+
+// layers of one memory (b null), or of two memories of equal depth side by side
+static int rnn_step_pair(lg_rnn* a, const float* xa, float* ha, float* ca, float* outa, lg_rnn* b, const float* xb, float* hb, float* cb, float* outb,
+                         int64_t n, const float* reset, hipStream_t st) {
+  const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
+  for (int l = 0; l < a->num_layers; ++l) {
+    const RnnStepArgs s0 = rnn_args(a, l, xa, n, ha, ca, reset, outa);
+    const RnnStepArgs s1 = b ? rnn_args(b, l, xb, n, hb, cb, reset, outb) : s0;
+    hipLaunchKernelGGL(rnn_layer_kernel, dim3(tiles, b ? 2 : 1), dim3(MLP_THREADS), 0, st, s0, s1, n);
+  }
+  RNN_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+int lg_rnn_step(lg_rnn* m, const float* x, int64_t n, float* h, float* c, const float* reset, float* out, void* stream) {
+  if (!x) return LG_ERR_INVALID;
+  int rc = rnn_check(m, h, c, n);
+  if (rc != LG_OK || n == 0) return rc;
+  DeviceScope ds_(m->device);
+  return rnn_step_pair(m, x, h, c, out, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, (hipStream_t)stream);
+}
+
+int lg_rnn_reset_rows(lg_rnn* m, float* h, float* c, const float* dones, int64_t n, void* stream) {
+  if (!dones) return LG_ERR_INVALID;
+  int rc = rnn_check(m, h, c, n);
+  if (rc != LG_OK || n == 0) return rc;
+  DeviceScope ds_(m->device);
+  const int64_t total = (int64_t)m->num_layers * n * m->hidden;
+  hipLaunchKernelGGL(rnn_reset_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h, m->type == LG_RNN_LSTM ? c : nullptr, dones, n,
+                     m->hidden, m->num_layers);
+  RNN_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+int lg_policy_act_recurrent(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* obs, const float* critic_obs, int64_t n, const float* std_,
+                            uint64_t seed, uint64_t call, int32_t deterministic, float* h_a, float* c_a, float* h_c, float* c_c, const float* reset,
+                            float* actions, float* action_mean, float* actions_log_prob, float* values, void* stream) {
+  if (!mem_a || !mem_c || !actor || !critic || !obs || !critic_obs) return LG_ERR_INVALID;
+  int rc = rnn_check(mem_a, h_a, c_a, n);
+  if (rc == LG_OK) rc = rnn_check(mem_c, h_c, c_c, n);
+  if (rc != LG_OK) return rc;
+  if (actor->h.dims[0] != mem_a->hidden || critic->h.dims[0] != mem_c->hidden) {
+    actor->err = "lg_policy_act_recurrent: an MLP's input width is not its memory's hidden width"; return LG_ERR_INVALID;
+  }
+  if (n == 0) return LG_OK;
+  DeviceScope ds_(mem_a->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mem_a->num_layers == mem_c->num_layers) {
+    rc = rnn_step_pair(mem_a, obs, h_a, c_a, nullptr, mem_c, critic_obs, h_c, c_c, nullptr, n, reset, st);
+  } else {
+    rc = rnn_step_pair(mem_a, obs, h_a, c_a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
+    if (rc == LG_OK) rc = rnn_step_pair(mem_c, critic_obs, h_c, c_c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
+  }
+  if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
+  // the MLPs read the top layers' h' where the memory kernels left it (ActorCriticRecurrent.act / evaluate: actor(memory_a(obs)), critic(memory_c(obs)))
+  const float* top_a = h_a + (size_t)(mem_a->num_layers - 1) * n * mem_a->hidden;
+  const float* top_c = h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden;
+  return lg_policy_act(actor, critic, top_a, top_c, n, std_, seed, call, deterministic, actions, action_mean, actions_log_prob, values, stream);
+}
+
+int lg_collect_rollout_recurrent(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
+                                 int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid,
+                                 float* h_a, float* c_a, float* h_c, float* c_c, void* stream) {
+  if (!env || !mem_a || !mem_c || !actor || !critic || !std || !out || !hid || T <= 0) return LG_ERR_INVALID;
+  DeviceScope ds_(actor->device);
+  if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
+      !out->sigma || !out->last_values) { actor->err = "lg_collect_rollout_recurrent: null output row"; return LG_ERR_INVALID; }
+  const bool lstm_a = mem_a->type == LG_RNN_LSTM, lstm_c = mem_c->type == LG_RNN_LSTM;
+  if (!hid->h_a || !hid->h_c || (lstm_a && !hid->c_a) || (lstm_c && !hid->c_c)) { actor->err = "lg_collect_rollout_recurrent: null hidden-state row"; return LG_ERR_INVALID; }
+  void* p; int64_t shp[4]; int32_t nd, dt;
+  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
+  const float* obs = (const float*)p; const int64_t n = shp[0], O = shp[1];
+  int rc = rnn_check(mem_a, h_a, c_a, n);
+  if (rc == LG_OK) rc = rnn_check(mem_c, h_c, c_c, n);
+  if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
+  const int A = actor->h.dims[actor->h.L];
+  int64_t ashp[4];
+  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
+  if (mem_a->input != O || mem_c->input != O || critic->h.dims[critic->h.L] != 1 || A != ashp[1]) {
+    actor->err = "lg_collect_rollout_recurrent: network widths do not match the env (obs width, one action per DOF, scalar value)"; return LG_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t sa = (size_t)mem_a->num_layers * n * mem_a->hidden, sc = (size_t)mem_c->num_layers * n * mem_c->hidden;
+  POL_TRY(actor, hipMemcpyAsync(out->observations, obs, (size_t)n * O * 4, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
+  for (int t = 0; t < T; ++t) {
+    // RolloutStorage._save_hidden_states (rollout_storage.py:123-140): the state BEFORE this step's act (ppo.py:148-149)
+    POL_TRY(actor, hipMemcpyAsync(hid->h_a + t * sa, h_a, sa * 4, hipMemcpyDeviceToDevice, st));
+    if (lstm_a) POL_TRY(actor, hipMemcpyAsync(hid->c_a + t * sa, c_a, sa * 4, hipMemcpyDeviceToDevice, st));
+    POL_TRY(actor, hipMemcpyAsync(hid->h_c + t * sc, h_c, sc * 4, hipMemcpyDeviceToDevice, st));
+    if (lstm_c) POL_TRY(actor, hipMemcpyAsync(hid->c_c + t * sc, c_c, sc * 4, hipMemcpyDeviceToDevice, st));
+    float* obs_t = out->observations + (size_t)t * n * O;
+    float* act_t = out->actions + (size_t)t * n * A;
+    float* dones_t = out->dones + (size_t)t * n;
+    rc = lg_policy_act_recurrent(mem_a, actor, mem_c, critic, obs_t, obs_t, n, std, seed, first_call + (uint64_t)t, 0, h_a, c_a, h_c, c_c, nullptr, act_t,
+                                 out->mu + (size_t)t * n * A, out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
+    if (rc != LG_OK) return rc;
+    rc = lg_step_transition(env, act_t, t + 1 < T ? out->observations + (size_t)(t + 1) * n * O : nullptr, out->values + (size_t)t * n, gamma,
+                            out->rewards + (size_t)t * n, dones_t, stream);
+    if (rc != LG_OK) { actor->err = std::string("lg_collect_rollout_recurrent: lg_step_transition failed: ") + lg_last_error(env); return rc; }
+    // PPO.process_env_step ends with policy.reset(dones) (ppo.py:188)
+    rc = lg_rnn_reset_rows(mem_a, h_a, c_a, dones_t, n, stream);
+    if (rc == LG_OK) rc = lg_rnn_reset_rows(mem_c, h_c, c_c, dones_t, n, stream);
+    if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
+  }
+  // last_values = policy.evaluate(last obs) (ppo.py:190-192): goes through Memory.forward, so the critic memory advances once more
+  rc = lg_rnn_step(mem_c, obs, n, h_c, c_c, nullptr, nullptr, stream);
+  if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
+  rc = lg_mlp_forward(critic, h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden, n, out->last_values, stream);
+  if (rc != LG_OK) return rc;
+  if (out->returns && out->advantages)
+    rc = lg_compute_returns(out->rewards, out->dones, out->values, out->last_values, T, n, gamma, lam, normalize_advantage, out->returns,
+                            out->advantages, stream);
+  POL_TRY(actor, hipGetLastError());
+  return rc;
+}
+
+}  // extern "C"

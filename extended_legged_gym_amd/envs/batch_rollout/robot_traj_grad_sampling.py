@@ -3,8 +3,8 @@ actions -- every `step` is followed by a shift of the node trajectories, `optimi
 `rollout_batch`.  The optimiser is `utils/traj_sampler.NativeTrajSampler` (the reference delegates to the external `traj_sampling`
 package).  Built: `update_method = "mppi"`, `interp_method` linear / spline, action (de)normalisation (`:283-346`), and (round 6) the RL warm start
 (`cfg.rl_warmstart`, `:59-125,179-207,234-237,269-280`: the node trajectories start from a rollout of a trained policy through the rollout envs, and with
-`use_for_append` the node entering at the end of the horizon is the policy's action on the observation the mean trajectory ended in; MLP actors, the env's own
-observations).  Not built: `wbfo` / `avwbfo` updates, LSTM actors and privileged observations of the warm start, the predicted-state visualisation."""
+`use_for_append` the node entering at the end of the horizon is the policy's action on the observation the mean trajectory ended in; MLP or LSTM / GRU (`ActorCriticRecurrent`) actors, the env's own
+observations).  Not built: `wbfo` / `avwbfo` updates, privileged observations of the warm start, the predicted-state visualisation."""
 import torch
 
 from extended_legged_gym_amd.utils.traj_sampler import NativeTrajSampler

@@ -1,7 +1,8 @@
 """`collect_rollout`: the data-collection loop of `OnPolicyRunner.learn` (`rsl_rl/runners/on_policy_runner.py:395-445`:
 `PPO.act` -> `env.step` -> `PPO.process_env_step`, `num_steps_per_env` times, then `PPO.compute_returns`) as ONE call
 into the library (`lg_collect_rollout`, include/lgpolicy.h).  The host enqueues the whole rollout and returns; the rows
-come back as the tensors `RolloutStorage` holds (`storage/rollout_storage.py:47-76`)."""
+come back as the tensors `RolloutStorage` holds (`storage/rollout_storage.py:47-76`).  A recurrent policy (`policy.is_recurrent`) goes through
+`lg_collect_rollout_recurrent`, which also keeps the hidden-state rows of `RolloutStorage._save_hidden_states` (`:123-140`)."""
 import ctypes as C
 
 import torch
@@ -11,9 +12,12 @@ from .policy import _lib
 
 
 def collect_rollout(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_advantage=True, compute_returns=True):
-    """env: a native `LeggedRobot` (its `core` holds the context); policy: `NativeActorCritic`.  Returns a dict of
-    (T, N, .) tensors: observations, actions, rewards, dones, values, actions_log_prob, mu, sigma, returns, advantages
-    (+ last_values (N, 1)).  Draws the same samples as `num_steps` calls of `policy.act_and_evaluate`."""
+    """env: a native `LeggedRobot` (its `core` holds the context); policy: `NativeActorCritic` or `NativeActorCriticRecurrent`.  Returns a
+    dict of (T, N, .) tensors: observations, actions, rewards, dones, values, actions_log_prob, mu, sigma, returns, advantages
+    (+ last_values (N, 1)).  Draws the same samples as `num_steps` calls of `policy.act_and_evaluate`.
+    Recurrent policy: also `hidden_states_a` / `hidden_states_c`, the state of each memory BEFORE step t's act (`ppo.py:148-149`), (T, L, N, H)
+    -- a tuple `(h, c)` for an LSTM; the memories are reset on `dones[t]` after each step (`ppo.py:188`), and `last_values` advances the critic
+    memory once more, as `policy.evaluate` does in the reference (`ppo.py:190-192`)."""
     lib = _lib()
     dev = policy.device
     T, N, O, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
@@ -26,6 +30,8 @@ def collect_rollout(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_adva
         out.update(returns=z(T, N, 1), advantages=z(T, N, 1))
     rows = abi.lg_rollout(**{k: v.data_ptr() for k, v in out.items()})
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    if getattr(policy, "is_recurrent", False):
+        return _collect_recurrent(lib, env, policy, out, rows, T, N, gamma, lam, normalize_advantage, stream)
     rc = lib.lg_collect_rollout(env.core.ctx, policy.actor.handle, policy.critic.handle, C.c_void_p(policy.std.data_ptr()),
                                 policy.seed, policy._call + 1, T, float(gamma), float(lam), int(bool(normalize_advantage)),
                                 C.byref(rows), stream)
@@ -34,4 +40,25 @@ def collect_rollout(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_adva
     policy._call += T
     if hasattr(env, "common_step_counter"):
         env.common_step_counter += T
+    return out
+
+
+def _collect_recurrent(lib, env, policy, out, rows, T, N, gamma, lam, normalize_advantage, stream):
+    mems = (policy.memory_a, policy.memory_c)
+    stacks = []
+    for m in mems:
+        m.ensure_state(N)
+        stacks.append([torch.empty(T, m.num_layers, N, m.hidden_size, device=policy.device) for _ in range(2 if m.rnn_type == "lstm" else 1)])
+    ptr = [[s.data_ptr() for s in st] + [None] * (2 - len(st)) for st in stacks]
+    hidden = abi.lg_rollout_hidden(h_a=ptr[0][0], c_a=ptr[0][1], h_c=ptr[1][0], c_c=ptr[1][1])
+    rc = lib.lg_collect_rollout_recurrent(env.core.ctx, policy.memory_a.handle, policy.actor.handle, policy.memory_c.handle, policy.critic.handle,
+                                          C.c_void_p(policy.std.data_ptr()), policy.seed, policy._call + 1, T, float(gamma), float(lam),
+                                          int(bool(normalize_advantage)), C.byref(rows), C.byref(hidden), *mems[0]._ptrs(), *mems[1]._ptrs(), stream)
+    if rc != abi.LG_OK:
+        raise RuntimeError("lg_collect_rollout_recurrent failed: " + (lib.lg_mlp_last_error(policy.actor.handle) or b"").decode())
+    policy._call += T
+    if hasattr(env, "common_step_counter"):
+        env.common_step_counter += T
+    out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
+    out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
     return out

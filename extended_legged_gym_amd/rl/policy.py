@@ -2,7 +2,11 @@
 MLPs evaluated by `lg_mlp_forward` / `lg_policy_act` (include/lgpolicy.h): all layers of a network in one launch on the fp32
 matrix cores, and `PPO.act` (`algorithms/ppo.py:147-159`: sample, value, log-prob, mean, sigma) as ONE launch instead of
 ~25.  Inference only: the weights come from a trained / initialised torch `ActorCritic` (its `state_dict`), gradients
-stay in PyTorch."""
+stay in PyTorch.
+
+`NativeActorCriticRecurrent`: rsl_rl's `ActorCriticRecurrent` (`modules/actor_critic_recurrent.py:16-85`: an `nn.LSTM` / `nn.GRU`
+`Memory`, `networks/memory.py:16-51`, in front of each MLP) on `lg_rnn_step` / `lg_policy_act_recurrent`: one launch per memory layer
+(both memories side by side) plus the `PPO.act` launch.  The hidden state lives in torch tensors the kernels update in place."""
 import ctypes as C
 
 import numpy as np
@@ -147,3 +151,171 @@ class NativeActorCritic:
     @property
     def entropy(self):
         return (0.5 + 0.9189385332046727 + torch.log(self.std)).sum().expand(self._mean.shape[0])
+
+
+class NativeMemory:
+    """One `Memory` (`networks/memory.py:16-51`) in inference mode.  `layers`: per RNN layer (weight_ih, weight_hh, bias_ih, bias_hh) in torch's
+    layout; input width, hidden width and depth come from the shapes.  The state (`h`, and `c` for an LSTM; (L, n, H)) is allocated, zeroed,
+    on the first step and again when the number of rows changes, as `Memory` does with `hidden_states = None`."""
+
+    def __init__(self, layers, rnn_type="lstm", device="cuda:0"):
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("the policy kernels run on the GPU only (no CPU path)")
+        rnn_type = rnn_type.lower()
+        if rnn_type not in abi.RNN_TYPES:
+            raise ValueError(f"Unknown rnn_type: {rnn_type}. Should be 'lstm' or 'gru'")
+        self.lib, self.device, self.rnn_type = _lib(), dev, rnn_type
+        G = 4 if rnn_type == "lstm" else 3
+        arrs = [[np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in layer] for layer in layers]
+        self.num_layers, self.hidden_size, self.input_size = len(arrs), arrs[0][1].shape[1], arrs[0][0].shape[1]
+        H = self.hidden_size
+        for l, (wi, wh, bi, bh) in enumerate(arrs):
+            assert wi.shape == (G * H, self.input_size if l == 0 else H) and wh.shape == (G * H, H) and bi.shape == bh.shape == (G * H,), \
+                f"layer {l}: shapes do not belong to an nn.{rnn_type.upper()} of hidden size {H}"
+        fp = C.POINTER(C.c_float)
+        lists = [(fp * len(arrs))(*[layer[j].ctypes.data_as(fp) for layer in arrs]) for j in range(4)]
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        self.handle = self.lib.lg_rnn_create(abi.RNN_TYPES[rnn_type], self.num_layers, self.input_size, H, *lists, index)
+        if not self.handle:
+            raise RuntimeError("lg_rnn_create failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        self.h = self.c = None
+
+    @classmethod
+    def from_state(cls, state, prefix, rnn_type="lstm", device="cuda:0"):
+        """Layers `prefix.rnn.weight_ih_l0`, ... of an `ActorCriticRecurrent` state dict."""
+        L = len([k for k in state if k.startswith(prefix + ".rnn.weight_ih_l")])
+        if L == 0:
+            raise KeyError(f"no {prefix}.rnn.weight_ih_l0 in the state dict: not an ActorCriticRecurrent checkpoint")
+        layers = [[state[f"{prefix}.rnn.{name}_l{l}"].detach().cpu().numpy() for name in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] for l in range(L)]
+        return cls(layers, rnn_type, device)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def ensure_state(self, n):
+        if self.h is None or self.h.shape[1] != n:
+            self.h = torch.zeros(self.num_layers, n, self.hidden_size, device=self.device)
+            self.c = torch.zeros_like(self.h) if self.rnn_type == "lstm" else None
+
+    def _ptrs(self):
+        return C.c_void_p(self.h.data_ptr()), C.c_void_p(self.c.data_ptr() if self.c is not None else None)
+
+    @property
+    def hidden_states(self):
+        """As `Memory.hidden_states`: `(h, c)` for an LSTM, `h` for a GRU, None before the first step; views of the live state."""
+        if self.h is None:
+            return None
+        return (self.h, self.c) if self.rnn_type == "lstm" else self.h
+
+    def __call__(self, x, reset=None):
+        """`Memory.forward(input)` (inference mode): advances the state, returns the top layer's h' (n, H) -- a view of the state."""
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        assert x.dim() == 2 and x.shape[1] == self.input_size
+        n = x.shape[0]
+        self.ensure_state(n)
+        if reset is not None:
+            reset = reset.to(device=self.device, dtype=torch.float32).contiguous().view(-1)
+        rc = self.lib.lg_rnn_step(self.handle, C.c_void_p(x.data_ptr()), n, *self._ptrs(), C.c_void_p(reset.data_ptr() if reset is not None else None), None,
+                                  self._stream())
+        if rc != abi.LG_OK:
+            raise RuntimeError("lg_rnn_step failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        return self.h[-1]
+
+    def reset(self, dones=None):
+        """`Memory.reset(dones)` (`memory.py:35-51`): None forgets the state; else rows with dones != 0 are zeroed."""
+        if dones is None:
+            self.h = self.c = None
+        elif self.h is not None:
+            d = dones.to(device=self.device, dtype=torch.float32).contiguous().view(-1)
+            assert d.shape[0] == self.h.shape[1]
+            rc = self.lib.lg_rnn_reset_rows(self.handle, *self._ptrs(), C.c_void_p(d.data_ptr()), d.shape[0], self._stream())
+            if rc != abi.LG_OK:
+                raise RuntimeError("lg_rnn_reset_rows failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize(self.device)
+            self.lib.lg_rnn_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeActorCriticRecurrent(NativeActorCritic):
+    """Same surface as `ActorCriticRecurrent` for rollout collection (`actor_critic_recurrent.py:62-85`): `act`, `act_inference`, `evaluate`,
+    `reset(dones)`, `get_hidden_states`, and what `NativeActorCritic` has.  Built from an `ActorCriticRecurrent.state_dict()`
+    (`memory_a.rnn.*`, `memory_c.rnn.*`, `actor.*`, `critic.*`, `std` / `log_std`).  The batch mode of `PPO.update` (`masks=` /
+    `hidden_states=`) is not built."""
+    is_recurrent = True
+
+    def __init__(self, state_dict, activation="elu", rnn_type="lstm", noise_std_type="scalar", device="cuda:0", seed=0):
+        super().__init__(state_dict, activation, noise_std_type, device, seed)
+        self.memory_a = NativeMemory.from_state(state_dict, "memory_a", rnn_type, device)
+        self.memory_c = NativeMemory.from_state(state_dict, "memory_c", rnn_type, device)
+        if self.actor.dims[0] != self.memory_a.hidden_size or self.critic.dims[0] != self.memory_c.hidden_size:
+            raise ValueError("the MLPs of an ActorCriticRecurrent take their memory's hidden state as input")
+
+    @staticmethod
+    def _no_batch_mode(masks, hidden_states):
+        if masks is not None or hidden_states is not None:
+            raise NotImplementedError("masks= / hidden_states= (the batch mode of PPO.update) is PyTorch's job: the native policy collects rollouts only")
+
+    def reset(self, dones=None):
+        self.memory_a.reset(dones)
+        self.memory_c.reset(dones)
+
+    def get_hidden_states(self):
+        return self.memory_a.hidden_states, self.memory_c.hidden_states
+
+    def _run(self, obs, critic_obs, deterministic):
+        lib = self.actor.lib
+        obs = obs.to(device=self.device, dtype=torch.float32).contiguous()
+        cobs = obs if critic_obs is None else critic_obs.to(device=self.device, dtype=torch.float32).contiguous()
+        n = obs.shape[0]
+        assert obs.shape[1] == self.memory_a.input_size and cobs.shape == (n, self.memory_c.input_size)
+        self.memory_a.ensure_state(n)
+        self.memory_c.ensure_state(n)
+        self._actions = torch.empty(n, self.num_actions, device=self.device)
+        self._mean = torch.empty(n, self.num_actions, device=self.device)
+        self._logp = torch.empty(n, device=self.device)
+        self._values = torch.empty(n, self.critic.dims[-1], device=self.device)
+        self._call += 1
+        rc = lib.lg_policy_act_recurrent(self.memory_a.handle, self.actor.handle, self.memory_c.handle, self.critic.handle, C.c_void_p(obs.data_ptr()),
+                                         C.c_void_p(cobs.data_ptr()), n, C.c_void_p(self.std.data_ptr()), self.seed, self._call, int(deterministic),
+                                         *self.memory_a._ptrs(), *self.memory_c._ptrs(), None, C.c_void_p(self._actions.data_ptr()),
+                                         C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._logp.data_ptr()), C.c_void_p(self._values.data_ptr()),
+                                         self.actor._stream())
+        if rc != abi.LG_OK:
+            raise RuntimeError("lg_policy_act_recurrent failed: " + (lib.lg_mlp_last_error(self.actor.handle) or b"").decode())
+
+    def act(self, observations, masks=None, hidden_states=None):
+        """`ActorCriticRecurrent.act`: advances the ACTOR memory only (the critic's waits for `evaluate`); samples with `lg_policy_act` on its
+        output, so the draw for (seed, call, row) is the one `act_and_evaluate` makes.  The critic MLP of that launch runs on zeros, unused."""
+        self._no_batch_mode(masks, hidden_states)
+        lib = self.actor.lib
+        top = self.memory_a(observations)
+        n = top.shape[0]
+        idle = torch.zeros(n, self.critic.dims[0], device=self.device)
+        self._actions = torch.empty(n, self.num_actions, device=self.device)
+        self._mean = torch.empty(n, self.num_actions, device=self.device)
+        self._logp = torch.empty(n, device=self.device)
+        unused = torch.empty(n, self.critic.dims[-1], device=self.device)
+        self._call += 1
+        rc = lib.lg_policy_act(self.actor.handle, self.critic.handle, C.c_void_p(top.data_ptr()), C.c_void_p(idle.data_ptr()), n,
+                               C.c_void_p(self.std.data_ptr()), self.seed, self._call, 0, C.c_void_p(self._actions.data_ptr()),
+                               C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._logp.data_ptr()), C.c_void_p(unused.data_ptr()), self.actor._stream())
+        if rc != abi.LG_OK:
+            raise RuntimeError("lg_policy_act failed: " + (lib.lg_mlp_last_error(self.actor.handle) or b"").decode())
+        return self._actions
+
+    def act_inference(self, observations):
+        return self.actor(self.memory_a(observations))
+
+    def evaluate(self, critic_observations, masks=None, hidden_states=None):
+        self._no_batch_mode(masks, hidden_states)
+        return self.critic(self.memory_c(critic_observations))

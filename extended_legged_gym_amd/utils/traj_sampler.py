@@ -94,16 +94,23 @@ class NativeTrajSampler:
     # ---- RL warm start
     def init_rl_policy(self, rl_cfg, num_obs):
         """Load the actor of an rsl_rl checkpoint (`cfg.rl_warmstart.policy_checkpoint`: `model_state_dict` with `actor.*` / `critic.*` / `std`, optionally
-        the observation normaliser's running mean / variance) into the fused policy kernels (`NativeActorCritic.act_inference`)."""
-        from extended_legged_gym_amd.rl.policy import NativeActorCritic
-        if getattr(rl_cfg, "actor_network", "mlp") != "mlp":
-            raise NotImplementedError("rl_warmstart.actor_network: only 'mlp' (the reference's LSTM actor lives in the external traj_sampling package)")
+        the observation normaliser's running mean / variance) into the fused policy kernels (`NativeActorCritic.act_inference`).
+        `actor_network = "lstm" | "gru"`: an `ActorCriticRecurrent` checkpoint (`memory_a.rnn.*` / `memory_c.rnn.*` in front of the MLPs; the reference's planner
+        imports that class at `robot_traj_grad_sampling.py:22`) on `NativeActorCriticRecurrent`; its memory is reset before every warm-start roll-out
+        (the sampler side lives in the absent traj_sampling package: restated, unpinned)."""
+        from extended_legged_gym_amd.rl.policy import NativeActorCritic, NativeActorCriticRecurrent
+        kind = str(getattr(rl_cfg, "actor_network", "mlp")).lower()
+        if kind not in ("mlp", "lstm", "gru"):
+            raise ValueError(f"rl_warmstart.actor_network: unknown network {kind!r} (mlp | lstm | gru)")
         ck = torch.load(rl_cfg.policy_checkpoint, map_location="cpu")
         sd = ck.get("model_state_dict", ck)
-        first = sd["actor.0.weight"]
+        first = sd["actor.0.weight"] if kind == "mlp" else sd["memory_a.rnn.weight_ih_l0"]
         if first.shape[1] != num_obs:
             raise ValueError(f"rl_warmstart: the checkpoint's actor takes {first.shape[1]} observations, the env builds {num_obs}")
-        self.rl_policy = NativeActorCritic(sd, getattr(rl_cfg, "activation", "elu"), device=str(self.device))
+        if kind == "mlp":
+            self.rl_policy = NativeActorCritic(sd, getattr(rl_cfg, "activation", "elu"), device=str(self.device))
+        else:
+            self.rl_policy = NativeActorCriticRecurrent(sd, getattr(rl_cfg, "activation", "elu"), rnn_type=kind, device=str(self.device))
         norm = ck.get("obs_norm_state_dict") if isinstance(ck, dict) else None
         if getattr(rl_cfg, "standardize_obs", True) and norm is not None and "_mean" in norm and "_var" in norm:
             self.obs_mean, self.obs_var = norm["_mean"].to(self.device).float(), norm["_var"].to(self.device).float()
@@ -116,7 +123,9 @@ class NativeTrajSampler:
 
     def init_trajectories_from_rl(self, rollout_callback):
         """`rollout_callback(policy_fn)` rolls the policy out through the rollout envs and returns its actions, (M, H + 1, A) (`:78-125`); the node
-        trajectories start as that plan read off at the node times instead of zeros."""
+        trajectories start as that plan read off at the node times instead of zeros.  A recurrent actor starts the roll-out from a zero memory, so a warm
+        start never inherits state from the previous control step (restated, unpinned: the sampler side is the absent traj_sampling package)."""
+        self.rl_policy.reset()
         traj = rollout_callback(self._policy_action)
         self.mean = torch.einsum("kh,mha->mka", self.u2node, traj[:, :self.H].to(self.device)).contiguous()
         self.rl_traj_initialized = True

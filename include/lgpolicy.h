@@ -72,6 +72,64 @@ typedef struct lg_rollout {
 int lg_collect_rollout(struct lg_ctx* env, lg_mlp* actor, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
                        int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, void* stream);
 
+/* ---- recurrent actor-critic: the nn.LSTM / nn.GRU "memory" in front of each MLP (vendored rsl_rl: networks/memory.py:16-51,
+ * modules/actor_critic_recurrent.py:16-85; selected by runner.policy_class_name = "ActorCriticRecurrent" with the knobs rnn_type,
+ * rnn_hidden_size, rnn_num_layers of legged_robot_config.py:279).  Inference / collection only: the masked batch mode of PPO.update
+ * (act(obs, masks=, hidden_states=)) stays in PyTorch.
+ *
+ * One memory step for n rows, ONE launch per memory layer (the actor's and the critic's memory share a launch when they step together):
+ *     gates = W_ih x + b_ih + W_hh h + b_hh                                     (n, G H), one fp32 MFMA k-chain over [x ; h]
+ *     LSTM (torch's gate order i, f, g, o):  c' = sig(f) c + sig(i) tanh(g);   h' = sig(o) tanh(c')
+ *     GRU  (r, z, n):  n = tanh(W_in x + b_in + r * (W_hn h + b_hn));          h' = (1 - z) n + z h
+ * State: h (and c for an LSTM; NULL for a GRU), (num_layers, n, hidden) row-major f32 on the device, owned by the caller and updated IN
+ * PLACE (a workgroup owns whole rows and reads them before it writes them).  Layer l > 0 reads the h' of layer l - 1. */
+enum lg_rnn_type { LG_RNN_LSTM = 0, LG_RNN_GRU = 1 };
+typedef struct lg_rnn lg_rnn;
+
+/* One Memory.rnn (memory.py:20-22).  w_ih[l]: weight_ih_l{l} (G hidden, input or hidden), w_hh[l]: weight_hh_l{l} (G hidden, hidden),
+ * b_ih[l] / b_hh[l]: (G hidden) -- HOST pointers in torch's layout, re-tiled for the matrix cores and uploaded.  Limits: input 1..512,
+ * hidden 1..512 (any value), 1..4 layers; NULL + a message in lg_mlp_last_error(NULL) otherwise. */
+lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t hidden, const float* const* w_ih, const float* const* w_hh,
+                      const float* const* b_ih, const float* const* b_hh, int device_id);
+void lg_rnn_destroy(lg_rnn* rnn);
+
+/* The host re-tiling of one layer, a pure function (no device): tiled[((c (nb + 1) + b) G + g) 64 + lane][s] = Wcat[g hidden + 16 c + (lane & 15)][16 b + 4 s + (lane >> 4)]
+ * with Wcat[:, 0 .. input) = w_ih, Wcat[:, Ip .. Ip + hidden) = w_hh, zero elsewhere; Ip = input rounded up to 16, nb = (Ip + hidden rounded up to 16) / 16 blocks
+ * (block nb of every chunk is all zero), chunks c of 16 hidden units.  Returns the number of floats of `tiled` (HOST; NULL: only the count), negative on bad arguments. */
+int64_t lg_rnn_tile_weights(int32_t type, int32_t input, int32_t hidden, const float* w_ih, const float* w_hh, float* tiled);
+
+/* Memory.forward in inference mode (memory.py:31-33: out, hidden_states = rnn(input.unsqueeze(0), hidden_states)) for all layers.
+ * x (n, input); reset (n) f32 0 / 1 or NULL: rows with reset != 0 enter the step with h = c = 0 (Memory.reset(dones), memory.py:45-51,
+ * folded into the next step); out (n, hidden) or NULL: a copy of the top layer's h'. */
+int lg_rnn_step(lg_rnn* rnn, const float* x, int64_t n, float* h, float* c, const float* reset, float* out, void* stream);
+
+/* Memory.reset(dones) on its own (memory.py:45-51; PPO.process_env_step resets AFTER the step, ppo.py:188): rows with dones != 0 of every layer's h / c = 0. */
+int lg_rnn_reset_rows(lg_rnn* rnn, float* h, float* c, const float* dones, int64_t n, void* stream);
+
+/* PPO.act (ppo.py:147-159) for an ActorCriticRecurrent (actor_critic_recurrent.py:66-80): both memories step (one launch per layer), then
+ * lg_policy_act on the top layers' h'.  Sampling is lg_policy_act's: for equal (seed, call, row) a recurrent and a feed-forward policy
+ * draw the same standard normals.  h_a / c_a, h_c / c_c: the actor / critic memory state, in place; reset as in lg_rnn_step (both memories). */
+int lg_policy_act_recurrent(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* obs, const float* critic_obs, int64_t n,
+                            const float* std, uint64_t seed, uint64_t call, int32_t deterministic, float* h_a, float* c_a, float* h_c, float* c_c,
+                            const float* reset, float* actions, float* action_mean, float* actions_log_prob, float* values, void* stream);
+
+/* The rows RolloutStorage._save_hidden_states keeps (rollout_storage.py:123-140): per memory and state tensor (T, num_layers, n, hidden),
+ * the state BEFORE step t's act (ppo.py:148-149).  c_a / c_c NULL for a GRU. */
+typedef struct lg_rollout_hidden {
+  float* h_a;
+  float* c_a;
+  float* h_c;
+  float* c_c;
+} lg_rollout_hidden;
+
+/* lg_collect_rollout for a recurrent policy (on_policy_runner.py:395-445 with ppo.py:147-192): per step t the hidden rows are saved, both
+ * memories and MLPs run, the env steps, and both memories are reset on dones[t] (ppo.py:188).  last_values = policy.evaluate(last obs)
+ * (ppo.py:190-192) goes through Memory.forward as in the reference, so it ADVANCES the critic memory once more: the next iteration's
+ * first evaluate sees the same observation a second time.  h_a .. c_c: the live memory state, left as the loop leaves it. */
+int lg_collect_rollout_recurrent(struct lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed,
+                                 uint64_t first_call, int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* rows,
+                                 const lg_rollout_hidden* hidden, float* h_a, float* c_a, float* h_c, float* c_c, void* stream);
+
 /* ---- the sampling planner's arithmetic around rollout_batch.
  * The reference's planner envs (envs/batch_rollout/robot_traj_grad_sampling.py:210-280) hand `rollout_batch` as a callback to the
  * optimiser of the external package `traj_sampling` (imported at :18, not in the reference tree, no pinned version): per diffusion step

@@ -1,0 +1,119 @@
+"""CPU side of the recurrent policy path (include/lgpolicy.h, `lg_rnn_*`): the built library exports and declares every new entry point,
+`lg_rnn_create` refuses what the kernel cannot hold with a message, the memory kernels' code-object metadata shows no scratch and an LDS
+size a gfx950 workgroup can have, and the host re-tiling of the `[x ; h]` weights is a pure, invertible function.  No GPU needed."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from extended_legged_gym_amd import abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
+LIB = os.path.join(CSRC, "liblgstep.so")
+HIPCC = "/opt/rocm/bin/hipcc"
+LLVM = "/opt/rocm/lib/llvm/bin"
+NEW = ["lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",
+       "lg_collect_rollout_recurrent"]
+
+
+def _lib():
+    return abi.declare_policy(C.CDLL(LIB))
+
+
+def test_new_symbols_are_exported_and_declared():
+    lib = C.CDLL(LIB)
+    for sym in NEW:
+        assert sym in abi.POLICY_SYMBOLS and hasattr(lib, sym), sym
+    abi.declare_policy(lib)
+    for sym in NEW:
+        assert getattr(lib, sym).argtypes, sym
+    assert C.sizeof(abi.lg_rollout_hidden) == 4 * C.sizeof(C.c_void_p)
+    hdr = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
+    body = re.search(r"enum\s+lg_rnn_type\s*\{(.*?)\};", hdr, re.S).group(1)
+    vals = {k.strip(): int(v) for k, v in (item.split("=") for item in body.split(",") if "=" in item)}
+    assert {k[len("LG_RNN_"):].lower(): v for k, v in vals.items()} == abi.RNN_TYPES
+
+
+def test_create_refuses_out_of_range_shapes_with_a_message():
+    lib = _lib()
+    fp = C.POINTER(C.c_float)
+    w = np.zeros(4 * 513 * 513, np.float32)
+    lists = [(fp * 4)(*[w.ctypes.data_as(fp)] * 4) for _ in range(4)]
+    for args, word in (((0, 1, 48, 513), "hidden"), ((0, 0, 48, 64), "layers"), ((0, 5, 48, 64), "layers"), ((7, 1, 48, 64), "type"),
+                       ((1, 1, 513, 64), "input"), ((1, 1, 0, 64), "input")):
+        assert not lib.lg_rnn_create(*args, *lists, 0), args
+        msg = (lib.lg_mlp_last_error(None) or b"").decode()
+        assert word in msg, (args, msg)
+
+
+def _kernel_metadata(tmp_path):
+    """Metadata notes of the gfx950 code object of csrc/lg_policy.hip, compiled with the Makefile's flags (the route of tests/test_kernel_resources.py)."""
+    obj, fat, co = (str(tmp_path / n) for n in ("lg_policy.o", "fat.bin", "k.co"))
+    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize", "-c", "-o", obj,
+                    os.path.join(CSRC, "lg_policy.hip")], check=True, capture_output=True)
+    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
+    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
+                    "--unbundle"], check=True, capture_output=True)
+    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+    blocks, cur = {}, None
+    for line in notes.splitlines():
+        line = line.strip()
+        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
+            cur = {}
+        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
+        if m and cur is not None:
+            if m.group(1) == "name":
+                blocks[m.group(2)] = cur
+            elif m.group(2).isdigit():
+                cur[m.group(1)] = int(m.group(2))
+    return blocks
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_memory_kernels_use_no_scratch_and_fit_the_lds(tmp_path):
+    blocks = _kernel_metadata(tmp_path)
+    new = {k: v for k, v in blocks.items() if "rnn_" in k}
+    assert any("rnn_layer_kernel" in k for k in new) and any("rnn_reset_rows_kernel" in k for k in new), sorted(blocks)
+    for name, r in new.items():
+        print(name, r)
+        assert r["private_segment_fixed_size"] == 0 and r.get("vgpr_spill_count", 0) == 0, (name, r)
+        assert r["group_segment_fixed_size"] <= 160 * 1024, (name, r)
+    layer = [v for k, v in new.items() if "rnn_layer_kernel" in k][0]
+    # 32 rows of [x ; h] at 512 + 512 floats, nothing else staged; two waves per SIMD need <= 256 registers each
+    assert layer["group_segment_fixed_size"] == 32 * 1024 * 4 and layer["vgpr_count"] <= 256, layer
+
+
+@pytest.mark.parametrize("rnn_type,I,H", [("lstm", 48, 100), ("gru", 235, 40), ("lstm", 7, 1), ("gru", 16, 512)])
+def test_weight_tiling_round_trips(rnn_type, I, H):
+    """`lg_rnn_tile_weights` against the layout include/lgpolicy.h documents, inverted here in numpy: every weight comes back, everything else in the
+    tiled image (padding rows / columns, the zero block that ends each chunk) is zero."""
+    lib = _lib()
+    G = 4 if rnn_type == "lstm" else 3
+    rng = np.random.default_rng(I * 1000 + H)
+    w_ih, w_hh = rng.normal(size=(G * H, I)).astype(np.float32), rng.normal(size=(G * H, H)).astype(np.float32)
+    t = abi.RNN_TYPES[rnn_type]
+    count = lib.lg_rnn_tile_weights(t, I, H, None, None, None)
+    Ip, Hp = (I + 15) // 16 * 16, (H + 15) // 16 * 16
+    nb, nch = (Ip + Hp) // 16, Hp // 16
+    assert count == nch * (nb + 1) * G * 64 * 4
+    tiled = np.full(count, np.nan, np.float32)
+    assert lib.lg_rnn_tile_weights(t, I, H, w_ih.ctypes.data, w_hh.ctypes.data, tiled.ctypes.data) == count
+    tl = tiled.reshape(nch, nb + 1, G, 64, 4)
+    # tl[c, b, g, lane, s] = Wcat[g H + 16 c + (lane & 15)][16 b + 4 s + (lane >> 4)]
+    lane = np.arange(64)
+    wcat = np.zeros((G, Hp, (nb + 1) * 16), np.float32)
+    for c in range(nch):
+        for b in range(nb + 1):
+            for s in range(4):
+                wcat[:, 16 * c + (lane & 15), 16 * b + 4 * s + (lane >> 4)] = tl[c, b, :, :, s]
+    np.testing.assert_array_equal(wcat[:, :H, :I].reshape(G * H, I), w_ih)
+    np.testing.assert_array_equal(wcat[:, :H, Ip:Ip + H].reshape(G * H, H), w_hh)
+    rest = wcat.copy()
+    rest[:, :H, :I] = 0
+    rest[:, :H, Ip:Ip + H] = 0
+    assert not rest.any() and np.isfinite(tiled).all()
+    assert lib.lg_rnn_tile_weights(t, I, 513, None, None, None) < 0 and lib.lg_rnn_tile_weights(5, I, H, None, None, None) < 0
