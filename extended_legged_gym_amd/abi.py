@@ -276,6 +276,18 @@ class lg_rollout_hidden(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("h_a", "c_a", "h_c", "c_c")]
 
 
+class lg_distill_rollout(C.Structure):
+    """include/lgpolicy.h: device pointers to the (T, n, .) rows of one collected distillation rollout (+ the student's row after the last step)."""
+    _fields_ = [(k, C.c_void_p) for k in ("observations", "privileged_observations", "actions", "privileged_actions", "rewards", "dones",
+                                          "last_observations")]
+
+
+class lg_obs_history(C.Structure):
+    """include/lgpolicy.h: the observation-history layer between the env's row and the student."""
+    _fields_ = [("history", C.c_void_p), ("H", i32), ("W", i32), ("noise_scale", C.c_void_p), ("clip", f32), ("noise_seed", C.c_uint64),
+                ("inject_u", C.c_void_p)]
+
+
 def declare_policy(lib):
     """Prototypes of the rollout-collection entry points (include/lgpolicy.h), same library."""
     vp = C.c_void_p
@@ -318,13 +330,24 @@ def declare_policy(lib):
     lib.lg_collect_rollout_recurrent.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, f32, f32, i32, C.POINTER(lg_rollout), C.POINTER(lg_rollout_hidden),
                                                  vp, vp, vp, vp, vp]
     lib.lg_collect_rollout_recurrent.restype = C.c_int
+    lib.lg_obs_history_step.argtypes = [vp, C.c_int64, i32, i32, vp, C.c_int64, vp, vp, vp, u64, u64, f32, vp, vp]
+    lib.lg_obs_history_step.restype = C.c_int
+    lib.lg_distill_act.argtypes = [vp, vp, vp, vp, C.c_int64, vp, u64, u64, i32, vp, vp, vp, vp]
+    lib.lg_distill_act.restype = C.c_int
+    lib.lg_distill_act_recurrent.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, vp, u64, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lg_distill_act_recurrent.restype = C.c_int
+    lib.lg_collect_distillation.argtypes = [vp, vp, vp, vp, u64, u64, i32, C.POINTER(lg_obs_history), C.POINTER(lg_distill_rollout), vp]
+    lib.lg_collect_distillation.restype = C.c_int
+    lib.lg_collect_distillation_recurrent.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, C.POINTER(lg_obs_history), C.POINTER(lg_distill_rollout)] + [vp] * 9
+    lib.lg_collect_distillation_recurrent.restype = C.c_int
     return lib
 
 
 POLICY_SYMBOLS = ["lg_mlp_create", "lg_mlp_destroy", "lg_mlp_last_error", "lg_mlp_forward", "lg_policy_act", "lg_compute_returns",
                   "lg_collect_rollout", "lg_plan_from_nodes", "lg_mppi_update", "lg_mppi_sample_plans", "lg_planner_diffuse",
                   "lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",
-                  "lg_collect_rollout_recurrent"]
+                  "lg_collect_rollout_recurrent", "lg_obs_history_step", "lg_distill_act", "lg_distill_act_recurrent", "lg_collect_distillation",
+                  "lg_collect_distillation_recurrent"]
 RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2, "lrelu": 3, "selu": 4}
 

@@ -185,15 +185,16 @@ __global__ __launch_bounds__(MLP_THREADS) void mlp_forward_kernel(MlpDev M, cons
   mlp_tile(M, x, (int64_t)blockIdx.x * MLP_ROWS, n, buf0, buf1, nullptr, y);
 }
 
-// PPO.act: blockIdx.y = 0 actor (+ sampling, log-prob), 1 critic
-__global__ __launch_bounds__(MLP_THREADS) void policy_act_kernel(MlpDev A, MlpDev Cr, const float* __restrict__ obs, const float* __restrict__ cobs,
-                                                         int64_t n, const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi,
-                                                         uint32_t call_lo, uint32_t call_hi, int deterministic, float* __restrict__ actions,
-                                                         float* __restrict__ mean, float* __restrict__ logp, float* __restrict__ values) {
+// PPO.act: blockIdx.y = 0 actor (+ sampling, log-prob), 1 critic.  LOGP = false is Distillation.act (lg_distill_act): the second network is the teacher
+// (its whole output row goes to `values`), and no log-prob is kept (distillation.py:89-96 stores none).
+template <bool LOGP>
+LG_DEV void policy_act_body(const MlpDev& A, const MlpDev& Cr, const float* __restrict__ obs, const float* __restrict__ cobs, int64_t n,
+                            const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi, uint32_t call_lo, uint32_t call_hi, int deterministic,
+                            float* __restrict__ actions, float* __restrict__ mean, float* __restrict__ logp, float* __restrict__ values) {
   __shared__ __attribute__((aligned(16))) float buf0[MLP_IMG];
   __shared__ __attribute__((aligned(16))) float buf1[MLP_IMG];
   __shared__ float yrows[MLP_ROWS * 16 * 2];       // output rows of the actor (<= 32 actions)
-  __shared__ float lp[MLP_ROWS][32];
+  __shared__ float lp[LOGP ? MLP_ROWS : 1][32];
   const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
   if (blockIdx.y == 1) { mlp_tile(Cr, cobs, row0, n, buf0, buf1, nullptr, values); return; }
   const int na = A.dims[A.L], stride = 16 * A.nchunks[A.L - 1];
@@ -215,17 +216,34 @@ __global__ __launch_bounds__(MLP_THREADS) void policy_act_kernel(MlpDev A, MlpDe
         act = mu + sd * z;
       }
       actions[(row0 + r) * na + a] = act;
-      const float d = act - mu;
-      term = -(d * d) / (2.f * sd * sd) - logf(sd) - 0.91893853320467274178f;      // Normal.log_prob
+      if (LOGP) {
+        const float d = act - mu;
+        term = -(d * d) / (2.f * sd * sd) - logf(sd) - 0.91893853320467274178f;      // Normal.log_prob
+      }
     }
-    lp[r][a] = term;
+    if (LOGP) lp[r][a] = term;
   }
+  if (!LOGP) return;
   lds_barrier();
   if (tid < MLP_ROWS && row0 + tid < n) {
     float sacc = 0.f;
     for (int a = 0; a < na; ++a) sacc += lp[tid][a];
     logp[row0 + tid] = sacc;
   }
+}
+
+__global__ __launch_bounds__(MLP_THREADS) void policy_act_kernel(MlpDev A, MlpDev Cr, const float* __restrict__ obs, const float* __restrict__ cobs,
+                                                         int64_t n, const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi,
+                                                         uint32_t call_lo, uint32_t call_hi, int deterministic, float* __restrict__ actions,
+                                                         float* __restrict__ mean, float* __restrict__ logp, float* __restrict__ values) {
+  policy_act_body<true>(A, Cr, obs, cobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, logp, values);
+}
+
+__global__ __launch_bounds__(MLP_THREADS) void distill_act_kernel(MlpDev S, MlpDev Te, const float* __restrict__ obs, const float* __restrict__ tobs,
+                                                          int64_t n, const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi,
+                                                          uint32_t call_lo, uint32_t call_hi, int deterministic, float* __restrict__ actions,
+                                                          float* __restrict__ mean, float* __restrict__ teacher_actions) {
+  policy_act_body<false>(S, Te, obs, tobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, nullptr, teacher_actions);
 }
 
 // GAE (rollout_storage.py:145-160): one lane per env, the T-step recursion in registers
@@ -942,6 +960,210 @@ int lg_collect_rollout_recurrent(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_r
                             out->advantages, stream);
   POL_TRY(actor, hipGetLastError());
   return rc;
+}
+
+}  // extern "C"
+
+
+// ============================================================================================ teacher-student distillation (lgpolicy.h)
+// The observation-history layer (AnymalStudent.compute_observations, anymal.py:336-383) in one launch.  One lane owns one (row, column) and walks
+// its H slots from the oldest to the newest: slot s takes what slot s - 1 held, so every location is read before the same lane overwrites it and
+// the shift needs no second buffer; a row's slots are never split across lanes.  Memory-bound and tiny (4 MB at 4096 x 240): the point is one
+// launch instead of five and no host work inside the collection loop.  The noise is torch's sequence of rounded fp32 operations (2 u, - 1,
+// * scale, +): contraction is switched off for the kernel, so nothing fuses to an FMA.
+__global__ __launch_bounds__(256) void obs_history_kernel(float* __restrict__ hist, int64_t n, int H, int W, const float* __restrict__ obs, int64_t stride,
+                                                          const float* __restrict__ dones, const float* __restrict__ scale, const float* __restrict__ inject,
+                                                          uint32_t seed_lo, uint32_t seed_hi, uint32_t call_lo, uint32_t call_hi, float clip,
+                                                          float* __restrict__ out) {
+#pragma clang fp contract(off)       // every product below is rounded before it is added, as in the torch function (the compiler's default fuses them)
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * W) return;
+  const int64_t row = idx / W;
+  const int j = (int)(idx - row * W);
+  const float keep = (dones && dones[row] != 0.f) ? 0.f : 1.f;       // history * (~reset): a product, as in the torch function (-x * 0 = -0)
+  const size_t base = (size_t)row * H * W;
+  for (int s = H - 1; s >= 0; --s) {
+    const int k = s * W + j;
+    float v = s > 0 ? hist[base + k - W] * keep : obs[row * stride + j];
+    if (scale) {
+      float u;
+      if (inject) {
+        u = inject[base + k];
+      } else {
+        uint32_t o[4];
+        philox4((uint32_t)row, (uint32_t)((uint64_t)row >> 32), 0x80000000u | (uint32_t)k, call_lo ^ (call_hi * 0x9E3779B9u), seed_lo, seed_hi, o);
+        u = u01(o[0]);
+      }
+      const float t2 = 2.f * u, t1 = t2 - 1.f, ns = t1 * scale[k];
+      v = v + ns;
+    }
+    hist[base + k] = v;
+    if (out) out[base + k] = v < -clip ? -clip : (v > clip ? clip : v);           // torch.clip: a NaN stays a NaN
+  }
+}
+
+// observations[0] of a collection: the clipped copy of the history as it stands
+__global__ __launch_bounds__(256) void obs_clip_kernel(const float* __restrict__ src, int64_t count, float clip, float* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const float v = src[i];
+  dst[i] = v < -clip ? -clip : (v > clip ? clip : v);
+}
+
+static int distill_widths(lg_mlp* student, lg_mlp* teacher, const char* who) {
+  const int A = student->h.dims[student->h.L], At = teacher->h.dims[teacher->h.L];
+  if (A != At) { student->err = g_pol_err = std::string(who) + ": the student and the teacher end in different action widths"; return LG_ERR_INVALID; }
+  if (A > 32) { student->err = g_pol_err = std::string(who) + " supports up to 32 actions"; return LG_ERR_UNSUPPORTED; }
+  return LG_OK;
+}
+
+extern "C" {
+
+int lg_obs_history_step(float* history, int64_t n, int32_t H, int32_t W, const float* obs, int64_t obs_stride, const float* dones,
+                        const float* noise_scale, const float* inject_u, uint64_t seed, uint64_t call, float clip, float* obs_out, void* stream) {
+  if (H < 1 || W < 1) { g_pol_err = "lg_obs_history_step: history length H and row width W must be at least 1"; return LG_ERR_INVALID; }
+  if (obs_stride < W) { g_pol_err = "lg_obs_history_step: the observation row stride is smaller than W"; return LG_ERR_INVALID; }
+  if (!(clip > 0.f)) { g_pol_err = "lg_obs_history_step: clip must be positive (INFINITY: no clip)"; return LG_ERR_INVALID; }
+  if (!history || !obs || n < 0) { g_pol_err = "lg_obs_history_step: null history or observation pointer"; return LG_ERR_INVALID; }
+  if (n == 0) return LG_OK;
+  const int dev = device_of(history);
+  if (dev < 0) { g_pol_err = "lg_obs_history_step: the history is not device memory"; return LG_ERR_INVALID; }
+  DeviceScope ds_(dev);
+  hipLaunchKernelGGL(obs_history_kernel, dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, (hipStream_t)stream, history, n, H, W, obs, obs_stride, dones,
+                     noise_scale, inject_u, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), clip, obs_out);
+  RNN_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+int lg_distill_act(lg_mlp* student, lg_mlp* teacher, const float* obs, const float* teacher_obs, int64_t n, const float* std_, uint64_t seed,
+                   uint64_t call, int32_t deterministic, float* actions, float* action_mean, float* teacher_actions, void* stream) {
+  if (!student || !teacher || !obs || !teacher_obs || !std_ || !actions || !teacher_actions || n < 0) {
+    g_pol_err = "lg_distill_act: null network or row"; return LG_ERR_INVALID;
+  }
+  const int rc = distill_widths(student, teacher, "lg_distill_act");
+  if (rc != LG_OK) return rc;
+  if (n == 0) return LG_OK;
+  DeviceScope ds_(student->device);
+  hipLaunchKernelGGL(distill_act_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 2), dim3(MLP_THREADS), 0, (hipStream_t)stream, student->h, teacher->h,
+                     obs, teacher_obs, n, std_, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), deterministic,
+                     actions, action_mean, teacher_actions);
+  POL_TRY(student, hipGetLastError());
+  return LG_OK;
+}
+
+int lg_distill_act_recurrent(lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* obs, const float* teacher_obs, int64_t n,
+                             const float* std_, uint64_t seed, uint64_t call, int32_t deterministic, float* h_s, float* c_s, float* h_t, float* c_t,
+                             const float* reset, float* actions, float* action_mean, float* teacher_actions, void* stream) {
+  if (!mem_s || !student || !teacher || !obs || !teacher_obs) { g_pol_err = "lg_distill_act_recurrent: null network or row"; return LG_ERR_INVALID; }
+  int rc = rnn_check(mem_s, h_s, c_s, n);
+  if (rc == LG_OK && mem_t) rc = rnn_check(mem_t, h_t, c_t, n);
+  if (rc != LG_OK) return rc;
+  if (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden)) {
+    student->err = g_pol_err = "lg_distill_act_recurrent: an MLP's input width is not its memory's hidden width"; return LG_ERR_INVALID;
+  }
+  rc = distill_widths(student, teacher, "lg_distill_act_recurrent");
+  if (rc != LG_OK || n == 0) return rc;
+  DeviceScope ds_(mem_s->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mem_t && mem_t->num_layers == mem_s->num_layers) {
+    rc = rnn_step_pair(mem_s, obs, h_s, c_s, nullptr, mem_t, teacher_obs, h_t, c_t, nullptr, n, reset, st);
+  } else {
+    rc = rnn_step_pair(mem_s, obs, h_s, c_s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
+    if (rc == LG_OK && mem_t) rc = rnn_step_pair(mem_t, teacher_obs, h_t, c_t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
+  }
+  if (rc != LG_OK) { student->err = g_pol_err; return rc; }
+  const float* top_s = h_s + (size_t)(mem_s->num_layers - 1) * n * mem_s->hidden;
+  const float* top_t = mem_t ? h_t + (size_t)(mem_t->num_layers - 1) * n * mem_t->hidden : teacher_obs;
+  return lg_distill_act(student, teacher, top_s, top_t, n, std_, seed, call, deterministic, actions, action_mean, teacher_actions, stream);
+}
+
+// both collectors: mem_s NULL = the feed-forward StudentTeacher
+static int collect_distillation(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed, uint64_t first_call,
+                                int32_t T, const lg_obs_history* hist, const lg_distill_rollout* out, float* h_s, float* c_s, float* h_t, float* c_t, void* stream,
+                                const char* who) {
+  DeviceScope ds_(student->device);
+  auto fail = [&](const char* what, int rc) { student->err = g_pol_err = std::string(who) + ": " + what; return rc; };
+  if (!out->observations || !out->privileged_observations || !out->actions || !out->privileged_actions || !out->rewards || !out->dones)
+    return fail("null output row", LG_ERR_INVALID);
+  void* p; int64_t shp[4], ashp[4]; int32_t nd, dt;
+  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
+  const float* env_obs = (const float*)p; const int64_t n = shp[0], Ot = shp[1];
+  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
+  int rc = distill_widths(student, teacher, who);
+  if (rc != LG_OK) return rc;
+  const int A = student->h.dims[student->h.L];
+  const int64_t Os = mem_s ? mem_s->input : student->h.dims[0];
+  if ((mem_t ? mem_t->input : teacher->h.dims[0]) != Ot || A != ashp[1])
+    return fail("network widths do not match the env (the teacher reads the env's observation row, one action per DOF)", LG_ERR_INVALID);
+  if (mem_s && (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden)))
+    return fail("an MLP's input width is not its memory's hidden width", LG_ERR_INVALID);
+  if (hist) {
+    if (!hist->history || hist->H < 1 || hist->W < 1 || hist->W > Ot || !(hist->clip > 0.f)) return fail("bad history layer (pointer, H, W <= env row, clip > 0)", LG_ERR_INVALID);
+    if ((int64_t)hist->H * hist->W != Os) return fail("the student's input width is not H x W of the history layer", LG_ERR_INVALID);
+  } else if (Os > Ot) {
+    return fail("without a history layer the student reads a prefix of the env's observation row", LG_ERR_INVALID);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t so = (size_t)n * Os, sp = (size_t)n * Ot, sa = (size_t)n * A;
+  // the student's row after a step: the history layer, or the head of the teacher's row
+  auto student_row = [&](int t, const float* dones_t, float* dst) -> int {
+    if (hist) return lg_obs_history_step(hist->history, n, hist->H, hist->W, env_obs, Ot, dones_t, hist->noise_scale,
+                                         hist->inject_u ? hist->inject_u + (size_t)t * so : nullptr, hist->noise_seed, first_call + (uint64_t)t, hist->clip, dst, stream);
+    if (dst) POL_TRY(student, hipMemcpy2DAsync(dst, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+    return LG_OK;
+  };
+  POL_TRY(student, hipMemcpyAsync(out->privileged_observations, env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
+  if (hist) hipLaunchKernelGGL(obs_clip_kernel, dim3((unsigned)((so + 255) / 256)), dim3(256), 0, st, hist->history, (int64_t)so, hist->clip, out->observations);
+  else POL_TRY(student, hipMemcpy2DAsync(out->observations, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+  for (int t = 0; t < T; ++t) {
+    float* act_t = out->actions + t * sa;
+    float* dones_t = out->dones + (size_t)t * n;
+    if (mem_s) rc = lg_distill_act_recurrent(mem_s, student, mem_t, teacher, out->observations + t * so, out->privileged_observations + t * sp, n, std, seed,
+                                             first_call + (uint64_t)t, 0, h_s, c_s, h_t, c_t, nullptr, act_t, nullptr, out->privileged_actions + t * sa, stream);
+    else rc = lg_distill_act(student, teacher, out->observations + t * so, out->privileged_observations + t * sp, n, std, seed, first_call + (uint64_t)t, 0, act_t,
+                             nullptr, out->privileged_actions + t * sa, stream);
+    if (rc != LG_OK) return rc;
+    // Distillation.process_env_step (distillation.py:98-101) stores the env's reward as it is: no value row, no time-out bootstrap
+    rc = lg_step_transition(env, act_t, t + 1 < T ? out->privileged_observations + (t + 1) * sp : nullptr, nullptr, 0.f, out->rewards + (size_t)t * n, dones_t, stream);
+    if (rc != LG_OK) { student->err = std::string(who) + ": lg_step_transition failed: " + lg_last_error(env); return rc; }
+    rc = student_row(t, dones_t, t + 1 < T ? out->observations + (t + 1) * so : out->last_observations);
+    if (rc != LG_OK) { if (student->err.empty()) student->err = g_pol_err; return rc; }
+    if (mem_s) {                                       // policy.reset(dones) (distillation.py:105)
+      rc = lg_rnn_reset_rows(mem_s, h_s, c_s, dones_t, n, stream);
+      if (rc == LG_OK && mem_t) rc = lg_rnn_reset_rows(mem_t, h_t, c_t, dones_t, n, stream);
+      if (rc != LG_OK) { student->err = g_pol_err; return rc; }
+    }
+  }
+  POL_TRY(student, hipGetLastError());
+  return LG_OK;
+}
+
+int lg_collect_distillation(lg_ctx* env, lg_mlp* student, lg_mlp* teacher, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
+                            const lg_obs_history* history, const lg_distill_rollout* rows, void* stream) {
+  if (!env || !student || !teacher || !std || !rows || T <= 0) { g_pol_err = "lg_collect_distillation: null argument or T < 1"; return LG_ERR_INVALID; }
+  return collect_distillation(env, nullptr, student, nullptr, teacher, std, seed, first_call, T, history, rows, nullptr, nullptr, nullptr, nullptr, stream,
+                              "lg_collect_distillation");
+}
+
+int lg_collect_distillation_recurrent(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed,
+                                      uint64_t first_call, int32_t T, const lg_obs_history* history, const lg_distill_rollout* rows, float* h_s0, float* c_s0,
+                                      float* h_t0, float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, void* stream) {
+  if (!env || !mem_s || !student || !teacher || !std || !rows || T <= 0) { g_pol_err = "lg_collect_distillation_recurrent: null argument or T < 1"; return LG_ERR_INVALID; }
+  void* p; int64_t shp[4]; int32_t nd, dt;
+  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
+  const int64_t n = shp[0];
+  int rc = rnn_check(mem_s, h_s, c_s, n);
+  if (rc == LG_OK && mem_t) rc = rnn_check(mem_t, h_t, c_t, n);
+  if (rc != LG_OK) { student->err = g_pol_err; return rc; }
+  DeviceScope ds_(student->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t ss = (size_t)mem_s->num_layers * n * mem_s->hidden * 4, stt = mem_t ? (size_t)mem_t->num_layers * n * mem_t->hidden * 4 : 0;
+  if (h_s0) POL_TRY(student, hipMemcpyAsync(h_s0, h_s, ss, hipMemcpyDeviceToDevice, st));
+  if (c_s0 && mem_s->type == LG_RNN_LSTM) POL_TRY(student, hipMemcpyAsync(c_s0, c_s, ss, hipMemcpyDeviceToDevice, st));
+  if (mem_t && h_t0) POL_TRY(student, hipMemcpyAsync(h_t0, h_t, stt, hipMemcpyDeviceToDevice, st));
+  if (mem_t && c_t0 && mem_t->type == LG_RNN_LSTM) POL_TRY(student, hipMemcpyAsync(c_t0, c_t, stt, hipMemcpyDeviceToDevice, st));
+  return collect_distillation(env, mem_s, student, mem_t, teacher, std, seed, first_call, T, history, rows, h_s, c_s, h_t, c_t, stream,
+                              "lg_collect_distillation_recurrent");
 }
 
 }  // extern "C"

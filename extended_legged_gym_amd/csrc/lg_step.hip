@@ -2971,7 +2971,8 @@ int lg_step_transition(lg_ctx* c, const float* actions, float* next_observations
                        float* dones, void* stream) {
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);
-  if (!actions || !values || !rewards || !dones) { c->err = "lg_step_transition: null row"; return LG_ERR_INVALID; }
+  // values NULL: no time-out bootstrap (the post-physics kernel reads a missing value row as 0): the raw reward, what Distillation.process_env_step stores
+  if (!actions || !rewards || !dones) { c->err = "lg_step_transition: null row"; return LG_ERR_INVALID; }
   return launch_step(c, (hipStream_t)stream, step_shape(c, true, false, 1), actions, nullptr, c->h.N, NDOF, 0, PostSink{next_observations, values, rewards, dones, gamma});
 }
 

@@ -1,5 +1,7 @@
 """Rollout-collection side of PPO on the GPU: `NativeActorCritic`, `NativeActorCriticRecurrent`
-(LSTM / GRU memory in front of each MLP), `compute_returns`, `collect_rollout`."""
-from .policy import NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP          # noqa: F401
+(LSTM / GRU memory in front of each MLP), `compute_returns`, `collect_rollout`; teacher-student distillation: `NativeStudentTeacher`, `NativeStudentTeacherRecurrent`,
+`collect_distillation`, `obs_history_step`."""
+from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
+                     NativeStudentTeacher, NativeStudentTeacherRecurrent)
 from .storage import compute_returns                      # noqa: F401
-from .collector import collect_rollout                    # noqa: F401
+from .collector import collect_distillation, collect_rollout, obs_history_step          # noqa: F401

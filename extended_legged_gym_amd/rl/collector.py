@@ -62,3 +62,103 @@ def _collect_recurrent(lib, env, policy, out, rows, T, N, gamma, lam, normalize_
     out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
     out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
     return out
+
+
+def obs_history_step(history, obs, dones=None, noise_scale=None, clip=float("inf"), noise_uniforms=None, seed=0, call=0):
+    """`lg_obs_history_step` (include/lgpolicy.h): one step of an observation-history layer, `student_history_update` + clip
+    (`envs/anymal_c/anymal.py`) in one launch.  history (N, H, W) float32 contiguous, updated IN PLACE; obs (N, >= W): its first W columns enter
+    slot 0 (rows may be strided); dones (N) or None; noise_scale (H W) or None: no noise; noise_uniforms (N, H W) replaces the Philox draws of
+    (seed, call).  Returns the clipped observations (N, H W)."""
+    lib = _lib()
+    assert history.is_cuda and history.dtype == torch.float32 and history.is_contiguous() and history.dim() == 3
+    N, H, W = history.shape
+    dev = history.device
+    obs = obs.to(dev, torch.float32)
+    if obs.stride(1) != 1:
+        obs = obs.contiguous()
+    assert obs.shape[0] == N and obs.shape[1] >= W
+
+    def opt(x, shape):
+        if x is None:
+            return None
+        x = x.to(dev, torch.float32).contiguous()
+        assert x.shape == shape, (tuple(x.shape), shape)
+        return x
+    dones, scale, u = opt(dones, (N,)), opt(noise_scale, (H * W,)), opt(noise_uniforms, (N, H * W))
+    out = torch.empty(N, H * W, device=dev)
+
+    def ptr(x):
+        return C.c_void_p(x.data_ptr()) if x is not None else None
+    rc = lib.lg_obs_history_step(ptr(history), N, H, W, ptr(obs), obs.stride(0), ptr(dones), ptr(scale), ptr(u), int(seed), int(call), float(clip), ptr(out),
+                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != abi.LG_OK:
+        raise RuntimeError("lg_obs_history_step failed: " + (lib.lg_mlp_last_error(None) or b"").decode())
+    return out
+
+
+def collect_distillation(env, policy, num_steps, noise_uniforms=None):
+    """The collection loop of `OnPolicyRunner.learn` with `Distillation.act` / `process_env_step` (`rsl_rl/algorithms/distillation.py:89-105`) as ONE call
+    into the library (`lg_collect_distillation`, include/lgpolicy.h).  env: a native `LeggedRobot`; policy: `NativeStudentTeacher` or
+    `NativeStudentTeacherRecurrent`.  Returns the (T, N, .) tensors `RolloutStorage` holds in "distillation" mode (`storage/rollout_storage.py:65-67,
+    102-104`): observations, privileged_observations, actions, privileged_actions, rewards (the env's raw reward: no time-out bootstrap), dones.
+    Draws the same samples as `num_steps` calls of `policy.act_and_teach`.
+
+    An env with an observation history (`AnymalStudent`: `obs_history`, (N, H, 48)) hands that buffer to the library, which steps it in place
+    (`lg_obs_history_step`); `env.obs_buf` is left as the student's observation after the last step, so a following `env.step` or
+    `collect_distillation` continues the same history.  Noise follows `env.add_noise`, drawn by Philox (seed derived from the policy's, call = the
+    sampling call); `noise_uniforms` (T, N, H * 48) replaces the draws (the checker mode).  Any other env: the student reads the first columns of
+    the env's observation row.  Recurrent policy: also `hidden_states`, the `(memory_s, memory_t)` state BEFORE step 0 in `get_hidden_states()` form --
+    distillation keeps no per-step hidden rows; this seeds `policy.reset(hidden_states=...)` of the update."""
+    lib = _lib()
+    dev = policy.device
+    rec = getattr(policy, "is_recurrent", False)
+    T, N, Ot, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
+    Os = policy.memory_s.input_size if rec else policy.student.dims[0]
+
+    def z(*shape):
+        return torch.empty(*shape, device=dev, dtype=torch.float32)
+    out = dict(observations=z(T, N, Os), privileged_observations=z(T, N, Ot), actions=z(T, N, A), privileged_actions=z(T, N, A), rewards=z(T, N, 1),
+               dones=z(T, N, 1))
+    last = z(N, Os)
+    rows = abi.lg_distill_rollout(last_observations=last.data_ptr(), **{k: v.data_ptr() for k, v in out.items()})
+    hist = getattr(env, "obs_history", None)
+    layer, keep = None, []
+    if hist is not None:
+        if not (hist.is_contiguous() and hist.dtype == torch.float32 and hist.shape[0] == N):
+            raise ValueError("env.obs_history must be a contiguous float32 (N, H, W) tensor")
+        H, W = hist.shape[1], hist.shape[2]
+        scale = env.noise_scale_vec[:H * W].to(dev, torch.float32).contiguous() if getattr(env, "add_noise", False) else None
+        if noise_uniforms is not None:
+            noise_uniforms = noise_uniforms.to(dev, torch.float32).contiguous()
+            assert noise_uniforms.shape == (T, N, H * W)
+        keep = [scale, noise_uniforms]
+        layer = abi.lg_obs_history(history=hist.data_ptr(), H=H, W=W, noise_scale=scale.data_ptr() if scale is not None else None,
+                                   clip=float(env.cfg.normalization.clip_observations), noise_seed=(policy.seed ^ 0x5DEECE66D) & (2 ** 64 - 1),
+                                   inject_u=noise_uniforms.data_ptr() if noise_uniforms is not None else None)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    lp = C.byref(layer) if layer is not None else None
+    if rec:
+        mems = (policy.memory_s, policy.memory_t)
+        before = []
+        for m in mems:
+            if m is not None:
+                m.ensure_state(N)
+            before.append(None if m is None else [torch.empty_like(m.h)] + ([torch.empty_like(m.c)] if m.rnn_type == "lstm" else []))
+        p0 = [[C.c_void_p(b.data_ptr()) for b in bs] + [None] * (2 - len(bs)) if bs is not None else [None, None] for bs in before]
+        live = [m._ptrs() if m is not None else (None, None) for m in mems]
+        rc = lib.lg_collect_distillation_recurrent(env.core.ctx, mems[0].handle, policy.student.handle, mems[1].handle if mems[1] is not None else None,
+                                                   policy.teacher.handle, C.c_void_p(policy.std.data_ptr()), policy.seed, policy._call + 1, T, lp, C.byref(rows),
+                                                   *p0[0], *p0[1], *live[0], *live[1], stream)
+        out["hidden_states"] = tuple(None if bs is None else (tuple(bs) if len(bs) == 2 else bs[0]) for bs in before)
+    else:
+        rc = lib.lg_collect_distillation(env.core.ctx, policy.student.handle, policy.teacher.handle, C.c_void_p(policy.std.data_ptr()), policy.seed,
+                                         policy._call + 1, T, lp, C.byref(rows), stream)
+    if rc != abi.LG_OK:
+        raise RuntimeError("lg_collect_distillation failed: " + (lib.lg_mlp_last_error(policy.student.handle) or b"").decode())
+    del keep
+    policy._call += T
+    if hasattr(env, "common_step_counter"):
+        env.common_step_counter += T
+    if hist is not None:
+        env.obs_buf = last
+    return out

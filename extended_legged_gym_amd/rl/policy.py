@@ -319,3 +319,169 @@ class NativeActorCriticRecurrent(NativeActorCritic):
     def evaluate(self, critic_observations, masks=None, hidden_states=None):
         self._no_batch_mode(masks, hidden_states)
         return self.critic(self.memory_c(critic_observations))
+
+
+TEACHER_MEMORY_MESSAGE = "Loading recurrent memory for the teacher is not implemented yet"
+
+
+def _split_distillation_state(state_dict, student_state_dict):
+    """The two loading rules of `StudentTeacher.load_state_dict` (`student_teacher.py:111-146`): a PPO checkpoint (`actor.*`) fills the teacher only --
+    the student then comes from `student_state_dict` (`student.*`, `std`, `memory_s.*`) --, a distillation checkpoint (`student.*` / `teacher.*` / `std`)
+    fills both.  Returns (dict with the teacher, dict with the student, teacher prefix, resumed)."""
+    if any("actor" in k for k in state_dict):
+        if student_state_dict is None or not any(k.startswith("student.") for k in student_state_dict):
+            raise ValueError("a PPO checkpoint (actor.*) holds the teacher only: pass the student's parameters (student.*, std) as student_state_dict")
+        return state_dict, student_state_dict, "actor", False
+    if any("student" in k for k in state_dict):
+        return state_dict, state_dict, "teacher", True
+    raise ValueError("state_dict does not contain student or teacher parameters")
+
+
+class NativeStudentTeacher:
+    """Same surface as rsl_rl's `StudentTeacher` (`modules/student_teacher.py:75-152`) for collection with `Distillation` (`distillation.py:89-105`)
+    and for `get_inference_policy`: `act`, `act_inference`, `evaluate`, `reset`, `get_hidden_states`, `action_mean`, `action_std`, `loaded_teacher`;
+    `act_and_teach(obs, teacher_obs)` is `Distillation.act` as ONE launch (`lg_distill_act`).  Inference only: `Distillation.update` trains a torch
+    `StudentTeacher` whose state dict builds this object."""
+    is_recurrent = False
+
+    def __init__(self, state_dict, student_state_dict=None, activation="elu", device="cuda:0", seed=0):
+        self.device = torch.device(device)
+        tsd, ssd, tprefix, self.resumed = _split_distillation_state(state_dict, student_state_dict)
+        self._check_teacher_memory(tprefix)
+        self.teacher = NativeMLP.from_sequential_state(tsd, tprefix, activation, device)
+        self.student = NativeMLP.from_sequential_state(ssd, "student", activation, device)
+        self.loaded_teacher = True
+        self.std = ssd["std"].detach().to(self.device, torch.float32).contiguous()
+        self.num_actions = self.student.dims[-1]
+        if self.teacher.dims[-1] != self.num_actions:
+            raise ValueError(f"the teacher ends in {self.teacher.dims[-1]} actions, the student in {self.num_actions}")
+        self.seed, self._call = int(seed), 0
+        self._mean = self._actions = self._teacher_actions = None
+        self._sources = (tsd, ssd)
+
+    def _check_teacher_memory(self, tprefix):
+        pass
+
+    def reset(self, dones=None, hidden_states=None):
+        pass
+
+    def get_hidden_states(self):
+        return None
+
+    def detach_hidden_states(self, dones=None):
+        pass
+
+    def _rows(self, n):
+        self._actions = torch.empty(n, self.num_actions, device=self.device)
+        self._mean = torch.empty(n, self.num_actions, device=self.device)
+        self._teacher_actions = torch.empty(n, self.num_actions, device=self.device)
+        self._call += 1
+
+    def _launch(self, obs, tobs, deterministic=False):
+        lib = self.student.lib
+        n = obs.shape[0]
+        assert obs.shape == (n, self.student.dims[0]) and tobs.shape == (n, self.teacher.dims[0])
+        self._rows(n)
+        rc = lib.lg_distill_act(self.student.handle, self.teacher.handle, C.c_void_p(obs.data_ptr()), C.c_void_p(tobs.data_ptr()), n,
+                                C.c_void_p(self.std.data_ptr()), self.seed, self._call, int(deterministic), C.c_void_p(self._actions.data_ptr()),
+                                C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._teacher_actions.data_ptr()), self.student._stream())
+        if rc != abi.LG_OK:
+            raise RuntimeError("lg_distill_act failed: " + (lib.lg_mlp_last_error(self.student.handle) or b"").decode())
+
+    def _f32(self, x):
+        return x.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def act_and_teach(self, obs, teacher_obs):
+        """`Distillation.act` in one launch: (actions, privileged_actions)."""
+        self._launch(self._f32(obs), self._f32(teacher_obs))
+        return self._actions, self._teacher_actions
+
+    def act(self, observations):
+        """`StudentTeacher.act`: the same launch with the teacher on zeros (unused), so the draw for (seed, call, row) is `act_and_teach`'s."""
+        obs = self._f32(observations)
+        self._launch(obs, torch.zeros(obs.shape[0], self.teacher.dims[0], device=self.device))
+        return self._actions
+
+    def act_inference(self, observations):
+        return self.student(observations)
+
+    def evaluate(self, teacher_observations):
+        return self.teacher(teacher_observations)
+
+    @property
+    def action_mean(self):
+        return self._mean
+
+    @property
+    def action_std(self):
+        return self.std.expand_as(self._mean)
+
+    @property
+    def entropy(self):
+        return (0.5 + 0.9189385332046727 + torch.log(self.std)).sum().expand(self._mean.shape[0])
+
+
+class NativeStudentTeacherRecurrent(NativeStudentTeacher):
+    """`StudentTeacherRecurrent` (`modules/student_teacher_recurrent.py:15-100`): an `nn.LSTM` / `nn.GRU` `Memory` in front of the student and, with
+    `teacher_recurrent`, in front of the teacher (`memory_s.rnn.*`, `memory_t.rnn.*`).  A recurrent teacher cannot come from a PPO checkpoint: the
+    reference raises `NotImplementedError` there (`student_teacher.py:133-134`), and so does this class."""
+    is_recurrent = True
+
+    def __init__(self, state_dict, student_state_dict=None, activation="elu", rnn_type="lstm", teacher_recurrent=False, device="cuda:0", seed=0):
+        self.teacher_recurrent = bool(teacher_recurrent)
+        super().__init__(state_dict, student_state_dict, activation, device, seed)
+        tsd, ssd = self._sources
+        self.memory_s = NativeMemory.from_state(ssd, "memory_s", rnn_type, device)
+        self.memory_t = NativeMemory.from_state(tsd, "memory_t", rnn_type, device) if self.teacher_recurrent else None
+        if self.student.dims[0] != self.memory_s.hidden_size or (self.memory_t is not None and self.teacher.dims[0] != self.memory_t.hidden_size):
+            raise ValueError("the MLPs of a StudentTeacherRecurrent take their memory's hidden state as input")
+
+    def _check_teacher_memory(self, tprefix):
+        if tprefix == "actor" and self.teacher_recurrent:
+            raise NotImplementedError(TEACHER_MEMORY_MESSAGE)
+
+    def reset(self, dones=None, hidden_states=None):
+        """`StudentTeacherRecurrent.reset` (`:71-76`) with `Memory.reset(dones, hidden_states)` (`memory.py:35-51`): `dones` None installs
+        `hidden_states` (None: forgets the state), else zeroes the done rows."""
+        hs = hidden_states if hidden_states is not None else (None, None)
+        for mem, h in ((self.memory_s, hs[0]), (self.memory_t, hs[1])):
+            if mem is None:
+                continue
+            if dones is None and h is not None:
+                parts = h if isinstance(h, (tuple, list)) else (h,)
+                mem.h = parts[0].detach().to(self.device, torch.float32).clone().contiguous()
+                mem.c = parts[1].detach().to(self.device, torch.float32).clone().contiguous() if mem.rnn_type == "lstm" else None
+            else:
+                mem.reset(dones)
+
+    def get_hidden_states(self):
+        return self.memory_s.hidden_states, (self.memory_t.hidden_states if self.memory_t is not None else None)
+
+    def _launch(self, obs, tobs, deterministic=False):
+        lib = self.student.lib
+        n = obs.shape[0]
+        mt = self.memory_t
+        assert obs.shape == (n, self.memory_s.input_size) and tobs.shape == (n, mt.input_size if mt is not None else self.teacher.dims[0])
+        self.memory_s.ensure_state(n)
+        if mt is not None:
+            mt.ensure_state(n)
+        self._rows(n)
+        tptrs = mt._ptrs() if mt is not None else (None, None)
+        rc = lib.lg_distill_act_recurrent(self.memory_s.handle, self.student.handle, mt.handle if mt is not None else None, self.teacher.handle,
+                                          C.c_void_p(obs.data_ptr()), C.c_void_p(tobs.data_ptr()), n, C.c_void_p(self.std.data_ptr()), self.seed, self._call,
+                                          int(deterministic), *self.memory_s._ptrs(), *tptrs, None, C.c_void_p(self._actions.data_ptr()),
+                                          C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._teacher_actions.data_ptr()), self.student._stream())
+        if rc != abi.LG_OK:
+            raise RuntimeError("lg_distill_act_recurrent failed: " + (lib.lg_mlp_last_error(self.student.handle) or b"").decode())
+
+    def act(self, observations):
+        """Advances the STUDENT memory only (the teacher's waits for `evaluate`), then samples with the feed-forward launch on its output."""
+        top = self.memory_s(observations)
+        NativeStudentTeacher._launch(self, top, torch.zeros(top.shape[0], self.teacher.dims[0], device=self.device))
+        return self._actions
+
+    def act_inference(self, observations):
+        return self.student(self.memory_s(observations))
+
+    def evaluate(self, teacher_observations):
+        return self.teacher(self.memory_t(teacher_observations) if self.memory_t is not None else teacher_observations)

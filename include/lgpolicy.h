@@ -130,6 +130,77 @@ int lg_collect_rollout_recurrent(struct lg_ctx* env, lg_rnn* mem_a, lg_mlp* acto
                                  uint64_t first_call, int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* rows,
                                  const lg_rollout_hidden* hidden, float* h_a, float* c_a, float* h_c, float* c_c, void* stream);
 
+/* ---- teacher-student distillation (vendored rsl_rl: algorithms/distillation.py:89-105, modules/student_teacher.py:93-109,
+ * modules/student_teacher_recurrent.py:71-95; selected by runner.policy_class_name = "StudentTeacher" / "StudentTeacherRecurrent" with
+ * algorithm_class_name = "Distillation").  Collection only: Distillation.update (distillation.py:107-153) stays in PyTorch.
+ *
+ * lg_obs_history_step: the observation-history layer of a student env, AnymalStudent.compute_observations (envs/anymal_c/anymal.py:336-383)
+ * after reset_idx zeroed the rows of the envs that were reset (:330-334), in ONE launch, on an (n, H, W) history IN PLACE:
+ *     1. rows with dones != 0 are zeroed;   2. slots shift by one, oldest out;   3. slot 0 = obs[row, 0 .. W) (obs has row stride obs_stride >= W);
+ *     4. history[row, k] += (2 u - 1) * noise_scale[k] for ALL k = slot * W + column in [0, H W): the reference adds the noise to a view of the history,
+ *        so older slots collect a fresh draw every step;   5. obs_out[row, k] = clamp(history[row, k], -clip, clip); the stored history stays unclipped.
+ * u: inject_u (n, H W) when given (the checker mode: the result then equals the torch function bit for bit -- 2 u, - 1, * scale, + are four rounded fp32
+ * operations, no FMA); otherwise Philox4x32-10 with counter (row_lo, row_hi, 0x80000000 | k, call_lo ^ (call_hi * 0x9E3779B9)) and key (seed_lo, seed_hi),
+ * u = u01 of its first word (the generator of lg_policy_act; bit 31 of the third counter word keeps the draws apart from lg_policy_act's for equal
+ * seed and call).  noise_scale NULL: no noise.  dones (n) f32 0 / 1 or NULL; obs_out (n, H W) or NULL; clip > 0 (INFINITY: no clip).
+ * LG_ERR_INVALID for H < 1, W < 1, obs_stride < W, clip <= 0 or a NULL history / obs (message in lg_mlp_last_error(NULL)). */
+int lg_obs_history_step(float* history, int64_t n, int32_t H, int32_t W, const float* obs, int64_t obs_stride, const float* dones,
+                        const float* noise_scale, const float* inject_u, uint64_t seed, uint64_t call, float clip, float* obs_out, void* stream);
+
+/* Distillation.act (distillation.py:89-96) for a StudentTeacher (student_teacher.py:93-109): one launch of lg_policy_act's kernel with the teacher
+ * in the second slot and no log-prob:
+ *   action_mean = student(obs); actions = action_mean + std * z (deterministic != 0: actions = action_mean); teacher_actions = teacher(teacher_obs).
+ * For equal (seed, call, row) z is what lg_policy_act draws.  Both networks must end in the same width A <= 32; action_mean (n, A) or NULL. */
+int lg_distill_act(lg_mlp* student, lg_mlp* teacher, const float* obs, const float* teacher_obs, int64_t n, const float* std, uint64_t seed,
+                   uint64_t call, int32_t deterministic, float* actions, float* action_mean, float* teacher_actions, void* stream);
+
+/* The same for a StudentTeacherRecurrent (student_teacher_recurrent.py:78-89): the student's memory steps, and the teacher's when it has one (both
+ * in one launch per layer when their depths agree, as in lg_policy_act_recurrent); mem_t NULL: the teacher MLP reads teacher_obs directly
+ * (teacher_recurrent = False; h_t / c_t are then ignored).  h_s / c_s, h_t / c_t: memory state, in place; reset as in lg_rnn_step. */
+int lg_distill_act_recurrent(lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* obs, const float* teacher_obs, int64_t n,
+                             const float* std, uint64_t seed, uint64_t call, int32_t deterministic, float* h_s, float* c_s, float* h_t, float* c_t,
+                             const float* reset, float* actions, float* action_mean, float* teacher_actions, void* stream);
+
+/* The rows RolloutStorage keeps in "distillation" mode (rollout_storage.py:65-67, 102-104, 170-182), (T, n, .) row-major f32. */
+typedef struct lg_distill_rollout {
+  float* observations;              /* (T, n, O_s)  the student's */
+  float* privileged_observations;   /* (T, n, O_t)  the teacher's: the env's observation row */
+  float* actions;                   /* (T, n, A)    the student's sampled actions */
+  float* privileged_actions;        /* (T, n, A)    the teacher's */
+  float* rewards;                   /* (T, n)       the env's raw reward: no time-out bootstrap (distillation.py:98-101) */
+  float* dones;                     /* (T, n) */
+  float* last_observations;         /* (n, O_s) or NULL: the student's observation after the last step */
+} lg_distill_rollout;
+
+/* The history layer between the env's row and the student (lg_obs_history_step): step t of a collection uses noise call first_call + t and,
+ * when given, the uniforms inject_u[t]. */
+typedef struct lg_obs_history {
+  float* history;             /* (n, H, W), in place */
+  int32_t H, W;
+  const float* noise_scale;   /* (H W) or NULL: no noise */
+  float clip;
+  uint64_t noise_seed;
+  const float* inject_u;      /* (T, n, H W) or NULL: Philox */
+} lg_obs_history;
+
+/* The collection loop of OnPolicyRunner.learn (on_policy_runner.py:395-445) with Distillation.act / process_env_step (distillation.py:89-105), without
+ * returning to the host between steps: for t in [0, T):
+ *     lg_distill_act on observations[t], privileged_observations[t] -> actions[t], privileged_actions[t]   (Philox call first_call + t);
+ *     one env step (lg_step_transition without a value row: rewards[t] = the env's reward, dones[t] = reset_buf), the next teacher row written
+ *     straight into privileged_observations[t + 1];
+ *     the student's next row: lg_obs_history_step on `history` -> observations[t + 1] (last_observations after the last step).
+ * Row 0: privileged_observations[0] = the env's observation row, observations[0] = clamp(history, +-clip).  history NULL: the student sees the first
+ * O_s columns of the teacher's row.  O_s = the student's input width, O_t = the env's observation width = the teacher's input width. */
+int lg_collect_distillation(struct lg_ctx* env, lg_mlp* student, lg_mlp* teacher, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
+                            const lg_obs_history* history, const lg_distill_rollout* rows, void* stream);
+
+/* The same for a StudentTeacherRecurrent; both memories are reset on dones[t] after each step (distillation.py:105).  h_s .. c_t: the live memory
+ * state, left as the loop leaves it.  h_s0 .. c_t0 (each (L, n, hidden), or NULL): the state BEFORE step 0 -- distillation mode keeps no per-step
+ * hidden rows (Distillation.act never sets transition.hidden_states); this is what seeds policy.reset(hidden_states=...) for the update. */
+int lg_collect_distillation_recurrent(struct lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std,
+                                      uint64_t seed, uint64_t first_call, int32_t T, const lg_obs_history* history, const lg_distill_rollout* rows,
+                                      float* h_s0, float* c_s0, float* h_t0, float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, void* stream);
+
 /* ---- the sampling planner's arithmetic around rollout_batch.
  * The reference's planner envs (envs/batch_rollout/robot_traj_grad_sampling.py:210-280) hand `rollout_batch` as a callback to the
  * optimiser of the external package `traj_sampling` (imported at :18, not in the reference tree, no pinned version): per diffusion step

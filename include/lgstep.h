@@ -363,7 +363,8 @@ int lg_step_physics(lg_ctx* ctx, const float* actions, void* stream);
 /* lg_step for a caller that keeps a rollout storage (rsl_rl's runner loop, on_policy_runner.py:401-445): the post-physics
  * kernel also writes the new observation rows to `next_observations` (num_envs, num_obs; RolloutStorage.observations[t + 1],
  * may be NULL), rewards[k] = rew + gamma * values[k] * time_out (PPO.process_env_step, ppo.py:179-183) and dones[k]
- * (ppo.py:165) -- no copy / transition kernels after the step.  Device pointers. */
+ * (ppo.py:165) -- no copy / transition kernels after the step.  Device pointers.  values NULL: rewards[k] = rew, no
+ * bootstrap (Distillation.process_env_step, distillation.py:98-101). */
 int lg_step_transition(lg_ctx* ctx, const float* actions, float* next_observations, const float* values, float gamma,
                        float* rewards, float* dones, void* stream);
 
