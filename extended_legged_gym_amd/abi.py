@@ -340,6 +340,18 @@ def declare_policy(lib):
     lib.lg_collect_distillation.restype = C.c_int
     lib.lg_collect_distillation_recurrent.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, C.POINTER(lg_obs_history), C.POINTER(lg_distill_rollout)] + [vp] * 9
     lib.lg_collect_distillation_recurrent.restype = C.c_int
+    lib.lg_conv_encoder_create.argtypes = [i32, i32, i32, i32, fpp, fpp, C.c_int]
+    lib.lg_conv_encoder_create.restype = vp
+    lib.lg_conv_encoder_destroy.argtypes = [vp]
+    lib.lg_conv_encoder_destroy.restype = None
+    lib.lg_conv_tile_weights.argtypes = [i32, i32, i32, i32, vp, vp]
+    lib.lg_conv_tile_weights.restype = C.c_int64
+    lib.lg_conv_encoder_forward.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
+    lib.lg_conv_encoder_forward.restype = C.c_int
+    lib.lg_mlp_set_output_activation.argtypes = [vp, i32]
+    lib.lg_mlp_set_output_activation.restype = C.c_int
+    lib.lg_estimator_step.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.lg_estimator_step.restype = C.c_int
     return lib
 
 
@@ -347,7 +359,11 @@ POLICY_SYMBOLS = ["lg_mlp_create", "lg_mlp_destroy", "lg_mlp_last_error", "lg_ml
                   "lg_collect_rollout", "lg_plan_from_nodes", "lg_mppi_update", "lg_mppi_sample_plans", "lg_planner_diffuse",
                   "lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",
                   "lg_collect_rollout_recurrent", "lg_obs_history_step", "lg_distill_act", "lg_distill_act_recurrent", "lg_collect_distillation",
-                  "lg_collect_distillation_recurrent"]
+                  "lg_collect_distillation_recurrent", "lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights",
+                  "lg_conv_encoder_forward", "lg_mlp_set_output_activation", "lg_estimator_step"]
+ESTIMATOR_SYMBOLS = ["lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights", "lg_conv_encoder_forward",
+                     "lg_mlp_set_output_activation", "lg_estimator_step"]
+ENCODER_MAX_SIDE, ENCODER_MIN_SIDE, ENCODER_MAX_OUT = 128, 8, 512          # limits of lg_conv_encoder_create
 RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2, "lrelu": 3, "selu": 4}
 

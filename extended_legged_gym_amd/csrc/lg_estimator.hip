@@ -1,0 +1,349 @@
+// lg_estimator.hip — gfx950 kernels of the terrain estimator (include/lgpolicy.h, section "terrain estimator"): the depth-image CNN encoder of
+// rsl_rl's TerrainEstimator (modules/terrain_estimator.py:80-109) as implicit GEMMs on the fp32 matrix cores, and the estimator's single step
+// (encoder -> cat with the base velocities -> Linear + act -> memory -> decoder, :162-198) on top of lg_mlp_forward / lg_rnn_step.
+//
+// One kernel serves the four convolutions and the two linear layers.  A layer is the product  rows x K x C_out  with
+//     rows = (env, output pixel) over ALL envs of the call -- a 64-row tile spans envs, so the 28-pixel maps of conv3 / conv4 fill their
+//            tiles and a weight fragment is used by every env of the tile;
+//     K    = kh * kw * C_in, ordered (ky, kx, ci) with ci fastest, over activations held (env, y, x, channel): 16 successive k of one row are
+//            64 contiguous bytes for C_in >= 16;
+// (a linear layer is the 1 x 1 convolution of a 1 x 1 image).  Workgroup = 4 waves = 64 rows x 64 output channels; wave w owns rows 16 w .. 16 w + 15
+// and four accumulators (one per 16-channel chunk).  K runs in chunks of 64: all 256 lanes gather the chunk's 64 x 64 patch values (zero outside
+// the image and beyond K; the per-k offset and tap come from a table built at create time, so the loop has no division) into an LDS image
+// [k / 16][row][k % 4][(k / 4) % 4] -- the one of lg_policy.hip: a lane's four successive A operands of v_mfma_f32_16x16x4_f32 are one
+// ds_read_b128, 1 KB contiguous per wave -- double-buffered, one barrier per chunk, the next chunk's global loads in flight under the current
+// chunk's 64 MFMAs per wave.  Weights are re-tiled once on the host (lg_conv_tile_weights): [16-channel chunk][k / 16][lane][(k / 4) % 4], one
+// coalesced 16-byte load per lane and four k-steps.  Exact fp32: each output is one k-ordered fmaf chain, no atomics, no split K -- the same
+// input gives the same bits.
+//
+// Maps go layer by layer through global memory (two ping-pong workspaces owned by the encoder): that one path serves every image size up to the
+// limit (at 58 x 87 the first map alone is 163 KB per env, more than a compute unit's LDS), and the maps of a 64-row tile are small enough to stay
+// in L2 between layers.  AdaptiveAvgPool2d((4, 4)) + Flatten is a kernel of its own (one lane per output, torch's windows
+// [floor(i L / 4), ceil((i + 1) L / 4))), writing torch's channel-major order so the first linear layer reads its weights as torch stores them.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "lg_device.h"
+#include "lg_policy_internal.h"
+#include "../../include/lgpolicy.h"
+#include "../../include/lgstep.h"
+
+#define CONV_ROWS 64         // rows (env, pixel) per workgroup
+#define CONV_COLS 64         // output channels per workgroup (grid.y walks the groups)
+#define CONV_THREADS 256     // four waves, one 16-row tile each
+#define CONV_KC 64           // k per staged chunk (four blocks of 16)
+#define ENC_LAYERS 6         // conv 0 2 4 6, linear 10 12 of the nn.Sequential
+#define ENC_MAX_HW 128
+#define ENC_MAX_OUT 512
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct ConvLayerDev {
+  int Hin, Win, Cin, Hout, Wout, Cout, stride, pad, act;
+  int nkb;                 // K rounded up to 64, / 16
+  const float* w;          // tiled [chunk][k / 16][lane][4], Cout rounded up to 64
+  const float* b;          // bias, zero-padded to the same width
+  const int32_t* ktab;     // [16 nkb]: (ky << 26) | (kx << 22) | offset of tap k from the patch's first pixel, -1 beyond K
+};
+
+LG_DEV float enc_act(float x, int act) {
+  switch (act) {
+    case LG_ACT_RELU: return fmaxf(x, 0.f);
+    case LG_ACT_TANH: return tanhf(x);
+    default: return x > 0.f ? x : expm1f(x);        // nn.ELU
+  }
+}
+
+__global__ __launch_bounds__(CONV_THREADS) void conv_gemm_kernel(ConvLayerDev L, const float* __restrict__ in, int64_t in_estride, int64_t n,
+                                                                  float* __restrict__ out, int64_t out_estride) {
+  __shared__ __attribute__((aligned(16))) float a_lds[2][CONV_KC * CONV_ROWS];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int HW = L.Hout * L.Wout;
+  const int64_t M = n * HW, row0 = (int64_t)blockIdx.x * CONV_ROWS;
+  // gather role: tap kk of the block, rows rb + 16 j
+  const int kk = tid & 15, rb = tid >> 4;
+  const float* src[4]; int iy0[4], ix0[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int64_t m = row0 + rb + 16 * j;
+    if (m < M) {
+      const int64_t e = m / HW; const int pix = (int)(m - e * HW), oy = pix / L.Wout, ox = pix - oy * L.Wout;
+      iy0[j] = oy * L.stride - L.pad; ix0[j] = ox * L.stride - L.pad;
+      src[j] = in + e * in_estride + ((int64_t)iy0[j] * L.Win + ix0[j]) * L.Cin;
+    } else { iy0[j] = -(1 << 20); ix0[j] = 0; src[j] = in; }          // every tap out of the image: zeros
+  }
+  float v[16];
+  auto gather = [&](int kb0) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int t = L.ktab[(kb0 + b) * 16 + kk];
+      const int ky = (t >> 26) & 15, kx = (t >> 22) & 15, off = t & 0x3fffff;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int iy = iy0[j] + ky, ix = ix0[j] + kx;
+        const bool ok = t >= 0 && iy >= 0 && iy < L.Hin && ix >= 0 && ix < L.Win;
+        v[b * 4 + j] = ok ? src[j][off] : 0.f;
+      }
+    }
+  };
+  const float4* wl = reinterpret_cast<const float4*>(L.w) + (size_t)blockIdx.y * 4 * L.nkb * 64 + lane;
+  f32x4 acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  gather(0);
+  for (int kb0 = 0, it = 0; kb0 < L.nkb; kb0 += 4, ++it) {
+    float* buf = a_lds[it & 1];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) buf[((b * CONV_ROWS + rb + 16 * j) * 4 + (kk & 3)) * 4 + (kk >> 2)] = v[b * 4 + j];
+    __syncthreads();
+    if (kb0 + 4 < L.nkb) gather(kb0 + 4);
+    const float4* ap = reinterpret_cast<const float4*>(buf) + (wv * 16 + (lane & 15)) * 4 + (lane >> 4);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float4 a = ap[b * CONV_ROWS * 4];
+      float4 w[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) w[c] = wl[((size_t)c * L.nkb + kb0 + b) * 64];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[c].x, acc[c], 0, 0, 0);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[c].y, acc[c], 0, 0, 0);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[c].z, acc[c], 0, 0, 0);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[c].w, acc[c], 0, 0, 0);
+    }
+  }
+  // epilogue: accumulator entry i of a lane is C[row 4 (lane >> 4) + i][channel lane & 15]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t m = row0 + wv * 16 + 4 * (lane >> 4) + i;
+    if (m >= M) continue;
+    const int64_t e = m / HW; const int pix = (int)(m - e * HW);
+    float* dst = out + e * out_estride + (int64_t)pix * L.Cout;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int col = blockIdx.y * CONV_COLS + c * 16 + (lane & 15);
+      if (col < L.Cout) dst[col] = enc_act(acc[c][i] + L.b[col], L.act);
+    }
+  }
+}
+
+// AdaptiveAvgPool2d((4, 4)) + Flatten: x (n, H, W, C) -> y (n, C 16), y[e, c 16 + i 4 + j]
+__global__ __launch_bounds__(256) void pool_flatten_kernel(const float* __restrict__ x, int64_t n, int H, int W, int C, float* __restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * 16 * C) return;
+  const int c = (int)(idx % C); const int64_t t = idx / C; const int ij = (int)(t & 15); const int64_t e = t >> 4;
+  const int i = ij >> 2, j = ij & 3;
+  const int y0 = (i * H) / 4, y1 = ((i + 1) * H + 3) / 4, x0 = (j * W) / 4, x1 = ((j + 1) * W + 3) / 4;
+  float s = 0.f;
+  for (int yy = y0; yy < y1; ++yy)
+    for (int xx = x0; xx < x1; ++xx) s += x[((e * H + yy) * W + xx) * C + c];
+  y[e * 16 * C + c * 16 + ij] = s / (float)((y1 - y0) * (x1 - x0));
+}
+
+// columns [col0, col0 + P) of the (n, stride) staging rows = proprio (n, P): the second half of torch.cat
+__global__ __launch_bounds__(256) void cat_columns_kernel(const float* __restrict__ src, int64_t n, int P, float* __restrict__ dst, int stride, int col0) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * P) return;
+  const int64_t r = idx / P; const int k = (int)(idx - r * P);
+  dst[r * stride + col0 + k] = src[idx];
+}
+
+struct lg_conv_encoder {
+  int device = 0, H = 0, W = 0, out_dim = 0, act = 0;
+  ConvLayerDev layer[ENC_LAYERS];
+  int Hp = 0, Wp = 0;                      // the map the pooling reads
+  size_t floats_a = 0, floats_b = 0;       // per env: workspace A holds the maps of layers 0, 2 and the pooled row, B those of 1, 3 and the first linear
+  int64_t cap = 0;                         // envs the workspaces hold
+  float *ws_a = nullptr, *ws_b = nullptr;
+  float *cat = nullptr, *comb = nullptr, *memo = nullptr;   // lg_estimator_step: (cap, cat_w), (cap, comb_w), (cap, mem_w)
+  int64_t step_cap = 0; int cat_w = 0, comb_w = 0, mem_w = 0;
+  std::vector<void*> allocs;
+};
+
+static const int kConvShape[4][5] = {{1, 32, 5, 2, 2}, {32, 64, 3, 2, 1}, {64, 128, 3, 2, 1}, {128, 64, 3, 1, 1}};   // C_in, C_out, k, stride, pad
+
+static int64_t conv_tiled_count(int cout, int cin, int kh, int kw) {
+  const int64_t K = (int64_t)cin * kh * kw, nkb = ((K + 63) & ~(int64_t)63) / 16, nch = ((cout + 63) & ~63) / 16;
+  return nch * nkb * 64 * 4;
+}
+
+static void conv_tile_weights(int cout, int cin, int kh, int kw, const float* w, float* tiled) {
+  const int K = cin * kh * kw, nkb = ((K + 63) & ~63) / 16, nch = ((cout + 63) & ~63) / 16;
+  for (int c = 0; c < nch; ++c)
+    for (int b = 0; b < nkb; ++b)
+      for (int ln = 0; ln < 64; ++ln)
+        for (int s = 0; s < 4; ++s) {
+          const int col = c * 16 + (ln & 15), k = b * 16 + s * 4 + (ln >> 4);
+          float v = 0.f;
+          if (col < cout && k < K) {
+            const int ci = k % cin, tap = k / cin, ky = tap / kw, kx = tap - ky * kw;
+            v = w[(((size_t)col * cin + ci) * kh + ky) * kw + kx];
+          }
+          tiled[(((size_t)c * nkb + b) * 64 + ln) * 4 + s] = v;
+        }
+}
+
+static bool enc_grow(float** p, size_t floats) {
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  return hipMalloc((void**)p, floats * sizeof(float)) == hipSuccess;
+}
+
+extern "C" {
+
+int64_t lg_conv_tile_weights(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw, const float* weight, float* tiled) {
+  if (c_out < 1 || c_out > ENC_MAX_OUT || c_in < 1 || c_in > 1024 || kh < 1 || kh > 15 || kw < 1 || kw > 15) return LG_ERR_INVALID;
+  if (tiled) {
+    if (!weight) return LG_ERR_INVALID;
+    conv_tile_weights(c_out, c_in, kh, kw, weight, tiled);
+  }
+  return conv_tiled_count(c_out, c_in, kh, kw);
+}
+
+void lg_conv_encoder_destroy(lg_conv_encoder* e) {
+  if (!e) return;
+  DeviceScope ds_(e->device);
+  for (void* p : e->allocs) (void)hipFree(p);
+  for (float* p : {e->ws_a, e->ws_b, e->cat, e->comb, e->memo}) if (p) (void)hipFree(p);
+  delete e;
+}
+
+lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
+                                        const float* const* biases, int device_id) {
+  if (height < 8 || height > ENC_MAX_HW || width < 8 || width > ENC_MAX_HW) { lg_policy_set_error("lg_conv_encoder_create: image size out of range (8..128 per side)"); return nullptr; }
+  if (out_dim < 1 || out_dim > ENC_MAX_OUT) { lg_policy_set_error("lg_conv_encoder_create: out_dim out of range (1..512)"); return nullptr; }
+  if (activation != LG_ACT_ELU && activation != LG_ACT_RELU && activation != LG_ACT_TANH) { lg_policy_set_error("lg_conv_encoder_create: activation must be elu, relu or tanh"); return nullptr; }
+  if (!weights || !biases) { lg_policy_set_error("lg_conv_encoder_create: null weight list"); return nullptr; }
+  for (int l = 0; l < ENC_LAYERS; ++l) if (!weights[l] || !biases[l]) { lg_policy_set_error("lg_conv_encoder_create: null weight"); return nullptr; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { lg_policy_set_error("no HIP device: the estimator kernels have no CPU path"); return nullptr; }
+  if (device_id < 0 || device_id >= ndev) { lg_policy_set_error("bad device"); return nullptr; }
+  DeviceScope ds_(device_id);
+  if (!ds_.ok) { lg_policy_set_error("bad device"); return nullptr; }
+  lg_conv_encoder* e = new lg_conv_encoder();
+  e->device = device_id; e->H = height; e->W = width; e->out_dim = out_dim; e->act = activation;
+  int h = height, w = width;
+  size_t map_floats[ENC_LAYERS];
+  for (int l = 0; l < ENC_LAYERS; ++l) {
+    ConvLayerDev& L = e->layer[l];
+    int kh = 1;
+    if (l < 4) {
+      const int* s = kConvShape[l];
+      kh = s[2];
+      L.Hin = h; L.Win = w; L.Cin = s[0]; L.Cout = s[1]; L.stride = s[3]; L.pad = s[4];
+      L.Hout = (h + 2 * s[4] - s[2]) / s[3] + 1; L.Wout = (w + 2 * s[4] - s[2]) / s[3] + 1;
+      h = L.Hout; w = L.Wout;
+    } else {
+      L.Hin = L.Win = L.Hout = L.Wout = 1; L.stride = 1; L.pad = 0;
+      L.Cin = l == 4 ? 64 * 16 : 128; L.Cout = l == 4 ? 128 : out_dim;
+    }
+    L.act = activation;
+    const int K = L.Cin * kh * kh;
+    L.nkb = ((K + 63) & ~63) / 16;
+    map_floats[l] = (size_t)L.Hout * L.Wout * L.Cout;
+    std::vector<float> tw((size_t)conv_tiled_count(L.Cout, L.Cin, kh, kh)), tb((size_t)((L.Cout + 63) & ~63), 0.f);
+    conv_tile_weights(L.Cout, L.Cin, kh, kh, weights[l], tw.data());
+    for (int i = 0; i < L.Cout; ++i) tb[i] = biases[l][i];
+    std::vector<int32_t> kt((size_t)L.nkb * 16, -1);
+    for (int k = 0; k < K; ++k) {
+      const int ci = k % L.Cin, tap = k / L.Cin, ky = tap / kh, kx = tap - ky * kh;
+      kt[k] = (ky << 26) | (kx << 22) | ((ky * L.Win + kx) * L.Cin + ci);         // offset < 15 * 128 * 1024 + ... < 2^22 for every supported shape
+    }
+    void *dw = nullptr, *db = nullptr, *dk = nullptr;
+    const bool ok = hipMalloc(&dw, tw.size() * 4) == hipSuccess && hipMalloc(&db, tb.size() * 4) == hipSuccess && hipMalloc(&dk, kt.size() * 4) == hipSuccess &&
+                    hipMemcpy(dw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(db, tb.data(), tb.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(dk, kt.data(), kt.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    for (void* p : {dw, db, dk}) if (p) e->allocs.push_back(p);
+    if (!ok) { lg_policy_set_error("lg_conv_encoder_create: weight upload failed"); lg_conv_encoder_destroy(e); return nullptr; }
+    L.w = (const float*)dw; L.b = (const float*)db; L.ktab = (const int32_t*)dk;
+  }
+  e->Hp = h; e->Wp = w;
+  e->floats_a = std::max(std::max(map_floats[0], map_floats[2]), (size_t)1024);
+  e->floats_b = std::max(std::max(map_floats[1], map_floats[3]), (size_t)128);
+  return e;
+}
+
+#define EST_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { lg_policy_set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); return LG_ERR_HIP; } } while (0)
+
+static int enc_launch(const ConvLayerDev& L, const float* in, int64_t in_estride, int64_t n, float* out, int64_t out_estride, hipStream_t st) {
+  const int64_t tiles = (n * L.Hout * L.Wout + CONV_ROWS - 1) / CONV_ROWS;
+  if (tiles > 0x7fffffff) { lg_policy_set_error("lg_conv_encoder_forward: too many rows for one launch"); return LG_ERR_UNSUPPORTED; }
+  hipLaunchKernelGGL(conv_gemm_kernel, dim3((unsigned)tiles, (unsigned)((L.Cout + CONV_COLS - 1) / CONV_COLS)), dim3(CONV_THREADS), 0, st, L, in, in_estride, n, out,
+                     out_estride);
+  return LG_OK;
+}
+
+// features rows are `feat_stride` floats apart (lg_estimator_step writes them straight into the first columns of its cat rows)
+static int enc_forward(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* features, int64_t feat_stride, hipStream_t st) {
+  if (n > e->cap) {          // the workspaces grow to the largest n seen; hipFree waits for the device, so a caller that alternates streams stays safe
+    if (!enc_grow(&e->ws_a, (size_t)n * e->floats_a) || !enc_grow(&e->ws_b, (size_t)n * e->floats_b)) {
+      e->cap = 0; lg_policy_set_error("lg_conv_encoder_forward: workspace allocation failed"); return LG_ERR_HIP;
+    }
+    e->cap = n;
+  }
+  const ConvLayerDev* L = e->layer;
+  int rc;
+  if ((rc = enc_launch(L[0], depth, depth_stride, n, e->ws_a, (int64_t)L[0].Hout * L[0].Wout * L[0].Cout, st)) != LG_OK) return rc;
+  if ((rc = enc_launch(L[1], e->ws_a, (int64_t)L[1].Hin * L[1].Win * L[1].Cin, n, e->ws_b, (int64_t)L[1].Hout * L[1].Wout * L[1].Cout, st)) != LG_OK) return rc;
+  if ((rc = enc_launch(L[2], e->ws_b, (int64_t)L[2].Hin * L[2].Win * L[2].Cin, n, e->ws_a, (int64_t)L[2].Hout * L[2].Wout * L[2].Cout, st)) != LG_OK) return rc;
+  if ((rc = enc_launch(L[3], e->ws_a, (int64_t)L[3].Hin * L[3].Win * L[3].Cin, n, e->ws_b, (int64_t)L[3].Hout * L[3].Wout * L[3].Cout, st)) != LG_OK) return rc;
+  hipLaunchKernelGGL(pool_flatten_kernel, dim3((unsigned)((n * 1024 + 255) / 256)), dim3(256), 0, st, e->ws_b, n, e->Hp, e->Wp, 64, e->ws_a);
+  if ((rc = enc_launch(L[4], e->ws_a, 1024, n, e->ws_b, 128, st)) != LG_OK) return rc;
+  if ((rc = enc_launch(L[5], e->ws_b, 128, n, features, feat_stride, st)) != LG_OK) return rc;
+  EST_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+int lg_conv_encoder_forward(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* features, void* stream) {
+  if (!e || !depth || !features) { lg_policy_set_error("lg_conv_encoder_forward: null argument"); return LG_ERR_INVALID; }
+  if (n <= 0) { lg_policy_set_error("lg_conv_encoder_forward: n must be positive"); return LG_ERR_INVALID; }
+  if (depth_stride < (int64_t)e->H * e->W) { lg_policy_set_error("lg_conv_encoder_forward: depth_stride is smaller than one image"); return LG_ERR_INVALID; }
+  DeviceScope ds_(e->device);
+  return enc_forward(e, depth, depth_stride, n, features, e->out_dim, (hipStream_t)stream);
+}
+
+int lg_estimator_step(lg_conv_encoder* e, lg_mlp* combine, lg_rnn* mem, lg_mlp* decoder, const float* depth, int64_t depth_stride, const float* proprio,
+                      int64_t n, float* h, float* c, const float* reset, float* predictions, void* stream) {
+  if (!e || !combine || !mem || !decoder || !depth || !h || !predictions) { lg_policy_set_error("lg_estimator_step: null argument"); return LG_ERR_INVALID; }
+  if (n <= 0) { lg_policy_set_error("lg_estimator_step: n must be positive"); return LG_ERR_INVALID; }
+  if (depth_stride < (int64_t)e->H * e->W) { lg_policy_set_error("lg_estimator_step: depth_stride is smaller than one image"); return LG_ERR_INVALID; }
+  int cl, cin, cout, cdev, rtype, rin, rhid, rdev, dl, din, dout, ddev;
+  lg_mlp_widths(combine, &cl, &cin, &cout, &cdev);
+  lg_rnn_widths(mem, &rtype, &rin, &rhid, &rdev);
+  lg_mlp_widths(decoder, &dl, &din, &dout, &ddev);
+  const int P = cin - e->out_dim;
+  if (cl != 1 || P < 0 || cout != rin || din != rhid) {
+    lg_policy_set_error("lg_estimator_step: stage widths do not chain (combine: one layer of encoder out_dim + proprio inputs; its outputs = the memory's input; decoder input = the memory's hidden width)");
+    return LG_ERR_INVALID;
+  }
+  if (P > 0 && !proprio) { lg_policy_set_error("lg_estimator_step: null proprio"); return LG_ERR_INVALID; }
+  if (rtype == LG_RNN_LSTM && !c) { lg_policy_set_error("lg_estimator_step: an LSTM needs its cell state"); return LG_ERR_INVALID; }
+  if (cdev != e->device || rdev != e->device || ddev != e->device) { lg_policy_set_error("lg_estimator_step: the stages live on different devices"); return LG_ERR_INVALID; }
+  DeviceScope ds_(e->device);
+  if (n > e->step_cap || cin != e->cat_w || cout != e->comb_w || rhid != e->mem_w) {
+    if (!enc_grow(&e->cat, (size_t)n * cin) || !enc_grow(&e->comb, (size_t)n * cout) || !enc_grow(&e->memo, (size_t)n * rhid)) {
+      e->step_cap = 0; lg_policy_set_error("lg_estimator_step: workspace allocation failed"); return LG_ERR_HIP;
+    }
+    e->step_cap = n; e->cat_w = cin; e->comb_w = cout; e->mem_w = rhid;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int rc = enc_forward(e, depth, depth_stride, n, e->cat, cin, st);
+  if (rc != LG_OK) return rc;
+  if (P > 0) hipLaunchKernelGGL(cat_columns_kernel, dim3((unsigned)((n * P + 255) / 256)), dim3(256), 0, st, proprio, n, P, e->cat, cin, e->out_dim);
+  EST_TRY(hipGetLastError());
+  if ((rc = lg_mlp_forward(combine, e->cat, n, e->comb, stream)) != LG_OK) { lg_policy_set_error(std::string("lg_estimator_step: combine: ") + lg_mlp_last_error(combine)); return rc; }
+  if ((rc = lg_rnn_step(mem, e->comb, n, h, c, reset, e->memo, stream)) != LG_OK) return rc;
+  if ((rc = lg_mlp_forward(decoder, e->memo, n, predictions, stream)) != LG_OK) { lg_policy_set_error(std::string("lg_estimator_step: decoder: ") + lg_mlp_last_error(decoder)); return rc; }
+  return LG_OK;
+}
+
+}  // extern "C"

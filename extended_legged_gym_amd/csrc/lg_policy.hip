@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "lg_device.h"
+#include "lg_policy_internal.h"
 #include "../../include/lgpolicy.h"
 #include "../../include/lgstep.h"
 
@@ -40,6 +41,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct MlpDev {
   int L, act;
+  int act_out;                       // != 0: the activation follows the last layer too (lg_mlp_set_output_activation); 0 for every network lg_mlp_create returns
   int dims[LG_MLP_MAX_LAYERS + 1];
   int kpad[LG_MLP_MAX_LAYERS];       // input width rounded up to 64 (four blocks of four k-steps of 4)
   int nchunks[LG_MLP_MAX_LAYERS];    // output width rounded up to 16, / 16
@@ -55,6 +57,7 @@ struct lg_mlp {
 };
 
 static thread_local std::string g_pol_err;
+void lg_policy_set_error(const std::string& msg) { g_pol_err = msg; }      // lg_policy_internal.h
 
 LG_DEV float apply_act(float x, int act) {
   switch (act) {
@@ -160,6 +163,7 @@ LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0,
           out[IMG(m, col)] = v0;
           out[IMG(m + 16, col)] = v1;
         } else if (col < nout) {
+          if (M.act_out) { v0 = apply_act(v0, M.act); v1 = apply_act(v1, M.act); }
           if (yrows) { yrows[m * 16 * nch + col] = v0; yrows[(m + 16) * 16 * nch + col] = v1; }
           if (y_global) {
             if (row0 + m < n) y_global[(row0 + m) * nout + col] = v0;
@@ -307,7 +311,7 @@ lg_mlp* lg_mlp_create(int32_t L, const int32_t* dims, const float* const* weight
   DeviceScope ds_(device_id);
   if (!ds_.ok) { g_pol_err = "bad device"; return nullptr; }
   lg_mlp* m = new lg_mlp();
-  m->device = device_id; m->h.L = L; m->h.act = activation;
+  m->device = device_id; m->h.L = L; m->h.act = activation; m->h.act_out = 0;
   for (int l = 0; l <= L; ++l) m->h.dims[l] = dims[l];
   for (int l = 0; l < L; ++l) {
     const int K = dims[l], N = dims[l + 1], Kp = (K + 63) & ~63, nb = Kp / 16;
@@ -337,6 +341,12 @@ lg_mlp* lg_mlp_create(int32_t L, const int32_t* dims, const float* const* weight
     m->h.w[l] = (const float*)dw; m->h.b[l] = (const float*)db;
   }
   return m;
+}
+
+int lg_mlp_set_output_activation(lg_mlp* m, int32_t enabled) {
+  if (!m) return LG_ERR_INVALID;
+  m->h.act_out = enabled != 0;
+  return LG_OK;
 }
 
 #define POL_TRY(m, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { (m)->err = std::string(#expr) + ": " + hipGetErrorString(_e); return LG_ERR_HIP; } } while (0)
@@ -597,6 +607,9 @@ struct lg_rnn {
   RnnLayerDev layer[RNN_MAX_LAYERS];
   std::vector<void*> allocs;
 };
+
+void lg_mlp_widths(const lg_mlp* m, int* layers, int* in, int* out, int* device) { *layers = m->h.L; *in = m->h.dims[0]; *out = m->h.dims[m->h.L]; *device = m->device; }
+void lg_rnn_widths(const lg_rnn* m, int* type, int* input, int* hidden, int* device) { *type = m->type; *input = m->input; *hidden = m->hidden; *device = m->device; }
 
 LG_DEV float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 

@@ -162,3 +162,55 @@ def collect_distillation(env, policy, num_steps, noise_uniforms=None):
     if hist is not None:
         env.obs_buf = last
     return out
+
+
+def estimation_row(env):
+    """`TerrainEstimatorRunner._get_environment_data` (`rsl_rl/runners/terrain_estimator_runner.py:247-277`) on an env with both sensors: the
+    camera's latest frame (a view of its FIFO), `cat[base_lin_vel, base_ang_vel]`, the ray caster's un-normalised distances."""
+    depth = env.get_depth_images() if hasattr(env, "get_depth_images") else None
+    if depth is None or not hasattr(env, "_get_raycast_distances"):
+        raise ValueError("collect_estimation needs an env with the depth camera and the ray caster enabled (e.g. elspider_air_rough_raycast)")
+    if depth.dim() == 4:
+        depth = depth[:, -1]
+    return depth, torch.cat([env.base_lin_vel, env.base_ang_vel], dim=-1), env._get_raycast_distances(normalize=False)
+
+
+def collect_estimation(env, policy, num_steps, estimator=None):
+    """The data-collection loop of `TerrainEstimatorRunner.learn` (`rsl_rl/runners/terrain_estimator_runner.py:392-438`) over an env that carries
+    the depth camera and the ray caster.  Per step t: the camera's latest frame, `cat[base_lin_vel, base_ang_vel]` and the un-normalised ray
+    distances are copied into row t of preallocated (T, N, .) tensors (what `EstimatorRolloutStorage.add_transitions` keeps,
+    `algorithms/distillation.py:398-407`), the env is stepped with `policy.act_inference(env.obs_buf)` (a native policy; `policy=None`:
+    `0.5 * randn`, as `:427`), and `dones[t]` = the step's `reset_buf`.  The reference's storage never fills its `dones` (they stay zero, so its
+    update never resets the memory at an episode boundary); the REAL ones are returned here.  A host loop over `env.step`: the sensors are driven
+    from the env classes.
+
+    Returns a dict: depth_images (T, N, h, w), proprio_data (T, N, 6), raycast_targets (T, N, R), dones (T, N).  With `estimator`
+    (a `NativeTerrainEstimator`) it is also stepped on every row and reset on `dones[t]` after the step (`distillation.py:275`): the evaluation
+    loop of `play` (`:637-730`), adding predictions (T, N, R) and the per-step `mse` / `mae` (T) it prints (`:666-670`)."""
+    T = int(num_steps)
+    depth, proprio, target = estimation_row(env)
+    N, dev = depth.shape[0], depth.device
+    out = dict(depth_images=torch.empty(T, N, *depth.shape[1:], device=dev), proprio_data=torch.empty(T, N, proprio.shape[1], device=dev),
+               raycast_targets=torch.empty(T, N, target.shape[1], device=dev), dones=torch.empty(T, N, device=dev))
+    if estimator is not None:
+        out.update(predictions=torch.empty(T, N, target.shape[1], device=dev), mse=torch.empty(T, device=dev), mae=torch.empty(T, device=dev))
+    for t in range(T):
+        if t > 0:
+            depth, proprio, target = estimation_row(env)
+        out["depth_images"][t].copy_(depth)
+        out["proprio_data"][t].copy_(proprio)
+        out["raycast_targets"][t].copy_(target)
+        if estimator is not None:
+            pred = estimator.act_inference(depth, proprio)
+            out["predictions"][t].copy_(pred)
+            out["mse"][t] = torch.mean((pred - target) ** 2)
+            out["mae"][t] = torch.mean(torch.abs(pred - target))
+        if policy is None:
+            actions = torch.randn(N, env.num_actions, device=env.device) * 0.5
+        else:
+            actions = policy.act_inference(env.obs_buf)
+        dones = env.step(actions)[3]
+        out["dones"][t].copy_(dones)
+        if estimator is not None:
+            estimator.reset(dones)
+    return out

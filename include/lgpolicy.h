@@ -201,6 +201,49 @@ int lg_collect_distillation_recurrent(struct lg_ctx* env, lg_rnn* mem_s, lg_mlp*
                                       uint64_t seed, uint64_t first_call, int32_t T, const lg_obs_history* history, const lg_distill_rollout* rows,
                                       float* h_s0, float* c_s0, float* h_t0, float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, void* stream);
 
+/* ---- terrain estimator: depth image + base velocities -> the ray caster's distances (vendored rsl_rl: modules/terrain_estimator.py:13-218;
+ * trained by algorithms/distillation.py:190-433 through runners/terrain_estimator_runner.py).  Inference / collection only: the update
+ * (EstimatorDistillation.update, distillation.py:277-332) stays in PyTorch.
+ *
+ * lg_conv_encoder: TerrainEstimator._build_cnn_encoder (terrain_estimator.py:80-109), forward only, fp32, for a (height, width) image:
+ *     Conv2d(1, 32, k5, s2, p2) act  Conv2d(32, 64, k3, s2, p1) act  Conv2d(64, 128, k3, s2, p1) act  Conv2d(128, 64, k3, s1, p1) act
+ *     AdaptiveAvgPool2d((4, 4)) Flatten  Linear(1024, 128) act  Linear(128, out_dim) act
+ * act: the module's one shared activation (:44-51): LG_ACT_ELU, LG_ACT_RELU or LG_ACT_TANH.  weights[6] / biases[6]: HOST pointers in torch's
+ * layouts, in the order of the layers above (Sequential indices 0 2 4 6 10 12): conv (C_out, C_in, kh, kw), linear (out, in).  Every layer is an
+ * implicit GEMM on the fp32 matrix cores over rows = (env, output pixel); no atomics, no split reductions: equal inputs give equal bits.
+ * Limits: 8 <= height, width <= 128, 1 <= out_dim <= 512; NULL + a message in lg_mlp_last_error(NULL) beyond them.  The encoder owns its
+ * workspaces (the intermediate maps of all n rows); they grow on the first call with a larger n, which waits for the device once.  Calls on
+ * one encoder must not overlap on different streams. */
+typedef struct lg_conv_encoder lg_conv_encoder;
+lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
+                                        const float* const* biases, int device_id);
+void lg_conv_encoder_destroy(lg_conv_encoder* enc);
+
+/* The host re-tiling of one layer, a pure function (no device).  With K = kh kw c_in and tap index k = (ky kw + kx) c_in + ci (channel fastest:
+ * the kernels keep activations (env, y, x, channel)), nkb = (K rounded up to 64) / 16 blocks and nch = (c_out rounded up to 64) / 16 chunks:
+ *     tiled[((c nkb + b) 64 + lane) 4 + s] = weight[16 c + (lane & 15)][ci][ky][kx]   for k = 16 b + 4 s + (lane >> 4),   zero for k >= K or a channel >= c_out.
+ * A linear layer (out, in) is c_out = out, c_in = in, kh = kw = 1.  Returns the number of floats of `tiled` (HOST; NULL: only the count);
+ * LG_ERR_INVALID for c_out outside 1..512, c_in outside 1..1024, kh / kw outside 1..15, or a NULL weight with a non-NULL `tiled`. */
+int64_t lg_conv_tile_weights(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw, const float* weight, float* tiled);
+
+/* features (n, out_dim) = depth_encoder(depth.unsqueeze(1)) (terrain_estimator.py:164-167).  Image e starts at depth + e * depth_stride and is
+ * (height, width) row-major: depth_stride = buffer_len * height * width reads the latest frame of the camera's (n, buffer_len, height, width)
+ * FIFO in place (depth_buffer[:, -1]).  LG_ERR_INVALID for n <= 0, a NULL pointer or depth_stride < height * width; nothing is launched then. */
+int lg_conv_encoder_forward(lg_conv_encoder* enc, const float* depth, int64_t depth_stride, int64_t n, float* features, void* stream);
+
+/* enabled != 0: the activation also follows the LAST layer of the network, as nn.Sequential(Linear, act) has it -- the estimator's combination_mlp
+ * (terrain_estimator.py:58-61).  Networks keep a linear last layer unless this is called. */
+int lg_mlp_set_output_activation(lg_mlp* mlp, int32_t enabled);
+
+/* TerrainEstimator.forward in single-step mode (terrain_estimator.py:162-198):
+ *     features = encoder(depth);  x = combine(cat[features, proprio]);  memory step on x (lg_rnn_step: h / c in place, rows with reset != 0 enter
+ *     with zero state);  predictions (n, decoder out) = decoder(h' of the top layer).
+ * combine: an lg_mlp of ONE layer, (out_dim + P) -> the memory's input width, with lg_mlp_set_output_activation enabled; P = the width of a
+ * proprio row (n, P) (base_lin_vel, base_ang_vel: 6).  decoder: an lg_mlp whose input is the memory's hidden width.  LG_ERR_INVALID with a
+ * message in lg_mlp_last_error(NULL) when the widths do not chain, n <= 0, or a pointer is NULL (c may be NULL for a GRU, reset always). */
+int lg_estimator_step(lg_conv_encoder* enc, lg_mlp* combine, lg_rnn* mem, lg_mlp* decoder, const float* depth, int64_t depth_stride,
+                      const float* proprio, int64_t n, float* h, float* c, const float* reset, float* predictions, void* stream);
+
 /* ---- the sampling planner's arithmetic around rollout_batch.
  * The reference's planner envs (envs/batch_rollout/robot_traj_grad_sampling.py:210-280) hand `rollout_batch` as a callback to the
  * optimiser of the external package `traj_sampling` (imported at :18, not in the reference tree, no pinned version): per diffusion step

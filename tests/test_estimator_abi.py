@@ -1,0 +1,128 @@
+"""CPU side of the terrain estimator (include/lgpolicy.h, section "terrain estimator"): the header names, the library's exports and the ctypes
+mirror agree; `lg_conv_tile_weights` (a pure host function) against a numpy restatement of the documented layout for the four conv shapes and a
+linear one, and its error returns; what is refused before any device is touched; the new kernels' code-object metadata (cross-compiled for
+gfx950): no spills, no scratch, LDS within one workgroup's share of a compute unit.  No GPU needed."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from extended_legged_gym_amd import abi
+from tests.test_policy_recurrent_abi import HIPCC, LLVM
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
+LIB = os.path.join(CSRC, "liblgstep.so")
+NEW = ["lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights", "lg_conv_encoder_forward", "lg_mlp_set_output_activation",
+       "lg_estimator_step"]
+
+
+def _lib():
+    return abi.declare_policy(C.CDLL(LIB))
+
+
+def test_new_symbols_are_in_the_header_exported_and_declared():
+    header = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
+    lib = C.CDLL(LIB)
+    for sym in NEW:
+        assert re.search(r"\b%s\(" % sym, header), sym
+        assert sym in abi.ESTIMATOR_SYMBOLS and hasattr(lib, sym), sym
+    assert "terrain_estimator.py:80-109" in header and "terrain_estimator.py:162-198" in header
+    abi.declare_policy(lib)
+    for sym in NEW:
+        assert getattr(lib, sym).argtypes, sym
+    from extended_legged_gym_amd import rl
+    for name in ("NativeTerrainEstimator", "NativeConvEncoder", "collect_estimation", "parse_estimator_state"):
+        assert hasattr(rl, name), name
+
+
+def _tile_numpy(w):
+    """The layout documented at lg_conv_tile_weights, restated."""
+    cout, cin, kh, kw = w.shape
+    K = cin * kh * kw
+    nkb, nch = -(-K // 64) * 4, -(-cout // 64) * 4
+    wk = np.zeros((nch * 16, nkb * 16), np.float32)
+    wk[:cout, :K] = w.transpose(0, 2, 3, 1).reshape(cout, K)          # k = (ky kw + kx) c_in + ci
+    lane, s = np.arange(64)[:, None], np.arange(4)[None, :]
+    out = np.empty((nch, nkb, 64, 4), np.float32)
+    for c in range(nch):
+        for b in range(nkb):
+            out[c, b] = wk[16 * c + (lane & 15), 16 * b + 4 * s + (lane >> 4)]
+    return out.reshape(-1)
+
+
+@pytest.mark.parametrize("shape", [(32, 1, 5, 5), (64, 32, 3, 3), (128, 64, 3, 3), (64, 128, 3, 3), (128, 1024, 1, 1), (70, 128, 1, 1)])
+def test_conv_tile_weights_matches_the_documented_layout(shape):
+    lib = _lib()
+    rng = np.random.default_rng(sum(shape))
+    w = rng.standard_normal(shape).astype(np.float32)
+    count = lib.lg_conv_tile_weights(*shape, None, None)
+    want = _tile_numpy(w)
+    assert count == want.size
+    tiled = np.full(count, np.nan, np.float32)
+    assert lib.lg_conv_tile_weights(*shape, w.ctypes.data, tiled.ctypes.data) == count
+    assert np.array_equal(tiled, want)
+    assert np.count_nonzero(tiled) == np.count_nonzero(w)           # every weight exactly once, zeros elsewhere
+
+
+def test_conv_tile_weights_error_returns():
+    lib = _lib()
+    buf = np.zeros(64 * 64 * 4, np.float32)
+    for bad in ((0, 1, 3, 3), (513, 1, 3, 3), (32, 0, 3, 3), (32, 1025, 3, 3), (32, 1, 0, 3), (32, 1, 3, 16)):
+        assert lib.lg_conv_tile_weights(*bad, None, None) == abi.LG_ERR_INVALID, bad
+    assert lib.lg_conv_tile_weights(32, 1, 5, 5, None, buf.ctypes.data) == abi.LG_ERR_INVALID       # output asked for, no weights given
+
+
+def test_refusals_that_need_no_device():
+    lib = _lib()
+    fp = C.POINTER(C.c_float)
+    arrs = [np.zeros(4, np.float32) for _ in range(6)]
+    lists = (fp * 6)(*[a.ctypes.data_as(fp) for a in arrs])         # never read: the sizes are refused first
+    for args, word in (((129, 56, 64, 0), "image size"), ((28, 7, 64, 0), "image size"), ((28, 56, 513, 0), "out_dim"), ((28, 56, 0, 0), "out_dim"),
+                       ((28, 56, 64, 3), "activation")):
+        assert not lib.lg_conv_encoder_create(*args, lists, lists, 0), args
+        msg = (lib.lg_mlp_last_error(None) or b"").decode()
+        assert "lg_conv_encoder_create" in msg and word in msg, (args, msg)
+    assert not lib.lg_conv_encoder_create(28, 56, 64, 0, None, lists, 0)
+    assert "null" in (lib.lg_mlp_last_error(None) or b"").decode()
+    p = 0x1000
+    assert lib.lg_conv_encoder_forward(None, p, 1568, 4, p, None) == abi.LG_ERR_INVALID
+    assert "lg_conv_encoder_forward" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert lib.lg_estimator_step(None, None, None, None, p, 1568, p, 4, p, None, None, p, None) == abi.LG_ERR_INVALID
+    assert "lg_estimator_step" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert lib.lg_mlp_set_output_activation(None, 1) == abi.LG_ERR_INVALID
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_estimator_kernels_do_not_spill_and_fit_the_lds(tmp_path):
+    """The route of tests/test_kernel_resources.py on csrc/lg_estimator.hip.  LDS bar: 160 KB per compute unit; the conv kernel is meant to run
+    several workgroups per compute unit (two waves per SIMD at least), so one workgroup may take at most half of it."""
+    obj, fat, co = (str(tmp_path / n) for n in ("lg_estimator.o", "fat.bin", "k.co"))
+    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize", "-c", "-o", obj,
+                    os.path.join(CSRC, "lg_estimator.hip")], check=True, capture_output=True)
+    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
+    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
+                    "--unbundle"], check=True, capture_output=True)
+    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+    blocks, cur = {}, None
+    for line in notes.splitlines():
+        line = line.strip()
+        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
+            cur = {}
+        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
+        if m and cur is not None:
+            if m.group(1) == "name":
+                blocks[m.group(2)] = cur
+            elif m.group(2).isdigit():
+                cur[m.group(1)] = int(m.group(2))
+    for part in ("conv_gemm_kernel", "pool_flatten_kernel", "cat_columns_kernel"):
+        hit = [v for k, v in blocks.items() if part in k]
+        assert len(hit) == 1, (part, sorted(blocks))
+        r = hit[0]
+        print(part, r)
+        assert r.get("vgpr_spill_count", 0) == 0 and r.get("sgpr_spill_count", 0) == 0 and r["private_segment_fixed_size"] == 0, (part, r)
+        assert r["group_segment_fixed_size"] <= 80 * 1024, (part, r)
+        assert r["vgpr_count"] <= 128, (part, r)          # 256 lanes x 128 registers: two workgroups' waves per SIMD
