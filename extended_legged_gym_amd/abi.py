@@ -348,6 +348,10 @@ def declare_policy(lib):
     lib.lg_conv_tile_weights.restype = C.c_int64
     lib.lg_conv_encoder_forward.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
     lib.lg_conv_encoder_forward.restype = C.c_int
+    lib.lg_conv_encoder_stage_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    lib.lg_conv_encoder_stage_shape.restype = C.c_int64
+    lib.lg_conv_encoder_forward_stages.argtypes = [vp, vp, C.c_int64, C.c_int64, i32, vp, vp]
+    lib.lg_conv_encoder_forward_stages.restype = C.c_int
     lib.lg_mlp_set_output_activation.argtypes = [vp, i32]
     lib.lg_mlp_set_output_activation.restype = C.c_int
     lib.lg_estimator_step.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp]
@@ -360,10 +364,12 @@ POLICY_SYMBOLS = ["lg_mlp_create", "lg_mlp_destroy", "lg_mlp_last_error", "lg_ml
                   "lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",
                   "lg_collect_rollout_recurrent", "lg_obs_history_step", "lg_distill_act", "lg_distill_act_recurrent", "lg_collect_distillation",
                   "lg_collect_distillation_recurrent", "lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights",
-                  "lg_conv_encoder_forward", "lg_mlp_set_output_activation", "lg_estimator_step"]
+                  "lg_conv_encoder_forward", "lg_mlp_set_output_activation", "lg_estimator_step", "lg_conv_encoder_stage_shape",
+                  "lg_conv_encoder_forward_stages"]
 ESTIMATOR_SYMBOLS = ["lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights", "lg_conv_encoder_forward",
-                     "lg_mlp_set_output_activation", "lg_estimator_step"]
+                     "lg_mlp_set_output_activation", "lg_estimator_step", "lg_conv_encoder_stage_shape", "lg_conv_encoder_forward_stages"]
 ENCODER_MAX_SIDE, ENCODER_MIN_SIDE, ENCODER_MAX_OUT = 128, 8, 512          # limits of lg_conv_encoder_create
+MLP_MAX_WIDTH = 512          # widest layer of an lg_mlp, inputs included: MLP_MAXW of csrc/lg_policy.hip, held to it by tests/test_estimator_abi.py
 RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2, "lrelu": 3, "selu": 4}
 

@@ -276,30 +276,44 @@ lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t o
 
 static int enc_launch(const ConvLayerDev& L, const float* in, int64_t in_estride, int64_t n, float* out, int64_t out_estride, hipStream_t st) {
   const int64_t tiles = (n * L.Hout * L.Wout + CONV_ROWS - 1) / CONV_ROWS;
-  if (tiles > 0x7fffffff) { lg_policy_set_error("lg_conv_encoder_forward: too many rows for one launch"); return LG_ERR_UNSUPPORTED; }
+  if (tiles > 0x7fffffff) { lg_policy_set_error("lg_conv_encoder: too many rows for one launch"); return LG_ERR_UNSUPPORTED; }
   hipLaunchKernelGGL(conv_gemm_kernel, dim3((unsigned)tiles, (unsigned)((L.Cout + CONV_COLS - 1) / CONV_COLS)), dim3(CONV_THREADS), 0, st, L, in, in_estride, n, out,
                      out_estride);
   return LG_OK;
 }
 
-// features rows are `feat_stride` floats apart (lg_estimator_step writes them straight into the first columns of its cat rows)
-static int enc_forward(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* features, int64_t feat_stride, hipStream_t st) {
+// floats of one env's output of stage k = 1..7 (conv 1-4, pool + flatten, linear 1, linear 2), and its map: (H, W, C) of a conv stage, (1, 1, width) else
+static int64_t enc_stage_shape(const lg_conv_encoder* e, int k, int* h, int* w, int* c) {
+  const ConvLayerDev& L = e->layer[k <= 4 ? k - 1 : k == 5 ? 3 : k - 2];
+  *h = k <= 4 ? L.Hout : 1; *w = k <= 4 ? L.Wout : 1; *c = k == 5 ? 16 * L.Cout : L.Cout;
+  return (int64_t)*h * *w * *c;
+}
+
+// The encoder's launch list, cut after `stages` of its seven stages: stage k reads stage k - 1's rows (the depth images for k = 1) and writes workspace
+// A (k odd) or B (k even); the last one, linear 2, writes `features`, rows `feat_stride` floats apart (lg_estimator_step has them written straight into
+// the first columns of its cat rows).  *last (if asked for) = where the rows of the last stage run are.
+static int enc_forward(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* features, int64_t feat_stride, hipStream_t st,
+                       int stages = ENC_LAYERS + 1, const float** last = nullptr) {
   if (n > e->cap) {          // the workspaces grow to the largest n seen; hipFree waits for the device, so a caller that alternates streams stays safe
     if (!enc_grow(&e->ws_a, (size_t)n * e->floats_a) || !enc_grow(&e->ws_b, (size_t)n * e->floats_b)) {
-      e->cap = 0; lg_policy_set_error("lg_conv_encoder_forward: workspace allocation failed"); return LG_ERR_HIP;
+      e->cap = 0; lg_policy_set_error("lg_conv_encoder: workspace allocation failed"); return LG_ERR_HIP;
     }
     e->cap = n;
   }
-  const ConvLayerDev* L = e->layer;
-  int rc;
-  if ((rc = enc_launch(L[0], depth, depth_stride, n, e->ws_a, (int64_t)L[0].Hout * L[0].Wout * L[0].Cout, st)) != LG_OK) return rc;
-  if ((rc = enc_launch(L[1], e->ws_a, (int64_t)L[1].Hin * L[1].Win * L[1].Cin, n, e->ws_b, (int64_t)L[1].Hout * L[1].Wout * L[1].Cout, st)) != LG_OK) return rc;
-  if ((rc = enc_launch(L[2], e->ws_b, (int64_t)L[2].Hin * L[2].Win * L[2].Cin, n, e->ws_a, (int64_t)L[2].Hout * L[2].Wout * L[2].Cout, st)) != LG_OK) return rc;
-  if ((rc = enc_launch(L[3], e->ws_a, (int64_t)L[3].Hin * L[3].Win * L[3].Cin, n, e->ws_b, (int64_t)L[3].Hout * L[3].Wout * L[3].Cout, st)) != LG_OK) return rc;
-  hipLaunchKernelGGL(pool_flatten_kernel, dim3((unsigned)((n * 1024 + 255) / 256)), dim3(256), 0, st, e->ws_b, n, e->Hp, e->Wp, 64, e->ws_a);
-  if ((rc = enc_launch(L[4], e->ws_a, 1024, n, e->ws_b, 128, st)) != LG_OK) return rc;
-  if ((rc = enc_launch(L[5], e->ws_b, 128, n, features, feat_stride, st)) != LG_OK) return rc;
+  const float* in = depth; int64_t in_stride = depth_stride;
+  for (int k = 1; k <= stages; ++k) {
+    int h, w, c;
+    float* out = k == ENC_LAYERS + 1 ? features : (k & 1) ? e->ws_a : e->ws_b;
+    const int64_t out_stride = k == ENC_LAYERS + 1 ? feat_stride : enc_stage_shape(e, k, &h, &w, &c);
+    if (k == 5) hipLaunchKernelGGL(pool_flatten_kernel, dim3((unsigned)((n * 1024 + 255) / 256)), dim3(256), 0, st, in, n, e->Hp, e->Wp, 64, out);
+    else {
+      const int rc = enc_launch(e->layer[k < 5 ? k - 1 : k - 2], in, in_stride, n, out, out_stride, st);
+      if (rc != LG_OK) return rc;
+    }
+    in = out; in_stride = out_stride;
+  }
   EST_TRY(hipGetLastError());
+  if (last) *last = in;
   return LG_OK;
 }
 
@@ -309,6 +323,30 @@ int lg_conv_encoder_forward(lg_conv_encoder* e, const float* depth, int64_t dept
   if (depth_stride < (int64_t)e->H * e->W) { lg_policy_set_error("lg_conv_encoder_forward: depth_stride is smaller than one image"); return LG_ERR_INVALID; }
   DeviceScope ds_(e->device);
   return enc_forward(e, depth, depth_stride, n, features, e->out_dim, (hipStream_t)stream);
+}
+
+int64_t lg_conv_encoder_stage_shape(const lg_conv_encoder* e, int32_t stage, int32_t* h, int32_t* w, int32_t* c) {
+  if (!e || stage < 1 || stage > ENC_LAYERS + 1) { lg_policy_set_error("lg_conv_encoder_stage_shape: null encoder or stage outside 1..7"); return LG_ERR_INVALID; }
+  int hh, ww, cc;
+  const int64_t count = enc_stage_shape(e, stage, &hh, &ww, &cc);
+  if (h) *h = hh;
+  if (w) *w = ww;
+  if (c) *c = cc;
+  return count;
+}
+
+int lg_conv_encoder_forward_stages(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, int32_t stages, float* out, void* stream) {
+  if (!e || !depth || !out) { lg_policy_set_error("lg_conv_encoder_forward_stages: null argument"); return LG_ERR_INVALID; }
+  if (n <= 0) { lg_policy_set_error("lg_conv_encoder_forward_stages: n must be positive"); return LG_ERR_INVALID; }
+  if (depth_stride < (int64_t)e->H * e->W) { lg_policy_set_error("lg_conv_encoder_forward_stages: depth_stride is smaller than one image"); return LG_ERR_INVALID; }
+  if (stages < 1 || stages > ENC_LAYERS + 1) { lg_policy_set_error("lg_conv_encoder_forward_stages: stages must be 1..7"); return LG_ERR_INVALID; }
+  DeviceScope ds_(e->device);
+  const float* last = nullptr;
+  const int rc = enc_forward(e, depth, depth_stride, n, out, e->out_dim, (hipStream_t)stream, stages, &last);
+  if (rc != LG_OK || last == out) return rc;
+  int h, w, c;
+  EST_TRY(hipMemcpyAsync(out, last, (size_t)n * enc_stage_shape(e, stages, &h, &w, &c) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return LG_OK;
 }
 
 int lg_estimator_step(lg_conv_encoder* e, lg_mlp* combine, lg_rnn* mem, lg_mlp* decoder, const float* depth, int64_t depth_stride, const float* proprio,

@@ -24,7 +24,8 @@ def parse_estimator_state(state_dict, depth_image_shape, proprio_dim, memory_typ
     dict holding one under `model_state_dict` (`terrain_estimator_runner.py:568-578`).  Returns a dict: `encoder` [(weight, bias)] x 6,
     `combine` (weight, bias), `memory` [(w_ih, w_hh, b_ih, b_hh)] per layer, `decoder` [(weight, bias)], and the widths read from the shapes
     (`encoder_output_dim`, `memory_hidden_size`, `memory_num_layers`, `decoder_hidden_dims`, `num_raycast_outputs`).  ValueError naming the
-    key whose shape does not fit the declared image, `proprio_dim` or memory type; KeyError for a missing key."""
+    key whose shape does not fit the declared image, `proprio_dim` or memory type, or the width of a combination layer wider than an `lg_mlp`
+    takes; KeyError for a missing key."""
     if "model_state_dict" in state_dict and "depth_encoder.0.weight" not in state_dict:
         state_dict = state_dict["model_state_dict"]
     height, width = (int(v) for v in depth_image_shape)
@@ -56,6 +57,9 @@ def parse_estimator_state(state_dict, depth_image_shape, proprio_dim, memory_typ
         raise ValueError(f"depth_encoder.12.weight has shape {w12.shape}, expected (encoder_output_dim <= {abi.ENCODER_MAX_OUT}, 128)")
     enc.append(pair("depth_encoder.12", None, ""))
     F = w12.shape[0]
+    if F + int(proprio_dim) > abi.MLP_MAX_WIDTH:
+        raise ValueError(f"the combination layer reads encoder_output_dim {F} + proprio_dim {int(proprio_dim)} = {F + int(proprio_dim)} inputs, more than the "
+                         f"{abi.MLP_MAX_WIDTH} an lg_mlp layer takes")
     comb = pair("combination_mlp.0", (F, F + int(proprio_dim)), f"encoder_output_dim {F} + proprio_dim {int(proprio_dim)} inputs")
     G = 4 if memory_type == "lstm" else 3
     L = len([k for k in state_dict if k.startswith("memory.rnn.weight_ih_l")])
@@ -135,6 +139,31 @@ class NativeConvEncoder:
         if rc != abi.LG_OK:
             raise RuntimeError("lg_conv_encoder_forward failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
         return y
+
+    def stage_shape(self, k):
+        """(floats of one row, (H, W, C)) of stage k's output: k = 1..4 the convolutions, 5 pool + flatten, 6 and 7 the linear layers."""
+        h, w, c = C.c_int32(), C.c_int32(), C.c_int32()
+        count = self.lib.lg_conv_encoder_stage_shape(self.handle, int(k), C.byref(h), C.byref(w), C.byref(c))
+        if count < 0:
+            raise ValueError("lg_conv_encoder_stage_shape failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        return int(count), (h.value, w.value, c.value)
+
+    def stage(self, depth_images, k, out=None):
+        """The encoder cut after stage k (`lg_conv_encoder_forward_stages`): torch's (n, C, H, W) view of a convolution's map (the kernels keep it
+        channel last), (n, 1024) after pool + flatten, (n, 128), (n, out_dim).  `out`: a flat float32 buffer of at least n x count floats to
+        write into instead of a fresh one."""
+        x = self.latest_frame(depth_images)
+        n = x.shape[0]
+        count, (h, w, c) = self.stage_shape(k)
+        if out is None:
+            out = torch.empty(n * count, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.device == self.device and out.numel() >= n * count
+        rc = self.lib.lg_conv_encoder_forward_stages(self.handle, C.c_void_p(x.data_ptr()), max(x.stride(0), self.height * self.width), n, int(k),
+                                                     C.c_void_p(out.data_ptr()), self._stream())
+        if rc != abi.LG_OK:
+            raise RuntimeError("lg_conv_encoder_forward_stages failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        y = out.view(-1)[:n * count]
+        return y.view(n, h, w, c).permute(0, 3, 1, 2) if k <= 4 else y.view(n, count)
 
     def close(self):
         if getattr(self, "handle", None):

@@ -231,6 +231,16 @@ int64_t lg_conv_tile_weights(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw
  * FIFO in place (depth_buffer[:, -1]).  LG_ERR_INVALID for n <= 0, a NULL pointer or depth_stride < height * width; nothing is launched then. */
 int lg_conv_encoder_forward(lg_conv_encoder* enc, const float* depth, int64_t depth_stride, int64_t n, float* features, void* stream);
 
+/* The encoder cut after its first `stages` stages, for checking a layer on its own.  Stages 1..7: conv 1-4 (each with its activation), pool + flatten,
+ * linear 1, linear 2.  It runs the launches lg_conv_encoder_forward runs for those stages -- same kernels, grids, workspaces and order, through the same
+ * code -- and copies the last one's rows to `out` (device, n x count floats, asynchronous on `stream`) in the layout the kernels keep:
+ *     conv stage: (n, H_out, W_out, C_out), channel last;   pool: (n, 1024), channel major (torch's Flatten);   linear 1: (n, 128);   linear 2: (n, out_dim).
+ * stages = 7 writes what lg_conv_encoder_forward writes, bit for bit.  LG_ERR_INVALID as there, and for stages outside 1..7; nothing is launched then.
+ * lg_conv_encoder_stage_shape: the floats of one row of stage `stage`'s output (the `count` above), and through h / w / c (each may be NULL) the map
+ * (H_out, W_out, C_out) of a conv stage, (1, 1, width) of the others; LG_ERR_INVALID for a NULL encoder or a stage outside 1..7.  No device work. */
+int64_t lg_conv_encoder_stage_shape(const lg_conv_encoder* enc, int32_t stage, int32_t* h, int32_t* w, int32_t* c);
+int lg_conv_encoder_forward_stages(lg_conv_encoder* enc, const float* depth, int64_t depth_stride, int64_t n, int32_t stages, float* out, void* stream);
+
 /* enabled != 0: the activation also follows the LAST layer of the network, as nn.Sequential(Linear, act) has it -- the estimator's combination_mlp
  * (terrain_estimator.py:58-61).  Networks keep a linear last layer unless this is called. */
 int lg_mlp_set_output_activation(lg_mlp* mlp, int32_t enabled);

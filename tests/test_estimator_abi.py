@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
 LIB = os.path.join(CSRC, "liblgstep.so")
 NEW = ["lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights", "lg_conv_encoder_forward", "lg_mlp_set_output_activation",
-       "lg_estimator_step"]
+       "lg_estimator_step", "lg_conv_encoder_stage_shape", "lg_conv_encoder_forward_stages"]
 
 
 def _lib():
@@ -91,9 +91,23 @@ def test_refusals_that_need_no_device():
     p = 0x1000
     assert lib.lg_conv_encoder_forward(None, p, 1568, 4, p, None) == abi.LG_ERR_INVALID
     assert "lg_conv_encoder_forward" in (lib.lg_mlp_last_error(None) or b"").decode()
+    for stages in (1, 7, 0, 8):
+        assert lib.lg_conv_encoder_forward_stages(None, p, 1568, 4, stages, p, None) == abi.LG_ERR_INVALID
+        assert "lg_conv_encoder_forward_stages" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert lib.lg_conv_encoder_stage_shape(None, 1, None, None, None) == abi.LG_ERR_INVALID
+    assert "lg_conv_encoder_stage_shape" in (lib.lg_mlp_last_error(None) or b"").decode()
     assert lib.lg_estimator_step(None, None, None, None, p, 1568, p, 4, p, None, None, p, None) == abi.LG_ERR_INVALID
     assert "lg_estimator_step" in (lib.lg_mlp_last_error(None) or b"").decode()
     assert lib.lg_mlp_set_output_activation(None, 1) == abi.LG_ERR_INVALID
+    # abi.MLP_MAX_WIDTH, which parse_estimator_state holds the combination layer to, is the library's own limit: one more is refused for its width
+    w, b = np.zeros((4, abi.MLP_MAX_WIDTH + 1), np.float32), np.zeros(4, np.float32)
+    one = lambda a: (fp * 1)(a.ctypes.data_as(fp))          # noqa: E731
+    assert not lib.lg_mlp_create(1, (C.c_int32 * 2)(abi.MLP_MAX_WIDTH + 1, 4), one(w), one(b), 0, 0)
+    assert "layer width out of range (1..%d)" % abi.MLP_MAX_WIDTH in (lib.lg_mlp_last_error(None) or b"").decode()
+    mlp = lib.lg_mlp_create(1, (C.c_int32 * 2)(abi.MLP_MAX_WIDTH, 4), one(w[:, :-1].copy()), one(b), 0, 0)
+    assert mlp or "layer width" not in (lib.lg_mlp_last_error(None) or b"").decode()          # without a device it fails later, for that reason
+    if mlp:
+        lib.lg_mlp_destroy(mlp)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")

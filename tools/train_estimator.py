@@ -101,6 +101,21 @@ class TerrainEstimatorTorch(nn.Module):
         return self.memory.hidden_states
 
 
+ENCODER_STAGE_ENDS = (2, 4, 6, 8, 10, 12, 14)          # depth_encoder[:end] = stage k: conv + act x 4, pool + flatten, linear + act x 2
+
+
+def encoder_stages(module, depth_images):
+    """The seven stage outputs of `module.depth_encoder` on (n, h, w) images, each the Sequential cut after the stage's last module: four maps
+    (n, C, H, W), the pooled rows (n, 1024), (n, 128), (n, encoder_output_dim).  What `NativeConvEncoder.stage` is compared with."""
+    out, x = [], depth_images.unsqueeze(1)
+    with torch.no_grad():
+        for i, layer in enumerate(module.depth_encoder):
+            x = layer(x)
+            if i + 1 in ENCODER_STAGE_ENDS:
+                out.append(x)
+    return out
+
+
 def closed_form_state(module, salt=0):
     """Weights as a closed-form rule of the flat index, no RNG: tensor number j of `module.state_dict()` (in its own order), entry i:
         u = ((2654435761 i + 40503 j + 12345 + 7919 salt) mod 2^32) / 2^32;   value = (2 u - 1) * a,
