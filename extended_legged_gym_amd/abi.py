@@ -356,6 +356,12 @@ def declare_policy(lib):
     lib.lg_mlp_set_output_activation.restype = C.c_int
     lib.lg_estimator_step.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp]
     lib.lg_estimator_step.restype = C.c_int
+    lib.lg_conv_encoder_create_precision.argtypes = [i32, i32, i32, i32, fpp, fpp, C.c_int, i32]
+    lib.lg_conv_encoder_create_precision.restype = vp
+    lib.lg_conv_encoder_precision.argtypes = [vp]
+    lib.lg_conv_encoder_precision.restype = i32
+    lib.lg_conv_tile_weights_bf16.argtypes = [i32, i32, i32, i32, vp, vp]
+    lib.lg_conv_tile_weights_bf16.restype = C.c_int64
     return lib
 
 
@@ -365,9 +371,12 @@ POLICY_SYMBOLS = ["lg_mlp_create", "lg_mlp_destroy", "lg_mlp_last_error", "lg_ml
                   "lg_collect_rollout_recurrent", "lg_obs_history_step", "lg_distill_act", "lg_distill_act_recurrent", "lg_collect_distillation",
                   "lg_collect_distillation_recurrent", "lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights",
                   "lg_conv_encoder_forward", "lg_mlp_set_output_activation", "lg_estimator_step", "lg_conv_encoder_stage_shape",
-                  "lg_conv_encoder_forward_stages"]
+                  "lg_conv_encoder_forward_stages", "lg_conv_encoder_create_precision", "lg_conv_encoder_precision"]
 ESTIMATOR_SYMBOLS = ["lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights", "lg_conv_encoder_forward",
                      "lg_mlp_set_output_activation", "lg_estimator_step", "lg_conv_encoder_stage_shape", "lg_conv_encoder_forward_stages"]
+ESTIMATOR_BF16_SYMBOLS = ["lg_conv_encoder_create_precision", "lg_conv_encoder_precision", "lg_conv_tile_weights_bf16"]
+LG_PREC_F32, LG_PREC_BF16 = 0, 1          # the encoder's precision modes (include/lgpolicy.h)
+ENCODER_PRECISIONS = {"fp32": LG_PREC_F32, "bf16": LG_PREC_BF16}
 ENCODER_MAX_SIDE, ENCODER_MIN_SIDE, ENCODER_MAX_OUT = 128, 8, 512          # limits of lg_conv_encoder_create
 MLP_MAX_WIDTH = 512          # widest layer of an lg_mlp, inputs included: MLP_MAXW of csrc/lg_policy.hip, held to it by tests/test_estimator_abi.py
 RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type

@@ -20,9 +20,14 @@
 // limit (at 58 x 87 the first map alone is 163 KB per env, more than a compute unit's LDS), and the maps of a 64-row tile are small enough to stay
 // in L2 between layers.  AdaptiveAvgPool2d((4, 4)) + Flatten is a kernel of its own (one lane per output, torch's windows
 // [floor(i L / 4), ceil((i + 1) L / 4))), writing torch's channel-major order so the first linear layer reads its weights as torch stores them.
+//
+// Precision LG_PREC_BF16 (opt-in; the code below the marker "bf16 encoder") runs the same seven stages on v_mfma_f32_16x16x32_bf16: bf16 operands,
+// fp32 accumulators, bias and activation in fp32, maps of stages 1-6 kept as bf16 (round to nearest even), features in fp32.  The fp32 kernels and
+// their launch list are not touched by it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -46,6 +51,7 @@ struct ConvLayerDev {
   int Hin, Win, Cin, Hout, Wout, Cout, stride, pad, act;
   int nkb;                 // K rounded up to 64, / 16
   const float* w;          // tiled [chunk][k / 16][lane][4], Cout rounded up to 64
+  const uint16_t* w16;     // bf16 mode instead of w: tiled [chunk][k / 32][lane][8] (lg_conv_tile_weights_bf16); nkb and ktab are then those of enc_bf16_gemm_kernel
   const float* b;          // bias, zero-padded to the same width
   const int32_t* ktab;     // [16 nkb]: (ky << 26) | (kx << 22) | offset of tap k from the patch's first pixel, -1 beyond K
 };
@@ -156,11 +162,148 @@ __global__ __launch_bounds__(256) void cat_columns_kernel(const float* __restric
   dst[r * stride + col0 + k] = src[idx];
 }
 
+// ------------------------------------------------------------------------------------------------------------ bf16 encoder (LG_PREC_BF16)
+// The same product rows x K x C_out, the same 64 x 64 workgroup tile and the same accumulator map (entry i of a lane is C[row 4 (lane >> 4) + i]
+// [channel lane & 15]) on v_mfma_f32_16x16x32_bf16, whose operands are A[row lane & 15][k = 8 (lane >> 4) + j] and B[k = 8 (lane >> 4) + j]
+// [channel lane & 15], j = 0..7.  K runs in steps of 32.  Behind conv 1 every C_in is a multiple of 32 and the maps are bf16 (env, y, x, channel),
+// so a k-step lies inside one tap and a lane's eight A values are 16 contiguous, 16-byte aligned bytes of the map: the lane loads its operand
+// straight from global memory (zero outside the image), no LDS image, no barrier; the per-step tap and offset come from a table built at create
+// time (one entry per k-step, wave uniform).  conv 1 (C_in = 1, K = 25: one k-step, the cost is the gather) reads its eight taps one by one from
+// the fp32 image through the per-k table of the fp32 kernel and rounds them to bf16 there.  Weights: lg_conv_tile_weights_bf16, one coalesced
+// 16-byte load per lane, chunk and k-step.  The next step's operands are loaded before the current step's MFMAs.  Each output is one
+// accumulator over k-steps in ascending order: no atomics, no split K, equal inputs give equal bits.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+LG_DEV void enc_store(float* p, float v) { *p = v; }
+LG_DEV void enc_store(__bf16* p, float v) { *p = (__bf16)v; }          // v_cvt_pk_bf16_f32: round to nearest even
+
+// FIRST: `in` is the fp32 image (C_in = 1, ktab per k); else a bf16 map (C_in % 32 == 0, ktab per k-step).  TOut: __bf16 maps, float features.
+template <bool FIRST, typename TOut>
+__global__ __launch_bounds__(CONV_THREADS) void enc_bf16_gemm_kernel(ConvLayerDev L, const void* __restrict__ in_, int64_t in_estride, int64_t n,
+                                                                      TOut* __restrict__ out, int64_t out_estride) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4;
+  const int HW = L.Hout * L.Wout, nks = L.nkb;
+  const int64_t M = n * HW, row0 = (int64_t)blockIdx.x * CONV_ROWS + wv * 16;
+  // operand role: row lane & 15 of the wave's 16, k = 8 g + j of each step
+  const int64_t ma = row0 + (lane & 15);
+  int iy0 = -(1 << 20), ix0 = 0; int64_t base = 0;          // a row beyond M: every tap out of the image
+  if (ma < M) {
+    const int64_t e = ma / HW; const int pix = (int)(ma - e * HW), oy = pix / L.Wout, ox = pix - oy * L.Wout;
+    iy0 = oy * L.stride - L.pad; ix0 = ox * L.stride - L.pad;
+    base = e * in_estride + ((int64_t)iy0 * L.Win + ix0) * L.Cin + (FIRST ? 0 : 8 * g);
+  }
+  auto load_a = [&](int s) -> bf16x8 {
+    bf16x8 a;
+    if (FIRST) {
+      const float* in = static_cast<const float*>(in_);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int t = L.ktab[s * 32 + 8 * g + j];
+        const int iy = iy0 + ((t >> 26) & 15), ix = ix0 + ((t >> 22) & 15);
+        const bool ok = t >= 0 && iy >= 0 && iy < L.Hin && ix >= 0 && ix < L.Win;
+        a[j] = (__bf16)(ok ? in[base + (t & 0x3fffff)] : 0.f);
+      }
+    } else {
+      const int t = L.ktab[s];
+      const int iy = iy0 + ((t >> 26) & 15), ix = ix0 + ((t >> 22) & 15);
+      const bool ok = iy >= 0 && iy < L.Hin && ix >= 0 && ix < L.Win;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[j] = (__bf16)0.f;
+      if (ok) a = *reinterpret_cast<const bf16x8*>(static_cast<const __bf16*>(in_) + base + (t & 0x3fffff));
+    }
+    return a;
+  };
+  const int nch = min(4, (L.Cout - (int)blockIdx.y * CONV_COLS + 15) / 16);          // chunks of this column group that hold a channel (wave uniform); the rest are zero padding
+  const bf16x8* wl = reinterpret_cast<const bf16x8*>(L.w16) + (size_t)blockIdx.y * 4 * nks * 64 + lane;
+  f32x4 acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  bf16x8 a = load_a(0), w[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) w[c] = wl[(size_t)c * nks * 64];
+  for (int s = 0; s < nks; ++s) {
+    bf16x8 an = a, wn[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wn[c] = w[c];
+    if (s + 1 < nks) {
+      an = load_a(s + 1);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) wn[c] = wl[((size_t)c * nks + s + 1) * 64];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < nch) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, w[c], acc[c], 0, 0, 0);
+    a = an;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) w[c] = wn[c];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t m = row0 + 4 * g + i;
+    if (m >= M) continue;
+    const int64_t e = m / HW; const int pix = (int)(m - e * HW);
+    TOut* dst = out + e * out_estride + (int64_t)pix * L.Cout;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int col = blockIdx.y * CONV_COLS + c * 16 + (lane & 15);
+      if (col < L.Cout) enc_store(dst + col, enc_act(acc[c][i] + L.b[col], L.act));
+    }
+  }
+}
+
+// pool_flatten_kernel on a bf16 map: the window is averaged in fp32 and the mean rounded to bf16
+__global__ __launch_bounds__(256) void enc_bf16_pool_kernel(const __bf16* __restrict__ x, int64_t n, int H, int W, int C, __bf16* __restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * 16 * C) return;
+  const int c = (int)(idx % C); const int64_t t = idx / C; const int ij = (int)(t & 15); const int64_t e = t >> 4;
+  const int i = ij >> 2, j = ij & 3;
+  const int y0 = (i * H) / 4, y1 = ((i + 1) * H + 3) / 4, x0 = (j * W) / 4, x1 = ((j + 1) * W + 3) / 4;
+  float s = 0.f;
+  for (int yy = y0; yy < y1; ++yy)
+    for (int xx = x0; xx < x1; ++xx) s += (float)x[((e * H + yy) * W + xx) * C + c];
+  y[e * 16 * C + c * 16 + ij] = (__bf16)(s / (float)((y1 - y0) * (x1 - x0)));
+}
+
+// lg_conv_encoder_forward_stages on a bf16 encoder: the rows of a bf16 stage, expanded exactly
+__global__ __launch_bounds__(256) void enc_bf16_expand_kernel(const __bf16* __restrict__ x, int64_t count, float* __restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx < count) y[idx] = (float)x[idx];
+}
+
+// fp32 -> bf16, round to nearest even (NaN stays a quiet NaN)
+static uint16_t bf16_rne(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+static int64_t conv_tiled_count_bf16(int cout, int cin, int kh, int kw) {
+  const int64_t K = (int64_t)cin * kh * kw, nks = (K + 31) / 32, nch = ((cout + 63) & ~63) / 16;
+  return nch * nks * 64 * 8;
+}
+
+static void conv_tile_weights_bf16(int cout, int cin, int kh, int kw, const float* w, uint16_t* tiled) {
+  const int K = cin * kh * kw, nks = (K + 31) / 32, nch = ((cout + 63) & ~63) / 16;
+  for (int c = 0; c < nch; ++c)
+    for (int s = 0; s < nks; ++s)
+      for (int ln = 0; ln < 64; ++ln)
+        for (int j = 0; j < 8; ++j) {
+          const int col = c * 16 + (ln & 15), k = s * 32 + 8 * (ln >> 4) + j;
+          uint16_t v = 0;
+          if (col < cout && k < K) {
+            const int ci = k % cin, tap = k / cin, ky = tap / kw, kx = tap - ky * kw;
+            v = bf16_rne(w[(((size_t)col * cin + ci) * kh + ky) * kw + kx]);
+          }
+          tiled[(((size_t)c * nks + s) * 64 + ln) * 8 + j] = v;
+        }
+}
+
 struct lg_conv_encoder {
-  int device = 0, H = 0, W = 0, out_dim = 0, act = 0;
+  int device = 0, H = 0, W = 0, out_dim = 0, act = 0, prec = LG_PREC_F32;
   ConvLayerDev layer[ENC_LAYERS];
   int Hp = 0, Wp = 0;                      // the map the pooling reads
-  size_t floats_a = 0, floats_b = 0;       // per env: workspace A holds the maps of layers 0, 2 and the pooled row, B those of 1, 3 and the first linear
+  size_t floats_a = 0, floats_b = 0;       // per env: workspace A holds the maps of layers 0, 2 and the pooled row, B those of 1, 3 and the first linear (bf16 mode: elements of 2 bytes)
   int64_t cap = 0;                         // envs the workspaces hold
   float *ws_a = nullptr, *ws_b = nullptr;
   float *cat = nullptr, *comb = nullptr, *memo = nullptr;   // lg_estimator_step: (cap, cat_w), (cap, comb_w), (cap, mem_w)
@@ -208,6 +351,15 @@ int64_t lg_conv_tile_weights(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw
   return conv_tiled_count(c_out, c_in, kh, kw);
 }
 
+int64_t lg_conv_tile_weights_bf16(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw, const float* weight, uint16_t* tiled) {
+  if (c_out < 1 || c_out > ENC_MAX_OUT || c_in < 1 || c_in > 1024 || kh < 1 || kh > 15 || kw < 1 || kw > 15) return LG_ERR_INVALID;
+  if (tiled) {
+    if (!weight) return LG_ERR_INVALID;
+    conv_tile_weights_bf16(c_out, c_in, kh, kw, weight, tiled);
+  }
+  return conv_tiled_count_bf16(c_out, c_in, kh, kw);
+}
+
 void lg_conv_encoder_destroy(lg_conv_encoder* e) {
   if (!e) return;
   DeviceScope ds_(e->device);
@@ -216,8 +368,9 @@ void lg_conv_encoder_destroy(lg_conv_encoder* e) {
   delete e;
 }
 
-lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
-                                        const float* const* biases, int device_id) {
+lg_conv_encoder* lg_conv_encoder_create_precision(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
+                                                  const float* const* biases, int device_id, int32_t precision) {
+  if (precision != LG_PREC_F32 && precision != LG_PREC_BF16) { lg_policy_set_error("lg_conv_encoder_create: precision must be LG_PREC_F32 or LG_PREC_BF16"); return nullptr; }
   if (height < 8 || height > ENC_MAX_HW || width < 8 || width > ENC_MAX_HW) { lg_policy_set_error("lg_conv_encoder_create: image size out of range (8..128 per side)"); return nullptr; }
   if (out_dim < 1 || out_dim > ENC_MAX_OUT) { lg_policy_set_error("lg_conv_encoder_create: out_dim out of range (1..512)"); return nullptr; }
   if (activation != LG_ACT_ELU && activation != LG_ACT_RELU && activation != LG_ACT_TANH) { lg_policy_set_error("lg_conv_encoder_create: activation must be elu, relu or tanh"); return nullptr; }
@@ -229,7 +382,8 @@ lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t o
   DeviceScope ds_(device_id);
   if (!ds_.ok) { lg_policy_set_error("bad device"); return nullptr; }
   lg_conv_encoder* e = new lg_conv_encoder();
-  e->device = device_id; e->H = height; e->W = width; e->out_dim = out_dim; e->act = activation;
+  e->device = device_id; e->H = height; e->W = width; e->out_dim = out_dim; e->act = activation; e->prec = precision;
+  const bool bf16 = precision == LG_PREC_BF16;
   int h = height, w = width;
   size_t map_floats[ENC_LAYERS];
   for (int l = 0; l < ENC_LAYERS; ++l) {
@@ -247,15 +401,19 @@ lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t o
     }
     L.act = activation;
     const int K = L.Cin * kh * kh;
-    L.nkb = ((K + 63) & ~63) / 16;
+    L.nkb = bf16 ? (K + 31) / 32 : ((K + 63) & ~63) / 16;          // bf16: k-steps of 32
     map_floats[l] = (size_t)L.Hout * L.Wout * L.Cout;
-    std::vector<float> tw((size_t)conv_tiled_count(L.Cout, L.Cin, kh, kh)), tb((size_t)((L.Cout + 63) & ~63), 0.f);
-    conv_tile_weights(L.Cout, L.Cin, kh, kh, weights[l], tw.data());
+    // tw: the tiled weights as 4-byte words (bf16: two values per word)
+    std::vector<float> tw((size_t)(bf16 ? conv_tiled_count_bf16(L.Cout, L.Cin, kh, kh) / 2 : conv_tiled_count(L.Cout, L.Cin, kh, kh))), tb((size_t)((L.Cout + 63) & ~63), 0.f);
+    if (bf16) conv_tile_weights_bf16(L.Cout, L.Cin, kh, kh, weights[l], reinterpret_cast<uint16_t*>(tw.data()));
+    else conv_tile_weights(L.Cout, L.Cin, kh, kh, weights[l], tw.data());
     for (int i = 0; i < L.Cout; ++i) tb[i] = biases[l][i];
-    std::vector<int32_t> kt((size_t)L.nkb * 16, -1);
-    for (int k = 0; k < K; ++k) {
+    // per k (fp32, and conv 1 of bf16) or per k-step of 32 (bf16 behind conv 1: C_in % 32 == 0, a step lies inside one tap)
+    const bool per_step = bf16 && l > 0;
+    std::vector<int32_t> kt(per_step ? (size_t)L.nkb : bf16 ? (size_t)L.nkb * 32 : (size_t)L.nkb * 16, -1);
+    for (int k = 0; k < K; k += per_step ? 32 : 1) {
       const int ci = k % L.Cin, tap = k / L.Cin, ky = tap / kh, kx = tap - ky * kh;
-      kt[k] = (ky << 26) | (kx << 22) | ((ky * L.Win + kx) * L.Cin + ci);         // offset < 15 * 128 * 1024 + ... < 2^22 for every supported shape
+      kt[per_step ? k / 32 : k] = (ky << 26) | (kx << 22) | ((ky * L.Win + kx) * L.Cin + ci);         // offset < 15 * 128 * 1024 + ... < 2^22 for every supported shape
     }
     void *dw = nullptr, *db = nullptr, *dk = nullptr;
     const bool ok = hipMalloc(&dw, tw.size() * 4) == hipSuccess && hipMalloc(&db, tb.size() * 4) == hipSuccess && hipMalloc(&dk, kt.size() * 4) == hipSuccess &&
@@ -264,12 +422,22 @@ lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t o
                     hipMemcpy(dk, kt.data(), kt.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
     for (void* p : {dw, db, dk}) if (p) e->allocs.push_back(p);
     if (!ok) { lg_policy_set_error("lg_conv_encoder_create: weight upload failed"); lg_conv_encoder_destroy(e); return nullptr; }
-    L.w = (const float*)dw; L.b = (const float*)db; L.ktab = (const int32_t*)dk;
+    L.w = bf16 ? nullptr : (const float*)dw; L.w16 = bf16 ? (const uint16_t*)dw : nullptr; L.b = (const float*)db; L.ktab = (const int32_t*)dk;
   }
   e->Hp = h; e->Wp = w;
   e->floats_a = std::max(std::max(map_floats[0], map_floats[2]), (size_t)1024);
   e->floats_b = std::max(std::max(map_floats[1], map_floats[3]), (size_t)128);
   return e;
+}
+
+lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
+                                        const float* const* biases, int device_id) {
+  return lg_conv_encoder_create_precision(height, width, out_dim, activation, weights, biases, device_id, LG_PREC_F32);
+}
+
+int32_t lg_conv_encoder_precision(const lg_conv_encoder* e) {
+  if (!e) { lg_policy_set_error("lg_conv_encoder_precision: null encoder"); return LG_ERR_INVALID; }
+  return e->prec;
 }
 
 #define EST_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { lg_policy_set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); return LG_ERR_HIP; } } while (0)
@@ -279,6 +447,17 @@ static int enc_launch(const ConvLayerDev& L, const float* in, int64_t in_estride
   if (tiles > 0x7fffffff) { lg_policy_set_error("lg_conv_encoder: too many rows for one launch"); return LG_ERR_UNSUPPORTED; }
   hipLaunchKernelGGL(conv_gemm_kernel, dim3((unsigned)tiles, (unsigned)((L.Cout + CONV_COLS - 1) / CONV_COLS)), dim3(CONV_THREADS), 0, st, L, in, in_estride, n, out,
                      out_estride);
+  return LG_OK;
+}
+
+// bf16 mode: stage k = 1 reads the fp32 image, stage 7 writes fp32 features, everything between is bf16
+static int enc_launch_bf16(const ConvLayerDev& L, int k, const void* in, int64_t in_estride, int64_t n, void* out, int64_t out_estride, hipStream_t st) {
+  const int64_t tiles = (n * L.Hout * L.Wout + CONV_ROWS - 1) / CONV_ROWS;
+  if (tiles > 0x7fffffff) { lg_policy_set_error("lg_conv_encoder: too many rows for one launch"); return LG_ERR_UNSUPPORTED; }
+  const dim3 grid((unsigned)tiles, (unsigned)((L.Cout + CONV_COLS - 1) / CONV_COLS)), block(CONV_THREADS);
+  if (k == 1) hipLaunchKernelGGL((enc_bf16_gemm_kernel<true, __bf16>), grid, block, 0, st, L, in, in_estride, n, (__bf16*)out, out_estride);
+  else if (k == ENC_LAYERS + 1) hipLaunchKernelGGL((enc_bf16_gemm_kernel<false, float>), grid, block, 0, st, L, in, in_estride, n, (float*)out, out_estride);
+  else hipLaunchKernelGGL((enc_bf16_gemm_kernel<false, __bf16>), grid, block, 0, st, L, in, in_estride, n, (__bf16*)out, out_estride);
   return LG_OK;
 }
 
@@ -295,12 +474,29 @@ static int64_t enc_stage_shape(const lg_conv_encoder* e, int k, int* h, int* w, 
 static int enc_forward(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* features, int64_t feat_stride, hipStream_t st,
                        int stages = ENC_LAYERS + 1, const float** last = nullptr) {
   if (n > e->cap) {          // the workspaces grow to the largest n seen; hipFree waits for the device, so a caller that alternates streams stays safe
-    if (!enc_grow(&e->ws_a, (size_t)n * e->floats_a) || !enc_grow(&e->ws_b, (size_t)n * e->floats_b)) {
+    const size_t per = e->prec == LG_PREC_BF16 ? 2 : 1;          // bf16 maps: two elements per float
+    if (!enc_grow(&e->ws_a, ((size_t)n * e->floats_a + per - 1) / per) || !enc_grow(&e->ws_b, ((size_t)n * e->floats_b + per - 1) / per)) {
       e->cap = 0; lg_policy_set_error("lg_conv_encoder: workspace allocation failed"); return LG_ERR_HIP;
     }
     e->cap = n;
   }
   const float* in = depth; int64_t in_stride = depth_stride;
+  if (e->prec == LG_PREC_BF16) {          // the same stage list; `in` / `out` hold bf16 between the image and the features
+    for (int k = 1; k <= stages; ++k) {
+      int h, w, c;
+      float* out = k == ENC_LAYERS + 1 ? features : (k & 1) ? e->ws_a : e->ws_b;
+      const int64_t out_stride = k == ENC_LAYERS + 1 ? feat_stride : enc_stage_shape(e, k, &h, &w, &c);
+      if (k == 5) hipLaunchKernelGGL(enc_bf16_pool_kernel, dim3((unsigned)((n * 1024 + 255) / 256)), dim3(256), 0, st, (const __bf16*)in, n, e->Hp, e->Wp, 64, (__bf16*)out);
+      else {
+        const int rc = enc_launch_bf16(e->layer[k < 5 ? k - 1 : k - 2], k, in, in_stride, n, out, out_stride, st);
+        if (rc != LG_OK) return rc;
+      }
+      in = out; in_stride = out_stride;
+    }
+    EST_TRY(hipGetLastError());
+    if (last) *last = in;
+    return LG_OK;
+  }
   for (int k = 1; k <= stages; ++k) {
     int h, w, c;
     float* out = k == ENC_LAYERS + 1 ? features : (k & 1) ? e->ws_a : e->ws_b;
@@ -345,6 +541,12 @@ int lg_conv_encoder_forward_stages(lg_conv_encoder* e, const float* depth, int64
   const int rc = enc_forward(e, depth, depth_stride, n, out, e->out_dim, (hipStream_t)stream, stages, &last);
   if (rc != LG_OK || last == out) return rc;
   int h, w, c;
+  if (e->prec == LG_PREC_BF16) {
+    const int64_t count = n * enc_stage_shape(e, stages, &h, &w, &c);
+    hipLaunchKernelGGL(enc_bf16_expand_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)last, count, out);
+    EST_TRY(hipGetLastError());
+    return LG_OK;
+  }
   EST_TRY(hipMemcpyAsync(out, last, (size_t)n * enc_stage_shape(e, stages, &h, &w, &c) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return LG_OK;
 }

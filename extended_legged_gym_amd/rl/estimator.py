@@ -19,6 +19,13 @@ def estimator_activation(name):
     return name if name in ("elu", "relu", "tanh") else "elu"
 
 
+def parse_precision(name):
+    """`fp32 | bf16` -> LG_PREC_*; ValueError for anything else (no device needed)."""
+    if not isinstance(name, str) or name not in abi.ENCODER_PRECISIONS:
+        raise ValueError(f"encoder precision {name!r}: must be one of {sorted(abi.ENCODER_PRECISIONS)}")
+    return abi.ENCODER_PRECISIONS[name]
+
+
 def parse_estimator_state(state_dict, depth_image_shape, proprio_dim, memory_type="gru"):
     """The loading rules of `NativeTerrainEstimator`, without a device.  `state_dict`: a `TerrainEstimator.state_dict()`, or a runner file's
     dict holding one under `model_state_dict` (`terrain_estimator_runner.py:568-578`).  Returns a dict: `encoder` [(weight, bias)] x 6,
@@ -93,10 +100,14 @@ def parse_estimator_state(state_dict, depth_image_shape, proprio_dim, memory_typ
 
 
 class NativeConvEncoder:
-    """`TerrainEstimator.depth_encoder` (`terrain_estimator.py:80-109`) on the GPU: `layers` = [(weight, bias)] x 6 in torch's layouts."""
+    """`TerrainEstimator.depth_encoder` (`terrain_estimator.py:80-109`) on the GPU: `layers` = [(weight, bias)] x 6 in torch's layouts.
+    `precision`: "fp32" (default), or "bf16" for inference on the bf16 matrix cores (bf16 operands and maps, fp32 accumulation and features;
+    include/lgpolicy.h `lg_conv_encoder_create_precision`)."""
 
-    def __init__(self, layers, depth_image_shape, activation="elu", device="cuda:0"):
+    def __init__(self, layers, depth_image_shape, activation="elu", device="cuda:0", precision="fp32"):
         from .policy import _lib
+        prec = parse_precision(precision)
+        self.precision = precision
         dev = torch.device(device)
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("the estimator kernels run on the GPU only (no CPU path)")
@@ -109,7 +120,11 @@ class NativeConvEncoder:
         wp = (fp * 6)(*[w.ctypes.data_as(fp) for w in ws])
         bp = (fp * 6)(*[b.ctypes.data_as(fp) for b in bs])
         index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.handle = self.lib.lg_conv_encoder_create(self.height, self.width, self.out_dim, abi.ACTIVATIONS[estimator_activation(activation)], wp, bp, index)
+        if prec == abi.LG_PREC_F32:
+            self.handle = self.lib.lg_conv_encoder_create(self.height, self.width, self.out_dim, abi.ACTIVATIONS[estimator_activation(activation)], wp, bp, index)
+        else:
+            self.handle = self.lib.lg_conv_encoder_create_precision(self.height, self.width, self.out_dim, abi.ACTIVATIONS[estimator_activation(activation)], wp, bp,
+                                                                    index, prec)
         if not self.handle:
             raise RuntimeError("lg_conv_encoder_create failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
 
@@ -180,17 +195,20 @@ class NativeConvEncoder:
 
 class NativeTerrainEstimator:
     """Same surface as `TerrainEstimator` for inference (`terrain_estimator.py:200-218`): `act_inference`, `reset`, `get_hidden_states`,
-    `set_hidden_states`.  `encoder_output_dim`, the memory's width / depth and the decoder's widths are read from the checkpoint's shapes."""
+    `set_hidden_states`.  `encoder_output_dim`, the memory's width / depth and the decoder's widths are read from the checkpoint's shapes.
+    `encoder_precision`: "fp32" (default) or "bf16", the mode of the depth encoder alone; combination layer, memory and decoder stay fp32."""
 
-    def __init__(self, state_dict, depth_image_shape, proprio_dim, activation="elu", memory_type="gru", device="cuda:0"):
+    def __init__(self, state_dict, depth_image_shape, proprio_dim, activation="elu", memory_type="gru", device="cuda:0", encoder_precision="fp32"):
         from .policy import NativeMemory, NativeMLP
+        parse_precision(encoder_precision)          # refused before anything is parsed or built
+        self.precision = encoder_precision
         spec = parse_estimator_state(state_dict, depth_image_shape, proprio_dim, memory_type)
         self.spec = {k: v for k, v in spec.items() if k not in ("encoder", "combine", "memory", "decoder")}
         self.device = torch.device(device)
         act = estimator_activation(activation)
         self.depth_image_shape, self.proprio_dim = spec["depth_image_shape"], spec["proprio_dim"]
         self.num_raycast_outputs = spec["num_raycast_outputs"]
-        self.encoder = NativeConvEncoder(spec["encoder"], self.depth_image_shape, act, device)
+        self.encoder = NativeConvEncoder(spec["encoder"], self.depth_image_shape, act, device, precision=encoder_precision)
         self.combine = NativeMLP([spec["combine"]], act, device)
         if self.encoder.lib.lg_mlp_set_output_activation(self.combine.handle, 1) != abi.LG_OK:
             raise RuntimeError("lg_mlp_set_output_activation failed")

@@ -219,12 +219,34 @@ lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t o
                                         const float* const* biases, int device_id);
 void lg_conv_encoder_destroy(lg_conv_encoder* enc);
 
+/* The encoder's precision mode.  LG_PREC_F32 is lg_conv_encoder_create.  LG_PREC_BF16 (opt-in, inference on the bf16 matrix cores,
+ * v_mfma_f32_16x16x32_bf16): all six layers take bf16 operands and accumulate in fp32.  Rounding points, each fp32 -> bf16 to nearest even:
+ * the weights once at create time (lg_conv_tile_weights_bf16), the depth image on its way into conv 1 (zero padding stays exact), and the
+ * output of stages 1-6 (conv 1-4, pool + flatten, linear 1) as it is stored -- the workspaces hold bf16.  Biases stay fp32 and are added to the
+ * fp32 accumulator, the activation is evaluated in fp32, the pooling averages in fp32, and linear 2 writes fp32 features where the fp32 path
+ * writes them.  One fixed-order accumulation per output, no atomics, no split K: equal inputs give equal bits.  Same limits, same refusals;
+ * an unknown precision returns NULL with a message in lg_mlp_last_error(NULL), before any device is touched.  forward, forward_stages,
+ * stage_shape and lg_estimator_step take an encoder of either mode; the combination layer, memory and decoder stay fp32.
+ * lg_conv_encoder_precision: the mode of an encoder, LG_ERR_INVALID for NULL. */
+#define LG_PREC_F32 0
+#define LG_PREC_BF16 1
+lg_conv_encoder* lg_conv_encoder_create_precision(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
+                                                  const float* const* biases, int device_id, int32_t precision);
+int32_t lg_conv_encoder_precision(const lg_conv_encoder* enc);
+
 /* The host re-tiling of one layer, a pure function (no device).  With K = kh kw c_in and tap index k = (ky kw + kx) c_in + ci (channel fastest:
  * the kernels keep activations (env, y, x, channel)), nkb = (K rounded up to 64) / 16 blocks and nch = (c_out rounded up to 64) / 16 chunks:
  *     tiled[((c nkb + b) 64 + lane) 4 + s] = weight[16 c + (lane & 15)][ci][ky][kx]   for k = 16 b + 4 s + (lane >> 4),   zero for k >= K or a channel >= c_out.
  * A linear layer (out, in) is c_out = out, c_in = in, kh = kw = 1.  Returns the number of floats of `tiled` (HOST; NULL: only the count);
  * LG_ERR_INVALID for c_out outside 1..512, c_in outside 1..1024, kh / kw outside 1..15, or a NULL weight with a non-NULL `tiled`. */
 int64_t lg_conv_tile_weights(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw, const float* weight, float* tiled);
+
+/* The same for LG_PREC_BF16, in the operand order of v_mfma_f32_16x16x32_bf16.  With K and k as above, nks = (K rounded up to 32) / 32 k-steps and
+ * nch = (c_out rounded up to 64) / 16 chunks:
+ *     tiled[((c nks + s) 64 + lane) 8 + j] = bf16(weight[16 c + (lane & 15)][ci][ky][kx])   for k = 32 s + 8 (lane >> 4) + j,   zero for k >= K or a channel >= c_out,
+ * bf16(): the upper 16 bits of the fp32 value rounded to nearest even.  Returns the number of 16-bit elements of `tiled` (HOST; NULL: only the
+ * count); LG_ERR_INVALID as lg_conv_tile_weights. */
+int64_t lg_conv_tile_weights_bf16(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw, const float* weight, uint16_t* tiled);
 
 /* features (n, out_dim) = depth_encoder(depth.unsqueeze(1)) (terrain_estimator.py:164-167).  Image e starts at depth + e * depth_stride and is
  * (height, width) row-major: depth_stride = buffer_len * height * width reads the latest frame of the camera's (n, buffer_len, height, width)
@@ -235,6 +257,7 @@ int lg_conv_encoder_forward(lg_conv_encoder* enc, const float* depth, int64_t de
  * linear 1, linear 2.  It runs the launches lg_conv_encoder_forward runs for those stages -- same kernels, grids, workspaces and order, through the same
  * code -- and copies the last one's rows to `out` (device, n x count floats, asynchronous on `stream`) in the layout the kernels keep:
  *     conv stage: (n, H_out, W_out, C_out), channel last;   pool: (n, 1024), channel major (torch's Flatten);   linear 1: (n, 128);   linear 2: (n, out_dim).
+ * On an LG_PREC_BF16 encoder the bf16 rows of stages 1-6 are expanded exactly to fp32 on the way to `out`, in the same layouts.
  * stages = 7 writes what lg_conv_encoder_forward writes, bit for bit.  LG_ERR_INVALID as there, and for stages outside 1..7; nothing is launched then.
  * lg_conv_encoder_stage_shape: the floats of one row of stage `stage`'s output (the `count` above), and through h / w / c (each may be NULL) the map
  * (H_out, W_out, C_out) of a conv stage, (1, 1, width) of the others; LG_ERR_INVALID for a NULL encoder or a stage outside 1..7.  No device work. */

@@ -1,0 +1,157 @@
+"""CPU side of the encoder's bf16 mode (include/lgpolicy.h LG_PREC_BF16): the header names, the library's exports and the ctypes mirror agree;
+an unknown precision is refused without a device; `lg_conv_tile_weights_bf16` (a pure host function) against a numpy restatement of the header's
+formula; the rounding helper against torch's cast; and the power of the interval rule the GPU sweep applies (tests/bf16_encoder_rule.py): every
+fault of tests/test_encoder_reference_power.py, applied to the bf16-operand float64 reference, must leave the acceptance interval of its own
+stage in at least one entry.  No kernel runs here and no GPU is needed."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from extended_legged_gym_amd import abi
+from tests.bf16_encoder_rule import R, bf16_operand_pair, outside, rne_bf16_bits, stage_reference
+from tests.test_encoder_reference_power import CASES, SHAPES, camera_input, faults, model_pair, run_stage, wide_input
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "extended_legged_gym_amd", "csrc", "liblgstep.so")
+NEW = ["lg_conv_encoder_create_precision", "lg_conv_encoder_precision", "lg_conv_tile_weights_bf16"]
+
+
+def _lib():
+    return abi.declare_policy(C.CDLL(LIB))
+
+
+# ------------------------------------------------------------------------------------------------------------ 4. rounding
+def test_numpy_rounding_agrees_with_torchs_cast():
+    rng = np.random.default_rng(0)
+    x = np.concatenate([rng.standard_normal(60000).astype(np.float32) * np.float32(10.0) ** rng.integers(-6, 6, 60000).astype(np.float32),
+                        rng.integers(0, 0x7F800000, 39000, dtype=np.int64).astype(np.uint32).view(np.float32)])          # any finite positive pattern
+    top = rng.integers(0x0080, 0x7F7F, 1000, dtype=np.int64).astype(np.uint32) << 16          # a bf16 value ...
+    edge = np.concatenate([top | 0x8000, top | 0x7FFF, top | 0x8001,                        # ... its tie, just under it, just over it
+                           np.array([0, 0x80000000, 0x00008000, 0x00018000, 0x3F808000, 0x3F818000], np.uint32)]).view(np.float32)          # +-0, ties to even either way
+    x = np.concatenate([x, -x[:20000], edge, -edge])
+    assert x.size >= 100000 and np.isfinite(x).all()
+    want = torch.from_numpy(x).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    got = rne_bf16_bits(x)
+    assert np.array_equal(got, want), int((got != want).sum())
+    ties = (x.view(np.uint32) & 0xFFFF) == 0x8000
+    assert ties.sum() >= 2000 and np.all(got[ties] & 1 == 0), "a tie goes to the even neighbour"
+    assert rne_bf16_bits(np.float32(0.0))[()] == 0 and rne_bf16_bits(np.float32(-0.0))[()] == 0x8000
+    # R is the same rounding, as values
+    assert torch.equal(R(torch.from_numpy(x)), torch.from_numpy((got.astype(np.uint32) << 16).view(np.float32)))
+
+
+# ------------------------------------------------------------------------------------------------------------ 1. ABI
+def test_bf16_symbols_are_in_the_header_exported_and_declared():
+    header = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
+    lib = C.CDLL(LIB)
+    for sym in NEW:
+        assert re.search(r"\b%s\(" % sym, header), sym
+        assert sym in abi.ESTIMATOR_BF16_SYMBOLS and sym not in abi.ESTIMATOR_SYMBOLS and hasattr(lib, sym), sym
+    assert re.search(r"#define LG_PREC_F32 0\b", header) and re.search(r"#define LG_PREC_BF16 1\b", header)
+    assert (abi.LG_PREC_F32, abi.LG_PREC_BF16) == (0, 1)
+    abi.declare_policy(lib)
+    for sym in NEW:
+        assert getattr(lib, sym).argtypes, sym
+    assert lib.lg_conv_encoder_precision(None) == abi.LG_ERR_INVALID
+    assert "lg_conv_encoder_precision" in (lib.lg_mlp_last_error(None) or b"").decode()
+
+
+def test_an_unknown_precision_is_refused_without_a_device():
+    from extended_legged_gym_amd.rl import NativeConvEncoder, NativeTerrainEstimator
+    for bad in ("fp16", "BF16", "", None, 1):
+        with pytest.raises(ValueError, match="precision"):
+            NativeConvEncoder([], (28, 56), precision=bad)
+        with pytest.raises(ValueError, match="precision"):
+            NativeTerrainEstimator({}, (28, 56), 6, encoder_precision=bad)
+    # the C side refuses it on its own, before it looks at a size or a device
+    lib = _lib()
+    fp = C.POINTER(C.c_float)
+    lists = (fp * 6)(*[np.zeros(4, np.float32).ctypes.data_as(fp) for _ in range(6)])
+    for bad in (2, -1, 7):
+        assert not lib.lg_conv_encoder_create_precision(28, 56, 64, 0, lists, lists, 0, bad)
+        assert "precision" in (lib.lg_mlp_last_error(None) or b"").decode()
+    for prec in (abi.LG_PREC_F32, abi.LG_PREC_BF16):          # a known precision: the refusals of lg_conv_encoder_create
+        assert not lib.lg_conv_encoder_create_precision(129, 56, 64, 0, lists, lists, 0, prec)
+        assert "image size" in (lib.lg_mlp_last_error(None) or b"").decode()
+
+
+# ------------------------------------------------------------------------------------------------------------ 2. the weight tiles
+def _tile_numpy_bf16(w):
+    """The layout documented at lg_conv_tile_weights_bf16, restated."""
+    cout, cin, kh, kw = w.shape
+    K = cin * kh * kw
+    nks, nch = -(-K // 32), -(-cout // 64) * 4
+    wk = np.zeros((nch * 16, nks * 32), np.uint16)
+    wk[:cout, :K] = rne_bf16_bits(w.transpose(0, 2, 3, 1).reshape(cout, K))          # k = (ky kw + kx) c_in + ci
+    lane, j = np.arange(64)[:, None], np.arange(8)[None, :]
+    out = np.empty((nch, nks, 64, 8), np.uint16)
+    for c in range(nch):
+        for s in range(nks):
+            out[c, s] = wk[16 * c + (lane & 15), 32 * s + 8 * (lane >> 4) + j]
+    return out.reshape(-1)
+
+
+@pytest.mark.parametrize("shape", [(32, 1, 5, 5), (128, 64, 3, 3), (65, 128, 1, 1), (1, 1, 5, 5)], ids=["conv1", "conv3", "linear_128_65", "padded_1x25"])
+def test_conv_tile_weights_bf16_matches_the_documented_layout(shape):
+    lib = _lib()
+    rng = np.random.default_rng(sum(shape))
+    w = rng.standard_normal(shape).astype(np.float32)
+    w[w == 0] = 1.0
+    count = lib.lg_conv_tile_weights_bf16(*shape, None, None)          # the count-only call
+    want = _tile_numpy_bf16(w)
+    assert count == want.size == (-(-shape[0] // 64) * 4) * (-(-(shape[1] * shape[2] * shape[3]) // 32)) * 64 * 8
+    tiled = np.full(count, 0xFFFF, np.uint16)
+    assert lib.lg_conv_tile_weights_bf16(*shape, w.ctypes.data, tiled.ctypes.data) == count
+    assert np.array_equal(tiled, want)
+    # every weight exactly once as R(weight), zero padding elsewhere
+    rounded = R(torch.from_numpy(w)).numpy()
+    assert np.count_nonzero(tiled) == np.count_nonzero(rounded) == w.size
+    assert np.array_equal(np.sort((tiled[tiled != 0].astype(np.uint32) << 16).view(np.float32)), np.sort(rounded.reshape(-1)))
+
+
+def test_conv_tile_weights_bf16_error_returns():
+    lib = _lib()
+    buf = np.zeros(64 * 64 * 8, np.uint16)
+    for bad in ((0, 1, 3, 3), (513, 1, 3, 3), (32, 0, 3, 3), (32, 1025, 3, 3), (32, 1, 0, 3), (32, 1, 3, 16)):          # those of lg_conv_tile_weights
+        assert lib.lg_conv_tile_weights_bf16(*bad, None, None) == abi.LG_ERR_INVALID, bad
+        assert lib.lg_conv_tile_weights(*bad, None, None) == abi.LG_ERR_INVALID, bad
+    assert lib.lg_conv_tile_weights_bf16(32, 1, 5, 5, None, buf.ctypes.data) == abi.LG_ERR_INVALID       # output asked for, no weights given
+
+
+# ------------------------------------------------------------------------------------------------------------ 3. power of the interval rule
+def bf16_chain(r64, x):
+    """The input of every stage when every stage is exact: image through R, then R(stage k) for k = 1..6."""
+    inputs, cur = [R(x).unsqueeze(1)], R(x).unsqueeze(1)
+    with torch.no_grad():
+        for k in range(1, 7):
+            cur = R(run_stage(r64, k, cur.double()).float())
+            inputs.append(cur)
+    return inputs
+
+
+@pytest.mark.parametrize("shape,out_dim,kind,default_init", CASES, ids=[f"{s[0]}x{s[1]}-{o}-{k}{'-default' if d else ''}" for s, o, k, d in CASES])
+def test_every_fault_leaves_the_interval_of_its_stage(shape, out_dim, kind, default_init):
+    """No (fault, shape) pair is left out beyond the `applies` rules the fault list states itself."""
+    n = 3
+    m32, _ = model_pair(shape, salt=SHAPES.index(shape), out_dim=out_dim, default_init=default_init)
+    r32, r64 = bf16_operand_pair(m32)
+    inputs = bf16_chain(r64, (camera_input if kind == "camera" else wide_input)(n, shape))
+    seen = 0
+    for name, k, applies, broken in faults(out_dim):
+        if not applies(inputs[k - 1].double(), n):
+            continue
+        u, gap, bar = stage_reference(r32, r64, k, inputs[k - 1])
+        with torch.no_grad():
+            y = broken(r64, inputs[k - 1].double())
+        stored = y if k == 7 else R(y.float()).double()          # what a kernel with this fault would store
+        bad = int(outside(stored, u, bar, k).sum())
+        clean = int(outside(u if k == 7 else R(u.float()).double(), u, bar, k).sum())
+        print(f"{shape} {name}: stage {k}: {bad} of {u.numel()} entries outside (bar {bar:.3e}, gap {gap:.3e})")
+        assert clean == 0, (shape, name, k, "the unbroken stage must pass its own rule")
+        assert bad >= 1, (shape, name, k, bar)
+        seen += 1
+    assert seen >= 20

@@ -203,9 +203,11 @@ def collect_python_loop(env, policy, num_steps):
     return {k: torch.stack(v) for k, v in rows.items()}
 
 
-def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr=1e-3, gradient_length=15, out=None, log=print, small_terrain=False, update_device=None):
+def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr=1e-3, gradient_length=15, out=None, log=print, small_terrain=False, update_device=None,
+          eval_precision="fp32"):
     """update_device: where the torch update runs (default: the env's device).  "cpu" makes the update reproducible bit for bit -- the GPU's
-    convolution backward is not -- which is what a comparison of two collections needs."""
+    convolution backward is not -- which is what a comparison of two collections needs.  eval_precision: the encoder mode ("fp32" | "bf16") of the
+    native estimator that plays the trained module over the closing evaluation steps; training itself stays fp32 torch."""
     from extended_legged_gym_amd.rl import NativeActorCritic, NativeTerrainEstimator, collect_estimation
     torch.manual_seed(seed)
     env = make_env(envs, seed, small_terrain=small_terrain)
@@ -227,13 +229,13 @@ def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr
         curve.append(loss)
         log(f"iter {it:4d}  estimation loss {loss:.6f}")
     state = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-    native = NativeTerrainEstimator(state, shape, 6, device=str(env.device))          # the file below is one it loads
+    native = NativeTerrainEstimator(state, shape, 6, device=str(env.device), encoder_precision=eval_precision)          # the file below is one it loads
     with torch.inference_mode():
         ev = collect_estimation(env, policy, steps, estimator=native)
-    log(f"native estimator over {steps} fresh steps: mse {ev['mse'].mean().item():.6f}  mae {ev['mae'].mean().item():.6f}")
+    log(f"native estimator ({eval_precision} encoder) over {steps} fresh steps: mse {ev['mse'].mean().item():.6f}  mae {ev['mae'].mean().item():.6f}")
     if out:
         with open(out, "w") as f:
-            json.dump(dict(task="elspider_air_rough_raycast", envs=envs, steps=steps, seed=seed, loss=curve, eval_mse=ev["mse"].mean().item(),
+            json.dump(dict(task="elspider_air_rough_raycast", envs=envs, steps=steps, seed=seed, loss=curve, eval_precision=eval_precision, eval_mse=ev["mse"].mean().item(),
                            eval_mae=ev["mae"].mean().item()), f)
         torch.save(dict(model_state_dict=state, depth_image_shape=shape, proprio_dim=6, num_raycast_outputs=R), os.path.splitext(out)[0] + "_model.pt")
     native.close()
@@ -251,8 +253,9 @@ def main(argv=None):
     ap.add_argument("--python-loop", action="store_true", help="collect with a plain loop over env.step (the checker of collect_estimation)")
     ap.add_argument("--out", default=None, help="write the loss curve here (JSON) and the trained module next to it (_model.pt)")
     ap.add_argument("--small-terrain", action="store_true", help="2 x 3 terrain tiles (quick runs)")
+    ap.add_argument("--eval-precision", choices=("fp32", "bf16"), default="fp32", help="encoder mode of the native estimator that plays the trained module at the end")
     a = ap.parse_args(argv)
-    train(a.iters, a.envs, a.steps, a.seed, a.policy, a.python_loop, out=a.out, small_terrain=a.small_terrain)
+    train(a.iters, a.envs, a.steps, a.seed, a.policy, a.python_loop, out=a.out, small_terrain=a.small_terrain, eval_precision=a.eval_precision)
 
 
 if __name__ == "__main__":
