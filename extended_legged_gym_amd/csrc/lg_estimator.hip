@@ -343,18 +343,22 @@ static bool enc_grow(float** p, size_t floats) {
 extern "C" {
 
 int64_t lg_conv_tile_weights(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw, const float* weight, float* tiled) {
-  if (c_out < 1 || c_out > ENC_MAX_OUT || c_in < 1 || c_in > 1024 || kh < 1 || kh > 15 || kw < 1 || kw > 15) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (c_out < 1 || c_out > ENC_MAX_OUT || c_in < 1 || c_in > 1024 || kh < 1 || kh > 15 || kw < 1 || kw > 15)
+    return lg_policy_fail(LG_ERR_INVALID, "c_out outside 1..512, c_in outside 1..1024 or kh / kw outside 1..15");
   if (tiled) {
-    if (!weight) return LG_ERR_INVALID;
+    if (!weight) return lg_policy_fail(LG_ERR_INVALID, "null weight");
     conv_tile_weights(c_out, c_in, kh, kw, weight, tiled);
   }
   return conv_tiled_count(c_out, c_in, kh, kw);
 }
 
 int64_t lg_conv_tile_weights_bf16(int32_t c_out, int32_t c_in, int32_t kh, int32_t kw, const float* weight, uint16_t* tiled) {
-  if (c_out < 1 || c_out > ENC_MAX_OUT || c_in < 1 || c_in > 1024 || kh < 1 || kh > 15 || kw < 1 || kw > 15) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (c_out < 1 || c_out > ENC_MAX_OUT || c_in < 1 || c_in > 1024 || kh < 1 || kh > 15 || kw < 1 || kw > 15)
+    return lg_policy_fail(LG_ERR_INVALID, "c_out outside 1..512, c_in outside 1..1024 or kh / kw outside 1..15");
   if (tiled) {
-    if (!weight) return LG_ERR_INVALID;
+    if (!weight) return lg_policy_fail(LG_ERR_INVALID, "null weight");
     conv_tile_weights_bf16(c_out, c_in, kh, kw, weight, tiled);
   }
   return conv_tiled_count_bf16(c_out, c_in, kh, kw);
@@ -370,17 +374,16 @@ void lg_conv_encoder_destroy(lg_conv_encoder* e) {
 
 lg_conv_encoder* lg_conv_encoder_create_precision(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
                                                   const float* const* biases, int device_id, int32_t precision) {
-  if (precision != LG_PREC_F32 && precision != LG_PREC_BF16) { lg_policy_set_error("lg_conv_encoder_create: precision must be LG_PREC_F32 or LG_PREC_BF16"); return nullptr; }
-  if (height < 8 || height > ENC_MAX_HW || width < 8 || width > ENC_MAX_HW) { lg_policy_set_error("lg_conv_encoder_create: image size out of range (8..128 per side)"); return nullptr; }
-  if (out_dim < 1 || out_dim > ENC_MAX_OUT) { lg_policy_set_error("lg_conv_encoder_create: out_dim out of range (1..512)"); return nullptr; }
-  if (activation != LG_ACT_ELU && activation != LG_ACT_RELU && activation != LG_ACT_TANH) { lg_policy_set_error("lg_conv_encoder_create: activation must be elu, relu or tanh"); return nullptr; }
-  if (!weights || !biases) { lg_policy_set_error("lg_conv_encoder_create: null weight list"); return nullptr; }
-  for (int l = 0; l < ENC_LAYERS; ++l) if (!weights[l] || !biases[l]) { lg_policy_set_error("lg_conv_encoder_create: null weight"); return nullptr; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { lg_policy_set_error("no HIP device: the estimator kernels have no CPU path"); return nullptr; }
-  if (device_id < 0 || device_id >= ndev) { lg_policy_set_error("bad device"); return nullptr; }
+  POLICY_ENTRY;
+  if (precision != LG_PREC_F32 && precision != LG_PREC_BF16) { lg_policy_fail(LG_ERR_INVALID, "precision must be LG_PREC_F32 or LG_PREC_BF16"); return nullptr; }
+  if (height < 8 || height > ENC_MAX_HW || width < 8 || width > ENC_MAX_HW) { lg_policy_fail(LG_ERR_INVALID, "image size out of range (8..128 per side)"); return nullptr; }
+  if (out_dim < 1 || out_dim > ENC_MAX_OUT) { lg_policy_fail(LG_ERR_INVALID, "out_dim out of range (1..512)"); return nullptr; }
+  if (activation != LG_ACT_ELU && activation != LG_ACT_RELU && activation != LG_ACT_TANH) { lg_policy_fail(LG_ERR_INVALID, "activation must be elu, relu or tanh"); return nullptr; }
+  if (!weights || !biases) { lg_policy_fail(LG_ERR_INVALID, "null weight list"); return nullptr; }
+  for (int l = 0; l < ENC_LAYERS; ++l) if (!weights[l] || !biases[l]) { lg_policy_fail(LG_ERR_INVALID, "null weight"); return nullptr; }
+  if (!lg_policy_device_ok(device_id)) return nullptr;
   DeviceScope ds_(device_id);
-  if (!ds_.ok) { lg_policy_set_error("bad device"); return nullptr; }
+  if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_conv_encoder* e = new lg_conv_encoder();
   e->device = device_id; e->H = height; e->W = width; e->out_dim = out_dim; e->act = activation; e->prec = precision;
   const bool bf16 = precision == LG_PREC_BF16;
@@ -415,14 +418,11 @@ lg_conv_encoder* lg_conv_encoder_create_precision(int32_t height, int32_t width,
       const int ci = k % L.Cin, tap = k / L.Cin, ky = tap / kh, kx = tap - ky * kh;
       kt[per_step ? k / 32 : k] = (ky << 26) | (kx << 22) | ((ky * L.Win + kx) * L.Cin + ci);         // offset < 15 * 128 * 1024 + ... < 2^22 for every supported shape
     }
-    void *dw = nullptr, *db = nullptr, *dk = nullptr;
-    const bool ok = hipMalloc(&dw, tw.size() * 4) == hipSuccess && hipMalloc(&db, tb.size() * 4) == hipSuccess && hipMalloc(&dk, kt.size() * 4) == hipSuccess &&
-                    hipMemcpy(dw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(db, tb.data(), tb.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(dk, kt.data(), kt.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    for (void* p : {dw, db, dk}) if (p) e->allocs.push_back(p);
-    if (!ok) { lg_policy_set_error("lg_conv_encoder_create: weight upload failed"); lg_conv_encoder_destroy(e); return nullptr; }
-    L.w = bf16 ? nullptr : (const float*)dw; L.w16 = bf16 ? (const uint16_t*)dw : nullptr; L.b = (const float*)db; L.ktab = (const int32_t*)dk;
+    const void* dw = lg_policy_upload(tw.data(), tw.size() * 4, e->allocs);
+    L.b = dw ? (const float*)lg_policy_upload(tb.data(), tb.size() * 4, e->allocs) : nullptr;
+    L.ktab = L.b ? (const int32_t*)lg_policy_upload(kt.data(), kt.size() * 4, e->allocs) : nullptr;
+    if (!L.ktab) { lg_conv_encoder_destroy(e); return nullptr; }
+    L.w = bf16 ? nullptr : (const float*)dw; L.w16 = bf16 ? (const uint16_t*)dw : nullptr;
   }
   e->Hp = h; e->Wp = w;
   e->floats_a = std::max(std::max(map_floats[0], map_floats[2]), (size_t)1024);
@@ -432,19 +432,19 @@ lg_conv_encoder* lg_conv_encoder_create_precision(int32_t height, int32_t width,
 
 lg_conv_encoder* lg_conv_encoder_create(int32_t height, int32_t width, int32_t out_dim, int32_t activation, const float* const* weights,
                                         const float* const* biases, int device_id) {
+  POLICY_ENTRY;
   return lg_conv_encoder_create_precision(height, width, out_dim, activation, weights, biases, device_id, LG_PREC_F32);
 }
 
 int32_t lg_conv_encoder_precision(const lg_conv_encoder* e) {
-  if (!e) { lg_policy_set_error("lg_conv_encoder_precision: null encoder"); return LG_ERR_INVALID; }
+  POLICY_ENTRY;
+  if (!e) return lg_policy_fail(LG_ERR_INVALID, "null encoder");
   return e->prec;
 }
 
-#define EST_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { lg_policy_set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); return LG_ERR_HIP; } } while (0)
-
 static int enc_launch(const ConvLayerDev& L, const float* in, int64_t in_estride, int64_t n, float* out, int64_t out_estride, hipStream_t st) {
   const int64_t tiles = (n * L.Hout * L.Wout + CONV_ROWS - 1) / CONV_ROWS;
-  if (tiles > 0x7fffffff) { lg_policy_set_error("lg_conv_encoder: too many rows for one launch"); return LG_ERR_UNSUPPORTED; }
+  if (tiles > 0x7fffffff) return lg_policy_fail(LG_ERR_UNSUPPORTED, "too many rows for one launch");
   hipLaunchKernelGGL(conv_gemm_kernel, dim3((unsigned)tiles, (unsigned)((L.Cout + CONV_COLS - 1) / CONV_COLS)), dim3(CONV_THREADS), 0, st, L, in, in_estride, n, out,
                      out_estride);
   return LG_OK;
@@ -453,7 +453,7 @@ static int enc_launch(const ConvLayerDev& L, const float* in, int64_t in_estride
 // bf16 mode: stage k = 1 reads the fp32 image, stage 7 writes fp32 features, everything between is bf16
 static int enc_launch_bf16(const ConvLayerDev& L, int k, const void* in, int64_t in_estride, int64_t n, void* out, int64_t out_estride, hipStream_t st) {
   const int64_t tiles = (n * L.Hout * L.Wout + CONV_ROWS - 1) / CONV_ROWS;
-  if (tiles > 0x7fffffff) { lg_policy_set_error("lg_conv_encoder: too many rows for one launch"); return LG_ERR_UNSUPPORTED; }
+  if (tiles > 0x7fffffff) return lg_policy_fail(LG_ERR_UNSUPPORTED, "too many rows for one launch");
   const dim3 grid((unsigned)tiles, (unsigned)((L.Cout + CONV_COLS - 1) / CONV_COLS)), block(CONV_THREADS);
   if (k == 1) hipLaunchKernelGGL((enc_bf16_gemm_kernel<true, __bf16>), grid, block, 0, st, L, in, in_estride, n, (__bf16*)out, out_estride);
   else if (k == ENC_LAYERS + 1) hipLaunchKernelGGL((enc_bf16_gemm_kernel<false, float>), grid, block, 0, st, L, in, in_estride, n, (float*)out, out_estride);
@@ -476,7 +476,7 @@ static int enc_forward(lg_conv_encoder* e, const float* depth, int64_t depth_str
   if (n > e->cap) {          // the workspaces grow to the largest n seen; hipFree waits for the device, so a caller that alternates streams stays safe
     const size_t per = e->prec == LG_PREC_BF16 ? 2 : 1;          // bf16 maps: two elements per float
     if (!enc_grow(&e->ws_a, ((size_t)n * e->floats_a + per - 1) / per) || !enc_grow(&e->ws_b, ((size_t)n * e->floats_b + per - 1) / per)) {
-      e->cap = 0; lg_policy_set_error("lg_conv_encoder: workspace allocation failed"); return LG_ERR_HIP;
+      e->cap = 0; return lg_policy_fail(LG_ERR_HIP, "workspace allocation failed");
     }
     e->cap = n;
   }
@@ -493,7 +493,7 @@ static int enc_forward(lg_conv_encoder* e, const float* depth, int64_t depth_str
       }
       in = out; in_stride = out_stride;
     }
-    EST_TRY(hipGetLastError());
+    POLICY_TRY(hipGetLastError());
     if (last) *last = in;
     return LG_OK;
   }
@@ -508,21 +508,23 @@ static int enc_forward(lg_conv_encoder* e, const float* depth, int64_t depth_str
     }
     in = out; in_stride = out_stride;
   }
-  EST_TRY(hipGetLastError());
+  POLICY_TRY(hipGetLastError());
   if (last) *last = in;
   return LG_OK;
 }
 
 int lg_conv_encoder_forward(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* features, void* stream) {
-  if (!e || !depth || !features) { lg_policy_set_error("lg_conv_encoder_forward: null argument"); return LG_ERR_INVALID; }
-  if (n <= 0) { lg_policy_set_error("lg_conv_encoder_forward: n must be positive"); return LG_ERR_INVALID; }
-  if (depth_stride < (int64_t)e->H * e->W) { lg_policy_set_error("lg_conv_encoder_forward: depth_stride is smaller than one image"); return LG_ERR_INVALID; }
+  POLICY_ENTRY;
+  if (!e || !depth || !features) return lg_policy_fail(LG_ERR_INVALID, "null argument");
+  if (n <= 0) return lg_policy_fail(LG_ERR_INVALID, "n must be positive");
+  if (depth_stride < (int64_t)e->H * e->W) return lg_policy_fail(LG_ERR_INVALID, "depth_stride is smaller than one image");
   DeviceScope ds_(e->device);
   return enc_forward(e, depth, depth_stride, n, features, e->out_dim, (hipStream_t)stream);
 }
 
 int64_t lg_conv_encoder_stage_shape(const lg_conv_encoder* e, int32_t stage, int32_t* h, int32_t* w, int32_t* c) {
-  if (!e || stage < 1 || stage > ENC_LAYERS + 1) { lg_policy_set_error("lg_conv_encoder_stage_shape: null encoder or stage outside 1..7"); return LG_ERR_INVALID; }
+  POLICY_ENTRY;
+  if (!e || stage < 1 || stage > ENC_LAYERS + 1) return lg_policy_fail(LG_ERR_INVALID, "null encoder or stage outside 1..7");
   int hh, ww, cc;
   const int64_t count = enc_stage_shape(e, stage, &hh, &ww, &cc);
   if (h) *h = hh;
@@ -532,10 +534,11 @@ int64_t lg_conv_encoder_stage_shape(const lg_conv_encoder* e, int32_t stage, int
 }
 
 int lg_conv_encoder_forward_stages(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, int32_t stages, float* out, void* stream) {
-  if (!e || !depth || !out) { lg_policy_set_error("lg_conv_encoder_forward_stages: null argument"); return LG_ERR_INVALID; }
-  if (n <= 0) { lg_policy_set_error("lg_conv_encoder_forward_stages: n must be positive"); return LG_ERR_INVALID; }
-  if (depth_stride < (int64_t)e->H * e->W) { lg_policy_set_error("lg_conv_encoder_forward_stages: depth_stride is smaller than one image"); return LG_ERR_INVALID; }
-  if (stages < 1 || stages > ENC_LAYERS + 1) { lg_policy_set_error("lg_conv_encoder_forward_stages: stages must be 1..7"); return LG_ERR_INVALID; }
+  POLICY_ENTRY;
+  if (!e || !depth || !out) return lg_policy_fail(LG_ERR_INVALID, "null argument");
+  if (n <= 0) return lg_policy_fail(LG_ERR_INVALID, "n must be positive");
+  if (depth_stride < (int64_t)e->H * e->W) return lg_policy_fail(LG_ERR_INVALID, "depth_stride is smaller than one image");
+  if (stages < 1 || stages > ENC_LAYERS + 1) return lg_policy_fail(LG_ERR_INVALID, "stages must be 1..7");
   DeviceScope ds_(e->device);
   const float* last = nullptr;
   const int rc = enc_forward(e, depth, depth_stride, n, out, e->out_dim, (hipStream_t)stream, stages, &last);
@@ -544,34 +547,40 @@ int lg_conv_encoder_forward_stages(lg_conv_encoder* e, const float* depth, int64
   if (e->prec == LG_PREC_BF16) {
     const int64_t count = n * enc_stage_shape(e, stages, &h, &w, &c);
     hipLaunchKernelGGL(enc_bf16_expand_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)last, count, out);
-    EST_TRY(hipGetLastError());
+    POLICY_TRY(hipGetLastError());
     return LG_OK;
   }
-  EST_TRY(hipMemcpyAsync(out, last, (size_t)n * enc_stage_shape(e, stages, &h, &w, &c) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  POLICY_TRY(hipMemcpyAsync(out, last, (size_t)n * enc_stage_shape(e, stages, &h, &w, &c) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return LG_OK;
+}
+
+// a stage of lg_estimator_step failed: its name goes in front of the reason the stage left
+static int stage_fail(int rc, const char* stage) {
+  const std::string why = lg_mlp_last_error(nullptr);
+  const size_t at = why.find(": ");
+  return lg_policy_fail(rc, std::string(stage) + ": " + (at == std::string::npos ? why : why.substr(at + 2)));
 }
 
 int lg_estimator_step(lg_conv_encoder* e, lg_mlp* combine, lg_rnn* mem, lg_mlp* decoder, const float* depth, int64_t depth_stride, const float* proprio,
                       int64_t n, float* h, float* c, const float* reset, float* predictions, void* stream) {
-  if (!e || !combine || !mem || !decoder || !depth || !h || !predictions) { lg_policy_set_error("lg_estimator_step: null argument"); return LG_ERR_INVALID; }
-  if (n <= 0) { lg_policy_set_error("lg_estimator_step: n must be positive"); return LG_ERR_INVALID; }
-  if (depth_stride < (int64_t)e->H * e->W) { lg_policy_set_error("lg_estimator_step: depth_stride is smaller than one image"); return LG_ERR_INVALID; }
+  POLICY_ENTRY;
+  if (!e || !combine || !mem || !decoder || !depth || !h || !predictions) return lg_policy_fail(LG_ERR_INVALID, "null argument");
+  if (n <= 0) return lg_policy_fail(LG_ERR_INVALID, "n must be positive");
+  if (depth_stride < (int64_t)e->H * e->W) return lg_policy_fail(LG_ERR_INVALID, "depth_stride is smaller than one image");
   int cl, cin, cout, cdev, rtype, rin, rhid, rdev, dl, din, dout, ddev;
   lg_mlp_widths(combine, &cl, &cin, &cout, &cdev);
   lg_rnn_widths(mem, &rtype, &rin, &rhid, &rdev);
   lg_mlp_widths(decoder, &dl, &din, &dout, &ddev);
   const int P = cin - e->out_dim;
-  if (cl != 1 || P < 0 || cout != rin || din != rhid) {
-    lg_policy_set_error("lg_estimator_step: stage widths do not chain (combine: one layer of encoder out_dim + proprio inputs; its outputs = the memory's input; decoder input = the memory's hidden width)");
-    return LG_ERR_INVALID;
-  }
-  if (P > 0 && !proprio) { lg_policy_set_error("lg_estimator_step: null proprio"); return LG_ERR_INVALID; }
-  if (rtype == LG_RNN_LSTM && !c) { lg_policy_set_error("lg_estimator_step: an LSTM needs its cell state"); return LG_ERR_INVALID; }
-  if (cdev != e->device || rdev != e->device || ddev != e->device) { lg_policy_set_error("lg_estimator_step: the stages live on different devices"); return LG_ERR_INVALID; }
+  if (cl != 1 || P < 0 || cout != rin || din != rhid)
+    return lg_policy_fail(LG_ERR_INVALID, "stage widths do not chain (combine: one layer of encoder out_dim + proprio inputs; its outputs = the memory's input; decoder input = the memory's hidden width)");
+  if (P > 0 && !proprio) return lg_policy_fail(LG_ERR_INVALID, "null proprio");
+  if (rtype == LG_RNN_LSTM && !c) return lg_policy_fail(LG_ERR_INVALID, "an LSTM needs its cell state");
+  if (cdev != e->device || rdev != e->device || ddev != e->device) return lg_policy_fail(LG_ERR_INVALID, "the stages live on different devices");
   DeviceScope ds_(e->device);
   if (n > e->step_cap || cin != e->cat_w || cout != e->comb_w || rhid != e->mem_w) {
     if (!enc_grow(&e->cat, (size_t)n * cin) || !enc_grow(&e->comb, (size_t)n * cout) || !enc_grow(&e->memo, (size_t)n * rhid)) {
-      e->step_cap = 0; lg_policy_set_error("lg_estimator_step: workspace allocation failed"); return LG_ERR_HIP;
+      e->step_cap = 0; return lg_policy_fail(LG_ERR_HIP, "workspace allocation failed");
     }
     e->step_cap = n; e->cat_w = cin; e->comb_w = cout; e->mem_w = rhid;
   }
@@ -579,10 +588,10 @@ int lg_estimator_step(lg_conv_encoder* e, lg_mlp* combine, lg_rnn* mem, lg_mlp* 
   int rc = enc_forward(e, depth, depth_stride, n, e->cat, cin, st);
   if (rc != LG_OK) return rc;
   if (P > 0) hipLaunchKernelGGL(cat_columns_kernel, dim3((unsigned)((n * P + 255) / 256)), dim3(256), 0, st, proprio, n, P, e->cat, cin, e->out_dim);
-  EST_TRY(hipGetLastError());
-  if ((rc = lg_mlp_forward(combine, e->cat, n, e->comb, stream)) != LG_OK) { lg_policy_set_error(std::string("lg_estimator_step: combine: ") + lg_mlp_last_error(combine)); return rc; }
-  if ((rc = lg_rnn_step(mem, e->comb, n, h, c, reset, e->memo, stream)) != LG_OK) return rc;
-  if ((rc = lg_mlp_forward(decoder, e->memo, n, predictions, stream)) != LG_OK) { lg_policy_set_error(std::string("lg_estimator_step: decoder: ") + lg_mlp_last_error(decoder)); return rc; }
+  POLICY_TRY(hipGetLastError());
+  if ((rc = lg_mlp_forward(combine, e->cat, n, e->comb, stream)) != LG_OK) return stage_fail(rc, "combine");
+  if ((rc = lg_rnn_step(mem, e->comb, n, h, c, reset, e->memo, stream)) != LG_OK) return stage_fail(rc, "memory");
+  if ((rc = lg_mlp_forward(decoder, e->memo, n, predictions, stream)) != LG_OK) return stage_fail(rc, "decoder");
   return LG_OK;
 }
 

@@ -27,9 +27,6 @@
 #include "../../include/lgpolicy.h"
 #include "../../include/lgstep.h"
 
-#ifndef LG_AB
-#define LG_AB 0
-#endif
 #define MLP_ROWS 32          // batch rows per workgroup
 #define MLP_THREADS 512      // eight waves: two per SIMD
 #define MLP_MAXW 512         // widest layer
@@ -53,11 +50,36 @@ struct lg_mlp {
   MlpDev h;
   int device = 0;
   std::vector<void*> allocs;
-  std::string err;
 };
 
+// ---- the one error channel and the create functions' plumbing (lg_policy_internal.h)
+thread_local const char* lg_policy_entry = nullptr;
 static thread_local std::string g_pol_err;
-void lg_policy_set_error(const std::string& msg) { g_pol_err = msg; }      // lg_policy_internal.h
+
+int lg_policy_device_of(const void* p) {
+  hipPointerAttribute_t pa;
+  return hipPointerGetAttributes(&pa, p) == hipSuccess ? pa.device : -1;
+}
+
+int lg_policy_fail(int status, const std::string& what) {
+  g_pol_err = std::string(lg_policy_entry ? lg_policy_entry : "lg_policy") + ": " + what;
+  return status;
+}
+
+bool lg_policy_device_ok(int device_id) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { lg_policy_fail(LG_ERR_HIP, "no HIP device: these kernels have no CPU path"); return false; }
+  if (device_id < 0 || device_id >= ndev) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return false; }
+  return true;
+}
+
+const void* lg_policy_upload(const void* host, size_t bytes, std::vector<void*>& allocs) {
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) { lg_policy_fail(LG_ERR_HIP, "weight upload failed"); return nullptr; }
+  allocs.push_back(d);
+  if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) { lg_policy_fail(LG_ERR_HIP, "weight upload failed"); return nullptr; }
+  return d;
+}
 
 LG_DEV float apply_act(float x, int act) {
   switch (act) {
@@ -78,13 +100,6 @@ LG_DEV float apply_act(float x, int act) {
 LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0, int64_t n, float* buf0, float* buf1, float* yrows /* [32][16*?] */,
                      float* __restrict__ y_global) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#if LG_AB == 8      // diagnostic build: phase times of one workgroup (100 MHz wall clock), printed from the kernel
-  unsigned long long tstamp[8]; int ts_n = 0;
-#define TS() do { __builtin_amdgcn_s_waitcnt(0); tstamp[ts_n++] = wall_clock64(); } while (0)
-#else
-#define TS()
-#endif
-  TS();
   // stage the input tile: x (n, K0) row-major -> activation image.  Eight independent loads in flight per lane.
   const int K0 = M.dims[0], K0p = M.kpad[0];
   for (int base = 0; base < MLP_ROWS * K0p; base += 8 * MLP_THREADS) {
@@ -102,7 +117,6 @@ LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0,
     }
   }
   lds_barrier();
-  TS();
   float* in = buf0; float* out = buf1;
 // volatile asm keeps the two accumulator chains interleaved as written (the compiler otherwise issues the dependent MFMAs of one
 // accumulator back to back: 40-cycle dependent latency instead of the 32-cycle issue rate)
@@ -172,14 +186,9 @@ LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0,
         }
       }
     }
-    TS();
     lds_barrier();
     float* t = in; in = out; out = t;
   }
-#if LG_AB == 8
-  if (blockIdx.x == 5 && lane == 0 && M.L == 4) printf("wg %d,%d wave %d: stage %llu  L0 %llu  L1 %llu  L2 %llu  L3 %llu  (10 ns ticks)\n", blockIdx.x, blockIdx.y, wv,
-      tstamp[1] - tstamp[0], tstamp[2] - tstamp[1], tstamp[3] - tstamp[2], tstamp[4] - tstamp[3], tstamp[5] - tstamp[4]);
-#endif
 #undef MLP_BLOCK
 }
 
@@ -290,7 +299,7 @@ __global__ __launch_bounds__(1024) void normalize_kernel(float* __restrict__ adv
 
 extern "C" {
 
-const char* lg_mlp_last_error(lg_mlp* m) { return m ? m->err.c_str() : g_pol_err.c_str(); }
+const char* lg_mlp_last_error(lg_mlp*) { return g_pol_err.c_str(); }
 
 void lg_mlp_destroy(lg_mlp* m) {
   if (!m) return;
@@ -301,15 +310,14 @@ void lg_mlp_destroy(lg_mlp* m) {
 
 lg_mlp* lg_mlp_create(int32_t L, const int32_t* dims, const float* const* weights, const float* const* biases, int32_t activation,
                       int device_id) {
-  if (L <= 0 || L > LG_MLP_MAX_LAYERS || !dims || !weights || !biases) { g_pol_err = "bad layer list"; return nullptr; }
-  if (activation < LG_ACT_ELU || activation > LG_ACT_SELU) { g_pol_err = "unknown activation"; return nullptr; }
-  for (int l = 0; l <= L; ++l) if (dims[l] <= 0 || dims[l] > MLP_MAXW) { g_pol_err = "layer width out of range (1..512)"; return nullptr; }
-  if (dims[L] > 32) { /* fine for lg_mlp_forward; lg_policy_act checks its own limit */ }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_pol_err = "no HIP device: the policy kernels have no CPU path"; return nullptr; }
-  if (device_id < 0 || device_id >= ndev) { g_pol_err = "bad device"; return nullptr; }
+  POLICY_ENTRY;
+  if (L <= 0 || L > LG_MLP_MAX_LAYERS || !dims || !weights || !biases) { lg_policy_fail(LG_ERR_INVALID, "bad layer list"); return nullptr; }
+  if (activation < LG_ACT_ELU || activation > LG_ACT_SELU) { lg_policy_fail(LG_ERR_INVALID, "unknown activation"); return nullptr; }
+  // (an output wider than 32 is fine for lg_mlp_forward; lg_policy_act checks its own limit)
+  for (int l = 0; l <= L; ++l) if (dims[l] <= 0 || dims[l] > MLP_MAXW) { lg_policy_fail(LG_ERR_INVALID, "layer width out of range (1..512)"); return nullptr; }
+  if (!lg_policy_device_ok(device_id)) return nullptr;
   DeviceScope ds_(device_id);
-  if (!ds_.ok) { g_pol_err = "bad device"; return nullptr; }
+  if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_mlp* m = new lg_mlp();
   m->device = device_id; m->h.L = L; m->h.act = activation; m->h.act_out = 0;
   for (int l = 0; l <= L; ++l) m->h.dims[l] = dims[l];
@@ -329,60 +337,57 @@ lg_mlp* lg_mlp_create(int32_t L, const int32_t* dims, const float* const* weight
             if (nn < N && kk < K) tw[(((size_t)c * nb + b) * 64 + ln) * 4 + s] = weights[l][(size_t)nn * K + kk];
           }
     for (int i = 0; i < N; ++i) tb[i] = biases[l][i];
-    void *dw = nullptr, *db = nullptr;
-    if (hipMalloc(&dw, tw.size() * 4) != hipSuccess || hipMalloc(&db, tb.size() * 4) != hipSuccess ||
-        hipMemcpy(dw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(db, tb.data(), tb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      if (dw) m->allocs.push_back(dw);
-      if (db) m->allocs.push_back(db);
-      g_pol_err = "weight upload failed"; lg_mlp_destroy(m); return nullptr;
-    }
-    m->allocs.push_back(dw); m->allocs.push_back(db);
-    m->h.w[l] = (const float*)dw; m->h.b[l] = (const float*)db;
+    m->h.w[l] = (const float*)lg_policy_upload(tw.data(), tw.size() * 4, m->allocs);
+    m->h.b[l] = m->h.w[l] ? (const float*)lg_policy_upload(tb.data(), tb.size() * 4, m->allocs) : nullptr;
+    if (!m->h.b[l]) { lg_mlp_destroy(m); return nullptr; }
   }
   return m;
 }
 
 int lg_mlp_set_output_activation(lg_mlp* m, int32_t enabled) {
-  if (!m) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (!m) return lg_policy_fail(LG_ERR_INVALID, "null network");
   m->h.act_out = enabled != 0;
   return LG_OK;
 }
 
-#define POL_TRY(m, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { (m)->err = std::string(#expr) + ": " + hipGetErrorString(_e); return LG_ERR_HIP; } } while (0)
-
 int lg_mlp_forward(lg_mlp* m, const float* x, int64_t n, float* y, void* stream) {
-  if (!m || !x || !y || n < 0) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (!m || !x || !y || n < 0) return lg_policy_fail(LG_ERR_INVALID, "null network or row, or n < 0");
   DeviceScope ds_(m->device);
   if (n == 0) return LG_OK;
   hipLaunchKernelGGL(mlp_forward_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS)), dim3(MLP_THREADS), 0, (hipStream_t)stream, m->h, x, n, y);
-  POL_TRY(m, hipGetLastError());
+  POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
 
 int lg_policy_act(lg_mlp* actor, lg_mlp* critic, const float* obs, const float* critic_obs, int64_t n, const float* std_, uint64_t seed,
                   uint64_t call, int32_t deterministic, float* actions, float* action_mean, float* logp, float* values, void* stream) {
-  if (!actor || !critic || !obs || !critic_obs || !std_ || !actions || !action_mean || !logp || !values || n < 0) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (!actor || !critic || !obs || !critic_obs || !std_ || !actions || !action_mean || !logp || !values || n < 0)
+    return lg_policy_fail(LG_ERR_INVALID, "null network or row, or n < 0");
   DeviceScope ds_(actor->device);
-  if (actor->h.dims[actor->h.L] > 32) { actor->err = "lg_policy_act supports up to 32 actions"; return LG_ERR_UNSUPPORTED; }
+  if (actor->h.dims[actor->h.L] > 32) return lg_policy_fail(LG_ERR_UNSUPPORTED, "the actor ends in more than 32 actions");
   if (n == 0) return LG_OK;
   hipLaunchKernelGGL(policy_act_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 2), dim3(MLP_THREADS), 0, (hipStream_t)stream, actor->h, critic->h,
                      obs, critic_obs, n, std_, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), deterministic,
                      actions, action_mean, logp, values);
-  POL_TRY(actor, hipGetLastError());
+  POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
 
 int lg_compute_returns(const float* rewards, const float* dones, const float* values, const float* last_values, int32_t T, int64_t n,
                        float gamma, float lam, int32_t normalize, float* returns, float* advantages, void* stream) {
-  if (!rewards || !dones || !values || !last_values || !returns || !advantages || T <= 0 || n <= 0) return LG_ERR_INVALID;
-  hipPointerAttribute_t pa;                        // no context in this call: run where the rows live
-  if (hipPointerGetAttributes(&pa, rewards) != hipSuccess) return LG_ERR_INVALID;
-  DeviceScope ds_(pa.device);
+  POLICY_ENTRY;
+  if (!rewards || !dones || !values || !last_values || !returns || !advantages || T <= 0 || n <= 0) return lg_policy_fail(LG_ERR_INVALID, "null row, T < 1 or n < 1");
+  const int dev = lg_policy_device_of(rewards);          // no context in this call: run where the rows live
+  if (dev < 0) return lg_policy_fail(LG_ERR_INVALID, "the rewards are not device memory");
+  DeviceScope ds_(dev);
   hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rewards, dones, values, last_values, T, n,
                      gamma, lam, returns, advantages);
   if (normalize) hipLaunchKernelGGL(normalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, advantages, (int64_t)T * n);
-  return hipGetLastError() == hipSuccess ? LG_OK : LG_ERR_HIP;
+  POLICY_TRY(hipGetLastError());
+  return LG_OK;
 }
 
 // the sigma rows of all T transitions (ppo.py:155: action_std broadcast over the envs): one launch for the whole rollout
@@ -392,184 +397,7 @@ __global__ __launch_bounds__(256) void fill_sigma_kernel(int64_t rows, int A, co
   sigma[i] = std[i % A];
 }
 
-extern "C" int lg_step_transition(lg_ctx* ctx, const float* actions, float* next_observations, const float* values, float gamma,
-                                  float* rewards, float* dones, void* stream);
-
-int lg_collect_rollout(lg_ctx* env, lg_mlp* actor, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
-                       float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, void* stream) {
-  if (!env || !actor || !critic || !std || !out || T <= 0) return LG_ERR_INVALID;
-  DeviceScope ds_(actor->device);
-  if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
-      !out->sigma || !out->last_values) { actor->err = "lg_collect_rollout: null output row"; return LG_ERR_INVALID; }
-  void* p; int64_t shp[4]; int32_t nd, dt;
-  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
-  const float* obs = (const float*)p; const int64_t n = shp[0], O = shp[1];
-  const int A = actor->h.dims[actor->h.L];
-  int64_t ashp[4];
-  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
-  if (actor->h.dims[0] != O || critic->h.dims[0] != O || critic->h.dims[critic->h.L] != 1 || A != ashp[1]) {
-    actor->err = "lg_collect_rollout: network widths do not match the env (obs width, one action per DOF, scalar value)"; return LG_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  // the first observation row is copied from the env; every later one is written by the step itself (lg_step_transition),
-  // as are the reward (with the time-out bootstrap) and done rows: three launches per step (act, physics, post-physics)
-  POL_TRY(actor, hipMemcpyAsync(out->observations, obs, (size_t)n * O * 4, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
-  for (int t = 0; t < T; ++t) {
-    float* obs_t = out->observations + (size_t)t * n * O;
-    float* act_t = out->actions + (size_t)t * n * A;
-    int rc = lg_policy_act(actor, critic, obs_t, obs_t, n, std, seed, first_call + (uint64_t)t, 0, act_t, out->mu + (size_t)t * n * A,
-                           out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
-    if (rc != LG_OK) return rc;
-    rc = lg_step_transition(env, act_t, t + 1 < T ? out->observations + (size_t)(t + 1) * n * O : nullptr, out->values + (size_t)t * n, gamma,
-                            out->rewards + (size_t)t * n, out->dones + (size_t)t * n, stream);
-    if (rc != LG_OK) { actor->err = std::string("lg_collect_rollout: lg_step_transition failed: ") + lg_last_error(env); return rc; }
-  }
-  int rc = lg_mlp_forward(critic, obs, n, out->last_values, stream);
-  if (rc != LG_OK) return rc;
-  if (out->returns && out->advantages)
-    rc = lg_compute_returns(out->rewards, out->dones, out->values, out->last_values, T, n, gamma, lam, normalize_advantage, out->returns,
-                            out->advantages, stream);
-  POL_TRY(actor, hipGetLastError());
-  return rc;
-}
-
 }  // extern "C"
-
-
-// ============================================================================================ sampling planner arithmetic (lgpolicy.h)
-// plans[i, h, a] = sum_k phi[h, k] nodes[i, k, a]: one lane per output element, the K node rows of a sample are read coalesced along a
-__global__ __launch_bounds__(256) void plan_from_nodes_kernel(const float* __restrict__ nodes, const float* __restrict__ phi, int64_t n, int K, int H, int A,
-                                                              float* __restrict__ plans) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= n * H * A) return;
-  const int a = (int)(idx % A); const int64_t ih = idx / A; const int h = (int)(ih % H); const int64_t i = ih / H;
-  float acc = 0.f;
-  for (int k = 0; k < K; ++k) acc = fmaf(phi[h * K + k], nodes[(i * K + k) * A + a], acc);
-  plans[idx] = acc;
-}
-
-// One wave per main env: its R samples' mean rewards, standardised, softmax at the given temperature, weighted mean of the node rows.
-// R, H, K * A are tens to hundreds: the whole problem of a main env is a few KB, read once.
-__global__ __launch_bounds__(64) void mppi_update_kernel(const float* __restrict__ rewards, const float* __restrict__ nodes, int R, int H, int KA, float temperature,
-                                                         float* __restrict__ new_nodes, float* __restrict__ weights) {
-  extern __shared__ float w_lds[];                 // R weights
-  const int m = blockIdx.x, lane = threadIdx.x;
-  const float* rw = rewards + (size_t)m * R * H;
-  auto wave_sum = [](float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; };
-  auto wave_max = [](float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; };
-  float s1 = 0.f;
-  for (int i = lane; i < R; i += 64) {
-    float r = 0.f;
-    for (int h = 0; h < H; ++h) r += rw[(size_t)i * H + h];
-    r /= (float)H;
-    w_lds[i] = r; s1 += r;
-  }
-  const float mean = wave_sum(s1) / (float)R;
-  float s2 = 0.f;
-  for (int i = lane; i < R; i += 64) { const float d = w_lds[i] - mean; s2 += d * d; }
-  const float sd = sqrtf(wave_sum(s2) / (float)R);
-  const float scale = sd > 1e-12f ? 1.f / (sd * temperature) : 0.f;
-  float mx = -3.0e38f;
-  for (int i = lane; i < R; i += 64) { const float z = (w_lds[i] - mean) * scale; w_lds[i] = z; mx = fmaxf(mx, z); }
-  mx = wave_max(mx);
-  float se = 0.f;
-  for (int i = lane; i < R; i += 64) { const float e = __expf(w_lds[i] - mx); w_lds[i] = e; se += e; }
-  const float inv = 1.f / wave_sum(se);
-  for (int i = lane; i < R; i += 64) { const float w = w_lds[i] * inv; w_lds[i] = w; weights[(size_t)m * R + i] = w; }
-  __syncthreads();
-  const float* nd = nodes + (size_t)m * R * KA;
-  for (int j = lane; j < KA; j += 64) {
-    float acc = 0.f;
-    for (int i = 0; i < R; ++i) acc = fmaf(w_lds[i], nd[(size_t)i * KA + j], acc);
-    new_nodes[(size_t)m * KA + j] = acc;
-  }
-}
-
-static int device_of(const void* p) {
-  hipPointerAttribute_t pa;
-  return hipPointerGetAttributes(&pa, p) == hipSuccess ? pa.device : -1;
-}
-
-int lg_plan_from_nodes(const float* nodes, const float* phi, int64_t n, int32_t K, int32_t H, int32_t A, float* plans, void* stream) {
-  if (!nodes || !phi || !plans || n <= 0 || K <= 0 || H <= 0 || A <= 0) return LG_ERR_INVALID;
-  const int dev = device_of(nodes);
-  if (dev < 0) return LG_ERR_INVALID;
-  DeviceScope ds_(dev);
-  const int64_t total = n * H * A;
-  hipLaunchKernelGGL(plan_from_nodes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nodes, phi, n, K, H, A, plans);
-  return hipGetLastError() == hipSuccess ? LG_OK : LG_ERR_HIP;
-}
-
-int lg_mppi_update(const float* rewards, const float* nodes, int32_t num_main, int32_t R, int32_t H, int32_t K, int32_t A, float temperature,
-                   float* new_nodes, float* weights, void* stream) {
-  if (!rewards || !nodes || !new_nodes || !weights || num_main <= 0 || R <= 0 || H <= 0 || K <= 0 || A <= 0 || !(temperature > 0.f)) return LG_ERR_INVALID;
-  if ((size_t)R * sizeof(float) > 60 * 1024) return LG_ERR_UNSUPPORTED;          // the weights of one main env live in LDS
-  const int dev = device_of(rewards);
-  if (dev < 0) return LG_ERR_INVALID;
-  DeviceScope ds_(dev);
-  hipLaunchKernelGGL(mppi_update_kernel, dim3((unsigned)num_main), dim3(64), (size_t)R * sizeof(float), (hipStream_t)stream, rewards, nodes, R, H, K * A, temperature,
-                     new_nodes, weights);
-  return hipGetLastError() == hipSuccess ? LG_OK : LG_ERR_HIP;
-}
-
-// lg_mppi_sample_plans: one workgroup per sample row; the row's K x A nodes in LDS between the draw and the interpolation
-__global__ __launch_bounds__(128) void mppi_sample_plans_kernel(const float* __restrict__ mean, const float* __restrict__ sigma_nodes, float sigma_scale,
-                                                                const float* __restrict__ phi, int R, int K, int H, int A, uint32_t seed_lo, uint32_t seed_hi,
-                                                                uint32_t call_lo, uint32_t call_hi, float* __restrict__ nodes, float* __restrict__ plans) {
-  extern __shared__ float nd[];                      // [K * A]
-  const int i = blockIdx.x, m = i / R, smp = i - m * R, KA = K * A;
-  for (int j = threadIdx.x; j < KA; j += blockDim.x) {
-    float z = 0.f;
-    if (smp != 0) {
-      uint32_t o[4];
-      philox4((uint32_t)i, call_lo, (uint32_t)(j >> 1), call_hi, seed_lo, seed_hi, o);
-      const float u1 = fmaxf(u01(o[0]), 5.9604645e-8f), u2 = u01(o[1]);
-      const float rad = sqrtf(-2.f * logf(u1));
-      z = (j & 1) ? rad * sinf(6.28318530717958647692f * u2) : rad * cosf(6.28318530717958647692f * u2);
-    }
-    const float v = mean[(size_t)m * KA + j] + (sigma_scale * sigma_nodes[j / A]) * z;
-    nd[j] = v;
-    nodes[(size_t)i * KA + j] = v;
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < H * A; j += blockDim.x) {
-    const int h = j / A, a = j - h * A;
-    float acc = 0.f;
-    for (int k = 0; k < K; ++k) acc = fmaf(phi[h * K + k], nd[k * A + a], acc);
-    plans[(size_t)i * H * A + j] = acc;
-  }
-}
-
-int lg_mppi_sample_plans(const float* mean, const float* sigma_nodes, float sigma_scale, const float* phi, int32_t num_main, int32_t R, int32_t K, int32_t H,
-                         int32_t A, uint64_t seed, uint64_t call, float* nodes, float* plans, void* stream) {
-  if (!mean || !sigma_nodes || !phi || !nodes || !plans || num_main <= 0 || R <= 0 || K <= 0 || H <= 0 || A <= 0) return LG_ERR_INVALID;
-  if ((size_t)K * A * sizeof(float) > 48 * 1024) return LG_ERR_UNSUPPORTED;
-  const int dev = device_of(mean);
-  if (dev < 0) return LG_ERR_INVALID;
-  DeviceScope ds_(dev);
-  hipLaunchKernelGGL(mppi_sample_plans_kernel, dim3((unsigned)(num_main * R)), dim3(128), (size_t)K * A * sizeof(float), (hipStream_t)stream, mean, sigma_nodes,
-                     sigma_scale, phi, R, K, H, A, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), nodes, plans);
-  return hipGetLastError() == hipSuccess ? LG_OK : LG_ERR_HIP;
-}
-
-// the diffusion passes of one control step, enqueued by one call (see lgpolicy.h)
-int lg_planner_diffuse(lg_ctx* ctx, float* mean, const float* sigma_nodes, const float* phi, int32_t num_main, int32_t R, int32_t K, int32_t H, int32_t A,
-                       int32_t n_diffuse, float traj_diffuse_factor, float temperature, uint64_t seed, uint64_t call0, const int32_t* env_ids,
-                       int32_t rollouts_per_main, float pos_drift, float* nodes, float* plans, float* rewards, float* weights, void* stream) {
-  if (!ctx || !mean || !env_ids || !rewards || !weights || n_diffuse < 0 || rollouts_per_main != R) return LG_ERR_INVALID;
-  float scale = 1.f;
-  for (int pass = 0; pass < n_diffuse; ++pass) {
-    int rc = lg_mppi_sample_plans(mean, sigma_nodes, scale, phi, num_main, R, K, H, A, seed, call0 + (uint64_t)pass, nodes, plans, stream);
-    if (rc != LG_OK) return rc;
-    rc = lg_rollout_batch(ctx, plans, H, env_ids, num_main * R, rollouts_per_main, pos_drift, rewards, stream);
-    if (rc != LG_OK) return rc;
-    rc = lg_mppi_update(rewards, nodes, num_main, R, H, K, A, temperature, mean, weights, stream);      // (the update reads `nodes`, not `mean`: in place)
-    if (rc != LG_OK) return rc;
-    scale *= traj_diffuse_factor;
-  }
-  return LG_OK;
-}
 
 
 // ============================================================================================ recurrent memory (lgpolicy.h: lg_rnn_*)
@@ -774,8 +602,8 @@ static void rnn_tile_weights(int G, int I, int H, const float* w_ih, const float
 }
 
 static int rnn_check(const lg_rnn* m, const float* h, const float* c, int64_t n) {
-  if (!m || !h || n < 0) return LG_ERR_INVALID;
-  if (m->type == LG_RNN_LSTM && !c) { g_pol_err = "lg_rnn: an LSTM needs its cell state"; return LG_ERR_INVALID; }
+  if (!m || !h || n < 0) return lg_policy_fail(LG_ERR_INVALID, "null memory or hidden state, or n < 0");
+  if (m->type == LG_RNN_LSTM && !c) return lg_policy_fail(LG_ERR_INVALID, "an LSTM needs its cell state");
   return LG_OK;
 }
 
@@ -791,13 +619,58 @@ static RnnStepArgs rnn_args(const lg_rnn* m, int l, const float* x, int64_t n, f
   return a;
 }
 
+// layers of one memory (b null), or of two memories of equal depth side by side
+static int rnn_step_pair(lg_rnn* a, const float* xa, float* ha, float* ca, float* outa, lg_rnn* b, const float* xb, float* hb, float* cb, float* outb,
+                         int64_t n, const float* reset, hipStream_t st) {
+  const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
+  for (int l = 0; l < a->num_layers; ++l) {
+    const RnnStepArgs s0 = rnn_args(a, l, xa, n, ha, ca, reset, outa);
+    const RnnStepArgs s1 = b ? rnn_args(b, l, xb, n, hb, cb, reset, outb) : s0;
+    hipLaunchKernelGGL(rnn_layer_kernel, dim3(tiles, b ? 2 : 1), dim3(MLP_THREADS), 0, st, s0, s1, n);
+  }
+  POLICY_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+// The memories in front of two MLP heads step -- side by side when their depths agree, else one after the other; b null: a alone -- and *top_a / *top_b
+// point at the top layers' h', where the heads read it (ActorCriticRecurrent.act / evaluate: actor(memory_a(obs)), critic(memory_c(obs))).  A head
+// without a memory reads its row itself: *top_b = xb.
+static int rnn_step_heads(lg_rnn* a, const float* xa, float* ha, float* ca, lg_rnn* b, const float* xb, float* hb, float* cb, int64_t n, const float* reset,
+                          hipStream_t st, const float** top_a, const float** top_b) {
+  int rc;
+  if (b && b->num_layers == a->num_layers) {
+    rc = rnn_step_pair(a, xa, ha, ca, nullptr, b, xb, hb, cb, nullptr, n, reset, st);
+  } else {
+    rc = rnn_step_pair(a, xa, ha, ca, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
+    if (rc == LG_OK && b) rc = rnn_step_pair(b, xb, hb, cb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
+  }
+  *top_a = ha + (size_t)(a->num_layers - 1) * n * a->hidden;
+  *top_b = b ? hb + (size_t)(b->num_layers - 1) * n * b->hidden : xb;
+  return rc;
+}
+
+// the env's observation rows and (n, O, A): what every collector asks the env first
+static int env_shape(lg_ctx* env, const float** obs, int64_t* n, int64_t* O, int64_t* A) {
+  void* p; int64_t shp[4], ashp[4]; int32_t nd, dt;
+  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's observation rows: ") + lg_last_error(env));
+  *obs = (const float*)p; *n = shp[0]; *O = shp[1];
+  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's action rows: ") + lg_last_error(env));
+  *A = ashp[1];
+  return LG_OK;
+}
+
+extern "C" int lg_step_transition(lg_ctx* ctx, const float* actions, float* next_observations, const float* values, float gamma,
+                                  float* rewards, float* dones, void* stream);
+
 extern "C" {
 
 int64_t lg_rnn_tile_weights(int32_t type, int32_t input, int32_t hidden, const float* w_ih, const float* w_hh, float* tiled) {
-  if ((type != LG_RNN_LSTM && type != LG_RNN_GRU) || input < 1 || input > 512 || hidden < 1 || hidden > 512) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if ((type != LG_RNN_LSTM && type != LG_RNN_GRU) || input < 1 || input > 512 || hidden < 1 || hidden > 512)
+    return lg_policy_fail(LG_ERR_INVALID, "unknown memory type, or a width out of range (1..512)");
   const int G = type == LG_RNN_GRU ? 3 : 4;
   if (tiled) {
-    if (!w_ih || !w_hh) return LG_ERR_INVALID;
+    if (!w_ih || !w_hh) return lg_policy_fail(LG_ERR_INVALID, "null weight");
     rnn_tile_weights(G, input, hidden, w_ih, w_hh, tiled);
   }
   return (int64_t)rnn_tiled_count(G, input, hidden);
@@ -812,18 +685,17 @@ void lg_rnn_destroy(lg_rnn* m) {
 
 lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t hidden, const float* const* w_ih, const float* const* w_hh,
                       const float* const* b_ih, const float* const* b_hh, int device_id) {
-  if (type != LG_RNN_LSTM && type != LG_RNN_GRU) { g_pol_err = "lg_rnn_create: unknown memory type (lstm | gru)"; return nullptr; }
-  if (num_layers < 1 || num_layers > RNN_MAX_LAYERS) { g_pol_err = "lg_rnn_create: number of layers out of range (1..4)"; return nullptr; }
-  if (input < 1 || input > 512) { g_pol_err = "lg_rnn_create: input width out of range (1..512)"; return nullptr; }
-  if (hidden < 1 || hidden > 512) { g_pol_err = "lg_rnn_create: hidden width out of range (1..512)"; return nullptr; }
-  if (!w_ih || !w_hh || !b_ih || !b_hh) { g_pol_err = "lg_rnn_create: null weight list"; return nullptr; }
+  POLICY_ENTRY;
+  if (type != LG_RNN_LSTM && type != LG_RNN_GRU) { lg_policy_fail(LG_ERR_INVALID, "unknown memory type (lstm | gru)"); return nullptr; }
+  if (num_layers < 1 || num_layers > RNN_MAX_LAYERS) { lg_policy_fail(LG_ERR_INVALID, "number of layers out of range (1..4)"); return nullptr; }
+  if (input < 1 || input > 512) { lg_policy_fail(LG_ERR_INVALID, "input width out of range (1..512)"); return nullptr; }
+  if (hidden < 1 || hidden > 512) { lg_policy_fail(LG_ERR_INVALID, "hidden width out of range (1..512)"); return nullptr; }
+  if (!w_ih || !w_hh || !b_ih || !b_hh) { lg_policy_fail(LG_ERR_INVALID, "null weight list"); return nullptr; }
   for (int l = 0; l < num_layers; ++l)
-    if (!w_ih[l] || !w_hh[l] || !b_ih[l] || !b_hh[l]) { g_pol_err = "lg_rnn_create: null weight"; return nullptr; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_pol_err = "no HIP device: the policy kernels have no CPU path"; return nullptr; }
-  if (device_id < 0 || device_id >= ndev) { g_pol_err = "bad device"; return nullptr; }
+    if (!w_ih[l] || !w_hh[l] || !b_ih[l] || !b_hh[l]) { lg_policy_fail(LG_ERR_INVALID, "null weight"); return nullptr; }
+  if (!lg_policy_device_ok(device_id)) return nullptr;
   DeviceScope ds_(device_id);
-  if (!ds_.ok) { g_pol_err = "bad device"; return nullptr; }
+  if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_rnn* m = new lg_rnn();
   m->type = type; m->num_layers = num_layers; m->input = input; m->hidden = hidden; m->device = device_id;
   const int G = type == LG_RNN_GRU ? 3 : 4, H = hidden;
@@ -843,37 +715,16 @@ lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t h
         tb[(size_t)3 * Hp + u] = b_hh[l][2 * H + u];
       }
     }
-    void *dw = nullptr, *db = nullptr;
-    if (hipMalloc(&dw, tw.size() * 4) != hipSuccess || hipMalloc(&db, tb.size() * 4) != hipSuccess ||
-        hipMemcpy(dw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(db, tb.data(), tb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      if (dw) m->allocs.push_back(dw);
-      if (db) m->allocs.push_back(db);
-      g_pol_err = "lg_rnn_create: weight upload failed"; lg_rnn_destroy(m); return nullptr;
-    }
-    m->allocs.push_back(dw); m->allocs.push_back(db);
-    R.w = (const float*)dw; R.b = (const float*)db;
+    R.w = (const float*)lg_policy_upload(tw.data(), tw.size() * 4, m->allocs);
+    R.b = R.w ? (const float*)lg_policy_upload(tb.data(), tb.size() * 4, m->allocs) : nullptr;
+    if (!R.b) { lg_rnn_destroy(m); return nullptr; }
   }
   return m;
 }
 
-#define RNN_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_pol_err = std::string(#expr) + ": " + hipGetErrorString(_e); return LG_ERR_HIP; } } while (0)
-
-// layers of one memory (b null), or of two memories of equal depth side by side
-static int rnn_step_pair(lg_rnn* a, const float* xa, float* ha, float* ca, float* outa, lg_rnn* b, const float* xb, float* hb, float* cb, float* outb,
-                         int64_t n, const float* reset, hipStream_t st) {
-  const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
-  for (int l = 0; l < a->num_layers; ++l) {
-    const RnnStepArgs s0 = rnn_args(a, l, xa, n, ha, ca, reset, outa);
-    const RnnStepArgs s1 = b ? rnn_args(b, l, xb, n, hb, cb, reset, outb) : s0;
-    hipLaunchKernelGGL(rnn_layer_kernel, dim3(tiles, b ? 2 : 1), dim3(MLP_THREADS), 0, st, s0, s1, n);
-  }
-  RNN_TRY(hipGetLastError());
-  return LG_OK;
-}
-
 int lg_rnn_step(lg_rnn* m, const float* x, int64_t n, float* h, float* c, const float* reset, float* out, void* stream) {
-  if (!x) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (!x) return lg_policy_fail(LG_ERR_INVALID, "null input row");
   int rc = rnn_check(m, h, c, n);
   if (rc != LG_OK || n == 0) return rc;
   DeviceScope ds_(m->device);
@@ -881,98 +732,118 @@ int lg_rnn_step(lg_rnn* m, const float* x, int64_t n, float* h, float* c, const 
 }
 
 int lg_rnn_reset_rows(lg_rnn* m, float* h, float* c, const float* dones, int64_t n, void* stream) {
-  if (!dones) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (!dones) return lg_policy_fail(LG_ERR_INVALID, "null dones row");
   int rc = rnn_check(m, h, c, n);
   if (rc != LG_OK || n == 0) return rc;
   DeviceScope ds_(m->device);
   const int64_t total = (int64_t)m->num_layers * n * m->hidden;
   hipLaunchKernelGGL(rnn_reset_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h, m->type == LG_RNN_LSTM ? c : nullptr, dones, n,
                      m->hidden, m->num_layers);
-  RNN_TRY(hipGetLastError());
+  POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
 
 int lg_policy_act_recurrent(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* obs, const float* critic_obs, int64_t n, const float* std_,
                             uint64_t seed, uint64_t call, int32_t deterministic, float* h_a, float* c_a, float* h_c, float* c_c, const float* reset,
                             float* actions, float* action_mean, float* actions_log_prob, float* values, void* stream) {
-  if (!mem_a || !mem_c || !actor || !critic || !obs || !critic_obs) return LG_ERR_INVALID;
+  POLICY_ENTRY;
+  if (!mem_a || !mem_c || !actor || !critic || !obs || !critic_obs) return lg_policy_fail(LG_ERR_INVALID, "null network or row");
   int rc = rnn_check(mem_a, h_a, c_a, n);
   if (rc == LG_OK) rc = rnn_check(mem_c, h_c, c_c, n);
   if (rc != LG_OK) return rc;
-  if (actor->h.dims[0] != mem_a->hidden || critic->h.dims[0] != mem_c->hidden) {
-    actor->err = "lg_policy_act_recurrent: an MLP's input width is not its memory's hidden width"; return LG_ERR_INVALID;
-  }
+  if (actor->h.dims[0] != mem_a->hidden || critic->h.dims[0] != mem_c->hidden) return lg_policy_fail(LG_ERR_INVALID, "an MLP's input width is not its memory's hidden width");
   if (n == 0) return LG_OK;
   DeviceScope ds_(mem_a->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (mem_a->num_layers == mem_c->num_layers) {
-    rc = rnn_step_pair(mem_a, obs, h_a, c_a, nullptr, mem_c, critic_obs, h_c, c_c, nullptr, n, reset, st);
-  } else {
-    rc = rnn_step_pair(mem_a, obs, h_a, c_a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
-    if (rc == LG_OK) rc = rnn_step_pair(mem_c, critic_obs, h_c, c_c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
-  }
-  if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
-  // the MLPs read the top layers' h' where the memory kernels left it (ActorCriticRecurrent.act / evaluate: actor(memory_a(obs)), critic(memory_c(obs)))
-  const float* top_a = h_a + (size_t)(mem_a->num_layers - 1) * n * mem_a->hidden;
-  const float* top_c = h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden;
+  const float *top_a, *top_c;
+  rc = rnn_step_heads(mem_a, obs, h_a, c_a, mem_c, critic_obs, h_c, c_c, n, reset, (hipStream_t)stream, &top_a, &top_c);
+  if (rc != LG_OK) return rc;
   return lg_policy_act(actor, critic, top_a, top_c, n, std_, seed, call, deterministic, actions, action_mean, actions_log_prob, values, stream);
+}
+
+}  // extern "C"
+
+// both PPO collectors: mem_a NULL = the feed-forward ActorCritic (no memory state, no hidden-state rows)
+static int collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
+                           float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a, float* c_a,
+                           float* h_c, float* c_c, void* stream) {
+  DeviceScope ds_(actor->device);
+  if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
+      !out->sigma || !out->last_values) return lg_policy_fail(LG_ERR_INVALID, "null output row");
+  const bool lstm_a = mem_a && mem_a->type == LG_RNN_LSTM, lstm_c = mem_a && mem_c->type == LG_RNN_LSTM;
+  if (mem_a && (!hid->h_a || !hid->h_c || (lstm_a && !hid->c_a) || (lstm_c && !hid->c_c))) return lg_policy_fail(LG_ERR_INVALID, "null hidden-state row");
+  const float* obs; int64_t n, O, Aenv;
+  int rc = env_shape(env, &obs, &n, &O, &Aenv);
+  if (rc == LG_OK && mem_a) rc = rnn_check(mem_a, h_a, c_a, n);
+  if (rc == LG_OK && mem_a) rc = rnn_check(mem_c, h_c, c_c, n);
+  if (rc != LG_OK) return rc;
+  const int A = actor->h.dims[actor->h.L];
+  if ((mem_a ? mem_a->input : actor->h.dims[0]) != O || (mem_a ? mem_c->input : critic->h.dims[0]) != O || critic->h.dims[critic->h.L] != 1 || A != Aenv)
+    return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (obs width, one action per DOF, scalar value)");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t sa = mem_a ? (size_t)mem_a->num_layers * n * mem_a->hidden : 0, sc = mem_a ? (size_t)mem_c->num_layers * n * mem_c->hidden : 0;
+  // the first observation row is copied from the env; every later one is written by the step itself (lg_step_transition),
+  // as are the reward (with the time-out bootstrap) and done rows: three launches per step (act, physics, post-physics)
+  POLICY_TRY(hipMemcpyAsync(out->observations, obs, (size_t)n * O * 4, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
+  for (int t = 0; t < T; ++t) {
+    float* obs_t = out->observations + (size_t)t * n * O;
+    float* act_t = out->actions + (size_t)t * n * A;
+    float* dones_t = out->dones + (size_t)t * n;
+    if (mem_a) {
+      // RolloutStorage._save_hidden_states (rollout_storage.py:123-140): the state BEFORE this step's act (ppo.py:148-149)
+      POLICY_TRY(hipMemcpyAsync(hid->h_a + t * sa, h_a, sa * 4, hipMemcpyDeviceToDevice, st));
+      if (lstm_a) POLICY_TRY(hipMemcpyAsync(hid->c_a + t * sa, c_a, sa * 4, hipMemcpyDeviceToDevice, st));
+      POLICY_TRY(hipMemcpyAsync(hid->h_c + t * sc, h_c, sc * 4, hipMemcpyDeviceToDevice, st));
+      if (lstm_c) POLICY_TRY(hipMemcpyAsync(hid->c_c + t * sc, c_c, sc * 4, hipMemcpyDeviceToDevice, st));
+      rc = lg_policy_act_recurrent(mem_a, actor, mem_c, critic, obs_t, obs_t, n, std, seed, first_call + (uint64_t)t, 0, h_a, c_a, h_c, c_c, nullptr, act_t,
+                                   out->mu + (size_t)t * n * A, out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
+    } else {
+      rc = lg_policy_act(actor, critic, obs_t, obs_t, n, std, seed, first_call + (uint64_t)t, 0, act_t, out->mu + (size_t)t * n * A,
+                         out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
+    }
+    if (rc != LG_OK) return rc;
+    rc = lg_step_transition(env, act_t, t + 1 < T ? out->observations + (size_t)(t + 1) * n * O : nullptr, out->values + (size_t)t * n, gamma,
+                            out->rewards + (size_t)t * n, dones_t, stream);
+    if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
+    if (mem_a) {                                       // PPO.process_env_step ends with policy.reset(dones) (ppo.py:188)
+      rc = lg_rnn_reset_rows(mem_a, h_a, c_a, dones_t, n, stream);
+      if (rc == LG_OK) rc = lg_rnn_reset_rows(mem_c, h_c, c_c, dones_t, n, stream);
+      if (rc != LG_OK) return rc;
+    }
+  }
+  // last_values = critic(last obs) (ppo.py:186-192); a recurrent policy.evaluate goes through Memory.forward, so the critic memory advances once more
+  const float* last = obs;
+  if (mem_a) {
+    rc = lg_rnn_step(mem_c, obs, n, h_c, c_c, nullptr, nullptr, stream);
+    if (rc != LG_OK) return rc;
+    last = h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden;
+  }
+  rc = lg_mlp_forward(critic, last, n, out->last_values, stream);
+  if (rc == LG_OK && out->returns && out->advantages)
+    rc = lg_compute_returns(out->rewards, out->dones, out->values, out->last_values, T, n, gamma, lam, normalize_advantage, out->returns,
+                            out->advantages, stream);
+  if (rc != LG_OK) return rc;
+  POLICY_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+extern "C" {
+
+int lg_collect_rollout(lg_ctx* env, lg_mlp* actor, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
+                       float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, void* stream) {
+  POLICY_ENTRY;
+  if (!env || !actor || !critic || !std || !out || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
+  return collect_rollout(env, nullptr, actor, nullptr, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, stream);
 }
 
 int lg_collect_rollout_recurrent(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
                                  int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid,
                                  float* h_a, float* c_a, float* h_c, float* c_c, void* stream) {
-  if (!env || !mem_a || !mem_c || !actor || !critic || !std || !out || !hid || T <= 0) return LG_ERR_INVALID;
-  DeviceScope ds_(actor->device);
-  if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
-      !out->sigma || !out->last_values) { actor->err = "lg_collect_rollout_recurrent: null output row"; return LG_ERR_INVALID; }
-  const bool lstm_a = mem_a->type == LG_RNN_LSTM, lstm_c = mem_c->type == LG_RNN_LSTM;
-  if (!hid->h_a || !hid->h_c || (lstm_a && !hid->c_a) || (lstm_c && !hid->c_c)) { actor->err = "lg_collect_rollout_recurrent: null hidden-state row"; return LG_ERR_INVALID; }
-  void* p; int64_t shp[4]; int32_t nd, dt;
-  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
-  const float* obs = (const float*)p; const int64_t n = shp[0], O = shp[1];
-  int rc = rnn_check(mem_a, h_a, c_a, n);
-  if (rc == LG_OK) rc = rnn_check(mem_c, h_c, c_c, n);
-  if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
-  const int A = actor->h.dims[actor->h.L];
-  int64_t ashp[4];
-  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
-  if (mem_a->input != O || mem_c->input != O || critic->h.dims[critic->h.L] != 1 || A != ashp[1]) {
-    actor->err = "lg_collect_rollout_recurrent: network widths do not match the env (obs width, one action per DOF, scalar value)"; return LG_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t sa = (size_t)mem_a->num_layers * n * mem_a->hidden, sc = (size_t)mem_c->num_layers * n * mem_c->hidden;
-  POL_TRY(actor, hipMemcpyAsync(out->observations, obs, (size_t)n * O * 4, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
-  for (int t = 0; t < T; ++t) {
-    // RolloutStorage._save_hidden_states (rollout_storage.py:123-140): the state BEFORE this step's act (ppo.py:148-149)
-    POL_TRY(actor, hipMemcpyAsync(hid->h_a + t * sa, h_a, sa * 4, hipMemcpyDeviceToDevice, st));
-    if (lstm_a) POL_TRY(actor, hipMemcpyAsync(hid->c_a + t * sa, c_a, sa * 4, hipMemcpyDeviceToDevice, st));
-    POL_TRY(actor, hipMemcpyAsync(hid->h_c + t * sc, h_c, sc * 4, hipMemcpyDeviceToDevice, st));
-    if (lstm_c) POL_TRY(actor, hipMemcpyAsync(hid->c_c + t * sc, c_c, sc * 4, hipMemcpyDeviceToDevice, st));
-    float* obs_t = out->observations + (size_t)t * n * O;
-    float* act_t = out->actions + (size_t)t * n * A;
-    float* dones_t = out->dones + (size_t)t * n;
-    rc = lg_policy_act_recurrent(mem_a, actor, mem_c, critic, obs_t, obs_t, n, std, seed, first_call + (uint64_t)t, 0, h_a, c_a, h_c, c_c, nullptr, act_t,
-                                 out->mu + (size_t)t * n * A, out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
-    if (rc != LG_OK) return rc;
-    rc = lg_step_transition(env, act_t, t + 1 < T ? out->observations + (size_t)(t + 1) * n * O : nullptr, out->values + (size_t)t * n, gamma,
-                            out->rewards + (size_t)t * n, dones_t, stream);
-    if (rc != LG_OK) { actor->err = std::string("lg_collect_rollout_recurrent: lg_step_transition failed: ") + lg_last_error(env); return rc; }
-    // PPO.process_env_step ends with policy.reset(dones) (ppo.py:188)
-    rc = lg_rnn_reset_rows(mem_a, h_a, c_a, dones_t, n, stream);
-    if (rc == LG_OK) rc = lg_rnn_reset_rows(mem_c, h_c, c_c, dones_t, n, stream);
-    if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
-  }
-  // last_values = policy.evaluate(last obs) (ppo.py:190-192): goes through Memory.forward, so the critic memory advances once more
-  rc = lg_rnn_step(mem_c, obs, n, h_c, c_c, nullptr, nullptr, stream);
-  if (rc != LG_OK) { actor->err = g_pol_err; return rc; }
-  rc = lg_mlp_forward(critic, h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden, n, out->last_values, stream);
-  if (rc != LG_OK) return rc;
-  if (out->returns && out->advantages)
-    rc = lg_compute_returns(out->rewards, out->dones, out->values, out->last_values, T, n, gamma, lam, normalize_advantage, out->returns,
-                            out->advantages, stream);
-  POL_TRY(actor, hipGetLastError());
-  return rc;
+  POLICY_ENTRY;
+  if (!env || !mem_a || !mem_c || !actor || !critic || !std || !out || !hid || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
+  return collect_rollout(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c, stream);
 }
 
 }  // extern "C"
@@ -1023,10 +894,10 @@ __global__ __launch_bounds__(256) void obs_clip_kernel(const float* __restrict__
   dst[i] = v < -clip ? -clip : (v > clip ? clip : v);
 }
 
-static int distill_widths(lg_mlp* student, lg_mlp* teacher, const char* who) {
+static int distill_widths(lg_mlp* student, lg_mlp* teacher) {
   const int A = student->h.dims[student->h.L], At = teacher->h.dims[teacher->h.L];
-  if (A != At) { student->err = g_pol_err = std::string(who) + ": the student and the teacher end in different action widths"; return LG_ERR_INVALID; }
-  if (A > 32) { student->err = g_pol_err = std::string(who) + " supports up to 32 actions"; return LG_ERR_UNSUPPORTED; }
+  if (A != At) return lg_policy_fail(LG_ERR_INVALID, "the student and the teacher end in different action widths");
+  if (A > 32) return lg_policy_fail(LG_ERR_UNSUPPORTED, "the networks end in more than 32 actions");
   return LG_OK;
 }
 
@@ -1034,87 +905,75 @@ extern "C" {
 
 int lg_obs_history_step(float* history, int64_t n, int32_t H, int32_t W, const float* obs, int64_t obs_stride, const float* dones,
                         const float* noise_scale, const float* inject_u, uint64_t seed, uint64_t call, float clip, float* obs_out, void* stream) {
-  if (H < 1 || W < 1) { g_pol_err = "lg_obs_history_step: history length H and row width W must be at least 1"; return LG_ERR_INVALID; }
-  if (obs_stride < W) { g_pol_err = "lg_obs_history_step: the observation row stride is smaller than W"; return LG_ERR_INVALID; }
-  if (!(clip > 0.f)) { g_pol_err = "lg_obs_history_step: clip must be positive (INFINITY: no clip)"; return LG_ERR_INVALID; }
-  if (!history || !obs || n < 0) { g_pol_err = "lg_obs_history_step: null history or observation pointer"; return LG_ERR_INVALID; }
+  POLICY_ENTRY;
+  if (H < 1 || W < 1) return lg_policy_fail(LG_ERR_INVALID, "history length H and row width W must be at least 1");
+  if (obs_stride < W) return lg_policy_fail(LG_ERR_INVALID, "the observation row stride is smaller than W");
+  if (!(clip > 0.f)) return lg_policy_fail(LG_ERR_INVALID, "clip must be positive (INFINITY: no clip)");
+  if (!history || !obs || n < 0) return lg_policy_fail(LG_ERR_INVALID, "null history or observation pointer");
   if (n == 0) return LG_OK;
-  const int dev = device_of(history);
-  if (dev < 0) { g_pol_err = "lg_obs_history_step: the history is not device memory"; return LG_ERR_INVALID; }
+  const int dev = lg_policy_device_of(history);
+  if (dev < 0) return lg_policy_fail(LG_ERR_INVALID, "the history is not device memory");
   DeviceScope ds_(dev);
   hipLaunchKernelGGL(obs_history_kernel, dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, (hipStream_t)stream, history, n, H, W, obs, obs_stride, dones,
                      noise_scale, inject_u, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), clip, obs_out);
-  RNN_TRY(hipGetLastError());
+  POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
 
 int lg_distill_act(lg_mlp* student, lg_mlp* teacher, const float* obs, const float* teacher_obs, int64_t n, const float* std_, uint64_t seed,
                    uint64_t call, int32_t deterministic, float* actions, float* action_mean, float* teacher_actions, void* stream) {
-  if (!student || !teacher || !obs || !teacher_obs || !std_ || !actions || !teacher_actions || n < 0) {
-    g_pol_err = "lg_distill_act: null network or row"; return LG_ERR_INVALID;
-  }
-  const int rc = distill_widths(student, teacher, "lg_distill_act");
-  if (rc != LG_OK) return rc;
-  if (n == 0) return LG_OK;
+  POLICY_ENTRY;
+  if (!student || !teacher || !obs || !teacher_obs || !std_ || !actions || !teacher_actions || n < 0) return lg_policy_fail(LG_ERR_INVALID, "null network or row");
+  const int rc = distill_widths(student, teacher);
+  if (rc != LG_OK || n == 0) return rc;
   DeviceScope ds_(student->device);
   hipLaunchKernelGGL(distill_act_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 2), dim3(MLP_THREADS), 0, (hipStream_t)stream, student->h, teacher->h,
                      obs, teacher_obs, n, std_, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), deterministic,
                      actions, action_mean, teacher_actions);
-  POL_TRY(student, hipGetLastError());
+  POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
 
 int lg_distill_act_recurrent(lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* obs, const float* teacher_obs, int64_t n,
                              const float* std_, uint64_t seed, uint64_t call, int32_t deterministic, float* h_s, float* c_s, float* h_t, float* c_t,
                              const float* reset, float* actions, float* action_mean, float* teacher_actions, void* stream) {
-  if (!mem_s || !student || !teacher || !obs || !teacher_obs) { g_pol_err = "lg_distill_act_recurrent: null network or row"; return LG_ERR_INVALID; }
+  POLICY_ENTRY;
+  if (!mem_s || !student || !teacher || !obs || !teacher_obs) return lg_policy_fail(LG_ERR_INVALID, "null network or row");
   int rc = rnn_check(mem_s, h_s, c_s, n);
   if (rc == LG_OK && mem_t) rc = rnn_check(mem_t, h_t, c_t, n);
   if (rc != LG_OK) return rc;
-  if (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden)) {
-    student->err = g_pol_err = "lg_distill_act_recurrent: an MLP's input width is not its memory's hidden width"; return LG_ERR_INVALID;
-  }
-  rc = distill_widths(student, teacher, "lg_distill_act_recurrent");
+  if (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden))
+    return lg_policy_fail(LG_ERR_INVALID, "an MLP's input width is not its memory's hidden width");
+  rc = distill_widths(student, teacher);
   if (rc != LG_OK || n == 0) return rc;
   DeviceScope ds_(mem_s->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (mem_t && mem_t->num_layers == mem_s->num_layers) {
-    rc = rnn_step_pair(mem_s, obs, h_s, c_s, nullptr, mem_t, teacher_obs, h_t, c_t, nullptr, n, reset, st);
-  } else {
-    rc = rnn_step_pair(mem_s, obs, h_s, c_s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
-    if (rc == LG_OK && mem_t) rc = rnn_step_pair(mem_t, teacher_obs, h_t, c_t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, reset, st);
-  }
-  if (rc != LG_OK) { student->err = g_pol_err; return rc; }
-  const float* top_s = h_s + (size_t)(mem_s->num_layers - 1) * n * mem_s->hidden;
-  const float* top_t = mem_t ? h_t + (size_t)(mem_t->num_layers - 1) * n * mem_t->hidden : teacher_obs;
+  const float *top_s, *top_t;
+  rc = rnn_step_heads(mem_s, obs, h_s, c_s, mem_t, teacher_obs, h_t, c_t, n, reset, (hipStream_t)stream, &top_s, &top_t);
+  if (rc != LG_OK) return rc;
   return lg_distill_act(student, teacher, top_s, top_t, n, std_, seed, call, deterministic, actions, action_mean, teacher_actions, stream);
 }
 
 // both collectors: mem_s NULL = the feed-forward StudentTeacher
 static int collect_distillation(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed, uint64_t first_call,
-                                int32_t T, const lg_obs_history* hist, const lg_distill_rollout* out, float* h_s, float* c_s, float* h_t, float* c_t, void* stream,
-                                const char* who) {
+                                int32_t T, const lg_obs_history* hist, const lg_distill_rollout* out, float* h_s, float* c_s, float* h_t, float* c_t, void* stream) {
   DeviceScope ds_(student->device);
-  auto fail = [&](const char* what, int rc) { student->err = g_pol_err = std::string(who) + ": " + what; return rc; };
   if (!out->observations || !out->privileged_observations || !out->actions || !out->privileged_actions || !out->rewards || !out->dones)
-    return fail("null output row", LG_ERR_INVALID);
-  void* p; int64_t shp[4], ashp[4]; int32_t nd, dt;
-  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
-  const float* env_obs = (const float*)p; const int64_t n = shp[0], Ot = shp[1];
-  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
-  int rc = distill_widths(student, teacher, who);
+    return lg_policy_fail(LG_ERR_INVALID, "null output row");
+  const float* env_obs; int64_t n, Ot, Aenv;
+  int rc = env_shape(env, &env_obs, &n, &Ot, &Aenv);
+  if (rc == LG_OK) rc = distill_widths(student, teacher);
   if (rc != LG_OK) return rc;
   const int A = student->h.dims[student->h.L];
   const int64_t Os = mem_s ? mem_s->input : student->h.dims[0];
-  if ((mem_t ? mem_t->input : teacher->h.dims[0]) != Ot || A != ashp[1])
-    return fail("network widths do not match the env (the teacher reads the env's observation row, one action per DOF)", LG_ERR_INVALID);
+  if ((mem_t ? mem_t->input : teacher->h.dims[0]) != Ot || A != Aenv)
+    return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (the teacher reads the env's observation row, one action per DOF)");
   if (mem_s && (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden)))
-    return fail("an MLP's input width is not its memory's hidden width", LG_ERR_INVALID);
+    return lg_policy_fail(LG_ERR_INVALID, "an MLP's input width is not its memory's hidden width");
   if (hist) {
-    if (!hist->history || hist->H < 1 || hist->W < 1 || hist->W > Ot || !(hist->clip > 0.f)) return fail("bad history layer (pointer, H, W <= env row, clip > 0)", LG_ERR_INVALID);
-    if ((int64_t)hist->H * hist->W != Os) return fail("the student's input width is not H x W of the history layer", LG_ERR_INVALID);
+    if (!hist->history || hist->H < 1 || hist->W < 1 || hist->W > Ot || !(hist->clip > 0.f)) return lg_policy_fail(LG_ERR_INVALID, "bad history layer (pointer, H, W <= env row, clip > 0)");
+    if ((int64_t)hist->H * hist->W != Os) return lg_policy_fail(LG_ERR_INVALID, "the student's input width is not H x W of the history layer");
   } else if (Os > Ot) {
-    return fail("without a history layer the student reads a prefix of the env's observation row", LG_ERR_INVALID);
+    return lg_policy_fail(LG_ERR_INVALID, "without a history layer the student reads a prefix of the env's observation row");
   }
   hipStream_t st = (hipStream_t)stream;
   const size_t so = (size_t)n * Os, sp = (size_t)n * Ot, sa = (size_t)n * A;
@@ -1122,12 +981,12 @@ static int collect_distillation(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_
   auto student_row = [&](int t, const float* dones_t, float* dst) -> int {
     if (hist) return lg_obs_history_step(hist->history, n, hist->H, hist->W, env_obs, Ot, dones_t, hist->noise_scale,
                                          hist->inject_u ? hist->inject_u + (size_t)t * so : nullptr, hist->noise_seed, first_call + (uint64_t)t, hist->clip, dst, stream);
-    if (dst) POL_TRY(student, hipMemcpy2DAsync(dst, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+    if (dst) POLICY_TRY(hipMemcpy2DAsync(dst, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
     return LG_OK;
   };
-  POL_TRY(student, hipMemcpyAsync(out->privileged_observations, env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
+  POLICY_TRY(hipMemcpyAsync(out->privileged_observations, env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
   if (hist) hipLaunchKernelGGL(obs_clip_kernel, dim3((unsigned)((so + 255) / 256)), dim3(256), 0, st, hist->history, (int64_t)so, hist->clip, out->observations);
-  else POL_TRY(student, hipMemcpy2DAsync(out->observations, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+  else POLICY_TRY(hipMemcpy2DAsync(out->observations, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
   for (int t = 0; t < T; ++t) {
     float* act_t = out->actions + t * sa;
     float* dones_t = out->dones + (size_t)t * n;
@@ -1138,45 +997,43 @@ static int collect_distillation(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_
     if (rc != LG_OK) return rc;
     // Distillation.process_env_step (distillation.py:98-101) stores the env's reward as it is: no value row, no time-out bootstrap
     rc = lg_step_transition(env, act_t, t + 1 < T ? out->privileged_observations + (t + 1) * sp : nullptr, nullptr, 0.f, out->rewards + (size_t)t * n, dones_t, stream);
-    if (rc != LG_OK) { student->err = std::string(who) + ": lg_step_transition failed: " + lg_last_error(env); return rc; }
+    if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
     rc = student_row(t, dones_t, t + 1 < T ? out->observations + (t + 1) * so : out->last_observations);
-    if (rc != LG_OK) { if (student->err.empty()) student->err = g_pol_err; return rc; }
-    if (mem_s) {                                       // policy.reset(dones) (distillation.py:105)
+    if (rc == LG_OK && mem_s) {                        // policy.reset(dones) (distillation.py:105)
       rc = lg_rnn_reset_rows(mem_s, h_s, c_s, dones_t, n, stream);
       if (rc == LG_OK && mem_t) rc = lg_rnn_reset_rows(mem_t, h_t, c_t, dones_t, n, stream);
-      if (rc != LG_OK) { student->err = g_pol_err; return rc; }
     }
+    if (rc != LG_OK) return rc;
   }
-  POL_TRY(student, hipGetLastError());
+  POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
 
 int lg_collect_distillation(lg_ctx* env, lg_mlp* student, lg_mlp* teacher, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
                             const lg_obs_history* history, const lg_distill_rollout* rows, void* stream) {
-  if (!env || !student || !teacher || !std || !rows || T <= 0) { g_pol_err = "lg_collect_distillation: null argument or T < 1"; return LG_ERR_INVALID; }
-  return collect_distillation(env, nullptr, student, nullptr, teacher, std, seed, first_call, T, history, rows, nullptr, nullptr, nullptr, nullptr, stream,
-                              "lg_collect_distillation");
+  POLICY_ENTRY;
+  if (!env || !student || !teacher || !std || !rows || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
+  return collect_distillation(env, nullptr, student, nullptr, teacher, std, seed, first_call, T, history, rows, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int lg_collect_distillation_recurrent(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed,
                                       uint64_t first_call, int32_t T, const lg_obs_history* history, const lg_distill_rollout* rows, float* h_s0, float* c_s0,
                                       float* h_t0, float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, void* stream) {
-  if (!env || !mem_s || !student || !teacher || !std || !rows || T <= 0) { g_pol_err = "lg_collect_distillation_recurrent: null argument or T < 1"; return LG_ERR_INVALID; }
-  void* p; int64_t shp[4]; int32_t nd, dt;
-  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return LG_ERR_INVALID;
-  const int64_t n = shp[0];
-  int rc = rnn_check(mem_s, h_s, c_s, n);
+  POLICY_ENTRY;
+  if (!env || !mem_s || !student || !teacher || !std || !rows || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
+  const float* env_obs; int64_t n, Ot, Aenv;
+  int rc = env_shape(env, &env_obs, &n, &Ot, &Aenv);
+  if (rc == LG_OK) rc = rnn_check(mem_s, h_s, c_s, n);
   if (rc == LG_OK && mem_t) rc = rnn_check(mem_t, h_t, c_t, n);
-  if (rc != LG_OK) { student->err = g_pol_err; return rc; }
+  if (rc != LG_OK) return rc;
   DeviceScope ds_(student->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t ss = (size_t)mem_s->num_layers * n * mem_s->hidden * 4, stt = mem_t ? (size_t)mem_t->num_layers * n * mem_t->hidden * 4 : 0;
-  if (h_s0) POL_TRY(student, hipMemcpyAsync(h_s0, h_s, ss, hipMemcpyDeviceToDevice, st));
-  if (c_s0 && mem_s->type == LG_RNN_LSTM) POL_TRY(student, hipMemcpyAsync(c_s0, c_s, ss, hipMemcpyDeviceToDevice, st));
-  if (mem_t && h_t0) POL_TRY(student, hipMemcpyAsync(h_t0, h_t, stt, hipMemcpyDeviceToDevice, st));
-  if (mem_t && c_t0 && mem_t->type == LG_RNN_LSTM) POL_TRY(student, hipMemcpyAsync(c_t0, c_t, stt, hipMemcpyDeviceToDevice, st));
-  return collect_distillation(env, mem_s, student, mem_t, teacher, std, seed, first_call, T, history, rows, h_s, c_s, h_t, c_t, stream,
-                              "lg_collect_distillation_recurrent");
+  if (h_s0) POLICY_TRY(hipMemcpyAsync(h_s0, h_s, ss, hipMemcpyDeviceToDevice, st));
+  if (c_s0 && mem_s->type == LG_RNN_LSTM) POLICY_TRY(hipMemcpyAsync(c_s0, c_s, ss, hipMemcpyDeviceToDevice, st));
+  if (mem_t && h_t0) POLICY_TRY(hipMemcpyAsync(h_t0, h_t, stt, hipMemcpyDeviceToDevice, st));
+  if (mem_t && c_t0 && mem_t->type == LG_RNN_LSTM) POLICY_TRY(hipMemcpyAsync(c_t0, c_t, stt, hipMemcpyDeviceToDevice, st));
+  return collect_distillation(env, mem_s, student, mem_t, teacher, std, seed, first_call, T, history, rows, h_s, c_s, h_t, c_t, stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from extended_legged_gym_amd import abi
+from .policy import NativeMemory, NativeMLP, _NativeHandle, _ptr
 
 ENCODER_KEYS = (0, 2, 4, 6, 10, 12)                      # Conv2d x 4, Linear x 2 of depth_encoder (terrain_estimator.py:85-107)
 _CONV_SHAPES = ((32, 1, 5, 5), (64, 32, 3, 3), (128, 64, 3, 3), (64, 128, 3, 3))
@@ -99,19 +100,16 @@ def parse_estimator_state(state_dict, depth_image_shape, proprio_dim, memory_typ
                 decoder_hidden_dims=[w.shape[0] for w, _ in dec[:-1]], num_raycast_outputs=cur)
 
 
-class NativeConvEncoder:
+class NativeConvEncoder(_NativeHandle):
     """`TerrainEstimator.depth_encoder` (`terrain_estimator.py:80-109`) on the GPU: `layers` = [(weight, bias)] x 6 in torch's layouts.
     `precision`: "fp32" (default), or "bf16" for inference on the bf16 matrix cores (bf16 operands and maps, fp32 accumulation and features;
     include/lgpolicy.h `lg_conv_encoder_create_precision`)."""
+    _destroy = "lg_conv_encoder_destroy"
 
     def __init__(self, layers, depth_image_shape, activation="elu", device="cuda:0", precision="fp32"):
-        from .policy import _lib
         prec = parse_precision(precision)
         self.precision = precision
-        dev = torch.device(device)
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("the estimator kernels run on the GPU only (no CPU path)")
-        self.lib, self.device = _lib(), dev
+        index = self._open(device, "estimator")
         self.height, self.width = (int(v) for v in depth_image_shape)
         ws = [np.ascontiguousarray(np.asarray(w, dtype=np.float32)) for w, _ in layers]
         bs = [np.ascontiguousarray(np.asarray(b, dtype=np.float32)) for _, b in layers]
@@ -119,17 +117,12 @@ class NativeConvEncoder:
         fp = C.POINTER(C.c_float)
         wp = (fp * 6)(*[w.ctypes.data_as(fp) for w in ws])
         bp = (fp * 6)(*[b.ctypes.data_as(fp) for b in bs])
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
         if prec == abi.LG_PREC_F32:
-            self.handle = self.lib.lg_conv_encoder_create(self.height, self.width, self.out_dim, abi.ACTIVATIONS[estimator_activation(activation)], wp, bp, index)
+            handle = self.lib.lg_conv_encoder_create(self.height, self.width, self.out_dim, abi.ACTIVATIONS[estimator_activation(activation)], wp, bp, index)
         else:
-            self.handle = self.lib.lg_conv_encoder_create_precision(self.height, self.width, self.out_dim, abi.ACTIVATIONS[estimator_activation(activation)], wp, bp,
-                                                                    index, prec)
-        if not self.handle:
-            raise RuntimeError("lg_conv_encoder_create failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            handle = self.lib.lg_conv_encoder_create_precision(self.height, self.width, self.out_dim, abi.ACTIVATIONS[estimator_activation(activation)], wp, bp,
+                                                               index, prec)
+        self._created(handle, "lg_conv_encoder_create")
 
     def latest_frame(self, depth_images):
         """(n, h, w), or the camera's (n, buffer_len, h, w) FIFO of which the latest frame `[:, -1]` is taken as a view: no copy when the
@@ -149,10 +142,8 @@ class NativeConvEncoder:
         x = self.latest_frame(depth_images)
         n = x.shape[0]
         y = torch.empty(n, self.out_dim, device=self.device)
-        rc = self.lib.lg_conv_encoder_forward(self.handle, C.c_void_p(x.data_ptr()), max(x.stride(0), self.height * self.width), n, C.c_void_p(y.data_ptr()),
-                                              self._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_conv_encoder_forward failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        self._check(self.lib.lg_conv_encoder_forward(self.handle, _ptr(x), max(x.stride(0), self.height * self.width), n, _ptr(y), self._stream()),
+                    "lg_conv_encoder_forward")
         return y
 
     def stage_shape(self, k):
@@ -173,24 +164,10 @@ class NativeConvEncoder:
         if out is None:
             out = torch.empty(n * count, device=self.device)
         assert out.is_contiguous() and out.dtype == torch.float32 and out.device == self.device and out.numel() >= n * count
-        rc = self.lib.lg_conv_encoder_forward_stages(self.handle, C.c_void_p(x.data_ptr()), max(x.stride(0), self.height * self.width), n, int(k),
-                                                     C.c_void_p(out.data_ptr()), self._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_conv_encoder_forward_stages failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        self._check(self.lib.lg_conv_encoder_forward_stages(self.handle, _ptr(x), max(x.stride(0), self.height * self.width), n, int(k), _ptr(out), self._stream()),
+                    "lg_conv_encoder_forward_stages")
         y = out.view(-1)[:n * count]
         return y.view(n, h, w, c).permute(0, 3, 1, 2) if k <= 4 else y.view(n, count)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.lg_conv_encoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class NativeTerrainEstimator:
@@ -199,7 +176,6 @@ class NativeTerrainEstimator:
     `encoder_precision`: "fp32" (default) or "bf16", the mode of the depth encoder alone; combination layer, memory and decoder stay fp32."""
 
     def __init__(self, state_dict, depth_image_shape, proprio_dim, activation="elu", memory_type="gru", device="cuda:0", encoder_precision="fp32"):
-        from .policy import NativeMemory, NativeMLP
         parse_precision(encoder_precision)          # refused before anything is parsed or built
         self.precision = encoder_precision
         spec = parse_estimator_state(state_dict, depth_image_shape, proprio_dim, memory_type)
@@ -210,8 +186,7 @@ class NativeTerrainEstimator:
         self.num_raycast_outputs = spec["num_raycast_outputs"]
         self.encoder = NativeConvEncoder(spec["encoder"], self.depth_image_shape, act, device, precision=encoder_precision)
         self.combine = NativeMLP([spec["combine"]], act, device)
-        if self.encoder.lib.lg_mlp_set_output_activation(self.combine.handle, 1) != abi.LG_OK:
-            raise RuntimeError("lg_mlp_set_output_activation failed")
+        self.combine._check(self.combine.lib.lg_mlp_set_output_activation(self.combine.handle, 1), "lg_mlp_set_output_activation")
         self.memory = NativeMemory(spec["memory"], spec["memory_type"], device)
         self.decoder = NativeMLP(spec["decoder"], act, device)
 
@@ -233,11 +208,8 @@ class NativeTerrainEstimator:
             reset = reset.to(device=self.device, dtype=torch.float32).contiguous().view(-1)
             assert reset.shape[0] == n
         out = torch.empty(n, self.num_raycast_outputs, device=self.device)
-        rc = lib.lg_estimator_step(enc.handle, self.combine.handle, self.memory.handle, self.decoder.handle, C.c_void_p(x.data_ptr()),
-                                   max(x.stride(0), enc.height * enc.width), C.c_void_p(p.data_ptr()), n, *self.memory._ptrs(),
-                                   C.c_void_p(reset.data_ptr()) if reset is not None else None, C.c_void_p(out.data_ptr()), enc._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_estimator_step failed: " + (lib.lg_mlp_last_error(None) or b"").decode())
+        enc._check(lib.lg_estimator_step(enc.handle, self.combine.handle, self.memory.handle, self.decoder.handle, _ptr(x), max(x.stride(0), enc.height * enc.width),
+                                         _ptr(p), n, *self.memory._ptrs(), _ptr(reset), _ptr(out), enc._stream()), "lg_estimator_step")
         return out
 
     def reset(self, dones=None, hidden_states=None):
@@ -255,13 +227,7 @@ class NativeTerrainEstimator:
 
     def set_hidden_states(self, hidden_states):
         """`h` (L, n, H) for a GRU, `(h, c)` for an LSTM, None to forget; copied into the live state."""
-        if hidden_states is None:
-            self.memory.reset(None)
-            return
-        lstm = self.memory.rnn_type == "lstm"
-        h, c = hidden_states if lstm else (hidden_states, None)
-        self.memory.h = h.to(device=self.device, dtype=torch.float32).contiguous().clone()
-        self.memory.c = c.to(device=self.device, dtype=torch.float32).contiguous().clone() if lstm else None
+        self.memory.set_state(hidden_states)
 
     def close(self):
         for part in (self.encoder, self.combine, self.memory, self.decoder):

@@ -24,14 +24,65 @@ def _lib():
     return lib
 
 
-class NativeMLP:
-    """nn.Sequential(Linear, act, ..., Linear) on the GPU.  `layers`: list of (weight (out, in), bias (out))."""
+LOG_SQRT_2PI = 0.9189385332046727          # log sqrt(2 pi) of Normal.log_prob and Normal.entropy
 
-    def __init__(self, layers, activation="elu", device="cuda:0"):
+
+def _ptr(x):
+    """The device pointer of a tensor; NULL for None."""
+    return C.c_void_p(x.data_ptr()) if x is not None else None
+
+
+def _error(name):
+    """The library keeps one message per thread, whichever entry point failed (include/lgpolicy.h: `lg_mlp_last_error`)."""
+    return RuntimeError(f"{name} failed: " + (_lib().lg_mlp_last_error(None) or b"").decode())
+
+
+def _check(rc, name):
+    if rc != abi.LG_OK:
+        raise _error(name)
+
+
+class _NativeHandle:
+    """What the owners of a library handle share (`NativeMLP`, `NativeMemory`, `NativeConvEncoder`): the GPU check, `lib`, the device index, the
+    current stream, `_check`, and `close` / `__del__` through the class's destroy function."""
+    _destroy = None          # the name of the handle's destroy function
+    _check = staticmethod(_check)
+
+    def _open(self, device, kernels="policy"):
+        """Sets `lib` and `device`; returns the device index the create function takes."""
         dev = torch.device(device)
         if dev.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("the policy kernels run on the GPU only (no CPU path)")
+            raise RuntimeError(f"the {kernels} kernels run on the GPU only (no CPU path)")
         self.lib, self.device = _lib(), dev
+        return dev.index if dev.index is not None else torch.cuda.current_device()
+
+    def _created(self, handle, name):
+        if not handle:
+            raise _error(name)
+        self.handle = handle
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize(self.device)
+            getattr(self.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeMLP(_NativeHandle):
+    """nn.Sequential(Linear, act, ..., Linear) on the GPU.  `layers`: list of (weight (out, in), bias (out))."""
+    _destroy = "lg_mlp_destroy"
+
+    def __init__(self, layers, activation="elu", device="cuda:0"):
+        index = self._open(device)
         ws = [np.ascontiguousarray(np.asarray(w, dtype=np.float32)) for w, _ in layers]
         bs = [np.ascontiguousarray(np.asarray(b, dtype=np.float32)) for _, b in layers]
         dims = [ws[0].shape[1]] + [w.shape[0] for w in ws]
@@ -42,10 +93,7 @@ class NativeMLP:
         wp = (fp * L)(*[w.ctypes.data_as(fp) for w in ws])
         bp = (fp * L)(*[b.ctypes.data_as(fp) for b in bs])
         self.dims = dims
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.handle = self.lib.lg_mlp_create(L, (C.c_int32 * (L + 1))(*dims), wp, bp, abi.ACTIVATIONS[activation], index)
-        if not self.handle:
-            raise RuntimeError("lg_mlp_create failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        self._created(self.lib.lg_mlp_create(L, (C.c_int32 * (L + 1))(*dims), wp, bp, abi.ACTIVATIONS[activation], index), "lg_mlp_create")
 
     @classmethod
     def from_sequential_state(cls, state, prefix, activation="elu", device="cuda:0"):
@@ -54,32 +102,49 @@ class NativeMLP:
         layers = [(state[f"{prefix}.{i}.weight"].detach().cpu().numpy(), state[f"{prefix}.{i}.bias"].detach().cpu().numpy()) for i in idx]
         return cls(layers, activation, device)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def __call__(self, x):
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         assert x.dim() == 2 and x.shape[1] == self.dims[0]
         y = torch.empty(x.shape[0], self.dims[-1], device=self.device)
-        rc = self.lib.lg_mlp_forward(self.handle, C.c_void_p(x.data_ptr()), x.shape[0], C.c_void_p(y.data_ptr()), self._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_mlp_forward failed: " + (self.lib.lg_mlp_last_error(self.handle) or b"").decode())
+        self._check(self.lib.lg_mlp_forward(self.handle, _ptr(x), x.shape[0], _ptr(y), self._stream()), "lg_mlp_forward")
         return y
 
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.lg_mlp_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class _GaussianPolicy:
+    """What `NativeActorCritic` and `NativeStudentTeacher` share: the `std` vector, the rows every act writes (`_actions`, `_mean`) with the Philox call
+    number, and `action_mean` / `action_std` / `entropy` over them."""
+
+    def _load_std(self, state_dict, noise_std_type="scalar"):
+        if noise_std_type == "scalar":
+            self.std = state_dict["std"].detach().to(self.device, torch.float32).contiguous()
+        elif noise_std_type == "log":
+            self.std = torch.exp(state_dict["log_std"].detach().to(self.device, torch.float32)).contiguous()
+        else:
+            raise ValueError(f"Unknown standard deviation type: {noise_std_type}. Should be 'scalar' or 'log'")
+
+    def _f32(self, x):
+        return x.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _rows(self, n):
+        """Fresh output rows for one act on n rows, and the next call number."""
+        self._actions = torch.empty(n, self.num_actions, device=self.device)
+        self._mean = torch.empty(n, self.num_actions, device=self.device)
+        self._call += 1
+
+    @property
+    def action_mean(self):
+        return self._mean
+
+    @property
+    def action_std(self):
+        return self.std.expand_as(self._mean)
+
+    @property
+    def entropy(self):
+        return (0.5 + LOG_SQRT_2PI + torch.log(self.std)).sum().expand(self._mean.shape[0])
 
 
-class NativeActorCritic:
+class NativeActorCritic(_GaussianPolicy):
     """Same surface as `ActorCritic` for rollout collection: `act`, `act_inference`, `evaluate`, `get_actions_log_prob`,
     `action_mean`, `action_std`, `entropy` (`actor_critic.py:96-136`)."""
     is_recurrent = False
@@ -89,12 +154,7 @@ class NativeActorCritic:
         self.actor = NativeMLP.from_sequential_state(state_dict, "actor", activation, device)
         self.critic = NativeMLP.from_sequential_state(state_dict, "critic", activation, device)
         self.noise_std_type = noise_std_type
-        if noise_std_type == "scalar":
-            self.std = state_dict["std"].detach().to(self.device, torch.float32).contiguous()
-        elif noise_std_type == "log":
-            self.std = torch.exp(state_dict["log_std"].detach().to(self.device, torch.float32)).contiguous()
-        else:
-            raise ValueError(f"Unknown standard deviation type: {noise_std_type}. Should be 'scalar' or 'log'")
+        self._load_std(state_dict, noise_std_type)
         self.num_actions = self.actor.dims[-1]
         self.seed, self._call = int(seed), 0
         self._mean = self._actions = self._logp = self._values = None
@@ -102,22 +162,26 @@ class NativeActorCritic:
     def reset(self, dones=None):
         pass
 
-    def _run(self, obs, critic_obs, deterministic):
-        lib = self.actor.lib
-        obs = obs.to(device=self.device, dtype=torch.float32).contiguous()
-        cobs = obs if critic_obs is None else critic_obs.to(device=self.device, dtype=torch.float32).contiguous()
-        n = obs.shape[0]
-        self._actions = torch.empty(n, self.num_actions, device=self.device)
-        self._mean = torch.empty(n, self.num_actions, device=self.device)
+    def _rows(self, n, keep_values=True):
+        """Returns the row the critic writes: `_values`, or a scratch row for an act whose critic output means nothing (`_values` stays)."""
+        super()._rows(n)
         self._logp = torch.empty(n, device=self.device)
-        self._values = torch.empty(n, self.critic.dims[-1], device=self.device)
-        self._call += 1
-        rc = lib.lg_policy_act(self.actor.handle, self.critic.handle, C.c_void_p(obs.data_ptr()), C.c_void_p(cobs.data_ptr()), n,
-                               C.c_void_p(self.std.data_ptr()), self.seed, self._call, int(deterministic),
-                               C.c_void_p(self._actions.data_ptr()), C.c_void_p(self._mean.data_ptr()),
-                               C.c_void_p(self._logp.data_ptr()), C.c_void_p(self._values.data_ptr()), self.actor._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_policy_act failed: " + (lib.lg_mlp_last_error(self.actor.handle) or b"").decode())
+        values = torch.empty(n, self.critic.dims[-1], device=self.device)
+        if keep_values:
+            self._values = values
+        return values
+
+    def _act(self, obs, critic_obs, deterministic, keep_values=True):
+        """`lg_policy_act` on prepared rows (a feed-forward policy's observations, a recurrent one's memory outputs)."""
+        n = obs.shape[0]
+        values = self._rows(n, keep_values)
+        _check(self.actor.lib.lg_policy_act(self.actor.handle, self.critic.handle, _ptr(obs), _ptr(critic_obs), n, _ptr(self.std), self.seed, self._call,
+                                            int(deterministic), _ptr(self._actions), _ptr(self._mean), _ptr(self._logp), _ptr(values),
+                                            self.actor._stream()), "lg_policy_act")
+
+    def _run(self, obs, critic_obs, deterministic):
+        obs = self._f32(obs)
+        self._act(obs, obs if critic_obs is None else self._f32(critic_obs), deterministic)
 
     def act_and_evaluate(self, obs, critic_obs=None):
         """`PPO.act` in one launch: (actions, values, actions_log_prob, action_mean, action_sigma)."""
@@ -138,34 +202,21 @@ class NativeActorCritic:
         if actions is self._actions:
             return self._logp
         sd = self.std
-        return (-((actions - self._mean) ** 2) / (2 * sd * sd) - torch.log(sd) - 0.9189385332046727).sum(dim=-1)
-
-    @property
-    def action_mean(self):
-        return self._mean
-
-    @property
-    def action_std(self):
-        return self.std.expand_as(self._mean)
-
-    @property
-    def entropy(self):
-        return (0.5 + 0.9189385332046727 + torch.log(self.std)).sum().expand(self._mean.shape[0])
+        return (-((actions - self._mean) ** 2) / (2 * sd * sd) - torch.log(sd) - LOG_SQRT_2PI).sum(dim=-1)
 
 
-class NativeMemory:
+class NativeMemory(_NativeHandle):
     """One `Memory` (`networks/memory.py:16-51`) in inference mode.  `layers`: per RNN layer (weight_ih, weight_hh, bias_ih, bias_hh) in torch's
     layout; input width, hidden width and depth come from the shapes.  The state (`h`, and `c` for an LSTM; (L, n, H)) is allocated, zeroed,
     on the first step and again when the number of rows changes, as `Memory` does with `hidden_states = None`."""
+    _destroy = "lg_rnn_destroy"
 
     def __init__(self, layers, rnn_type="lstm", device="cuda:0"):
-        dev = torch.device(device)
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("the policy kernels run on the GPU only (no CPU path)")
+        index = self._open(device)
         rnn_type = rnn_type.lower()
         if rnn_type not in abi.RNN_TYPES:
             raise ValueError(f"Unknown rnn_type: {rnn_type}. Should be 'lstm' or 'gru'")
-        self.lib, self.device, self.rnn_type = _lib(), dev, rnn_type
+        self.rnn_type = rnn_type
         G = 4 if rnn_type == "lstm" else 3
         arrs = [[np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in layer] for layer in layers]
         self.num_layers, self.hidden_size, self.input_size = len(arrs), arrs[0][1].shape[1], arrs[0][0].shape[1]
@@ -175,10 +226,7 @@ class NativeMemory:
                 f"layer {l}: shapes do not belong to an nn.{rnn_type.upper()} of hidden size {H}"
         fp = C.POINTER(C.c_float)
         lists = [(fp * len(arrs))(*[layer[j].ctypes.data_as(fp) for layer in arrs]) for j in range(4)]
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.handle = self.lib.lg_rnn_create(abi.RNN_TYPES[rnn_type], self.num_layers, self.input_size, H, *lists, index)
-        if not self.handle:
-            raise RuntimeError("lg_rnn_create failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        self._created(self.lib.lg_rnn_create(abi.RNN_TYPES[rnn_type], self.num_layers, self.input_size, H, *lists, index), "lg_rnn_create")
         self.h = self.c = None
 
     @classmethod
@@ -190,16 +238,23 @@ class NativeMemory:
         layers = [[state[f"{prefix}.rnn.{name}_l{l}"].detach().cpu().numpy() for name in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] for l in range(L)]
         return cls(layers, rnn_type, device)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def ensure_state(self, n):
         if self.h is None or self.h.shape[1] != n:
             self.h = torch.zeros(self.num_layers, n, self.hidden_size, device=self.device)
             self.c = torch.zeros_like(self.h) if self.rnn_type == "lstm" else None
 
+    def set_state(self, hidden_states):
+        """Installs `(h, c)` (LSTM) or `h` (GRU), each (L, n, H), as the live state, as `Memory.reset(hidden_states=...)` does; the tensors are
+        copied.  None forgets the state."""
+        if hidden_states is None:
+            self.h = self.c = None
+            return
+        parts = hidden_states if isinstance(hidden_states, (tuple, list)) else (hidden_states,)
+        self.h = parts[0].detach().to(self.device, torch.float32).clone().contiguous()
+        self.c = parts[1].detach().to(self.device, torch.float32).clone().contiguous() if self.rnn_type == "lstm" else None
+
     def _ptrs(self):
-        return C.c_void_p(self.h.data_ptr()), C.c_void_p(self.c.data_ptr() if self.c is not None else None)
+        return _ptr(self.h), _ptr(self.c)
 
     @property
     def hidden_states(self):
@@ -216,10 +271,7 @@ class NativeMemory:
         self.ensure_state(n)
         if reset is not None:
             reset = reset.to(device=self.device, dtype=torch.float32).contiguous().view(-1)
-        rc = self.lib.lg_rnn_step(self.handle, C.c_void_p(x.data_ptr()), n, *self._ptrs(), C.c_void_p(reset.data_ptr() if reset is not None else None), None,
-                                  self._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_rnn_step failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
+        self._check(self.lib.lg_rnn_step(self.handle, _ptr(x), n, *self._ptrs(), _ptr(reset), None, self._stream()), "lg_rnn_step")
         return self.h[-1]
 
     def reset(self, dones=None):
@@ -229,21 +281,7 @@ class NativeMemory:
         elif self.h is not None:
             d = dones.to(device=self.device, dtype=torch.float32).contiguous().view(-1)
             assert d.shape[0] == self.h.shape[1]
-            rc = self.lib.lg_rnn_reset_rows(self.handle, *self._ptrs(), C.c_void_p(d.data_ptr()), d.shape[0], self._stream())
-            if rc != abi.LG_OK:
-                raise RuntimeError("lg_rnn_reset_rows failed: " + (self.lib.lg_mlp_last_error(None) or b"").decode())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.lg_rnn_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._check(self.lib.lg_rnn_reset_rows(self.handle, *self._ptrs(), _ptr(d), d.shape[0], self._stream()), "lg_rnn_reset_rows")
 
 
 class NativeActorCriticRecurrent(NativeActorCritic):
@@ -273,44 +311,24 @@ class NativeActorCriticRecurrent(NativeActorCritic):
         return self.memory_a.hidden_states, self.memory_c.hidden_states
 
     def _run(self, obs, critic_obs, deterministic):
-        lib = self.actor.lib
-        obs = obs.to(device=self.device, dtype=torch.float32).contiguous()
-        cobs = obs if critic_obs is None else critic_obs.to(device=self.device, dtype=torch.float32).contiguous()
+        obs = self._f32(obs)
+        cobs = obs if critic_obs is None else self._f32(critic_obs)
         n = obs.shape[0]
         assert obs.shape[1] == self.memory_a.input_size and cobs.shape == (n, self.memory_c.input_size)
         self.memory_a.ensure_state(n)
         self.memory_c.ensure_state(n)
-        self._actions = torch.empty(n, self.num_actions, device=self.device)
-        self._mean = torch.empty(n, self.num_actions, device=self.device)
-        self._logp = torch.empty(n, device=self.device)
-        self._values = torch.empty(n, self.critic.dims[-1], device=self.device)
-        self._call += 1
-        rc = lib.lg_policy_act_recurrent(self.memory_a.handle, self.actor.handle, self.memory_c.handle, self.critic.handle, C.c_void_p(obs.data_ptr()),
-                                         C.c_void_p(cobs.data_ptr()), n, C.c_void_p(self.std.data_ptr()), self.seed, self._call, int(deterministic),
-                                         *self.memory_a._ptrs(), *self.memory_c._ptrs(), None, C.c_void_p(self._actions.data_ptr()),
-                                         C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._logp.data_ptr()), C.c_void_p(self._values.data_ptr()),
-                                         self.actor._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_policy_act_recurrent failed: " + (lib.lg_mlp_last_error(self.actor.handle) or b"").decode())
+        self._rows(n)
+        _check(self.actor.lib.lg_policy_act_recurrent(self.memory_a.handle, self.actor.handle, self.memory_c.handle, self.critic.handle, _ptr(obs), _ptr(cobs), n,
+                                                      _ptr(self.std), self.seed, self._call, int(deterministic), *self.memory_a._ptrs(), *self.memory_c._ptrs(),
+                                                      None, _ptr(self._actions), _ptr(self._mean), _ptr(self._logp), _ptr(self._values), self.actor._stream()),
+               "lg_policy_act_recurrent")
 
     def act(self, observations, masks=None, hidden_states=None):
         """`ActorCriticRecurrent.act`: advances the ACTOR memory only (the critic's waits for `evaluate`); samples with `lg_policy_act` on its
         output, so the draw for (seed, call, row) is the one `act_and_evaluate` makes.  The critic MLP of that launch runs on zeros, unused."""
         self._no_batch_mode(masks, hidden_states)
-        lib = self.actor.lib
         top = self.memory_a(observations)
-        n = top.shape[0]
-        idle = torch.zeros(n, self.critic.dims[0], device=self.device)
-        self._actions = torch.empty(n, self.num_actions, device=self.device)
-        self._mean = torch.empty(n, self.num_actions, device=self.device)
-        self._logp = torch.empty(n, device=self.device)
-        unused = torch.empty(n, self.critic.dims[-1], device=self.device)
-        self._call += 1
-        rc = lib.lg_policy_act(self.actor.handle, self.critic.handle, C.c_void_p(top.data_ptr()), C.c_void_p(idle.data_ptr()), n,
-                               C.c_void_p(self.std.data_ptr()), self.seed, self._call, 0, C.c_void_p(self._actions.data_ptr()),
-                               C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._logp.data_ptr()), C.c_void_p(unused.data_ptr()), self.actor._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_policy_act failed: " + (lib.lg_mlp_last_error(self.actor.handle) or b"").decode())
+        self._act(top, torch.zeros(top.shape[0], self.critic.dims[0], device=self.device), False, keep_values=False)
         return self._actions
 
     def act_inference(self, observations):
@@ -337,7 +355,7 @@ def _split_distillation_state(state_dict, student_state_dict):
     raise ValueError("state_dict does not contain student or teacher parameters")
 
 
-class NativeStudentTeacher:
+class NativeStudentTeacher(_GaussianPolicy):
     """Same surface as rsl_rl's `StudentTeacher` (`modules/student_teacher.py:75-152`) for collection with `Distillation` (`distillation.py:89-105`)
     and for `get_inference_policy`: `act`, `act_inference`, `evaluate`, `reset`, `get_hidden_states`, `action_mean`, `action_std`, `loaded_teacher`;
     `act_and_teach(obs, teacher_obs)` is `Distillation.act` as ONE launch (`lg_distill_act`).  Inference only: `Distillation.update` trains a torch
@@ -351,7 +369,7 @@ class NativeStudentTeacher:
         self.teacher = NativeMLP.from_sequential_state(tsd, tprefix, activation, device)
         self.student = NativeMLP.from_sequential_state(ssd, "student", activation, device)
         self.loaded_teacher = True
-        self.std = ssd["std"].detach().to(self.device, torch.float32).contiguous()
+        self._load_std(ssd)
         self.num_actions = self.student.dims[-1]
         if self.teacher.dims[-1] != self.num_actions:
             raise ValueError(f"the teacher ends in {self.teacher.dims[-1]} actions, the student in {self.num_actions}")
@@ -372,24 +390,16 @@ class NativeStudentTeacher:
         pass
 
     def _rows(self, n):
-        self._actions = torch.empty(n, self.num_actions, device=self.device)
-        self._mean = torch.empty(n, self.num_actions, device=self.device)
+        super()._rows(n)
         self._teacher_actions = torch.empty(n, self.num_actions, device=self.device)
-        self._call += 1
 
     def _launch(self, obs, tobs, deterministic=False):
-        lib = self.student.lib
         n = obs.shape[0]
         assert obs.shape == (n, self.student.dims[0]) and tobs.shape == (n, self.teacher.dims[0])
         self._rows(n)
-        rc = lib.lg_distill_act(self.student.handle, self.teacher.handle, C.c_void_p(obs.data_ptr()), C.c_void_p(tobs.data_ptr()), n,
-                                C.c_void_p(self.std.data_ptr()), self.seed, self._call, int(deterministic), C.c_void_p(self._actions.data_ptr()),
-                                C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._teacher_actions.data_ptr()), self.student._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_distill_act failed: " + (lib.lg_mlp_last_error(self.student.handle) or b"").decode())
-
-    def _f32(self, x):
-        return x.to(device=self.device, dtype=torch.float32).contiguous()
+        _check(self.student.lib.lg_distill_act(self.student.handle, self.teacher.handle, _ptr(obs), _ptr(tobs), n, _ptr(self.std), self.seed, self._call,
+                                               int(deterministic), _ptr(self._actions), _ptr(self._mean), _ptr(self._teacher_actions), self.student._stream()),
+               "lg_distill_act")
 
     def act_and_teach(self, obs, teacher_obs):
         """`Distillation.act` in one launch: (actions, privileged_actions)."""
@@ -407,18 +417,6 @@ class NativeStudentTeacher:
 
     def evaluate(self, teacher_observations):
         return self.teacher(teacher_observations)
-
-    @property
-    def action_mean(self):
-        return self._mean
-
-    @property
-    def action_std(self):
-        return self.std.expand_as(self._mean)
-
-    @property
-    def entropy(self):
-        return (0.5 + 0.9189385332046727 + torch.log(self.std)).sum().expand(self._mean.shape[0])
 
 
 class NativeStudentTeacherRecurrent(NativeStudentTeacher):
@@ -448,9 +446,7 @@ class NativeStudentTeacherRecurrent(NativeStudentTeacher):
             if mem is None:
                 continue
             if dones is None and h is not None:
-                parts = h if isinstance(h, (tuple, list)) else (h,)
-                mem.h = parts[0].detach().to(self.device, torch.float32).clone().contiguous()
-                mem.c = parts[1].detach().to(self.device, torch.float32).clone().contiguous() if mem.rnn_type == "lstm" else None
+                mem.set_state(h)
             else:
                 mem.reset(dones)
 
@@ -458,7 +454,6 @@ class NativeStudentTeacherRecurrent(NativeStudentTeacher):
         return self.memory_s.hidden_states, (self.memory_t.hidden_states if self.memory_t is not None else None)
 
     def _launch(self, obs, tobs, deterministic=False):
-        lib = self.student.lib
         n = obs.shape[0]
         mt = self.memory_t
         assert obs.shape == (n, self.memory_s.input_size) and tobs.shape == (n, mt.input_size if mt is not None else self.teacher.dims[0])
@@ -467,12 +462,10 @@ class NativeStudentTeacherRecurrent(NativeStudentTeacher):
             mt.ensure_state(n)
         self._rows(n)
         tptrs = mt._ptrs() if mt is not None else (None, None)
-        rc = lib.lg_distill_act_recurrent(self.memory_s.handle, self.student.handle, mt.handle if mt is not None else None, self.teacher.handle,
-                                          C.c_void_p(obs.data_ptr()), C.c_void_p(tobs.data_ptr()), n, C.c_void_p(self.std.data_ptr()), self.seed, self._call,
-                                          int(deterministic), *self.memory_s._ptrs(), *tptrs, None, C.c_void_p(self._actions.data_ptr()),
-                                          C.c_void_p(self._mean.data_ptr()), C.c_void_p(self._teacher_actions.data_ptr()), self.student._stream())
-        if rc != abi.LG_OK:
-            raise RuntimeError("lg_distill_act_recurrent failed: " + (lib.lg_mlp_last_error(self.student.handle) or b"").decode())
+        _check(self.student.lib.lg_distill_act_recurrent(self.memory_s.handle, self.student.handle, mt.handle if mt is not None else None, self.teacher.handle,
+                                                         _ptr(obs), _ptr(tobs), n, _ptr(self.std), self.seed, self._call, int(deterministic),
+                                                         *self.memory_s._ptrs(), *tptrs, None, _ptr(self._actions), _ptr(self._mean),
+                                                         _ptr(self._teacher_actions), self.student._stream()), "lg_distill_act_recurrent")
 
     def act(self, observations):
         """Advances the STUDENT memory only (the teacher's waits for `evaluate`), then samples with the feed-forward launch on its output."""

@@ -24,6 +24,9 @@ typedef struct lg_mlp lg_mlp;
 lg_mlp* lg_mlp_create(int32_t num_layers, const int32_t* dims, const float* const* weights, const float* const* biases,
                       int32_t activation, int device_id);
 void lg_mlp_destroy(lg_mlp* mlp);
+/* The error channel of EVERY entry point of this header: the calling thread's last message, the same whether `mlp` is a handle or NULL.
+ * Each non-zero status (and each NULL from a create function) leaves a message "<entry point the caller called>: <reason>" -- a failure
+ * inside a collector names the collector, not the act it ran.  The pointer stays valid until the thread's next failing call. */
 const char* lg_mlp_last_error(lg_mlp* mlp);
 
 /* y (n, dims[L]) = mlp(x (n, dims[0])): all layers in one launch, activations stay in LDS, fp32 MFMA
