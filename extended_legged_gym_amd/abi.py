@@ -365,6 +365,59 @@ def declare_policy(lib):
     return lib
 
 
+
+class lg_ppo_rows(C.Structure):
+    """include/lgtrain.h: device pointers to the flattened (R, .) rows of a rollout."""
+    _fields_ = [(k, C.c_void_p) for k in ("observations", "critic_observations", "actions", "values", "returns", "advantages", "actions_log_prob",
+                                          "mu", "sigma")]
+
+
+class lg_ppo_hyper(C.Structure):
+    """include/lgtrain.h: the hyper-parameters of one optimiser step."""
+    _fields_ = [("clip_param", f32), ("value_loss_coef", f32), ("entropy_coef", f32), ("use_clipped_value_loss", i32), ("max_grad_norm", f32),
+                ("schedule", i32), ("desired_kl", C.c_double)]
+
+
+class lg_ppo_stats(C.Structure):
+    """include/lgtrain.h: what an update reports (float64, device memory)."""
+    _fields_ = [(k, C.c_double) for k in ("value_function", "surrogate", "entropy", "kl", "learning_rate")]
+
+
+def declare_train(lib):
+    """Prototypes of the training entry points (include/lgtrain.h), same library."""
+    vp, fpp = C.c_void_p, C.POINTER(C.POINTER(f32))
+    lib.lg_ppo_create.argtypes = [vp, vp, fpp, fpp, fpp, fpp, vp, i32, C.c_double, C.c_int64, vp]
+    lib.lg_ppo_create.restype = vp
+    lib.lg_ppo_destroy.argtypes = [vp]
+    lib.lg_ppo_destroy.restype = None
+    lib.lg_ppo_minibatch.argtypes = [vp, C.POINTER(lg_ppo_rows), vp, C.c_int64, C.POINTER(lg_ppo_hyper), vp]
+    lib.lg_ppo_minibatch.restype = C.c_int
+    lib.lg_ppo_update.argtypes = [vp, C.POINTER(lg_ppo_rows), C.c_int64, vp, i32, i32, C.POINTER(lg_ppo_hyper), vp, vp]
+    lib.lg_ppo_update.restype = C.c_int
+    lib.lg_ppo_parameter_count.argtypes = [vp]
+    lib.lg_ppo_parameter_count.restype = C.c_int64
+    lib.lg_ppo_gradients.argtypes = [vp, vp, vp, vp, vp]
+    lib.lg_ppo_gradients.restype = C.c_int
+    lib.lg_ppo_forward_outputs.argtypes = [vp, vp, vp, vp]
+    lib.lg_ppo_forward_outputs.restype = C.c_int
+    lib.lg_ppo_get_parameters.argtypes = [vp, vp, vp]
+    lib.lg_ppo_get_parameters.restype = C.c_int
+    lib.lg_ppo_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), vp]
+    lib.lg_ppo_get_state.restype = C.c_int
+    lib.lg_ppo_set_state.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, vp]
+    lib.lg_ppo_set_state.restype = C.c_int
+    lib.lg_ppo_set_learning_rate.argtypes = [vp, C.c_double, vp]
+    lib.lg_ppo_set_learning_rate.restype = C.c_int
+    lib.lg_ppo_wgrad_slab_rows.argtypes = []
+    lib.lg_ppo_wgrad_slab_rows.restype = i32
+    return lib
+
+
+TRAIN_SYMBOLS = ["lg_ppo_create", "lg_ppo_destroy", "lg_ppo_minibatch", "lg_ppo_update", "lg_ppo_parameter_count", "lg_ppo_gradients",
+                 "lg_ppo_forward_outputs", "lg_ppo_get_parameters", "lg_ppo_get_state", "lg_ppo_set_state", "lg_ppo_set_learning_rate", "lg_ppo_wgrad_slab_rows"]
+NOISE_STD_TYPES = {"scalar": 0, "log": 1}          # enum lg_noise_std_type
+LR_SCHEDULES = {"fixed": 0, "adaptive": 1}          # enum lg_lr_schedule
+
 POLICY_SYMBOLS = ["lg_mlp_create", "lg_mlp_destroy", "lg_mlp_last_error", "lg_mlp_forward", "lg_policy_act", "lg_compute_returns",
                   "lg_collect_rollout", "lg_plan_from_nodes", "lg_mppi_update", "lg_mppi_sample_plans", "lg_planner_diffuse",
                   "lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",

@@ -27,30 +27,7 @@
 #include "../../include/lgpolicy.h"
 #include "../../include/lgstep.h"
 
-#define MLP_ROWS 32          // batch rows per workgroup
-#define MLP_THREADS 512      // eight waves: two per SIMD
-#define MLP_MAXW 512         // widest layer
-#define MLP_IMG (MLP_MAXW * MLP_ROWS)          // floats of one activation image
-// element (row m, input k) of the activation image
-#define IMG(m, k) (((((k) >> 4) * MLP_ROWS + (m)) * 4 + ((k) & 3)) * 4 + (((k) >> 2) & 3))
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct MlpDev {
-  int L, act;
-  int act_out;                       // != 0: the activation follows the last layer too (lg_mlp_set_output_activation); 0 for every network lg_mlp_create returns
-  int dims[LG_MLP_MAX_LAYERS + 1];
-  int kpad[LG_MLP_MAX_LAYERS];       // input width rounded up to 64 (four blocks of four k-steps of 4)
-  int nchunks[LG_MLP_MAX_LAYERS];    // output width rounded up to 16, / 16
-  const float* w[LG_MLP_MAX_LAYERS]; // tiled weights [chunk][k/16][lane][4]
-  const float* b[LG_MLP_MAX_LAYERS]; // bias, padded to 16 * nchunks
-};
-
-struct lg_mlp {
-  MlpDev h;
-  int device = 0;
-  std::vector<void*> allocs;
-};
 
 // ---- the one error channel and the create functions' plumbing (lg_policy_internal.h)
 thread_local const char* lg_policy_entry = nullptr;
@@ -79,21 +56,6 @@ const void* lg_policy_upload(const void* host, size_t bytes, std::vector<void*>&
   allocs.push_back(d);
   if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) { lg_policy_fail(LG_ERR_HIP, "weight upload failed"); return nullptr; }
   return d;
-}
-
-LG_DEV float apply_act(float x, int act) {
-  switch (act) {
-    case LG_ACT_ELU: {   // x > 0 ? x : expm1(x): the degree-6 Taylor polynomial for |x| < 0.25 (truncation < 5e-8 relative), exp(x) - 1
-                         // below that (fast exp: ~1e-7 absolute on a result of magnitude >= 0.22); libm's expm1f is ~30 instructions
-      const float p = x * (1.f + x * (0.5f + x * (1.f / 6 + x * (1.f / 24 + x * (1.f / 120 + x * (1.f / 720))))));
-      return x > 0.f ? x : (x > -0.25f ? p : __expf(x) - 1.f);
-    }
-    case LG_ACT_RELU: return fmaxf(x, 0.f);
-    case LG_ACT_TANH: return tanhf(x);
-    case LG_ACT_LRELU: return x > 0.f ? x : 0.01f * x;
-    case LG_ACT_SELU: return 1.0507009873554805f * (x > 0.f ? x : 1.6732632423543772f * expm1f(x));
-  }
-  return x;
 }
 
 // 32 rows of x through the whole network; result rows (width dims[L], <= 16 * nchunks) left in `yrows` / written to `y_global`

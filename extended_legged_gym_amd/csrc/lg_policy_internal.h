@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
+#include "lg_device.h"
 #include "../../include/lgpolicy.h"
 
 // The exported entry point the caller called: the first line of every entry point that can fail is POLICY_ENTRY.  Entry points call each other
@@ -32,3 +33,44 @@ int lg_policy_device_of(const void* p);
 
 void lg_mlp_widths(const lg_mlp* m, int* layers, int* in, int* out, int* device);
 void lg_rnn_widths(const lg_rnn* m, int* type, int* input, int* hidden, int* device);
+
+// ---- the network handle, shared with the trainer (lg_train.hip), which rewrites the device buffers of an lg_mlp in place
+#define MLP_ROWS 32          // batch rows per workgroup
+#define MLP_THREADS 512      // eight waves: two per SIMD
+#define MLP_MAXW 512         // widest layer
+#define MLP_IMG (MLP_MAXW * MLP_ROWS)          // floats of one activation image
+// element (row m, input k) of the activation image
+#define IMG(m, k) (((((k) >> 4) * MLP_ROWS + (m)) * 4 + ((k) & 3)) * 4 + (((k) >> 2) & 3))
+
+struct MlpDev {
+  int L, act;
+  int act_out;                       // != 0: the activation follows the last layer too (lg_mlp_set_output_activation); 0 for every network lg_mlp_create returns
+  int dims[LG_MLP_MAX_LAYERS + 1];
+  int kpad[LG_MLP_MAX_LAYERS];       // input width rounded up to 64 (four blocks of four k-steps of 4)
+  int nchunks[LG_MLP_MAX_LAYERS];    // output width rounded up to 16, / 16
+  const float* w[LG_MLP_MAX_LAYERS]; // tiled weights [chunk][k/16][lane][4]
+  const float* b[LG_MLP_MAX_LAYERS]; // bias, padded to 16 * nchunks
+};
+
+struct lg_mlp {
+  MlpDev h;
+  int device = 0;
+  std::vector<void*> allocs;
+};
+
+// the activations, shared so that the trainer's forward values are lg_mlp_forward's bit for bit
+LG_DEV float apply_act(float x, int act) {
+  switch (act) {
+    case LG_ACT_ELU: {   // x > 0 ? x : expm1(x): the degree-6 Taylor polynomial for |x| < 0.25 (truncation < 5e-8 relative), exp(x) - 1
+                         // below that (fast exp: ~1e-7 absolute on a result of magnitude >= 0.22); libm's expm1f is ~30 instructions
+      const float p = x * (1.f + x * (0.5f + x * (1.f / 6 + x * (1.f / 24 + x * (1.f / 120 + x * (1.f / 720))))));
+      return x > 0.f ? x : (x > -0.25f ? p : __expf(x) - 1.f);
+    }
+    case LG_ACT_RELU: return fmaxf(x, 0.f);
+    case LG_ACT_TANH: return tanhf(x);
+    case LG_ACT_LRELU: return x > 0.f ? x : 0.01f * x;
+    case LG_ACT_SELU: return 1.0507009873554805f * (x > 0.f ? x : 1.6732632423543772f * expm1f(x));
+  }
+  return x;
+}
+

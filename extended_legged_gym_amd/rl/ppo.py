@@ -1,0 +1,205 @@
+"""`NativePPO`: `PPO.update` of the vendored rsl_rl (`algorithms/ppo.py:197-438`, mini-batches as `storage/rollout_storage.py:184-243`) for a
+`NativeActorCritic`, on the library's training kernels (include/lgtrain.h): forward with saved activations, the clipped losses, backward, global
+grad-norm clipping and Adam on the device.  The weights stay on the device and are updated in place, in the tiled images `policy.act*` and
+`collect_rollout` read: collect -> update -> collect never returns to the host for parameters."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from extended_legged_gym_amd import abi
+from .policy import NativeActorCritic, _NativeHandle, _lib, _ptr
+
+
+def _train_lib():
+    lib = _lib()
+    if not getattr(lib, "_train_declared", False):
+        abi.declare_train(lib)
+        lib._train_declared = True
+    return lib
+
+
+def _sequential_layers(state_dict, prefix):
+    idx = sorted({int(k[len(prefix) + 1:].split(".")[0]) for k in state_dict if k.startswith(prefix + ".") and k.endswith(".weight")})
+    return idx, [(np.ascontiguousarray(state_dict[f"{prefix}.{i}.weight"].detach().cpu().numpy(), dtype=np.float32),
+                  np.ascontiguousarray(state_dict[f"{prefix}.{i}.bias"].detach().cpu().numpy(), dtype=np.float32)) for i in idx]
+
+
+class NativePPO(_NativeHandle):
+    """rsl_rl's `PPO` for a feed-forward `NativeActorCritic`, with its names and defaults.  `state_dict`: the `ActorCritic` state dict `policy` was
+    built from (`actor.*`, `critic.*`, `std` / `log_std`); it seeds the fp32 master parameters.  After `update`, the same `policy` object acts with
+    the new weights; nothing is rebuilt."""
+    _destroy = "lg_ppo_destroy"
+
+    def __init__(self, policy, state_dict, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.0,
+                 learning_rate=1e-3, schedule="fixed", desired_kl=0.01, max_grad_norm=1.0, use_clipped_value_loss=True, max_rows=None,
+                 normalize_advantage_per_mini_batch=False, rnd_cfg=None, symmetry_cfg=None, multi_gpu_cfg=None):
+        if getattr(policy, "is_recurrent", False):
+            raise NotImplementedError("recurrent policies (the masked batch mode of PPO.update) are not built in the native update")
+        if not isinstance(policy, NativeActorCritic):
+            raise TypeError("NativePPO trains a NativeActorCritic")
+        for name, value in (("normalize_advantage_per_mini_batch", normalize_advantage_per_mini_batch), ("rnd_cfg", rnd_cfg),
+                            ("symmetry_cfg", symmetry_cfg), ("multi_gpu_cfg", multi_gpu_cfg)):
+            if value:
+                raise NotImplementedError(f"{name} is not built in the native update")
+        if schedule not in abi.LR_SCHEDULES:
+            raise ValueError(f"Unknown schedule: {schedule}. Should be 'fixed' or 'adaptive'")
+        self._open(policy.device, "training")
+        self.lib = _train_lib()
+        self.policy = policy
+        self.num_learning_epochs, self.num_mini_batches = int(num_learning_epochs), int(num_mini_batches)
+        self.clip_param, self.value_loss_coef, self.entropy_coef = float(clip_param), float(value_loss_coef), float(entropy_coef)
+        self.schedule, self.desired_kl, self.max_grad_norm = schedule, float(desired_kl if desired_kl is not None else 0.0), float(max_grad_norm)
+        self.use_clipped_value_loss = bool(use_clipped_value_loss)
+        self.learning_rate = float(learning_rate)
+        self.max_rows = max_rows
+        self.std_key = "std" if policy.noise_std_type == "scalar" else "log_std"
+        self._aidx, self._alayers = _sequential_layers(state_dict, "actor")
+        self._cidx, self._clayers = _sequential_layers(state_dict, "critic")
+        self._std0 = np.ascontiguousarray(state_dict[self.std_key].detach().cpu().numpy(), dtype=np.float32)
+        self._shapes = ([(f"actor.{i}", w.shape) for i, (w, _) in zip(self._aidx, self._alayers)] +
+                        [(f"critic.{i}", w.shape) for i, (w, _) in zip(self._cidx, self._clayers)])
+        self.handle = None
+        self._stats = torch.zeros(5, dtype=torch.float64, device=self.device)
+        if max_rows is not None:
+            self._create(int(max_rows))
+
+    # ---- handle
+    def _create(self, max_rows):
+        fp = C.POINTER(C.c_float)
+
+        def lists(layers):
+            return ((fp * len(layers))(*[w.ctypes.data_as(fp) for w, _ in layers]), (fp * len(layers))(*[b.ctypes.data_as(fp) for _, b in layers]))
+        aw, ab = lists(self._alayers)
+        cw, cb = lists(self._clayers)
+        state = self.optimizer_state() if self.handle else None
+        self.close()
+        torch.cuda.synchronize(self.device)
+        self._created(self.lib.lg_ppo_create(self.policy.actor.handle, self.policy.critic.handle, aw, ab, cw, cb, self._std0.ctypes.data,
+                                             abi.NOISE_STD_TYPES[self.policy.noise_std_type], self.learning_rate, max_rows, _ptr(self.policy.std)),
+                      "lg_ppo_create")
+        self.max_rows = max_rows
+        self.num_parameters = int(self.lib.lg_ppo_parameter_count(self.handle))
+        if state is not None:
+            self.load_optimizer_state(state)
+
+    def _ensure(self, rows):
+        if self.handle is None or rows > self.max_rows:
+            self._create(rows)
+
+    def _hyper(self):
+        return abi.lg_ppo_hyper(self.clip_param, self.value_loss_coef, self.entropy_coef, int(self.use_clipped_value_loss), self.max_grad_norm,
+                                abi.LR_SCHEDULES[self.schedule], self.desired_kl)
+
+    def _rows(self, rollout):
+        """The flattened (R, .) views of a `collect_rollout` dict (or of already flat rows), kept alive by the returned list."""
+        def flat(*keys):
+            t = rollout[next(k for k in keys if k in rollout)]
+            t = t.to(device=self.device, dtype=torch.float32)
+            return t.reshape(-1, t.shape[-1]).contiguous()
+        keep = dict(observations=flat("observations"), critic_observations=flat("critic_observations", "privileged_observations", "observations"), actions=flat("actions"),
+                    values=flat("values"), returns=flat("returns"), advantages=flat("advantages"), actions_log_prob=flat("actions_log_prob"),
+                    mu=flat("mu"), sigma=flat("sigma"))
+        R = keep["observations"].shape[0]
+        assert keep["observations"].shape[1] == self.policy.actor.dims[0] and keep["critic_observations"].shape[1] == self.policy.critic.dims[0]
+        assert keep["actions"].shape == (R, self.policy.num_actions)
+        return abi.lg_ppo_rows(**{k: v.data_ptr() for k, v in keep.items()}), R, keep
+
+    # ---- training
+    def minibatch(self, rollout, indices):
+        """One optimiser step on the rows `indices` (int64) of the flattened rollout."""
+        rows, R, keep = self._rows(rollout)
+        idx = indices.to(device=self.device, dtype=torch.int64).contiguous()
+        self._ensure(idx.numel())
+        hyper = self._hyper()
+        self._check(self.lib.lg_ppo_minibatch(self.handle, C.byref(rows), _ptr(idx), idx.numel(), C.byref(hyper), self._stream()), "lg_ppo_minibatch")
+        del keep
+
+    def update(self, rollout, indices=None):
+        """`PPO.update` on the dict `collect_rollout` returns.  `indices`: the permutation of the R = T * N rows every epoch reuses
+        (`rollout_storage.py:189-217`); None draws `torch.randperm` on the device.  Returns the loss dict of `PPO.update`; `learning_rate` (and
+        `kl`) are refreshed by the one device-to-host copy at the end."""
+        rows, R, keep = self._rows(rollout)
+        if indices is None:
+            indices = torch.randperm(R, device=self.device)
+        idx = indices.to(device=self.device, dtype=torch.int64).contiguous()
+        assert idx.numel() >= (R // self.num_mini_batches) * self.num_mini_batches
+        self._ensure(max(R // self.num_mini_batches, 1))
+        hyper = self._hyper()
+        self._check(self.lib.lg_ppo_update(self.handle, C.byref(rows), R, _ptr(idx), self.num_mini_batches, self.num_learning_epochs, C.byref(hyper),
+                                           _ptr(self._stats), self._stream()), "lg_ppo_update")
+        st = self._stats.cpu().tolist()
+        del keep
+        self.learning_rate, self.kl = st[4], st[3]
+        return {"value_function": st[0], "surrogate": st[1], "entropy": st[2]}
+
+    def set_learning_rate(self, learning_rate):
+        self.learning_rate = float(learning_rate)
+        if self.handle:
+            self._check(self.lib.lg_ppo_set_learning_rate(self.handle, self.learning_rate, self._stream()), "lg_ppo_set_learning_rate")
+
+    # ---- what the device holds
+    def _need_handle(self):
+        if self.handle is None:
+            self._create(1)
+
+    def _split(self, flat):
+        """A flat parameter-shaped vector -> dict in the state dict's names."""
+        out, off = {}, 0
+        for name, (o, i) in self._shapes:
+            out[name + ".weight"] = torch.from_numpy(flat[off:off + o * i].reshape(o, i).copy()); off += o * i
+            out[name + ".bias"] = torch.from_numpy(flat[off:off + o].copy()); off += o
+        out[self.std_key] = torch.from_numpy(flat[off:].copy())
+        return out
+
+    def _join(self, tensors):
+        parts = []
+        for name, _ in self._shapes:
+            parts += [tensors[name + ".weight"].detach().cpu().numpy().reshape(-1), tensors[name + ".bias"].detach().cpu().numpy().reshape(-1)]
+        parts.append(tensors[self.std_key].detach().cpu().numpy().reshape(-1))
+        flat = np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+        assert flat.size == self.num_parameters
+        return flat
+
+    def gradients(self):
+        """The gradients of the last mini-batch before the norm clip (dict in the state dict's names), the global norm, and the four loss means
+        (surrogate, value_function, entropy, kl)."""
+        self._need_handle()
+        g, norm, means = np.empty(self.num_parameters, np.float32), C.c_float(), (C.c_float * 4)()
+        self._check(self.lib.lg_ppo_gradients(self.handle, g.ctypes.data, C.byref(norm), means, self._stream()), "lg_ppo_gradients")
+        return self._split(g), norm.value, dict(zip(("surrogate", "value_function", "entropy", "kl"), [float(x) for x in means]))
+
+    def forward_outputs(self, count):
+        """The action means (count, A) and values (count, 1) the last mini-batch's forward pass computed, in mini-batch order."""
+        self._need_handle()
+        mu, val = np.empty((count, self.policy.num_actions), np.float32), np.empty((count, 1), np.float32)
+        self._check(self.lib.lg_ppo_forward_outputs(self.handle, mu.ctypes.data, val.ctypes.data, self._stream()), "lg_ppo_forward_outputs")
+        return torch.from_numpy(mu), torch.from_numpy(val)
+
+    def state_dict(self):
+        """An `ActorCritic` state dict (`actor.*`, `critic.*`, `std` / `log_std`): rsl_rl and `NativeActorCritic(...)` both load it."""
+        self._need_handle()
+        flat = np.empty(self.num_parameters, np.float32)
+        self._check(self.lib.lg_ppo_get_parameters(self.handle, flat.ctypes.data, self._stream()), "lg_ppo_get_parameters")
+        return self._split(flat)
+
+    def optimizer_state(self):
+        """Masters, both Adam moments, the step count and the learning rate."""
+        self._need_handle()
+        bufs = [np.empty(self.num_parameters, np.float32) for _ in range(3)]
+        step, lr = C.c_int64(), C.c_double()
+        self._check(self.lib.lg_ppo_get_state(self.handle, *[b.ctypes.data for b in bufs], C.byref(step), C.byref(lr), self._stream()), "lg_ppo_get_state")
+        return dict(parameters=self._split(bufs[0]), exp_avg=self._split(bufs[1]), exp_avg_sq=self._split(bufs[2]), step=step.value, learning_rate=lr.value)
+
+    def load_optimizer_state(self, state):
+        self._need_handle()
+        bufs = [self._join(state[k]) for k in ("parameters", "exp_avg", "exp_avg_sq")]
+        self._check(self.lib.lg_ppo_set_state(self.handle, *[b.ctypes.data for b in bufs], int(state["step"]), float(state["learning_rate"]), self._stream()),
+                    "lg_ppo_set_state")
+        self.learning_rate = float(state["learning_rate"])
+
+    def load_state_dict(self, state_dict):
+        """New parameters (an `ActorCritic` state dict); the moments, the step count and the learning rate stay."""
+        state = self.optimizer_state()
+        state["parameters"] = state_dict
+        self.load_optimizer_state(state)

@@ -170,6 +170,8 @@ def main(argv=None):
     ap.add_argument("--task", default="anymal_c_flat", help="registered task (anymal_c_rough: terrain curriculum; use --no-play)")
     ap.add_argument("--stages", action="store_true", help="multi-stage tasks: switch reward stages like the reference's runner (default: stay in the first stage, as the acceptance records were made)")
     ap.add_argument("--set", action="append", default=[], metavar="section.key=value", help="override of the task's env config, e.g. rewards.reward_min_stage=0")
+    ap.add_argument("--update", choices=("torch", "native"), default="torch", help="torch: the eager restatement of PPO.update below (autograd, optim.Adam); "
+                    "native: rl.NativePPO, the update on the library's training kernels -- one NativeActorCritic + NativePPO for the whole run")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "train_acceptance.json"))
     a = ap.parse_args(argv)
     torch.manual_seed(a.seed); np.random.seed(a.seed)
@@ -193,6 +195,15 @@ def main(argv=None):
     opt = torch.optim.Adam(ac.parameters(), lr=alg["learning_rate"])
     lr = alg["learning_rate"]
     layered = hasattr(env, "_after_native")          # env classes with a layer around the native step: the collection loop runs in Python
+    nat = trainer = None
+    if a.update == "native":
+        if layered:
+            raise SystemExit("--update native needs the native collection loop (this env class has a Python layer around the step)")
+        from extended_legged_gym_amd.rl import NativePPO
+        nat = native_policy(ac, seed=a.seed * 1000)
+        trainer = NativePPO(nat, {k: v.detach() for k, v in ac.state_dict().items()}, **{k: alg[k] for k in (
+            "num_learning_epochs", "num_mini_batches", "clip_param", "value_loss_coef", "entropy_coef", "learning_rate", "schedule", "desired_kl",
+            "max_grad_norm", "use_clipped_value_loss")})
     env.reset()
     # OnPolicyRunner.learn(init_at_random_ep_len=True), on_policy_runner.py:358-361
     env.episode_length_buf[:] = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
@@ -202,6 +213,8 @@ def main(argv=None):
     for it in range(a.iters):
         if layered:
             data = collect_rollout_py(env, ac, T, alg["gamma"], alg["lam"])
+        elif trainer is not None:
+            data = collect_rollout(env, nat, T, gamma=alg["gamma"], lam=alg["lam"])
         else:
             nat = native_policy(ac, seed=a.seed * 1000 + it)
             data = collect_rollout(env, nat, T, gamma=alg["gamma"], lam=alg["lam"])
@@ -215,13 +228,18 @@ def main(argv=None):
                 retbuf += ep_ret[d].tolist(); lenbuf += ep_len[d].tolist()
                 ep_ret[d] = 0; ep_len[d] = 0
         retbuf, lenbuf = retbuf[-100:], lenbuf[-100:]
-        lr, st = ppo_update(ac, opt, data, alg, lr)
+        if trainer is not None:
+            loss = trainer.update(data)
+            lr, st = trainer.learning_rate, dict(value=loss["value_function"], surrogate=loss["surrogate"], kl=trainer.kl)
+        else:
+            lr, st = ppo_update(ac, opt, data, alg, lr)
         if a.stages and env.cfg.rewards.multi_stage_rewards and retbuf:       # (the runner's call, on_policy_runner.py:472: next reward stage once the mean return clears the threshold)
             env.update_reward_scales(float(np.mean(retbuf)))
         names = env.setup.reward_names
         ep = env.core.t["extras_episode"][:len(names)].cpu().numpy()
         row = dict(iter=it, mean_reward=float(np.mean(retbuf)) if retbuf else 0.0, mean_episode_length=float(np.mean(lenbuf)) if lenbuf else 0.0,
-                   mean_step_reward=float(rew.mean()), dones_per_env_step=float(dones.float().mean()), lr=lr, action_std=float(ac.std.mean()),
+                   mean_step_reward=float(rew.mean()), dones_per_env_step=float(dones.float().mean()), lr=lr,
+                   action_std=float(nat.std.mean() if trainer is not None else ac.std.mean()),
                    **{"rew_" + n: float(v) for n, v in zip(names, ep)}, **st)
         if layered:
             row.update({k: float(v) for k, v in env.extras["episode"].items() if k.startswith("rew_raibert")})
@@ -235,6 +253,8 @@ def main(argv=None):
     env_steps = a.iters * T * a.envs
     wall = time.time() - t0
     env.core.close()
+    if trainer is not None:
+        ac.load_state_dict({k: v.to("cuda") for k, v in trainer.state_dict().items()})
     # play both policies under play.py conditions
     ac.eval()
     home = physx = None
@@ -246,7 +266,7 @@ def main(argv=None):
         ref = NativeActorCritic(sd, activation="elu", device="cuda:0")
         physx = gait_statistics(lambda o: ref.act_inference(o))
     last = curve[-10:]
-    summary = dict(task=a.task, final_terrain_level=float(np.mean([r.get("terrain_level", 0.0) for r in last])), envs=a.envs, iterations=a.iters, env_steps=env_steps, wall_s=wall,
+    summary = dict(task=a.task, update=a.update, final_terrain_level=float(np.mean([r.get("terrain_level", 0.0) for r in last])), envs=a.envs, iterations=a.iters, env_steps=env_steps, wall_s=wall,
                    final_rew_tracking_lin_vel=float(np.mean([r.get("rew_tracking_lin_vel", 0.0) for r in last])),
                    final_mean_episode_length=float(np.mean([r["mean_episode_length"] for r in last])),
                    home_trained_play=home, physx_trained_play=physx)
