@@ -413,6 +413,53 @@ def declare_train(lib):
     return lib
 
 
+class lg_distill_train_hyper(C.Structure):
+    """include/lgdistill.h: the loss and the clip of one optimiser step (max_grad_norm <= 0: no clip)."""
+    _fields_ = [("loss_type", i32), ("max_grad_norm", f32)]
+
+
+class lg_distill_train_stats(C.Structure):
+    """include/lgdistill.h: what an update reports (float64, device memory)."""
+    _fields_ = [(k, C.c_double) for k in ("behavior", "optimizer_steps", "grad_norm")]
+
+
+def declare_distill_train(lib):
+    """Prototypes of the distillation trainer (include/lgdistill.h), same library."""
+    vp, fpp, i64 = C.c_void_p, C.POINTER(C.POINTER(f32)), C.c_int64
+    hp = C.POINTER(lg_distill_train_hyper)
+    lib.lg_distill_train_create.argtypes = [vp, fpp, fpp, C.c_double, i64]
+    lib.lg_distill_train_create.restype = vp
+    lib.lg_distill_train_destroy.argtypes = [vp]
+    lib.lg_distill_train_destroy.restype = None
+    lib.lg_distill_train_group.argtypes = [vp, vp, vp, i64, i64, i64, i64, hp, vp]
+    lib.lg_distill_train_group.restype = C.c_int
+    lib.lg_distill_train_update.argtypes = [vp, vp, vp, i64, i64, i32, i32, hp, vp, vp]
+    lib.lg_distill_train_update.restype = C.c_int
+    lib.lg_distill_train_parameter_count.argtypes = [vp]
+    lib.lg_distill_train_parameter_count.restype = i64
+    lib.lg_distill_train_gradients.argtypes = [vp, vp, vp, vp, i64, vp]
+    lib.lg_distill_train_gradients.restype = C.c_int
+    lib.lg_distill_train_forward_outputs.argtypes = [vp, vp, vp]
+    lib.lg_distill_train_forward_outputs.restype = C.c_int
+    lib.lg_distill_train_step_losses.argtypes = [vp, vp, i64, vp]
+    lib.lg_distill_train_step_losses.restype = C.c_int
+    lib.lg_distill_train_get_parameters.argtypes = [vp, vp, vp]
+    lib.lg_distill_train_get_parameters.restype = C.c_int
+    lib.lg_distill_train_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
+    lib.lg_distill_train_get_state.restype = C.c_int
+    lib.lg_distill_train_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
+    lib.lg_distill_train_set_state.restype = C.c_int
+    lib.lg_distill_train_set_learning_rate.argtypes = [vp, C.c_double, vp]
+    lib.lg_distill_train_set_learning_rate.restype = C.c_int
+    return lib
+
+
+DISTILL_TRAIN_SYMBOLS = ["lg_distill_train_create", "lg_distill_train_destroy", "lg_distill_train_group", "lg_distill_train_update",
+                         "lg_distill_train_parameter_count", "lg_distill_train_gradients", "lg_distill_train_forward_outputs",
+                         "lg_distill_train_step_losses", "lg_distill_train_get_parameters", "lg_distill_train_get_state",
+                         "lg_distill_train_set_state", "lg_distill_train_set_learning_rate"]
+DISTILL_LOSSES = {"mse": 0, "huber": 1}          # enum lg_distill_loss
+
 TRAIN_SYMBOLS = ["lg_ppo_create", "lg_ppo_destroy", "lg_ppo_minibatch", "lg_ppo_update", "lg_ppo_parameter_count", "lg_ppo_gradients",
                  "lg_ppo_forward_outputs", "lg_ppo_get_parameters", "lg_ppo_get_state", "lg_ppo_set_state", "lg_ppo_set_learning_rate", "lg_ppo_wgrad_slab_rows"]
 NOISE_STD_TYPES = {"scalar": 0, "log": 1}          # enum lg_noise_std_type

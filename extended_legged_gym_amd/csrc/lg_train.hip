@@ -25,58 +25,20 @@
 
 #include "lg_device.h"
 #include "lg_policy_internal.h"
+#include "lg_train_internal.h"
 #include "../../include/lgtrain.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#define WGRAD_SLAB 256        // batch rows per slab of the weight-gradient pass
 #define LOSS_ROWS 256         // rows per block of the loss kernel
 #define LOSS_SLOTS 36         // surrogate, value, (entropy), KL, then up to 32 sigma gradients
-#define TRAIN_MAX_SEGS (2 * LG_MLP_MAX_LAYERS)
 
-// one network as the forward and the backward tile see it
-struct TrainNet {
-  int L, act;
-  int dims[LG_MLP_MAX_LAYERS + 1];
-  int fkpad[LG_MLP_MAX_LAYERS], fnch[LG_MLP_MAX_LAYERS];   // forward tiling of layer l (the lg_mlp's): padded input width, 16-column chunks
-  int bkpad[LG_MLP_MAX_LAYERS], bnch[LG_MLP_MAX_LAYERS];   // transposed tiling of layer l: dims[l + 1] padded to 64, chunks of dims[l] padded to 64
-  const float* fw[LG_MLP_MAX_LAYERS];
-  const float* fb[LG_MLP_MAX_LAYERS];
-  const float* bw[LG_MLP_MAX_LAYERS];                      // layer 0 has none: nothing is propagated into the observations
-  float* a[LG_MLP_MAX_LAYERS + 1];                         // a[l] (rows, dims[l]): output of layer l - 1; a[L] is the network's output; a[0] unused
-  float* d[LG_MLP_MAX_LAYERS];                             // d[l] (rows, dims[l + 1]): dL / d(pre-activation output of layer l)
-};
-
-// one (network, layer) of the weight-gradient, reduce and Adam passes; element e of a segment is (o, i) = (e / (dI + 1), e % (dI + 1)), i == dI the bias
-struct TrainSeg {
-  int net, layer, dO, dI;
-  int f_nb, b_nb;                    // 16-input blocks per chunk of the forward / transposed tiling
-  int64_t woff, boff;                // offsets of W and b in the flat parameter vector
-  const float* D;                    // (rows, dO)
-  const float* Ain;                  // (rows, dI); NULL: the gathered observation rows
-  float* partial;                    // [slab][dO][dI + 1]
-  float* fw; float* fb; float* bw;
-};
-
-struct TrainScalars {
-  double lr;
-  double acc[4];                     // sums over an update's steps: value, surrogate, entropy, KL
-  float means[4];                    // last mini-batch: surrogate, value, entropy, KL
-  float norm, clip, step_size, bc2_sqrt;
-  int64_t step;
-};
-
-struct lg_ppo {
+// the networks, segments, masters and workspaces are the shared core's (lg_train_internal.h); nstd = A: std / log_std trails the flat vector
+struct lg_ppo : TrainCore {
   lg_mlp* actor = nullptr; lg_mlp* critic = nullptr;
-  int device = 0, A = 0, std_type = 0, nseg = 0;
-  int64_t max_rows = 0, P = 0, std_off = 0, last_rows = 0;
-  int loss_blocks = 0, red_blocks = 0, wgrad_blocks = 0;
-  TrainNet net[2];
-  TrainSeg seg[TRAIN_MAX_SEGS];
-  TrainSeg* d_seg = nullptr;
-  float *theta = nullptr, *m = nullptr, *v = nullptr, *G = nullptr, *loss_part = nullptr, *norm_part = nullptr, *std_dev = nullptr;
-  TrainScalars* sc = nullptr;
-  std::vector<void*> allocs;
+  int A = 0;
+  int loss_blocks = 0;
+  float* loss_part = nullptr;
 };
 
 LG_DEV float act_grad_from_output(float a, int act) {
@@ -340,15 +302,6 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const TrainSeg* __restri
       }
 }
 
-// fixed-order tree over the 256 lanes of a block
-LG_DEV float block_sum_256(float x, float* red) {
-  const int tid = threadIdx.x;
-  red[tid] = x;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) { if (tid < off) red[tid] += red[tid + off]; __syncthreads(); }
-  return red[0];
-}
-
 __global__ __launch_bounds__(256) void ppo_grad_reduce_kernel(const TrainSeg* __restrict__ segs, int nslabs, float* __restrict__ G, float* __restrict__ norm_part) {
   __shared__ float red[256];
   const TrainSeg S = segs[blockIdx.y];
@@ -365,7 +318,7 @@ __global__ __launch_bounds__(256) void ppo_grad_reduce_kernel(const TrainSeg* __
 }
 
 __global__ __launch_bounds__(256) void ppo_norm_finish_kernel(const float* __restrict__ norm_part, int count, const float* __restrict__ gstd, int A, float max_grad_norm,
-                                                              TrainScalars* __restrict__ sc) {
+                                                              int clip_on, TrainScalars* __restrict__ sc) {
   __shared__ float red[256];
   float s = 0.f;
   for (int i = threadIdx.x; i < count; i += 256) s += norm_part[i];
@@ -374,7 +327,7 @@ __global__ __launch_bounds__(256) void ppo_norm_finish_kernel(const float* __res
   if (threadIdx.x == 0) {
     const float norm = sqrtf(total);
     sc->norm = norm;
-    sc->clip = fminf(1.f, max_grad_norm / (norm + 1e-6f));                 // clip_grad_norm_
+    sc->clip = clip_on ? fminf(1.f, max_grad_norm / (norm + 1e-6f)) : 1.f;  // clip_grad_norm_; off: the gradient passes as it is
     const int64_t t = sc->step + 1;
     sc->step = t;
     sc->step_size = (float)(sc->lr / (1.0 - pow(0.9, (double)t)));         // torch.optim.Adam, defaults
@@ -428,7 +381,8 @@ __global__ void ppo_stats_kernel(TrainScalars* __restrict__ sc, lg_ppo_stats* __
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host side
-static void* train_alloc(lg_ppo* p, size_t bytes, bool zero) {
+// ---- what the trainers share (lg_train_internal.h)
+void* train_alloc(TrainCore* p, size_t bytes, bool zero) {
   void* d = nullptr;
   if (bytes == 0) bytes = 4;
   if (hipMalloc(&d, bytes) != hipSuccess) { lg_policy_fail(LG_ERR_HIP, "workspace allocation failed"); return nullptr; }
@@ -437,15 +391,140 @@ static void* train_alloc(lg_ppo* p, size_t bytes, bool zero) {
   return d;
 }
 
-static int train_retile(lg_ppo* p, hipStream_t st, bool step) {
-  int64_t big = p->A;
-  for (int s = 0; s < p->nseg; ++s) { const int64_t c = (int64_t)p->seg[s].dO * (p->seg[s].dI + 1); if (c > big) big = c; }
-  hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((big + 255) / 256), p->nseg + 1), dim3(256), 0, st, p->d_seg, p->nseg, p->std_off, p->A, p->std_type,
-                     p->std_dev, p->theta, p->m, p->v, p->G, p->sc, step ? 0 : 1);
+void train_core_free(TrainCore* c) {
+  for (void* d : c->allocs) (void)hipFree(d);
+  c->allocs.clear();
+}
+
+bool train_core_add_net(TrainCore* c, const lg_mlp* net, int64_t* off) {
+  bool ok = true;
+  auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(c, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
+  const int slabs_max = (int)((c->max_rows + WGRAD_SLAB - 1) / WGRAD_SLAB);
+  const int k = c->nnet++;
+  const MlpDev& h = net->h;
+  TrainNet& N = c->net[k];
+  N.L = h.L; N.act = h.act;
+  for (int l = 0; l <= h.L; ++l) N.dims[l] = h.dims[l];
+  N.a[0] = nullptr;
+  for (int l = 0; l < h.L; ++l) {
+    const int dI = h.dims[l], dO = h.dims[l + 1];
+    N.fkpad[l] = h.kpad[l]; N.fnch[l] = h.nchunks[l]; N.fw[l] = h.w[l]; N.fb[l] = h.b[l];
+    N.bkpad[l] = (dO + 63) & ~63; N.bnch[l] = ((dI + 63) & ~63) / 16;
+    N.bw[l] = l > 0 ? alloc((size_t)N.bnch[l] * (N.bkpad[l] / 16) * 64 * 4, true) : nullptr;
+    N.a[l + 1] = alloc((size_t)c->max_rows * dO, false);
+    N.d[l] = alloc((size_t)c->max_rows * dO, false);
+    TrainSeg& S = c->seg[c->nseg++];
+    S.net = k; S.layer = l; S.dO = dO; S.dI = dI; S.f_nb = h.kpad[l] / 16; S.b_nb = N.bkpad[l] / 16;
+    S.woff = *off; *off += (int64_t)dO * dI; S.boff = *off; *off += dO;
+    S.D = N.d[l]; S.Ain = l > 0 ? N.a[l] : nullptr;
+    S.partial = alloc((size_t)slabs_max * dO * (dI + 1), false);
+    S.fw = const_cast<float*>(h.w[l]); S.fb = const_cast<float*>(h.b[l]); S.bw = const_cast<float*>(N.bw[l]);
+    const int64_t cnt = (int64_t)dO * (dI + 1);
+    if (cnt > c->big) c->big = cnt;
+    const int tiles = ((dO + 31) / 32) * ((dI + 1 + 63) / 64);
+    if ((tiles + 3) / 4 > c->wgrad_blocks) c->wgrad_blocks = (tiles + 3) / 4;
+  }
+  return ok;
+}
+
+static int train_core_retile_or_step(TrainCore* p, hipStream_t st, bool step) {
+  hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((p->big + 255) / 256), p->nseg + (p->nstd > 0 ? 1 : 0)), dim3(256), 0, st, p->d_seg, p->nseg, p->std_off,
+                     p->nstd, p->std_type, p->std_dev, p->theta, p->m, p->v, p->G, p->sc, step ? 0 : 1);
   POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
 
+int train_core_retile(TrainCore* c, hipStream_t st) { return train_core_retile_or_step(c, st, false); }
+
+int train_core_finish(TrainCore* c, int64_t off, const float* const* const* ws, const float* const* const* bs, const float* tail, double learning_rate) {
+  bool ok = true;
+  auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(c, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
+  c->std_off = off; c->P = off + c->nstd;
+  if (c->nstd > c->big) c->big = c->nstd;
+  c->red_blocks = (int)((c->big + 255) / 256);
+  c->theta = alloc(c->P, false); c->m = alloc(c->P, true); c->v = alloc(c->P, true); c->G = alloc(c->P, true);
+  c->norm_part = alloc((size_t)c->red_blocks * c->nseg, true);
+  c->sc = ok ? (TrainScalars*)train_alloc(c, sizeof(TrainScalars), true) : nullptr;
+  c->d_seg = ok && c->sc ? (TrainSeg*)train_alloc(c, sizeof(TrainSeg) * TRAIN_MAX_SEGS, true) : nullptr;
+  if (!ok || !c->sc || !c->d_seg) return LG_ERR_HIP;
+  // the masters, in the flat order of the module's parameters()
+  std::vector<float> flat((size_t)c->P);
+  for (int s = 0; s < c->nseg; ++s) {
+    const TrainSeg& S = c->seg[s];
+    const float* w = ws[S.net][S.layer]; const float* b = bs[S.net][S.layer];
+    for (int64_t e = 0; e < (int64_t)S.dO * S.dI; ++e) flat[S.woff + e] = w[e];
+    for (int o = 0; o < S.dO; ++o) flat[S.boff + o] = b[o];
+  }
+  for (int a = 0; a < c->nstd; ++a) flat[c->std_off + a] = tail[a];
+  TrainScalars sc0{};
+  sc0.lr = learning_rate; sc0.clip = 1.f;
+  if (hipMemcpy(c->theta, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->d_seg, c->seg, sizeof(TrainSeg) * c->nseg, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->sc, &sc0, sizeof(sc0), hipMemcpyHostToDevice) != hipSuccess)
+    return lg_policy_fail(LG_ERR_HIP, "parameter upload failed");
+  const int rc = train_core_retile(c, nullptr);
+  if (rc != LG_OK) return rc;
+  POLICY_TRY(hipDeviceSynchronize());
+  return LG_OK;
+}
+
+void train_launch_forward(const TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, hipStream_t st) {
+  const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
+  hipLaunchKernelGGL(ppo_forward_kernel, dim3(tiles, c->nnet), dim3(MLP_THREADS), 0, st, c->net[0], c->net[c->nnet - 1], obs, cobs, idx, n);
+}
+
+void train_launch_backward(const TrainCore* c, int64_t n, hipStream_t st) {
+  const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
+  bool any = false;
+  for (int k = 0; k < c->nnet; ++k) any |= c->net[k].L > 1;
+  if (any) hipLaunchKernelGGL(ppo_backward_kernel, dim3(tiles, c->nnet), dim3(MLP_THREADS), 0, st, c->net[0], c->net[c->nnet - 1], n);
+}
+
+int train_launch_optimise(TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, float max_grad_norm, int clip_on, hipStream_t st) {
+  const int nslabs = (int)((n + WGRAD_SLAB - 1) / WGRAD_SLAB);
+  hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(c->wgrad_blocks, nslabs, c->nseg), dim3(256), 0, st, (const TrainSeg*)c->d_seg, obs, cobs, idx, n);
+  hipLaunchKernelGGL(ppo_grad_reduce_kernel, dim3(c->red_blocks, c->nseg), dim3(256), 0, st, (const TrainSeg*)c->d_seg, nslabs, c->G, c->norm_part);
+  hipLaunchKernelGGL(ppo_norm_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)c->norm_part, c->red_blocks * c->nseg, (const float*)(c->G + c->std_off), c->nstd,
+                     max_grad_norm, clip_on, c->sc);
+  return train_core_retile_or_step(c, st, true);
+}
+
+int train_core_get_state(TrainCore* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, hipStream_t st) {
+  POLICY_TRY(hipStreamSynchronize(st));
+  const size_t bytes = (size_t)p->P * sizeof(float);
+  if (params) POLICY_TRY(hipMemcpy(params, p->theta, bytes, hipMemcpyDeviceToHost));
+  if (exp_avg) POLICY_TRY(hipMemcpy(exp_avg, p->m, bytes, hipMemcpyDeviceToHost));
+  if (exp_avg_sq) POLICY_TRY(hipMemcpy(exp_avg_sq, p->v, bytes, hipMemcpyDeviceToHost));
+  TrainScalars sc;
+  POLICY_TRY(hipMemcpy(&sc, p->sc, sizeof(sc), hipMemcpyDeviceToHost));
+  if (step) *step = sc.step;
+  if (lr) *lr = sc.lr;
+  return LG_OK;
+}
+
+int train_core_set_state(TrainCore* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, hipStream_t st) {
+  POLICY_TRY(hipStreamSynchronize(st));
+  const size_t bytes = (size_t)p->P * sizeof(float);
+  POLICY_TRY(hipMemcpy(p->theta, params, bytes, hipMemcpyHostToDevice));
+  POLICY_TRY(hipMemcpy(p->m, exp_avg, bytes, hipMemcpyHostToDevice));
+  POLICY_TRY(hipMemcpy(p->v, exp_avg_sq, bytes, hipMemcpyHostToDevice));
+  TrainScalars sc;
+  POLICY_TRY(hipMemcpy(&sc, p->sc, sizeof(sc), hipMemcpyDeviceToHost));
+  sc.step = step; sc.lr = lr;
+  POLICY_TRY(hipMemcpy(p->sc, &sc, sizeof(sc), hipMemcpyHostToDevice));
+  const int rc = train_core_retile(p, st);
+  if (rc != LG_OK) return rc;
+  POLICY_TRY(hipStreamSynchronize(st));
+  return LG_OK;
+}
+
+int train_core_set_learning_rate(TrainCore* p, double lr, hipStream_t st) {
+  POLICY_TRY(hipStreamSynchronize(st));
+  POLICY_TRY(hipMemcpy(&p->sc->lr, &lr, sizeof(double), hipMemcpyHostToDevice));
+  return LG_OK;
+}
+
+// ---- PPO
 static int train_check_call(lg_ppo* p, const lg_ppo_rows* r, const int64_t* idx, const lg_ppo_hyper* h) {
   if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
   if (!r || !idx || !h) return lg_policy_fail(LG_ERR_INVALID, "null rows, indices or hyper-parameters");
@@ -457,20 +536,15 @@ static int train_check_call(lg_ppo* p, const lg_ppo_rows* r, const int64_t* idx,
 
 static int train_step(lg_ppo* p, const lg_ppo_rows* r, const int64_t* idx, int64_t n, const lg_ppo_hyper* h, hipStream_t st, int accumulate) {
   p->last_rows = n;
-  const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
-  const int loss_blocks = (int)((n + LOSS_ROWS - 1) / LOSS_ROWS), nslabs = (int)((n + WGRAD_SLAB - 1) / WGRAD_SLAB);
+  const int loss_blocks = (int)((n + LOSS_ROWS - 1) / LOSS_ROWS);
   const TrainNet &NA = p->net[0], &NC = p->net[1];
-  hipLaunchKernelGGL(ppo_forward_kernel, dim3(tiles, 2), dim3(MLP_THREADS), 0, st, NA, NC, r->observations, r->critic_observations, idx, n);
+  train_launch_forward(p, r->observations, r->critic_observations, idx, n, st);
   hipLaunchKernelGGL(ppo_loss_kernel, dim3(loss_blocks), dim3(LOSS_ROWS), 0, st, *r, idx, n, p->A, (const float*)NA.a[NA.L], (const float*)NC.a[NC.L],
                      (const float*)p->std_dev, *h, NA.d[NA.L - 1], NC.d[NC.L - 1], p->loss_part);
   hipLaunchKernelGGL(ppo_loss_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)p->loss_part, loss_blocks, p->A, (const float*)p->std_dev, p->std_type, *h,
                      p->G + p->std_off, p->sc, accumulate);
-  if (NA.L > 1 || NC.L > 1) hipLaunchKernelGGL(ppo_backward_kernel, dim3(tiles, 2), dim3(MLP_THREADS), 0, st, NA, NC, n);
-  hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(p->wgrad_blocks, nslabs, p->nseg), dim3(256), 0, st, (const TrainSeg*)p->d_seg, r->observations, r->critic_observations, idx, n);
-  hipLaunchKernelGGL(ppo_grad_reduce_kernel, dim3(p->red_blocks, p->nseg), dim3(256), 0, st, (const TrainSeg*)p->d_seg, nslabs, p->G, p->norm_part);
-  hipLaunchKernelGGL(ppo_norm_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)p->norm_part, p->red_blocks * p->nseg, (const float*)(p->G + p->std_off), p->A,
-                     h->max_grad_norm, p->sc);
-  return train_retile(p, st, true);
+  train_launch_backward(p, n, st);
+  return train_launch_optimise(p, r->observations, r->critic_observations, idx, n, h->max_grad_norm, 1, st);
 }
 
 extern "C" {
@@ -481,7 +555,7 @@ void lg_ppo_destroy(lg_ppo* p) {
   if (!p) return;
   DeviceScope ds_(p->device);
   (void)hipDeviceSynchronize();
-  for (void* d : p->allocs) (void)hipFree(d);
+  train_core_free(p);
   delete p;
 }
 
@@ -507,63 +581,13 @@ lg_ppo* lg_ppo_create(lg_mlp* actor, lg_mlp* critic, const float* const* aw, con
   DeviceScope ds_(actor->device);
   if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_ppo* p = new lg_ppo();
-  p->actor = actor; p->critic = critic; p->device = actor->device; p->A = actor->h.dims[actor->h.L]; p->std_type = noise_std_type; p->max_rows = max_rows;
-  p->std_dev = std_device;
-  bool ok = true;
-  auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(p, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
-  int64_t off = 0, big = p->A;
-  int wg = 1;
-  const int slabs_max = (int)((max_rows + WGRAD_SLAB - 1) / WGRAD_SLAB);
-  for (int k = 0; k < 2; ++k) {
-    const MlpDev& h = nets[k]->h;
-    TrainNet& N = p->net[k];
-    N.L = h.L; N.act = h.act;
-    for (int l = 0; l <= h.L; ++l) N.dims[l] = h.dims[l];
-    N.a[0] = nullptr;
-    for (int l = 0; l < h.L; ++l) {
-      const int dI = h.dims[l], dO = h.dims[l + 1];
-      N.fkpad[l] = h.kpad[l]; N.fnch[l] = h.nchunks[l]; N.fw[l] = h.w[l]; N.fb[l] = h.b[l];
-      N.bkpad[l] = (dO + 63) & ~63; N.bnch[l] = ((dI + 63) & ~63) / 16;
-      N.bw[l] = l > 0 ? alloc((size_t)N.bnch[l] * (N.bkpad[l] / 16) * 64 * 4, true) : nullptr;
-      N.a[l + 1] = alloc((size_t)max_rows * dO, false);
-      N.d[l] = alloc((size_t)max_rows * dO, false);
-      TrainSeg& S = p->seg[p->nseg++];
-      S.net = k; S.layer = l; S.dO = dO; S.dI = dI; S.f_nb = h.kpad[l] / 16; S.b_nb = N.bkpad[l] / 16;
-      S.woff = off; off += (int64_t)dO * dI; S.boff = off; off += dO;
-      S.D = N.d[l]; S.Ain = l > 0 ? N.a[l] : nullptr;
-      S.partial = alloc((size_t)slabs_max * dO * (dI + 1), false);
-      S.fw = const_cast<float*>(h.w[l]); S.fb = const_cast<float*>(h.b[l]); S.bw = const_cast<float*>(N.bw[l]);
-      const int64_t cnt = (int64_t)dO * (dI + 1);
-      if (cnt > big) big = cnt;
-      const int tiles = ((dO + 31) / 32) * ((dI + 1 + 63) / 64);
-      if ((tiles + 3) / 4 > wg) wg = (tiles + 3) / 4;
-    }
-  }
-  p->std_off = off; p->P = off + p->A;
-  p->wgrad_blocks = wg; p->red_blocks = (int)((big + 255) / 256); p->loss_blocks = (int)((max_rows + LOSS_ROWS - 1) / LOSS_ROWS);
-  p->theta = alloc(p->P, false); p->m = alloc(p->P, true); p->v = alloc(p->P, true); p->G = alloc(p->P, true);
-  p->loss_part = alloc((size_t)p->loss_blocks * LOSS_SLOTS, true);
-  p->norm_part = alloc((size_t)p->red_blocks * p->nseg, true);
-  p->sc = ok ? (TrainScalars*)train_alloc(p, sizeof(TrainScalars), true) : nullptr;
-  p->d_seg = ok && p->sc ? (TrainSeg*)train_alloc(p, sizeof(TrainSeg) * TRAIN_MAX_SEGS, true) : nullptr;
-  if (!ok || !p->sc || !p->d_seg) { lg_ppo_destroy(p); return nullptr; }
-  // the masters, in the flat order of ActorCritic.parameters()
-  std::vector<float> flat((size_t)p->P);
-  for (int s = 0; s < p->nseg; ++s) {
-    const TrainSeg& S = p->seg[s];
-    const float* w = ws[S.net][S.layer]; const float* b = bs[S.net][S.layer];
-    for (int64_t e = 0; e < (int64_t)S.dO * S.dI; ++e) flat[S.woff + e] = w[e];
-    for (int o = 0; o < S.dO; ++o) flat[S.boff + o] = b[o];
-  }
-  for (int a = 0; a < p->A; ++a) flat[p->std_off + a] = std_host[a];
-  TrainScalars sc0{};
-  sc0.lr = learning_rate; sc0.clip = 1.f;
-  if (hipMemcpy(p->theta, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(p->d_seg, p->seg, sizeof(TrainSeg) * p->nseg, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(p->sc, &sc0, sizeof(sc0), hipMemcpyHostToDevice) != hipSuccess) {
-    lg_policy_fail(LG_ERR_HIP, "parameter upload failed"); lg_ppo_destroy(p); return nullptr;
-  }
-  if (train_retile(p, nullptr, false) != LG_OK || hipDeviceSynchronize() != hipSuccess) { lg_ppo_destroy(p); return nullptr; }
+  p->actor = actor; p->critic = critic; p->device = actor->device; p->A = actor->h.dims[actor->h.L]; p->max_rows = max_rows;
+  p->nstd = p->A; p->std_type = noise_std_type; p->std_dev = std_device;
+  int64_t off = 0;
+  bool ok = train_core_add_net(p, actor, &off) && train_core_add_net(p, critic, &off);
+  p->loss_blocks = (int)((max_rows + LOSS_ROWS - 1) / LOSS_ROWS);
+  p->loss_part = ok ? (float*)train_alloc(p, (size_t)p->loss_blocks * LOSS_SLOTS * sizeof(float), true) : nullptr;
+  if (!ok || !p->loss_part || train_core_finish(p, off, ws, bs, std_host, learning_rate) != LG_OK) { lg_ppo_destroy(p); return nullptr; }
   return p;
 }
 
@@ -634,16 +658,7 @@ int lg_ppo_get_state(lg_ppo* p, float* params, float* exp_avg, float* exp_avg_sq
   POLICY_ENTRY;
   if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
   DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  const size_t bytes = (size_t)p->P * sizeof(float);
-  if (params) POLICY_TRY(hipMemcpy(params, p->theta, bytes, hipMemcpyDeviceToHost));
-  if (exp_avg) POLICY_TRY(hipMemcpy(exp_avg, p->m, bytes, hipMemcpyDeviceToHost));
-  if (exp_avg_sq) POLICY_TRY(hipMemcpy(exp_avg_sq, p->v, bytes, hipMemcpyDeviceToHost));
-  TrainScalars sc;
-  POLICY_TRY(hipMemcpy(&sc, p->sc, sizeof(sc), hipMemcpyDeviceToHost));
-  if (step) *step = sc.step;
-  if (lr) *lr = sc.lr;
-  return LG_OK;
+  return train_core_get_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
 }
 
 int lg_ppo_get_parameters(lg_ppo* p, float* params, void* stream) {
@@ -657,20 +672,7 @@ int lg_ppo_set_state(lg_ppo* p, const float* params, const float* exp_avg, const
   if (!p || !params || !exp_avg || !exp_avg_sq) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
   if (step < 0 || !(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "step < 0 or learning rate <= 0");
   DeviceScope ds_(p->device);
-  hipStream_t st = (hipStream_t)stream;
-  POLICY_TRY(hipStreamSynchronize(st));
-  const size_t bytes = (size_t)p->P * sizeof(float);
-  POLICY_TRY(hipMemcpy(p->theta, params, bytes, hipMemcpyHostToDevice));
-  POLICY_TRY(hipMemcpy(p->m, exp_avg, bytes, hipMemcpyHostToDevice));
-  POLICY_TRY(hipMemcpy(p->v, exp_avg_sq, bytes, hipMemcpyHostToDevice));
-  TrainScalars sc;
-  POLICY_TRY(hipMemcpy(&sc, p->sc, sizeof(sc), hipMemcpyDeviceToHost));
-  sc.step = step; sc.lr = lr;
-  POLICY_TRY(hipMemcpy(p->sc, &sc, sizeof(sc), hipMemcpyHostToDevice));
-  const int rc = train_retile(p, st, false);
-  if (rc != LG_OK) return rc;
-  POLICY_TRY(hipStreamSynchronize(st));
-  return LG_OK;
+  return train_core_set_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
 }
 
 int lg_ppo_set_learning_rate(lg_ppo* p, double lr, void* stream) {
@@ -678,9 +680,7 @@ int lg_ppo_set_learning_rate(lg_ppo* p, double lr, void* stream) {
   if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
   if (!(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0");
   DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  POLICY_TRY(hipMemcpy(&p->sc->lr, &lr, sizeof(double), hipMemcpyHostToDevice));
-  return LG_OK;
+  return train_core_set_learning_rate(p, lr, (hipStream_t)stream);
 }
 
 }  // extern "C"

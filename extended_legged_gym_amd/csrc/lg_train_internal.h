@@ -1,0 +1,92 @@
+// lg_train_internal.h — what the trainers share (lg_train.hip: PPO over two networks; lg_distill_train.hip: distillation over one): the
+// description of a network and of a (network, layer) segment as the kernels of lg_train.hip see them, the scalars the optimiser keeps on the
+// device, and the host calls that size the workspaces and launch those kernels.  The kernels themselves live in lg_train.hip only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <vector>
+#include "lg_device.h"
+#include "lg_policy_internal.h"
+
+#define WGRAD_SLAB 256        // batch rows per slab of the weight-gradient pass
+#define TRAIN_MAX_NETS 2
+#define TRAIN_MAX_SEGS (TRAIN_MAX_NETS * LG_MLP_MAX_LAYERS)
+
+// one network as the forward and the backward tile see it
+struct TrainNet {
+  int L, act;
+  int dims[LG_MLP_MAX_LAYERS + 1];
+  int fkpad[LG_MLP_MAX_LAYERS], fnch[LG_MLP_MAX_LAYERS];   // forward tiling of layer l (the lg_mlp's): padded input width, 16-column chunks
+  int bkpad[LG_MLP_MAX_LAYERS], bnch[LG_MLP_MAX_LAYERS];   // transposed tiling of layer l: dims[l + 1] padded to 64, chunks of dims[l] padded to 64
+  const float* fw[LG_MLP_MAX_LAYERS];
+  const float* fb[LG_MLP_MAX_LAYERS];
+  const float* bw[LG_MLP_MAX_LAYERS];                      // layer 0 has none: nothing is propagated into the observations
+  float* a[LG_MLP_MAX_LAYERS + 1];                         // a[l] (rows, dims[l]): output of layer l - 1; a[L] is the network's output; a[0] unused
+  float* d[LG_MLP_MAX_LAYERS];                             // d[l] (rows, dims[l + 1]): dL / d(pre-activation output of layer l)
+};
+
+// one (network, layer) of the weight-gradient, reduce and Adam passes; element e of a segment is (o, i) = (e / (dI + 1), e % (dI + 1)), i == dI the bias
+struct TrainSeg {
+  int net, layer, dO, dI;
+  int f_nb, b_nb;                    // 16-input blocks per chunk of the forward / transposed tiling
+  int64_t woff, boff;                // offsets of W and b in the flat parameter vector
+  const float* D;                    // (rows, dO)
+  const float* Ain;                  // (rows, dI); NULL: the gathered observation rows
+  float* partial;                    // [slab][dO][dI + 1]
+  float* fw; float* fb; float* bw;
+};
+
+struct TrainScalars {
+  double lr;
+  double acc[4];                     // sums over an update's steps: value, surrogate, entropy, KL
+  float means[4];                    // last mini-batch: surrogate, value, entropy, KL
+  float norm, clip, step_size, bc2_sqrt;
+  int64_t step;
+};
+
+// The networks, their segments, the masters with Adam's moments and the workspaces for up to max_rows rows.  The flat parameter vector is the
+// networks' tensors in order (W0, b0, W1, b1, ...) and then nstd trailing floats at std_off (PPO's std / log_std; none for distillation).
+struct TrainCore {
+  int device = 0, nnet = 0, nseg = 0;
+  int nstd = 0, std_type = 0;
+  int64_t max_rows = 0, P = 0, std_off = 0, last_rows = 0, big = 0;
+  int red_blocks = 0, wgrad_blocks = 1;
+  TrainNet net[TRAIN_MAX_NETS];
+  TrainSeg seg[TRAIN_MAX_SEGS];
+  TrainSeg* d_seg = nullptr;
+  float *theta = nullptr, *m = nullptr, *v = nullptr, *G = nullptr, *norm_part = nullptr, *std_dev = nullptr;
+  TrainScalars* sc = nullptr;
+  std::vector<void*> allocs;
+};
+
+// fixed-order tree over the 256 lanes of a block
+LG_DEV float block_sum_256(float x, float* red) {
+  const int tid = threadIdx.x;
+  red[tid] = x;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) { if (tid < off) red[tid] += red[tid + off]; __syncthreads(); }
+  return red[0];
+}
+
+// a device allocation the core owns (train_core_free releases it); NULL + message on failure
+void* train_alloc(TrainCore* c, size_t bytes, bool zero);
+// appends `net`: its transposed tilings, the activation / delta workspaces for c->max_rows rows, one segment per layer at offset *off of the flat
+// vector (advanced).  false + message on failure.
+bool train_core_add_net(TrainCore* c, const lg_mlp* net, int64_t* off);
+// after the networks: c->P = off + c->nstd; masters, moments, gradient, norm partials, scalars, the device copy of the segments; uploads the masters
+// from HOST weights / biases per network in torch's layout (+ tail: the nstd trailing floats) and writes every tiling from them.
+int train_core_finish(TrainCore* c, int64_t off, const float* const* const* weights, const float* const* const* biases, const float* tail, double learning_rate);
+void train_core_free(TrainCore* c);
+
+// forward with saved activations over the rows obs[idx[0 .. n)] (cobs: the second network's rows), and the backward data pass from d[L - 1]
+void train_launch_forward(const TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, hipStream_t st);
+void train_launch_backward(const TrainCore* c, int64_t n, hipStream_t st);
+// weight gradients by slabs, their reduction, the global norm (clip_on == 0: the norm is reported and the gradient passes unscaled), Adam and the
+// rewrite of the tilings.  idx must not be NULL.
+int train_launch_optimise(TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, float max_grad_norm, int clip_on, hipStream_t st);
+// the masters -> the tilings (and std_dev), without a step
+int train_core_retile(TrainCore* c, hipStream_t st);
+
+int train_core_get_state(TrainCore* c, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, hipStream_t st);
+int train_core_set_state(TrainCore* c, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, hipStream_t st);
+int train_core_set_learning_rate(TrainCore* c, double lr, hipStream_t st);

@@ -359,7 +359,7 @@ class NativeStudentTeacher(_GaussianPolicy):
     """Same surface as rsl_rl's `StudentTeacher` (`modules/student_teacher.py:75-152`) for collection with `Distillation` (`distillation.py:89-105`)
     and for `get_inference_policy`: `act`, `act_inference`, `evaluate`, `reset`, `get_hidden_states`, `action_mean`, `action_std`, `loaded_teacher`;
     `act_and_teach(obs, teacher_obs)` is `Distillation.act` as ONE launch (`lg_distill_act`).  Inference only: `Distillation.update` trains a torch
-    `StudentTeacher` whose state dict builds this object."""
+    `StudentTeacher` whose state dict builds this object, or `rl.NativeDistillation` moves this object's student in place."""
     is_recurrent = False
 
     def __init__(self, state_dict, student_state_dict=None, activation="elu", device="cuda:0", seed=0):

@@ -8,7 +8,11 @@ per call), with the hyper-parameters of `AnymalCRoughStudentCfgPPO` (`anymal_c_r
 of the native collector: with noise off the rows, and so the loss sequence, are equal.  `--eager-policy` (with `--python-loop`) also acts with the torch
 modules instead of the native policy kernels.
 
+`--update native`: the gradient step runs on the device too (`rl.NativeDistillation`, include/lgdistill.h); the `NativeStudentTeacher` is built once
+and never rebuilt, and the saved checkpoint is the trainer's `state_dict()`.  The default, `torch`, is the eager update above.
+
 usage: python tools/train_distill.py [--teacher train_acceptance_model.pt] [--out distill.json] [--iters 100] [--envs 4096] [--python-loop]
+                                     [--update {torch,native}]
 """
 import argparse
 import ast
@@ -85,9 +89,10 @@ def collect_python_loop(env, native, num_steps, eager=None):
     return {k: torch.stack(v) for k, v in rows.items()}
 
 
-def run(task="anymal_c_rough_student", envs=4096, iters=100, seed=1, teacher=None, python_loop=False, eager_policy=False, overrides=(), log=print):
+def run(task="anymal_c_rough_student", envs=4096, iters=100, seed=1, teacher=None, python_loop=False, eager_policy=False, overrides=(), log=print,
+        update="torch"):
     from extended_legged_gym_amd.envs import task_registry
-    from extended_legged_gym_amd.rl import NativeStudentTeacher, collect_distillation
+    from extended_legged_gym_amd.rl import NativeDistillation, NativeStudentTeacher, collect_distillation
     from extended_legged_gym_amd.utils.helpers import class_to_dict, get_args
     torch.manual_seed(seed); np.random.seed(seed)
     env_cfg, train_cfg = task_registry.get_cfgs(task)
@@ -109,6 +114,19 @@ def run(task="anymal_c_rough_student", envs=4096, iters=100, seed=1, teacher=Non
     opt = torch.optim.Adam(policy.parameters(), lr=alg["learning_rate"])
     env.reset()
     losses = []
+    if update == "native":
+        if eager_policy:
+            raise ValueError("--eager-policy acts with the torch modules, which --update native never refreshes")
+        sd = {k: v.detach().clone() for k, v in policy.state_dict().items()}
+        native = NativeStudentTeacher(sd, activation=pol["activation"], device="cuda:0", seed=seed)          # built once: the trainer moves its student in place
+        trainer = NativeDistillation(native, sd, num_learning_epochs=alg.get("num_learning_epochs", 1), gradient_length=alg["gradient_length"],
+                                     learning_rate=alg["learning_rate"], max_grad_norm=alg["max_grad_norm"], loss_type=alg.get("loss_type", "mse"))
+        for it in range(iters):
+            rows = collect_python_loop(env, native, T) if python_loop else collect_distillation(env, native, T)
+            losses.append(trainer.update(rows)["behavior"])
+            log(f"iteration {it}: behaviour loss {losses[-1]:.9g}  mean reward {float(rows['rewards'].mean()):.5f}  dones {int(rows['dones'].sum())}")
+        policy.load_state_dict({k: v.to("cuda:0") for k, v in trainer.state_dict().items()})          # the checkpoint: the trainer's state dict
+        return losses, policy
     for it in range(iters):
         # the native policy is rebuilt from the torch module's weights after every update (tools/train_acceptance.py does the same for PPO)
         native = NativeStudentTeacher(policy.state_dict(), activation=pol["activation"], device="cuda:0", seed=seed)
@@ -132,14 +150,15 @@ def main(argv=None):
     ap.add_argument("--python-loop", action="store_true", help="collect with env.step from Python (the checker of the native collector)")
     ap.add_argument("--eager-policy", action="store_true", help="with --python-loop: act with the torch modules, not the native policy kernels")
     ap.add_argument("--set", action="append", default=[], metavar="section.key=value", help="override of the task's env config, e.g. noise.add_noise=False")
+    ap.add_argument("--update", choices=("torch", "native"), default="torch", help="the gradient step: eager PyTorch, or rl.NativeDistillation on the device")
     ap.add_argument("--out", default=None, help="write the loss curve here (JSON) and the trained modules next to it (_model.pt)")
     a = ap.parse_args(argv)
-    losses, policy = run(a.task, a.envs, a.iters, a.seed, a.teacher, a.python_loop, a.eager_policy, a.set)
+    losses, policy = run(a.task, a.envs, a.iters, a.seed, a.teacher, a.python_loop, a.eager_policy, a.set, update=a.update)
     if not a.out:
         return
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
-        json.dump({"task": a.task, "envs": a.envs, "python_loop": a.python_loop, "behaviour_loss": losses}, f)
+        json.dump({"task": a.task, "envs": a.envs, "python_loop": a.python_loop, "update": a.update, "behaviour_loss": losses}, f)
     torch.save({"model_state_dict": policy.state_dict(), "iter": a.iters}, os.path.splitext(a.out)[0] + "_model.pt")
 
 
