@@ -172,6 +172,17 @@ def test_free_fall_com_accelerates_at_g_with_an_error_that_shrinks_with_dt():
     assert errs[0] < 0.2 and errs[1] < 0.6 * errs[0], errs
 
 
+def test_contact_forces_account_for_the_momentum_of_a_landing():
+    """The biped's momentum theorem (tests/test_cassie.py) for the hexapod: dropped limp from 0.5 m in its default pose; over 100 substeps the momentum changes
+    by the sum of (contact forces - m g) dt within 2 % of the weight's impulse."""
+    from tests import physics_known_answers as K
+    sc = K.scenario("elspider_air", 4, control="T", free=True)
+    sim = sc.sim("oracle")
+    dP, impulse, peak = K.landing_run(sim, sc)
+    sim.close()
+    K.check_landing(sc, dP, impulse, peak)
+
+
 def test_reference_policy_walks_on_the_oracle_physics():
     """CPU: the PhysX-trained hexapod policy on the oracle's physics, payload {-5, 0, +5} kg x friction {0.5, 1.0, 1.5} x three commands."""
     from oracle.oracle_lib import OracleEnv

@@ -211,6 +211,17 @@ def test_sliding_friction_decelerates_at_mu_g(solver):
     o.close()
 
 
+def test_contact_forces_account_for_the_momentum_of_a_landing():
+    """The biped's momentum theorem (tests/test_cassie.py) for the quadruped: dropped limp from 0.9 m in its default pose, feet, shanks and belly hitting the
+    plane; over 100 substeps the momentum changes by the sum of (contact forces - m g) dt within 2 % of the weight's impulse."""
+    from tests import physics_known_answers as K
+    sc = K.scenario("anymal_c", 4, control="T", free=True)
+    sim = sc.sim("oracle")
+    dP, impulse, peak = K.landing_run(sim, sc)
+    sim.close()
+    K.check_landing(sc, dP, impulse, peak)
+
+
 def test_terrain_surface_is_the_grid_triangulation():
     rows = cols = 40
     H = np.zeros((rows, cols), np.int16)
