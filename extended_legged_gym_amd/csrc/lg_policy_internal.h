@@ -61,8 +61,11 @@ struct lg_mlp {
 // the activations, shared so that the trainer's forward values are lg_mlp_forward's bit for bit
 LG_DEV float apply_act(float x, int act) {
   switch (act) {
-    case LG_ACT_ELU: {   // x > 0 ? x : expm1(x): the degree-6 Taylor polynomial for |x| < 0.25 (truncation < 5e-8 relative), exp(x) - 1
-                         // below that (fast exp: ~1e-7 absolute on a result of magnitude >= 0.22); libm's expm1f is ~30 instructions
+    case LG_ACT_ELU: {   // x > 0 ? x : expm1(x): the degree-6 Taylor polynomial for -0.25 < x < 0 (truncation x^7 / 5040 < 1.3e-8), exp(x) - 1
+                         // from -0.25 down (fast exp, on a result of magnitude >= 0.22); libm's expm1f is ~30 instructions.  Measured against
+                         // float64 on MI355X over 5232 points in [-30, 30] (tests/test_hip_policy_sweep.py): polynomial 2.2e-8 absolute
+                         // (1.0e-7 relative), exp branch 4.8e-8 absolute (6.9e-8 relative) -- torch's fp32 ELU on the CPU: 4.7e-8 --, and
+                         // monotone across the switch: the step from -0.25 to the next float is 3.0e-8 where float64 has 1.2e-8
       const float p = x * (1.f + x * (0.5f + x * (1.f / 6 + x * (1.f / 24 + x * (1.f / 120 + x * (1.f / 720))))));
       return x > 0.f ? x : (x > -0.25f ? p : __expf(x) - 1.f);
     }

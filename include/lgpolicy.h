@@ -44,7 +44,8 @@ int lg_policy_act(lg_mlp* actor, lg_mlp* critic, const float* obs, const float* 
 
 /* RolloutStorage.compute_returns (rollout_storage.py:145-167): GAE over T transitions of n envs, all (T, n) row-major f32
  * (dones: 0 / 1 as f32), last_values (n); writes returns and advantages (T, n); normalize != 0: advantages =
- * (adv - mean) / (std + 1e-8) with the unbiased std over all T*n entries (torch.std). */
+ * (adv - mean) / (std + 1e-8) with the unbiased std over all T*n entries (torch.std).  T*n = 1: the std of one entry is
+ * taken as 0 and the one advantage comes back as 0 (torch.std, and so the reference, gives NaN there); returns are not touched. */
 int lg_compute_returns(const float* rewards, const float* dones, const float* values, const float* last_values, int32_t T,
                        int64_t n, float gamma, float lam, int32_t normalize, float* returns, float* advantages, void* stream);
 

@@ -106,3 +106,18 @@ def mppi_sample_plans_oracle(mean, sigma_nodes, sigma_scale, phi, R, seed, call)
     sig = (np.float32(sigma_scale) * np.asarray(sigma_nodes, np.float32))[np.arange(K * A) // A]
     nodes = (np.repeat(mean.reshape(M, K * A), R, axis=0) + sig[None, :] * z).astype(np.float32).reshape(M * R, K, A)
     return nodes, plan_from_nodes_oracle(nodes, phi)
+
+
+def policy_act_draw(seed, call, rows, num_actions):
+    """The standard normals z (rows, num_actions) `policy_act_body` draws (csrc/lg_policy.hip; lg_policy_act and lg_distill_act): actions = mean + std z.
+    Philox counter (row lo, row hi, a >> 1, call_lo ^ call_hi * 0x9E3779B9), key = seed; the cos branch of Box-Muller for even a, the sin branch for odd.
+    fp32 where the kernel is fp32: the uniforms, the clamp of u1, the radius and the angle."""
+    r = np.arange(rows, dtype=np.uint64)[:, None]
+    a = np.arange(num_actions, dtype=np.uint64)[None, :]
+    c3 = (call & 0xFFFFFFFF) ^ ((((call >> 32) & 0xFFFFFFFF) * 0x9E3779B9) & 0xFFFFFFFF)
+    o = philox4x32_10(r & np.uint64(0xFFFFFFFF), r >> np.uint64(32), a >> np.uint64(1), np.uint64(c3), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    u1 = np.maximum((o[0] >> 8).astype(np.float32) * np.float32(1.0 / 16777216.0), np.float32(5.9604645e-8))
+    u2 = (o[1] >> 8).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    rad = np.sqrt(np.float32(-2.0) * np.log(u1))
+    ang = np.float32(6.28318530717958647692) * u2
+    return np.where((np.arange(num_actions) & 1)[None, :] == 1, rad * np.sin(ang), rad * np.cos(ang)).astype(np.float32)
