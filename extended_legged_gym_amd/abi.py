@@ -413,6 +413,53 @@ def declare_train(lib):
     return lib
 
 
+class lg_ppo_recurrent_params(C.Structure):
+    """include/lgtrain_recurrent.h: HOST parameters of an ActorCriticRecurrent in torch's layout, and the shapes they were taken from."""
+    _fields_ = ([(k, i32) for k in ("rnn_type", "num_layers", "input_a", "hidden_a", "input_c", "hidden_c")] +
+                [(k, C.POINTER(C.POINTER(f32))) for k in ("mem_a_w_ih", "mem_a_w_hh", "mem_a_b_ih", "mem_a_b_hh", "mem_c_w_ih", "mem_c_w_hh", "mem_c_b_ih",
+                                                         "mem_c_b_hh", "actor_weights", "actor_biases", "critic_weights", "critic_biases")] +
+                [("std", C.c_void_p)])
+
+
+def declare_train_recurrent(lib):
+    """Prototypes of the recurrent PPO trainer (include/lgtrain_recurrent.h), same library."""
+    vp, i64 = C.c_void_p, C.c_int64
+    rows, hid, hyp = C.POINTER(lg_ppo_rows), C.POINTER(lg_rollout_hidden), C.POINTER(lg_ppo_hyper)
+    lib.lg_ppo_recurrent_create.argtypes = [vp, vp, vp, vp, C.POINTER(lg_ppo_recurrent_params), i32, C.c_double, i64, vp]
+    lib.lg_ppo_recurrent_create.restype = vp
+    lib.lg_ppo_recurrent_destroy.argtypes = [vp]
+    lib.lg_ppo_recurrent_destroy.restype = None
+    lib.lg_ppo_recurrent_minibatch.argtypes = [vp, rows, hid, vp, i32, i64, i64, i64, hyp, vp]
+    lib.lg_ppo_recurrent_minibatch.restype = C.c_int
+    lib.lg_ppo_recurrent_update.argtypes = [vp, rows, hid, vp, i32, i64, i32, i32, hyp, vp, vp]
+    lib.lg_ppo_recurrent_update.restype = C.c_int
+    lib.lg_ppo_recurrent_parameter_count.argtypes = [vp]
+    lib.lg_ppo_recurrent_parameter_count.restype = i64
+    lib.lg_ppo_recurrent_workspace_bytes.argtypes = [vp]
+    lib.lg_ppo_recurrent_workspace_bytes.restype = i64
+    lib.lg_ppo_recurrent_gradients.argtypes = [vp, vp, vp, vp, vp]
+    lib.lg_ppo_recurrent_gradients.restype = C.c_int
+    lib.lg_ppo_recurrent_forward_outputs.argtypes = [vp, vp, vp, vp]
+    lib.lg_ppo_recurrent_forward_outputs.restype = C.c_int
+    lib.lg_ppo_recurrent_get_parameters.argtypes = [vp, vp, vp]
+    lib.lg_ppo_recurrent_get_parameters.restype = C.c_int
+    lib.lg_ppo_recurrent_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
+    lib.lg_ppo_recurrent_get_state.restype = C.c_int
+    lib.lg_ppo_recurrent_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
+    lib.lg_ppo_recurrent_set_state.restype = C.c_int
+    lib.lg_ppo_recurrent_set_learning_rate.argtypes = [vp, C.c_double, vp]
+    lib.lg_ppo_recurrent_set_learning_rate.restype = C.c_int
+    lib.lg_ppo_recurrent_get_images.argtypes = [vp, i32, i32, vp, vp, vp]
+    lib.lg_ppo_recurrent_get_images.restype = C.c_int
+    return lib
+
+
+TRAIN_RECURRENT_SYMBOLS = ["lg_ppo_recurrent_create", "lg_ppo_recurrent_destroy", "lg_ppo_recurrent_minibatch", "lg_ppo_recurrent_update",
+                           "lg_ppo_recurrent_parameter_count", "lg_ppo_recurrent_workspace_bytes", "lg_ppo_recurrent_gradients",
+                           "lg_ppo_recurrent_forward_outputs", "lg_ppo_recurrent_get_parameters", "lg_ppo_recurrent_get_state",
+                           "lg_ppo_recurrent_set_state", "lg_ppo_recurrent_set_learning_rate", "lg_ppo_recurrent_get_images"]
+
+
 class lg_distill_train_hyper(C.Structure):
     """include/lgdistill.h: the loss and the clip of one optimiser step (max_grad_norm <= 0: no clip)."""
     _fields_ = [("loss_type", i32), ("max_grad_norm", f32)]

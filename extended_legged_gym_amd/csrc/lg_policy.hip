@@ -24,10 +24,9 @@
 
 #include "lg_device.h"
 #include "lg_policy_internal.h"
+#include "lg_rnn_tile.h"
 #include "../../include/lgpolicy.h"
 #include "../../include/lgstep.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- the one error channel and the create functions' plumbing (lg_policy_internal.h)
 thread_local const char* lg_policy_entry = nullptr;
@@ -374,161 +373,18 @@ __global__ __launch_bounds__(256) void fill_sigma_kernel(int64_t rows, int A, co
 // fragments of one gate for a block of 16 inputs with one coalesced dwordx4; the fragments of the next block are requested before
 // the MFMAs of the current one.
 // LDS: 32 rows x 1024 floats = 128 KB (input 512 + hidden 512, the widest allowed), static; nothing else is staged.
-#define RNN_KMAX 1024        // widest concatenated row: 512 inputs + 512 hidden, each padded to 16
-#define RNN_MAX_LAYERS 4
-
-struct RnnLayerDev {
-  int gru, I, H, Ip, nbx, nb, nch;   // Ip: x padded to 16; nbx = Ip / 16 blocks of x, nb blocks of [x ; h]; nch chunks of 16 hidden units
-  const float* w;                    // tiled [chunk][block][gate][lane][4]
-  const float* b;                    // [4][16 * nch]: LSTM b_ih + b_hh of i f g o; GRU (b_ir + b_hr), (b_iz + b_hz), b_in, b_hn
-};
-
-struct RnnStepArgs {                 // one memory's operands of a layer step (device pointers)
-  RnnLayerDev L;
-  const float* x;                    // (n, I): the observation, or the h' of the layer below
-  float* h;                          // (n, H) of this layer, updated in place
-  float* c;                          // (n, H) or null (GRU)
-  const float* reset;                // (n) or null
-  float* out;                        // (n, H) or null: a copy of h'
-};
-
-struct lg_rnn {
-  int type = 0, num_layers = 0, input = 0, hidden = 0, device = 0;
-  RnnLayerDev layer[RNN_MAX_LAYERS];
-  std::vector<void*> allocs;
-};
+// RnnLayerDev and struct lg_rnn: lg_policy_internal.h (the trainer reaches the images); the tile itself: lg_rnn_tile.h (SAVE = false here)
 
 void lg_mlp_widths(const lg_mlp* m, int* layers, int* in, int* out, int* device) { *layers = m->h.L; *in = m->h.dims[0]; *out = m->h.dims[m->h.L]; *device = m->device; }
 void lg_rnn_widths(const lg_rnn* m, int* type, int* input, int* hidden, int* device) { *type = m->type; *input = m->input; *hidden = m->hidden; *device = m->device; }
-
-LG_DEV float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
-
-// blocks [kb0, kb1) of a chunk: G gate fragments per block; gate 2 of a GRU accumulates into acc[NSLOT] (2: x part, 3: h part).
-// Two fragment sets: the loads of the next block are issued before the 8 G MFMAs of the current one (sched_barrier pins that order, as in
-// MLP_BLOCK), so the wait in front of a block's first MFMA is for loads issued a whole block earlier.
-template <int G>
-struct RnnFrag { float4 w[G], a0, a1; };
-template <int G>
-LG_DEV void rnn_load(RnnFrag<G>& f, const float4* __restrict__ wc, const float4* ap, int kb) {
-#pragma unroll
-  for (int g = 0; g < G; ++g) f.w[g] = wc[((size_t)kb * G + g) * 64];
-  f.a0 = ap[kb * 128]; f.a1 = ap[kb * 128 + 64];
-}
-template <int G, int NSLOT>
-LG_DEV void rnn_mfma(f32x4 (&acc)[4][2], const RnnFrag<G>& f) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float x0 = s == 0 ? f.a0.x : s == 1 ? f.a0.y : s == 2 ? f.a0.z : f.a0.w;
-    const float x1 = s == 0 ? f.a1.x : s == 1 ? f.a1.y : s == 2 ? f.a1.z : f.a1.w;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float wv = s == 0 ? f.w[g].x : s == 1 ? f.w[g].y : s == 2 ? f.w[g].z : f.w[g].w;
-      const int slot = (G == 3 && g == 2) ? NSLOT : g;
-      acc[slot][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0, wv, acc[slot][0], 0, 0, 0);
-      acc[slot][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1, wv, acc[slot][1], 0, 0, 0);
-    }
-  }
-}
-template <int G, int NSLOT>
-LG_DEV void rnn_blocks(f32x4 (&acc)[4][2], const float4* __restrict__ wc, const float4* ap, int kb0, int kb1, int kzero) {
-  if (kb0 >= kb1) return;
-  RnnFrag<G> f0, f1;
-  rnn_load<G>(f0, wc, ap, kb0);
-  for (int kb = kb0; kb < kb1; kb += 2) {
-    // an odd count's second half multiplies the chunk's all-zero weight block (kzero): no branch around the MFMAs, so the loads stay where they are
-    const bool two = kb + 1 < kb1, more = kb + 2 < kb1;
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < G; ++g) f1.w[g] = wc[((size_t)(two ? kb + 1 : kzero) * G + g) * 64];
-    f1.a0 = ap[(two ? kb + 1 : kb) * 128]; f1.a1 = ap[(two ? kb + 1 : kb) * 128 + 64];
-    __builtin_amdgcn_sched_barrier(0);
-    rnn_mfma<G, NSLOT>(acc, f0);
-    __builtin_amdgcn_sched_barrier(0);
-    rnn_load<G>(f0, wc, ap, more ? kb + 2 : kb);             // past the end: an in-bounds block, unused
-    __builtin_amdgcn_sched_barrier(0);
-    rnn_mfma<G, NSLOT>(acc, f1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-template <bool GRU>
-LG_DEV void rnn_tile(const RnnStepArgs& S, int64_t row0, int64_t n, float* img) {
-  const RnnLayerDev& R = S.L;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int I = R.I, H = R.H, Ip = R.Ip, Kp = R.nb * 16;
-  // stage [x ; h] of this workgroup's 32 rows.  The workgroup owns WHOLE rows and reads every h it will need here, before the barrier; h'
-  // (and c') are stored only after it, and no other workgroup touches these rows: the state is updated in place without a second buffer.
-  // A row whose reset flag is set enters with h = 0 (and c = 0 in the epilogue): Memory.reset(dones), memory.py:35-51, folded into the step.
-  for (int base = 0; base < MLP_ROWS * Kp; base += 8 * MLP_THREADS) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int idx = base + u * MLP_THREADS + tid, r = idx / Kp, k = idx - r * Kp;
-      const int64_t row = row0 + r;
-      float val = 0.f;
-      if (idx < MLP_ROWS * Kp && row < n) {
-        if (k < I) val = S.x[row * I + k];
-        else if (k >= Ip && k < Ip + H) val = (S.reset && S.reset[row] != 0.f) ? 0.f : S.h[row * H + (k - Ip)];
-      }
-      v[u] = val;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int idx = base + u * MLP_THREADS + tid, r = idx / Kp, k = idx - r * Kp;
-      if (idx < MLP_ROWS * Kp) img[IMG(r, k)] = v[u];
-    }
-  }
-  lds_barrier();
-  constexpr int G = GRU ? 3 : 4;
-  const float4* ap = reinterpret_cast<const float4*>(img) + (lane & 15) * 4 + (lane >> 4);
-  const int Hp = 16 * R.nch;
-  for (int c = wv; c < R.nch; c += MLP_THREADS / 64) {
-    f32x4 acc[4][2];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) { acc[g][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[g][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    const float4* wc = reinterpret_cast<const float4*>(R.w) + (size_t)c * (R.nb + 1) * G * 64 + lane;
-    if (GRU) {
-      rnn_blocks<G, 2>(acc, wc, ap, 0, R.nbx, R.nb);
-      rnn_blocks<G, 3>(acc, wc, ap, R.nbx, R.nb, R.nb);
-    } else {
-      rnn_blocks<G, 2>(acc, wc, ap, 0, R.nb, R.nb);
-    }
-    const int col = c * 16 + (lane & 15);
-    const float b0 = R.b[col], b1 = R.b[Hp + col], b2 = R.b[2 * Hp + col], b3 = R.b[3 * Hp + col];
-    // epilogue: C[m = 4 * (lane >> 4) + i (+ 16)][col]
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = 4 * (lane >> 4) + i + 16 * hf;
-        const int64_t row = row0 + m;
-        if (col >= H || row >= n) continue;
-        float hn;
-        if (GRU) {
-          const float r = sigmoidf_(acc[0][hf][i] + b0), z = sigmoidf_(acc[1][hf][i] + b1);
-          const float ng = tanhf((acc[2][hf][i] + b2) + r * (acc[3][hf][i] + b3));
-          const float hold = img[IMG(m, Ip + col)];                 // the h this step used (after the reset mask)
-          hn = (1.f - z) * ng + z * hold;
-        } else {
-          const float ig = sigmoidf_(acc[0][hf][i] + b0), fg = sigmoidf_(acc[1][hf][i] + b1);
-          const float gg = tanhf(acc[2][hf][i] + b2), og = sigmoidf_(acc[3][hf][i] + b3);
-          const float cold = (S.reset && S.reset[row] != 0.f) ? 0.f : S.c[row * H + col];
-          const float cn = fg * cold + ig * gg;
-          S.c[row * H + col] = cn;
-          hn = og * tanhf(cn);
-        }
-        S.h[row * H + col] = hn;
-        if (S.out) S.out[row * H + col] = hn;
-      }
-  }
-}
 
 // blockIdx.y picks the memory (0: the actor's or the only one, 1: the critic's)
 __global__ __launch_bounds__(MLP_THREADS) void rnn_layer_kernel(RnnStepArgs S0, RnnStepArgs S1, int64_t n) {
   __shared__ __attribute__((aligned(16))) float img[MLP_ROWS * RNN_KMAX];
   const RnnStepArgs& S = blockIdx.y == 0 ? S0 : S1;
   const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
-  if (S.L.gru) rnn_tile<true>(S, row0, n, img); else rnn_tile<false>(S, row0, n, img);
+  const RnnSaveArgs none{};
+  if (S.L.gru) rnn_tile<true, false>(S, none, row0, n, img); else rnn_tile<false, false>(S, none, row0, n, img);
 }
 
 // Memory.reset(dones) (memory.py:45-51): hidden_state[..., dones == 1, :] = 0 on every layer

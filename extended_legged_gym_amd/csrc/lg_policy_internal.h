@@ -77,3 +77,18 @@ LG_DEV float apply_act(float x, int act) {
   return x;
 }
 
+// ---- the memory handle, shared with the recurrent trainer (lg_train_recurrent.hip), which rewrites the device images of an lg_rnn in place
+#define RNN_KMAX 1024        // widest concatenated row: 512 inputs + 512 hidden, each padded to 16
+#define RNN_MAX_LAYERS 4
+
+struct RnnLayerDev {
+  int gru, I, H, Ip, nbx, nb, nch;   // Ip: x padded to 16; nbx = Ip / 16 blocks of x, nb blocks of [x ; h]; nch chunks of 16 hidden units
+  const float* w;                    // tiled [chunk][block][gate][lane][4]
+  const float* b;                    // [4][16 * nch]: LSTM b_ih + b_hh of i f g o; GRU (b_ir + b_hr), (b_iz + b_hz), b_in, b_hn
+};
+
+struct lg_rnn {
+  int type = 0, num_layers = 0, input = 0, hidden = 0, device = 0;
+  RnnLayerDev layer[RNN_MAX_LAYERS];
+  std::vector<void*> allocs;
+};

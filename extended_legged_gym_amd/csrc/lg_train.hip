@@ -365,9 +365,9 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(const TrainSeg* __restric
     theta[flat] = th;
   }
   if (is_std) { std_dev[e] = std_type == LG_STD_LOG ? expf(th) : th; return; }
-  if (i == S.dI) { S.fb[o] = th; return; }
+  if (i == S.dI) { if (S.fb) S.fb[o] = th; return; }
   // forward tiling: chunk o / 16, block i / 16, lane (o % 16) + 16 (i % 4), slot (i / 4) % 4 (lg_mlp_create)
-  S.fw[((((size_t)(o >> 4) * S.f_nb + (i >> 4)) * 64) + ((o & 15) | ((i & 3) << 4))) * 4 + ((i >> 2) & 3)] = th;
+  if (S.fw) S.fw[((((size_t)(o >> 4) * S.f_nb + (i >> 4)) * 64) + ((o & 15) | ((i & 3) << 4))) * 4 + ((i >> 2) & 3)] = th;
   // transposed tiling: the same with o and i exchanged
   if (S.bw) S.bw[((((size_t)(i >> 4) * S.b_nb + (o >> 4)) * 64) + ((i & 15) | ((o & 3) << 4))) * 4 + ((o >> 2) & 3)] = th;
 }
@@ -522,6 +522,21 @@ int train_core_set_learning_rate(TrainCore* p, double lr, hipStream_t st) {
   POLICY_TRY(hipStreamSynchronize(st));
   POLICY_TRY(hipMemcpy(&p->sc->lr, &lr, sizeof(double), hipMemcpyHostToDevice));
   return LG_OK;
+}
+
+size_t train_ppo_loss_floats(int64_t max_rows) { return (size_t)((max_rows + LOSS_ROWS - 1) / LOSS_ROWS) * LOSS_SLOTS; }
+
+void train_launch_ppo_loss(TrainCore* p, const lg_ppo_rows* r, const int64_t* idx, int64_t n, const lg_ppo_hyper* h, float* loss_part, int accumulate, hipStream_t st) {
+  const int loss_blocks = (int)((n + LOSS_ROWS - 1) / LOSS_ROWS);
+  const TrainNet &NA = p->net[0], &NC = p->net[1];
+  hipLaunchKernelGGL(ppo_loss_kernel, dim3(loss_blocks), dim3(LOSS_ROWS), 0, st, *r, idx, n, p->nstd, (const float*)NA.a[NA.L], (const float*)NC.a[NC.L],
+                     (const float*)p->std_dev, *h, NA.d[NA.L - 1], NC.d[NC.L - 1], loss_part);
+  hipLaunchKernelGGL(ppo_loss_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)loss_part, loss_blocks, p->nstd, (const float*)p->std_dev, p->std_type, *h,
+                     p->G + p->std_off, p->sc, accumulate);
+}
+
+void train_launch_ppo_stats(TrainCore* c, lg_ppo_stats* stats, int mode, int steps, hipStream_t st) {
+  hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(1), 0, st, c->sc, stats, mode, steps);
 }
 
 // ---- PPO

@@ -1,4 +1,5 @@
-// lg_train_internal.h — what the trainers share (lg_train.hip: PPO over two networks; lg_distill_train.hip: distillation over one): the
+// lg_train_internal.h — what the trainers share (lg_train.hip: PPO over two networks; lg_distill_train.hip: distillation over one;
+// lg_train_recurrent.hip: PPO over two networks behind two memories): the
 // description of a network and of a (network, layer) segment as the kernels of lg_train.hip see them, the scalars the optimiser keeps on the
 // device, and the host calls that size the workspaces and launch those kernels.  The kernels themselves live in lg_train.hip only.
 #pragma once
@@ -7,10 +8,12 @@
 #include <vector>
 #include "lg_device.h"
 #include "lg_policy_internal.h"
+#include "../../include/lgtrain.h"
 
 #define WGRAD_SLAB 256        // batch rows per slab of the weight-gradient pass
 #define TRAIN_MAX_NETS 2
-#define TRAIN_MAX_SEGS (TRAIN_MAX_NETS * LG_MLP_MAX_LAYERS)
+// the layers of two MLPs, and weight_ih / weight_hh of every layer of two memories (lg_train_recurrent.hip)
+#define TRAIN_MAX_SEGS (TRAIN_MAX_NETS * LG_MLP_MAX_LAYERS + TRAIN_MAX_NETS * 2 * RNN_MAX_LAYERS)
 
 // one network as the forward and the backward tile see it
 struct TrainNet {
@@ -20,7 +23,7 @@ struct TrainNet {
   int bkpad[LG_MLP_MAX_LAYERS], bnch[LG_MLP_MAX_LAYERS];   // transposed tiling of layer l: dims[l + 1] padded to 64, chunks of dims[l] padded to 64
   const float* fw[LG_MLP_MAX_LAYERS];
   const float* fb[LG_MLP_MAX_LAYERS];
-  const float* bw[LG_MLP_MAX_LAYERS];                      // layer 0 has none: nothing is propagated into the observations
+  const float* bw[LG_MLP_MAX_LAYERS];                      // layer 0 has none unless its owner adds one (the recurrent trainer): nothing is propagated into observations
   float* a[LG_MLP_MAX_LAYERS + 1];                         // a[l] (rows, dims[l]): output of layer l - 1; a[L] is the network's output; a[0] unused
   float* d[LG_MLP_MAX_LAYERS];                             // d[l] (rows, dims[l + 1]): dL / d(pre-activation output of layer l)
 };
@@ -33,7 +36,7 @@ struct TrainSeg {
   const float* D;                    // (rows, dO)
   const float* Ain;                  // (rows, dI); NULL: the gathered observation rows
   float* partial;                    // [slab][dO][dI + 1]
-  float* fw; float* fb; float* bw;
+  float* fw; float* fb; float* bw;    // fw / fb NULL: a segment whose forward image is not an lg_mlp's (a memory's: the owner rewrites it itself)
 };
 
 struct TrainScalars {
@@ -90,3 +93,11 @@ int train_core_retile(TrainCore* c, hipStream_t st);
 int train_core_get_state(TrainCore* c, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, hipStream_t st);
 int train_core_set_state(TrainCore* c, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, hipStream_t st);
 int train_core_set_learning_rate(TrainCore* c, double lr, hipStream_t st);
+
+// PPO's clipped losses on the mini-batch rows i (rollout rows idx[i]) from the forward outputs a[L] of networks 0 and 1: dL/dmu and dL/dvalue into
+// d[L - 1], the four loss means and the gradient of std / log_std (into G at std_off), the KL-adaptive learning rate.  loss_part: the caller's
+// train_ppo_loss_floats(max_rows) floats.
+size_t train_ppo_loss_floats(int64_t max_rows);
+void train_launch_ppo_loss(TrainCore* c, const lg_ppo_rows* rows, const int64_t* idx, int64_t n, const lg_ppo_hyper* hyper, float* loss_part, int accumulate, hipStream_t st);
+// mode 0: clear the update's sums; 1: the means over `steps` steps and the learning rate -> stats (device)
+void train_launch_ppo_stats(TrainCore* c, lg_ppo_stats* stats, int mode, int steps, hipStream_t st);

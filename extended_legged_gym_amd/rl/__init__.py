@@ -1,11 +1,13 @@
 """Rollout-collection side of PPO on the GPU: `NativeActorCritic`, `NativeActorCriticRecurrent`
 (LSTM / GRU memory in front of each MLP), `compute_returns`, `collect_rollout`; teacher-student distillation: `NativeStudentTeacher`, `NativeStudentTeacherRecurrent`,
 `collect_distillation`, `obs_history_step`; the terrain estimator (depth image -> ray distances): `NativeTerrainEstimator`, `NativeConvEncoder`, `collect_estimation`;
-the training side: `NativePPO` (`PPO.update` on the device, include/lgtrain.h) and `NativeDistillation` (`Distillation.update`, include/lgdistill.h)."""
+the training side: `NativePPO` (`PPO.update` on the device, include/lgtrain.h), `NativeRecurrentPPO` (the same through the LSTM / GRU memories,
+include/lgtrain_recurrent.h) and `NativeDistillation` (`Distillation.update`, include/lgdistill.h)."""
 from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
                      NativeStudentTeacher, NativeStudentTeacherRecurrent)
 from .storage import compute_returns                      # noqa: F401
 from .collector import collect_distillation, collect_estimation, collect_rollout, obs_history_step          # noqa: F401
 from .estimator import NativeConvEncoder, NativeTerrainEstimator, parse_estimator_state          # noqa: F401
 from .ppo import NativePPO          # noqa: F401
+from .ppo_recurrent import NativeRecurrentPPO          # noqa: F401
 from .distillation import NativeDistillation          # noqa: F401

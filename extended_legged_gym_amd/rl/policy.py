@@ -1,8 +1,8 @@
 """`NativeActorCritic`: the feed-forward `ActorCritic` of the vendored rsl_rl (`modules/actor_critic.py:16-136`) with its two
 MLPs evaluated by `lg_mlp_forward` / `lg_policy_act` (include/lgpolicy.h): all layers of a network in one launch on the fp32
 matrix cores, and `PPO.act` (`algorithms/ppo.py:147-159`: sample, value, log-prob, mean, sigma) as ONE launch instead of
-~25.  Inference only: the weights come from a trained / initialised torch `ActorCritic` (its `state_dict`), gradients
-stay in PyTorch.
+~25.  Inference only: the weights come from a trained / initialised torch `ActorCritic` (its `state_dict`); the gradients
+are `rl.NativePPO`'s (`rl.NativeRecurrentPPO`'s for the recurrent policy below), which moves these weights in place.
 
 `NativeActorCriticRecurrent`: rsl_rl's `ActorCriticRecurrent` (`modules/actor_critic_recurrent.py:16-85`: an `nn.LSTM` / `nn.GRU`
 `Memory`, `networks/memory.py:16-51`, in front of each MLP) on `lg_rnn_step` / `lg_policy_act_recurrent`: one launch per memory layer
@@ -287,8 +287,8 @@ class NativeMemory(_NativeHandle):
 class NativeActorCriticRecurrent(NativeActorCritic):
     """Same surface as `ActorCriticRecurrent` for rollout collection (`actor_critic_recurrent.py:62-85`): `act`, `act_inference`, `evaluate`,
     `reset(dones)`, `get_hidden_states`, and what `NativeActorCritic` has.  Built from an `ActorCriticRecurrent.state_dict()`
-    (`memory_a.rnn.*`, `memory_c.rnn.*`, `actor.*`, `critic.*`, `std` / `log_std`).  The batch mode of `PPO.update` (`masks=` /
-    `hidden_states=`) is not built."""
+    (`memory_a.rnn.*`, `memory_c.rnn.*`, `actor.*`, `critic.*`, `std` / `log_std`).  The batch mode of `PPO.update` is not a method of this
+    object (`masks=` / `hidden_states=` raise): `rl.NativeRecurrentPPO` runs it on the rollout dict and moves this object's weights in place."""
     is_recurrent = True
 
     def __init__(self, state_dict, activation="elu", rnn_type="lstm", noise_std_type="scalar", device="cuda:0", seed=0):
@@ -301,7 +301,8 @@ class NativeActorCriticRecurrent(NativeActorCritic):
     @staticmethod
     def _no_batch_mode(masks, hidden_states):
         if masks is not None or hidden_states is not None:
-            raise NotImplementedError("masks= / hidden_states= (the batch mode of PPO.update) is PyTorch's job: the native policy collects rollouts only")
+            raise NotImplementedError("masks= / hidden_states= (the batch mode of PPO.update) is not a method of the native policy: rl.NativeRecurrentPPO runs "
+                                      "the update on the rollout dict")
 
     def reset(self, dones=None):
         self.memory_a.reset(dones)

@@ -30,6 +30,10 @@ class NativePPO(_NativeHandle):
     built from (`actor.*`, `critic.*`, `std` / `log_std`); it seeds the fp32 master parameters.  After `update`, the same `policy` object acts with
     the new weights; nothing is rebuilt."""
     _destroy = "lg_ppo_destroy"
+    _prefix = "lg_ppo_"          # the entry points of include/lgtrain.h; `NativeRecurrentPPO` shares the checkpoint and inspection methods
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
 
     def __init__(self, policy, state_dict, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, schedule="fixed", desired_kl=0.01, max_grad_norm=1.0, use_clipped_value_loss=True, max_rows=None,
@@ -75,11 +79,11 @@ class NativePPO(_NativeHandle):
         state = self.optimizer_state() if self.handle else None
         self.close()
         torch.cuda.synchronize(self.device)
-        self._created(self.lib.lg_ppo_create(self.policy.actor.handle, self.policy.critic.handle, aw, ab, cw, cb, self._std0.ctypes.data,
-                                             abi.NOISE_STD_TYPES[self.policy.noise_std_type], self.learning_rate, max_rows, _ptr(self.policy.std)),
-                      "lg_ppo_create")
+        self._created(self._fn("create")(self.policy.actor.handle, self.policy.critic.handle, aw, ab, cw, cb, self._std0.ctypes.data,
+                                        abi.NOISE_STD_TYPES[self.policy.noise_std_type], self.learning_rate, max_rows, _ptr(self.policy.std)),
+                      self._prefix + "create")
         self.max_rows = max_rows
-        self.num_parameters = int(self.lib.lg_ppo_parameter_count(self.handle))
+        self.num_parameters = int(self._fn("parameter_count")(self.handle))
         if state is not None:
             self.load_optimizer_state(state)
 
@@ -112,7 +116,7 @@ class NativePPO(_NativeHandle):
         idx = indices.to(device=self.device, dtype=torch.int64).contiguous()
         self._ensure(idx.numel())
         hyper = self._hyper()
-        self._check(self.lib.lg_ppo_minibatch(self.handle, C.byref(rows), _ptr(idx), idx.numel(), C.byref(hyper), self._stream()), "lg_ppo_minibatch")
+        self._check(self._fn("minibatch")(self.handle, C.byref(rows), _ptr(idx), idx.numel(), C.byref(hyper), self._stream()), self._prefix + "minibatch")
         del keep
 
     def update(self, rollout, indices=None):
@@ -126,8 +130,8 @@ class NativePPO(_NativeHandle):
         assert idx.numel() >= (R // self.num_mini_batches) * self.num_mini_batches
         self._ensure(max(R // self.num_mini_batches, 1))
         hyper = self._hyper()
-        self._check(self.lib.lg_ppo_update(self.handle, C.byref(rows), R, _ptr(idx), self.num_mini_batches, self.num_learning_epochs, C.byref(hyper),
-                                           _ptr(self._stats), self._stream()), "lg_ppo_update")
+        self._check(self._fn("update")(self.handle, C.byref(rows), R, _ptr(idx), self.num_mini_batches, self.num_learning_epochs, C.byref(hyper),
+                                       _ptr(self._stats), self._stream()), self._prefix + "update")
         st = self._stats.cpu().tolist()
         del keep
         self.learning_rate, self.kl = st[4], st[3]
@@ -136,7 +140,7 @@ class NativePPO(_NativeHandle):
     def set_learning_rate(self, learning_rate):
         self.learning_rate = float(learning_rate)
         if self.handle:
-            self._check(self.lib.lg_ppo_set_learning_rate(self.handle, self.learning_rate, self._stream()), "lg_ppo_set_learning_rate")
+            self._check(self._fn("set_learning_rate")(self.handle, self.learning_rate, self._stream()), self._prefix + "set_learning_rate")
 
     # ---- what the device holds
     def _need_handle(self):
@@ -166,21 +170,21 @@ class NativePPO(_NativeHandle):
         (surrogate, value_function, entropy, kl)."""
         self._need_handle()
         g, norm, means = np.empty(self.num_parameters, np.float32), C.c_float(), (C.c_float * 4)()
-        self._check(self.lib.lg_ppo_gradients(self.handle, g.ctypes.data, C.byref(norm), means, self._stream()), "lg_ppo_gradients")
+        self._check(self._fn("gradients")(self.handle, g.ctypes.data, C.byref(norm), means, self._stream()), self._prefix + "gradients")
         return self._split(g), norm.value, dict(zip(("surrogate", "value_function", "entropy", "kl"), [float(x) for x in means]))
 
     def forward_outputs(self, count):
         """The action means (count, A) and values (count, 1) the last mini-batch's forward pass computed, in mini-batch order."""
         self._need_handle()
         mu, val = np.empty((count, self.policy.num_actions), np.float32), np.empty((count, 1), np.float32)
-        self._check(self.lib.lg_ppo_forward_outputs(self.handle, mu.ctypes.data, val.ctypes.data, self._stream()), "lg_ppo_forward_outputs")
+        self._check(self._fn("forward_outputs")(self.handle, mu.ctypes.data, val.ctypes.data, self._stream()), self._prefix + "forward_outputs")
         return torch.from_numpy(mu), torch.from_numpy(val)
 
     def state_dict(self):
         """An `ActorCritic` state dict (`actor.*`, `critic.*`, `std` / `log_std`): rsl_rl and `NativeActorCritic(...)` both load it."""
         self._need_handle()
         flat = np.empty(self.num_parameters, np.float32)
-        self._check(self.lib.lg_ppo_get_parameters(self.handle, flat.ctypes.data, self._stream()), "lg_ppo_get_parameters")
+        self._check(self._fn("get_parameters")(self.handle, flat.ctypes.data, self._stream()), self._prefix + "get_parameters")
         return self._split(flat)
 
     def optimizer_state(self):
@@ -188,14 +192,14 @@ class NativePPO(_NativeHandle):
         self._need_handle()
         bufs = [np.empty(self.num_parameters, np.float32) for _ in range(3)]
         step, lr = C.c_int64(), C.c_double()
-        self._check(self.lib.lg_ppo_get_state(self.handle, *[b.ctypes.data for b in bufs], C.byref(step), C.byref(lr), self._stream()), "lg_ppo_get_state")
+        self._check(self._fn("get_state")(self.handle, *[b.ctypes.data for b in bufs], C.byref(step), C.byref(lr), self._stream()), self._prefix + "get_state")
         return dict(parameters=self._split(bufs[0]), exp_avg=self._split(bufs[1]), exp_avg_sq=self._split(bufs[2]), step=step.value, learning_rate=lr.value)
 
     def load_optimizer_state(self, state):
         self._need_handle()
         bufs = [self._join(state[k]) for k in ("parameters", "exp_avg", "exp_avg_sq")]
-        self._check(self.lib.lg_ppo_set_state(self.handle, *[b.ctypes.data for b in bufs], int(state["step"]), float(state["learning_rate"]), self._stream()),
-                    "lg_ppo_set_state")
+        self._check(self._fn("set_state")(self.handle, *[b.ctypes.data for b in bufs], int(state["step"]), float(state["learning_rate"]), self._stream()),
+                    self._prefix + "set_state")
         self.learning_rate = float(state["learning_rate"])
 
     def load_state_dict(self, state_dict):

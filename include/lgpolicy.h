@@ -78,8 +78,8 @@ int lg_collect_rollout(struct lg_ctx* env, lg_mlp* actor, lg_mlp* critic, const 
 
 /* ---- recurrent actor-critic: the nn.LSTM / nn.GRU "memory" in front of each MLP (vendored rsl_rl: networks/memory.py:16-51,
  * modules/actor_critic_recurrent.py:16-85; selected by runner.policy_class_name = "ActorCriticRecurrent" with the knobs rnn_type,
- * rnn_hidden_size, rnn_num_layers of legged_robot_config.py:279).  Inference / collection only: the masked batch mode of PPO.update
- * (act(obs, masks=, hidden_states=)) stays in PyTorch.
+ * rnn_hidden_size, rnn_num_layers of legged_robot_config.py:279).  Inference / collection here; the batch mode of PPO.update (the reference's
+ * act(obs, masks=, hidden_states=) over padded trajectories) is the recurrent trainer of lgtrain_recurrent.h, which walks the same rows unpadded.
  *
  * One memory step for n rows, ONE launch per memory layer (the actor's and the critic's memory share a launch when they step together):
  *     gates = W_ih x + b_ih + W_hh h + b_hh                                     (n, G H), one fp32 MFMA k-chain over [x ; h]
