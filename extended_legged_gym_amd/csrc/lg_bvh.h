@@ -97,7 +97,9 @@ LG_DEV bool descend4(int cand[4], float key[4], int* stack_i, float* stack_k, in
 
 // A ray that runs within rounding of an edge two triangles share must hit one of them: the barycentric tests accept a band of RAY_EDGE_EPS (the rounding of
 // u, v for origins metres away from a decimetre triangle is ~2e-6; strict tests let 9 % of the vertical rays that start exactly on a lattice line of a
-// heightfield mesh fall through the crack).  The plane of either neighbour gives the same t to rounding.  The oracle's brute-force scan uses the same band.
+// heightfield mesh fall through the crack).  The plane of either neighbour gives the same t to rounding.  The oracle's brute-force scan uses the same band
+// (and the same fp32 arithmetic); the float64 reference of tests/ray_reference.py shares neither: it bounds what any fp32 evaluation of these formulas may
+// accept and must accept, and the kernels are held to those bounds on every ray (tests/test_hip_ray_reference.py).
 #define RAY_EDGE_EPS 1e-5f
 
 // One triangle against a ray (Moller-Trumbore, two-sided, barycentric band RAY_EDGE_EPS): updates the closest hit.  ONE body for the tree walk and the lattice
@@ -181,6 +183,9 @@ struct RayGrid { const float* __restrict__ xb; const float* __restrict__ yb; int
 // depth camera knows about its rays (they start at the camera and end within far_clip of it): no triangle in reach is higher than ztop, and the block
 // maxima may be walked in front of the cells.  (Measured and dropped, round 6: the cells' z ranges of the camera's square staged in LDS -- 18 KB and three
 // barriers per workgroup cost more than the L1-resident loads they replaced: 0.65 against 0.59 ms per step of config 4.)
+// How far from a lattice line a ray still touches the triangles on the other side of it: twice the band of the triangle test on a cell of average width, and
+// never less than four ulps of the coordinates themselves (60 m from the origin a cell of 1 cm has a band of 1e-7 m and coordinates 4e-6 m apart).
+LG_DEV float ray_line_band(float lo, float hi, int n) { return 2.f * RAY_EDGE_EPS * (hi - lo) / (float)n + 4.8e-7f * fmaxf(fabsf(lo), fabsf(hi)); }
 struct RayTables {
   const float* tb; const RayGrid* G; float ztop; bool blocks;
   LG_DEV float xb(int i) const { return tb[i]; }
@@ -189,6 +194,8 @@ struct RayTables {
   LG_DEV float x_hi() const { return tb[G->nx]; }
   LG_DEV float y_lo() const { return tb[G->nx + 1]; }
   LG_DEV float y_hi() const { return tb[G->nx + 1 + G->ny]; }
+  LG_DEV float x_band() const { return ray_line_band(tb[0], tb[G->nx], G->nx); }
+  LG_DEV float y_band() const { return ray_line_band(tb[G->nx + 1], tb[G->nx + 1 + G->ny], G->ny); }
   LG_DEV float z_top() const { return ztop; }       // no triangle the ray can reach is higher than this (3e38: unknown)
   LG_DEV bool coarse() const { return blocks; }     // walk the blocks in front of the cells
 };
@@ -202,16 +209,24 @@ LG_DEV int raygrid_locate(const Acc& A, bool xaxis, int n, float x, int guess) {
 // The stretch [t0, t1] of a ray its walk has to cover: [0, max_dist] cut to the part over the lattice and, where the caller knows a ceiling of the reachable
 // triangles (A.z_top()), to the part below that ceiling.  False: nothing to walk -- a miss.  (Its own function since round 6: the depth kernel sorts its rays
 // by this answer before it walks any.)
-struct RaySpan { V3 inv; bool mvx, mvy; float t0, t1; };
+struct RaySpan { V3 inv; bool mvx, mvy; float t0, t1, ex, ey; };
 template <class Acc>
 LG_DEV bool ray_span(const Acc& A, V3 o, V3 d, float max_dist, RaySpan& S) {
   S.inv = v3(1.f / (fabsf(d.x) > 1e-12f ? d.x : copysignf(1e-12f, d.x)), 1.f / (fabsf(d.y) > 1e-12f ? d.y : copysignf(1e-12f, d.y)),
              1.f / (fabsf(d.z) > 1e-12f ? d.z : copysignf(1e-12f, d.z)));
   const V3 inv = S.inv;
-  // a ray that does not move along an axis (|d| <= 1e-12: a vertical ray) never crosses that axis's lines: its boundary times are -inf / +inf while it
-  // is between the outer lines (those included), not the 0 * 1e12 a start exactly ON a line gives
-  const bool mvx = fabsf(d.x) > 1e-12f, mvy = fabsf(d.y) > 1e-12f;
-  S.mvx = mvx; S.mvy = mvy;
+  // a ray that does not move along an axis (a vertical ray) never crosses that axis's lines: its boundary times are -inf / +inf while it
+  // is between the outer lines (those included), not the 0 * 1e12 a start exactly ON a line gives.  "Does not move": its whole travel along the axis,
+  // |d| max_dist, stays within the band of the triangle test (ex, ey: twice RAY_EDGE_EPS of a cell width).  With |d| <= 1e-12 alone, a ray that starts ON
+  // a lattice line with 1e-12 < |d.x| << 1 was walked down ONE of the two columns that share the line, though the band makes it touch the faces of both
+  // (where the slope correction folded the surface the nearest hit was lost), and one that starts on the OUTER line and drifts outwards by 1e-11 m was cut
+  // to t1 = 0 -- misses where the tree walk hits (found by the float64 bounds of tests/ray_reference.py, tests/test_hip_ray_reference.py).  For the same
+  // reason the OUTER lines of the staged tables lie one band outside the mesh (raygrid_stage, lg_mesh.hip): the triangle test accepts a ray that far beyond
+  // the border, at any speed.  (What remains: a ray that starts on an INNER line and drifts faster than this, but slowly enough to be in the band of the
+  // column it left when it hits -- |d.x| between ex / max_dist and ex / t_hit.)
+  const float ex = A.x_band(), ey = A.y_band();
+  const bool mvx = fabsf(d.x) > 1e-12f && fabsf(d.x) * max_dist > ex, mvy = fabsf(d.y) > 1e-12f && fabsf(d.y) * max_dist > ey;
+  S.mvx = mvx; S.mvy = mvy; S.ex = ex; S.ey = ey;
   const float xlo = A.x_lo(), xhi = A.x_hi(), ylo = A.y_lo(), yhi = A.y_hi();
   // the part of the ray over the lattice
   float t0 = 0.f, t1 = max_dist;
@@ -251,7 +266,11 @@ LG_DEV float trace_ray_grid(const RayGrid& G, const Acc& A, V3 o, V3 d, float ma
   // ... and a ray without motion across the lines of an axis that starts exactly ON one of them runs down the border of two columns of cells: triangles
   // of the - side column reach it only with an edge (they are not listed in the + side cells), and where the slope correction folded the surface the
   // nearest hit may be one of theirs.  Such rays (a measure-zero set; tested wave-wide, so other waves pay three ballots) walk the - side column(s) too.
-  bool lx = !mvx && ix > 0 && px == A.xb(ix), ly = !mvy && iy > 0 && py == A.yb(iy);
+  // "ON a line": within the band of it (S.ex, S.ey), which a ray without motion along the axis then stays in to the end.
+  // (a ray that does not move along an axis and stands within the band below the line AHEAD of its cell belongs to that line as well: it is placed on its + side)
+  if (!mvx && ix < G.nx - 1 && A.xb(ix + 1) - px <= S.ex) ++ix;
+  if (!mvy && iy < G.ny - 1 && A.yb(iy + 1) - py <= S.ey) ++iy;
+  bool lx = !mvx && ix > 0 && px - A.xb(ix) <= S.ex, ly = !mvy && iy > 0 && py - A.yb(iy) <= S.ey;
   if (A.coarse() && A.z_top() < 3.0e37f && G.zb != nullptr && !lx && !ly) {
     // (round 6; callers that know a ceiling of the reachable triangles -- the depth camera -- also get the coarse walk)  Blocks of RAY_BLK x RAY_BLK cells
     // with the highest z of their triangles: the ray crosses the blocks in front of it one by one until it comes down to a block's top; the cell walk

@@ -188,9 +188,12 @@ struct RayGridHost {
 
 // ------------------------------------------------------------------------------------------------ kernels
 // boundary tables of the ray lattice -> LDS (every thread of the workgroup calls this; no-op without a lattice)
+// The two outer lines of either axis are staged one band of the triangle test (ray_line_band, lg_bvh.h) OUTSIDE the mesh: a ray that runs
+// that far beyond the border still touches the border triangles, and the walk must not cut it off there (ray_span, lg_bvh.h).
 LG_DEV void raygrid_stage(const RayGrid& G, float* tb) {
-  for (int i = threadIdx.x; i <= G.nx; i += blockDim.x) tb[i] = G.xb[i];
-  for (int i = threadIdx.x; i <= G.ny; i += blockDim.x) tb[G.nx + 1 + i] = G.yb[i];
+  const float ex = ray_line_band(G.xb[0], G.xb[G.nx], G.nx), ey = ray_line_band(G.yb[0], G.yb[G.ny], G.ny);
+  for (int i = threadIdx.x; i <= G.nx; i += blockDim.x) tb[i] = G.xb[i] + (i == 0 ? -ex : i == G.nx ? ex : 0.f);
+  for (int i = threadIdx.x; i <= G.ny; i += blockDim.x) tb[G.nx + 1 + i] = G.yb[i] + (i == 0 ? -ey : i == G.ny ? ey : 0.f);
   __syncthreads();
 }
 // GRID: the instance for meshes with a ray lattice -- a separate kernel, because the tree walk's per-lane stack lives in scratch and scratch limits the

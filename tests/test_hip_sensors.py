@@ -1,6 +1,10 @@
 """GPU: BVH ray casting / SDF / ray-caster sensor / depth camera (through the C ABI) against the brute-force mesh oracle
 and plain-PyTorch fp32 references.  Tolerances: hit points 1e-4 m, found masks identical except for rays that graze a
-triangle edge within 1e-5 (< 0.1 % allowed), SDF 1e-5, depth images 2e-4 (bicubic in fp32)."""
+triangle edge within 1e-5 (< 0.1 % allowed), SDF 1e-5, depth images 2e-4 (bicubic in fp32).
+
+The oracle here shares the kernels' fp32 arithmetic and band, and the allowances above do not say which rays they are for.  WHETHER a ray hits, and where, is
+decided in tests/test_hip_ray_reference.py: float64 bounds for every ray and every pixel (tests/ray_reference.py), no share of mismatches allowed; a lattice /
+tree or skip-mode difference is a failure there on every ray the bounds decide.  The assertions below stay as the coarse end-to-end check they were."""
 import numpy as np
 import pytest
 import torch
