@@ -507,6 +507,72 @@ DISTILL_TRAIN_SYMBOLS = ["lg_distill_train_create", "lg_distill_train_destroy", 
                          "lg_distill_train_set_state", "lg_distill_train_set_learning_rate"]
 DISTILL_LOSSES = {"mse": 0, "huber": 1}          # enum lg_distill_loss
 
+class lg_estimator_train_hyper(C.Structure):
+    """include/lgestimator_train.h: the loss, the clip (max_grad_norm <= 0: no clip) and whether the rows' dones reset the memory."""
+    _fields_ = [("loss_type", i32), ("max_grad_norm", f32), ("use_dones", i32)]
+
+
+class lg_estimator_train_params(C.Structure):
+    """include/lgestimator_train.h: HOST pointers to the module's tensors in torch's layout."""
+    _fields_ = [(k, C.POINTER(f32) if k.startswith("combine") else C.POINTER(C.POINTER(f32)))
+                for k in ("encoder_weights", "encoder_biases", "combine_weight", "combine_bias", "memory_w_ih", "memory_w_hh", "memory_b_ih", "memory_b_hh",
+                          "decoder_weights", "decoder_biases")]
+
+
+class lg_estimator_train_stats(C.Structure):
+    """include/lgestimator_train.h: what an update reports (float64, device memory)."""
+    _fields_ = [(k, C.c_double) for k in ("estimation", "optimizer_steps", "grad_norm")]
+
+
+def declare_estimator_train(lib):
+    """Prototypes of the terrain estimator's trainer (include/lgestimator_train.h), same library."""
+    vp, i64 = C.c_void_p, C.c_int64
+    hp = C.POINTER(lg_estimator_train_hyper)
+    lib.lg_estimator_train_create.argtypes = [vp, vp, vp, vp, C.POINTER(lg_estimator_train_params), C.c_double, i64]
+    lib.lg_estimator_train_create.restype = vp
+    lib.lg_estimator_train_destroy.argtypes = [vp]
+    lib.lg_estimator_train_destroy.restype = None
+    lib.lg_estimator_train_group.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, hp, vp]
+    lib.lg_estimator_train_group.restype = C.c_int
+    lib.lg_estimator_train_update.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, hp, vp, vp]
+    lib.lg_estimator_train_update.restype = C.c_int
+    lib.lg_estimator_train_parameter_count.argtypes = [vp]
+    lib.lg_estimator_train_parameter_count.restype = i64
+    lib.lg_estimator_train_workspace_bytes.argtypes = [vp]
+    lib.lg_estimator_train_workspace_bytes.restype = i64
+    lib.lg_estimator_train_wgrad_slab_rows.argtypes = []
+    lib.lg_estimator_train_wgrad_slab_rows.restype = i32
+    lib.lg_estimator_train_gradients.argtypes = [vp, vp, vp, vp, i64, vp]
+    lib.lg_estimator_train_gradients.restype = C.c_int
+    lib.lg_estimator_train_forward_outputs.argtypes = [vp, vp, vp]
+    lib.lg_estimator_train_forward_outputs.restype = C.c_int
+    lib.lg_estimator_train_step_losses.argtypes = [vp, vp, i64, vp]
+    lib.lg_estimator_train_step_losses.restype = C.c_int
+    lib.lg_estimator_train_get_carry.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.lg_estimator_train_get_carry.restype = i64
+    lib.lg_estimator_train_set_carry.argtypes = [vp, vp, vp, i64, vp]
+    lib.lg_estimator_train_set_carry.restype = C.c_int
+    lib.lg_estimator_train_reset_carry.argtypes = [vp, vp]
+    lib.lg_estimator_train_reset_carry.restype = C.c_int
+    lib.lg_estimator_train_get_parameters.argtypes = [vp, vp, vp]
+    lib.lg_estimator_train_get_parameters.restype = C.c_int
+    lib.lg_estimator_train_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
+    lib.lg_estimator_train_get_state.restype = C.c_int
+    lib.lg_estimator_train_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
+    lib.lg_estimator_train_set_state.restype = C.c_int
+    lib.lg_estimator_train_set_learning_rate.argtypes = [vp, C.c_double, vp]
+    lib.lg_estimator_train_set_learning_rate.restype = C.c_int
+    return lib
+
+
+ESTIMATOR_TRAIN_SYMBOLS = ["lg_estimator_train_create", "lg_estimator_train_destroy", "lg_estimator_train_group", "lg_estimator_train_update",
+                           "lg_estimator_train_parameter_count", "lg_estimator_train_workspace_bytes", "lg_estimator_train_wgrad_slab_rows",
+                           "lg_estimator_train_gradients", "lg_estimator_train_forward_outputs", "lg_estimator_train_step_losses",
+                           "lg_estimator_train_get_carry", "lg_estimator_train_set_carry", "lg_estimator_train_reset_carry",
+                           "lg_estimator_train_get_parameters", "lg_estimator_train_get_state", "lg_estimator_train_set_state",
+                           "lg_estimator_train_set_learning_rate"]
+ESTIMATOR_LOSSES = {"mse": 0, "huber": 1, "l1": 2}          # enum lg_estimator_loss
+
 TRAIN_SYMBOLS = ["lg_ppo_create", "lg_ppo_destroy", "lg_ppo_minibatch", "lg_ppo_update", "lg_ppo_parameter_count", "lg_ppo_gradients",
                  "lg_ppo_forward_outputs", "lg_ppo_get_parameters", "lg_ppo_get_state", "lg_ppo_set_state", "lg_ppo_set_learning_rate", "lg_ppo_wgrad_slab_rows"]
 NOISE_STD_TYPES = {"scalar": 0, "log": 1}          # enum lg_noise_std_type

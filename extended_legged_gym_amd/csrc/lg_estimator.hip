@@ -34,27 +34,9 @@
 
 #include "lg_device.h"
 #include "lg_policy_internal.h"
+#include "lg_estimator_internal.h"
 #include "../../include/lgpolicy.h"
 #include "../../include/lgstep.h"
-
-#define CONV_ROWS 64         // rows (env, pixel) per workgroup
-#define CONV_COLS 64         // output channels per workgroup (grid.y walks the groups)
-#define CONV_THREADS 256     // four waves, one 16-row tile each
-#define CONV_KC 64           // k per staged chunk (four blocks of 16)
-#define ENC_LAYERS 6         // conv 0 2 4 6, linear 10 12 of the nn.Sequential
-#define ENC_MAX_HW 128
-#define ENC_MAX_OUT 512
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct ConvLayerDev {
-  int Hin, Win, Cin, Hout, Wout, Cout, stride, pad, act;
-  int nkb;                 // K rounded up to 64, / 16
-  const float* w;          // tiled [chunk][k / 16][lane][4], Cout rounded up to 64
-  const uint16_t* w16;     // bf16 mode instead of w: tiled [chunk][k / 32][lane][8] (lg_conv_tile_weights_bf16); nkb and ktab are then those of enc_bf16_gemm_kernel
-  const float* b;          // bias, zero-padded to the same width
-  const int32_t* ktab;     // [16 nkb]: (ky << 26) | (kx << 22) | offset of tap k from the patch's first pixel, -1 beyond K
-};
 
 LG_DEV float enc_act(float x, int act) {
   switch (act) {
@@ -298,20 +280,6 @@ static void conv_tile_weights_bf16(int cout, int cin, int kh, int kw, const floa
           tiled[(((size_t)c * nks + s) * 64 + ln) * 8 + j] = v;
         }
 }
-
-struct lg_conv_encoder {
-  int device = 0, H = 0, W = 0, out_dim = 0, act = 0, prec = LG_PREC_F32;
-  ConvLayerDev layer[ENC_LAYERS];
-  int Hp = 0, Wp = 0;                      // the map the pooling reads
-  size_t floats_a = 0, floats_b = 0;       // per env: workspace A holds the maps of layers 0, 2 and the pooled row, B those of 1, 3 and the first linear (bf16 mode: elements of 2 bytes)
-  int64_t cap = 0;                         // envs the workspaces hold
-  float *ws_a = nullptr, *ws_b = nullptr;
-  float *cat = nullptr, *comb = nullptr, *memo = nullptr;   // lg_estimator_step: (cap, cat_w), (cap, comb_w), (cap, mem_w)
-  int64_t step_cap = 0; int cat_w = 0, comb_w = 0, mem_w = 0;
-  std::vector<void*> allocs;
-};
-
-static const int kConvShape[4][5] = {{1, 32, 5, 2, 2}, {32, 64, 3, 2, 1}, {64, 128, 3, 2, 1}, {128, 64, 3, 1, 1}};   // C_in, C_out, k, stride, pad
 
 static int64_t conv_tiled_count(int cout, int cin, int kh, int kw) {
   const int64_t K = (int64_t)cin * kh * kw, nkb = ((K + 63) & ~(int64_t)63) / 16, nch = ((cout + 63) & ~63) / 16;
@@ -596,3 +564,23 @@ int lg_estimator_step(lg_conv_encoder* e, lg_mlp* combine, lg_rnn* mem, lg_mlp* 
 }
 
 }  // extern "C"
+
+// lg_estimator_internal.h: the fp32 launch list onto the caller's maps -- the same kernels, the same grids, so stage k's rows are those of
+// lg_conv_encoder_forward_stages bit for bit.  maps[k - 1] / strides[k - 1]: where the rows of stage k go and how far apart they are.
+int enc_forward_saved(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* const* maps, const int64_t* strides, hipStream_t st) {
+  const float* in = depth; int64_t in_stride = depth_stride;
+  for (int k = 1; k <= ENC_LAYERS + 1; ++k) {
+    if (k == 5) hipLaunchKernelGGL(pool_flatten_kernel, dim3((unsigned)((n * 1024 + 255) / 256)), dim3(256), 0, st, in, n, e->Hp, e->Wp, 64, maps[k - 1]);
+    else {
+      const int rc = enc_launch(e->layer[k < 5 ? k - 1 : k - 2], in, in_stride, n, maps[k - 1], strides[k - 1], st);
+      if (rc != LG_OK) return rc;
+    }
+    in = maps[k - 1]; in_stride = strides[k - 1];
+  }
+  POLICY_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+void enc_launch_cat(const float* proprio, int64_t n, int P, float* dst, int stride, int col0, hipStream_t st) {
+  hipLaunchKernelGGL(cat_columns_kernel, dim3((unsigned)((n * P + 255) / 256)), dim3(256), 0, st, proprio, n, P, dst, stride, col0);
+}

@@ -489,6 +489,24 @@ int train_launch_optimise(TrainCore* c, const float* obs, const float* cobs, con
   return train_core_retile_or_step(c, st, true);
 }
 
+// the passes of train_launch_optimise one by one, for a trainer whose segments do not all share a row count (the estimator's convolutions bring their
+// own weight-gradient kernel and slab counts): segments [seg0, seg0 + count) only
+void train_launch_wgrad_range(const TrainCore* c, int seg0, int count, const float* obs, const float* cobs, const int64_t* idx, int64_t n, hipStream_t st) {
+  const int nslabs = (int)((n + WGRAD_SLAB - 1) / WGRAD_SLAB);
+  hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(c->wgrad_blocks, nslabs, count), dim3(256), 0, st, (const TrainSeg*)(c->d_seg + seg0), obs, cobs, idx, n);
+}
+
+void train_launch_reduce_range(const TrainCore* c, int seg0, int count, int nslabs, hipStream_t st) {
+  hipLaunchKernelGGL(ppo_grad_reduce_kernel, dim3(c->red_blocks, count), dim3(256), 0, st, (const TrainSeg*)(c->d_seg + seg0), nslabs, c->G,
+                     c->norm_part + (size_t)seg0 * c->red_blocks);
+}
+
+int train_launch_norm_adam(TrainCore* c, float max_grad_norm, int clip_on, hipStream_t st) {
+  hipLaunchKernelGGL(ppo_norm_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)c->norm_part, c->red_blocks * c->nseg, (const float*)(c->G + c->std_off), c->nstd,
+                     max_grad_norm, clip_on, c->sc);
+  return train_core_retile_or_step(c, st, true);
+}
+
 int train_core_get_state(TrainCore* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, hipStream_t st) {
   POLICY_TRY(hipStreamSynchronize(st));
   const size_t bytes = (size_t)p->P * sizeof(float);

@@ -87,6 +87,11 @@ void train_launch_backward(const TrainCore* c, int64_t n, hipStream_t st);
 // weight gradients by slabs, their reduction, the global norm (clip_on == 0: the norm is reported and the gradient passes unscaled), Adam and the
 // rewrite of the tilings.  idx must not be NULL.
 int train_launch_optimise(TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, float max_grad_norm, int clip_on, hipStream_t st);
+// the same passes one by one over segments [seg0, seg0 + count): the slab weight gradients of dense segments over n rows; the reduction of nslabs
+// partials (any kernel may have written them, in the layout of TrainSeg::partial); then, once every segment is reduced, norm + Adam + tilings
+void train_launch_wgrad_range(const TrainCore* c, int seg0, int count, const float* obs, const float* cobs, const int64_t* idx, int64_t n, hipStream_t st);
+void train_launch_reduce_range(const TrainCore* c, int seg0, int count, int nslabs, hipStream_t st);
+int train_launch_norm_adam(TrainCore* c, float max_grad_norm, int clip_on, hipStream_t st);
 // the masters -> the tilings (and std_dev), without a step
 int train_core_retile(TrainCore* c, hipStream_t st);
 

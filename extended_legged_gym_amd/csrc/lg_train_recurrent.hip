@@ -24,6 +24,7 @@
 #include "lg_policy_internal.h"
 #include "lg_rnn_tile.h"
 #include "lg_train_internal.h"
+#include "lg_train_recurrent_internal.h"
 #include "../../include/lgtrain_recurrent.h"
 
 #define BK_PASS 1024          // columns of D per pass of the backward tile: the 128 KB image of the forward tile
@@ -80,12 +81,6 @@ LG_DEV void rows_times_tiled(int K, int nbk, const float* __restrict__ wt, int n
   }
 }
 
-struct RowsMatArgs {
-  const float* A; int K, nbk;        // (n, K) and the k-blocks per chunk of the tiling
-  const float* wt; int nch, nout;
-  float* out;                        // (n, nout)
-};
-
 __global__ __launch_bounds__(MLP_THREADS) void rows_matmul_kernel(RowsMatArgs M0, RowsMatArgs M1, int64_t n) {
   __shared__ __attribute__((aligned(16))) float img[MLP_ROWS * BK_PASS];
   const RowsMatArgs& M = blockIdx.y == 0 ? M0 : M1;
@@ -100,19 +95,6 @@ __global__ __launch_bounds__(MLP_THREADS) void rows_matmul_kernel(RowsMatArgs M0
                      out[row * nout + col] = v;
                    });
 }
-
-struct RnnBackArgs {                 // one memory's operands of a backward layer step; row pointers at THIS step's first row
-  int gru, I, H, K, nbk;             // K = G H; nbk = K / 16 rounded up
-  int nchx, nchh;                    // 16-column chunks of dx (0: the layer reads observations, no dx) and of dh_prev
-  const float* wtx; const float* wth;
-  const float* gate[4]; const float* hin; const float* cin; const float* cnew;
-  const float* dup;                  // (n, H): dL/dh' from above (the MLP, or the layer above's dx)
-  const float* dh_in; const float* dc_in;          // the carries out of step t + 1, or null
-  const float* dprev;                // dones of step t - 1 (n), or null (t == 0): rows that entered from a saved row
-  float* dh_out; float* dc_out;      // the carries into step t - 1
-  float* dx;                         // (n, I) or null
-  float* Dih; float* Dhh;            // (n, K): the gate derivatives as the weight gradients of weight_ih / weight_hh take them (LSTM: Dhh == Dih)
-};
 
 // the derivative of the loss w.r.t. gate g's pre-activation of (row, unit u): vx as weight_ih / bias_ih see it, vh as weight_hh / bias_hh do
 // (they differ in a GRU's n gate, where r multiplies the hidden side only); dcp: dL/dc_prev (LSTM)
@@ -186,12 +168,6 @@ __global__ __launch_bounds__(MLP_THREADS) void rnn_backward_kernel(RnnBackPair P
   const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
   if (B.gru) rnn_back_tile<true>(B, row0, n, img); else rnn_back_tile<false>(B, row0, n, img);
 }
-
-struct RnnRetile {                   // one memory layer's forward images and where its masters sit in the flat vector
-  float* w; float* b;
-  int G, I, H, Ip, nb, nch;
-  int64_t wih, whh, bih, bhh;
-};
 
 // element e of the tiled weights (rnn_tile_weights of lg_policy.hip, the same index arithmetic), then of the bias rows
 __global__ __launch_bounds__(256) void rnn_retile_kernel(const RnnRetile* __restrict__ tab, const float* __restrict__ theta) {
@@ -599,3 +575,24 @@ int lg_ppo_recurrent_get_images(lg_ppo_recurrent* p, int32_t memory, int32_t lay
 }
 
 }  // extern "C"
+
+// ---- ONE memory through the kernels above (lg_train_recurrent_internal.h): the launches of rec_step with grid.y = 1
+void rec_launch_forward_one(const RnnStepArgs& S, const RnnSaveArgs& V, int64_t n, hipStream_t st) {
+  RnnTrainPair P{};
+  P.S[0] = S; P.V[0] = V;
+  hipLaunchKernelGGL(rnn_train_forward_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 1), dim3(MLP_THREADS), 0, st, P, n);
+}
+
+void rec_launch_backward_one(const RnnBackArgs& B, int64_t n, hipStream_t st) {
+  RnnBackPair P{};
+  P.B[0] = B;
+  hipLaunchKernelGGL(rnn_backward_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 1), dim3(MLP_THREADS), 0, st, P, n);
+}
+
+void rec_launch_rows_matmul_one(const RowsMatArgs& M, int64_t n, hipStream_t st) {
+  hipLaunchKernelGGL(rows_matmul_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 1), dim3(MLP_THREADS), 0, st, M, M, n);
+}
+
+void rec_launch_retile(const RnnRetile* tab, int count, int64_t big, const float* theta, hipStream_t st) {
+  hipLaunchKernelGGL(rnn_retile_kernel, dim3((unsigned)((big + 255) / 256), count), dim3(256), 0, st, tab, theta);
+}

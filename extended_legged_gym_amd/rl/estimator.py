@@ -1,7 +1,8 @@
 """`NativeTerrainEstimator`: the reference's `TerrainEstimator` (`rsl_rl/modules/terrain_estimator.py:13-218`: depth-image CNN encoder ->
 combination layer with the base velocities -> GRU / LSTM `Memory` -> MLP decoder, predicting the ray caster's distances) in inference mode on
 `lg_conv_encoder_forward` / `lg_estimator_step` (include/lgpolicy.h).  The weights come from a checkpoint of the reference's module, by its own
-key names; gradients (`EstimatorDistillation.update`) stay in PyTorch (`tools/train_estimator.py`)."""
+key names; gradients (`EstimatorDistillation.update`) are `rl.NativeEstimatorDistillation` (`rl/estimator_distillation.py`), which trains this
+object's weights in place, or eager PyTorch (`tools/train_estimator.py --update torch`)."""
 import ctypes as C
 
 import numpy as np

@@ -206,8 +206,8 @@ int lg_collect_distillation_recurrent(struct lg_ctx* env, lg_rnn* mem_s, lg_mlp*
                                       float* h_s0, float* c_s0, float* h_t0, float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, void* stream);
 
 /* ---- terrain estimator: depth image + base velocities -> the ray caster's distances (vendored rsl_rl: modules/terrain_estimator.py:13-218;
- * trained by algorithms/distillation.py:190-433 through runners/terrain_estimator_runner.py).  Inference / collection only: the update
- * (EstimatorDistillation.update, distillation.py:277-332) stays in PyTorch.
+ * trained by algorithms/distillation.py:190-433 through runners/terrain_estimator_runner.py).  Inference / collection here; the update
+ * (EstimatorDistillation.update, distillation.py:277-332) is lgestimator_train.h, which trains the images of these handles in place.
  *
  * lg_conv_encoder: TerrainEstimator._build_cnn_encoder (terrain_estimator.py:80-109), forward only, fp32, for a (height, width) image:
  *     Conv2d(1, 32, k5, s2, p2) act  Conv2d(32, 64, k3, s2, p1) act  Conv2d(64, 128, k3, s2, p1) act  Conv2d(128, 64, k3, s1, p1) act

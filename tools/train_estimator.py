@@ -6,11 +6,13 @@ counterpart of the reference's `legged_gym/scripts/terrain_est_train.py` (`Terra
   (`depth_encoder.{0,2,4,6,10,12}`, `combination_mlp.0`, `memory.rnn`, `decoder.{0,2,..}`), so checkpoints interchange with the reference's
   module and with `NativeTerrainEstimator`.  `tests/test_estimator_golden.py` pins it to outputs recorded from the reference's module.
 * `estimator_update`: `EstimatorDistillation.update` (`rsl_rl/algorithms/distillation.py:277-332`): one chunk = the `num_envs` rows of a step,
-  a gradient step every `gradient_length` chunks, the memory carried across chunks and detached after each gradient step.  It stays in PyTorch.
+  a gradient step every `gradient_length` chunks, the memory carried across chunks and detached after each gradient step, in eager PyTorch
+  (`--update torch`, the default); `--update native` runs the same update on the device through `rl.NativeEstimatorDistillation`
+  (include/lgestimator_train.h).
 * collection: `collect_estimation` (`extended_legged_gym_amd/rl/collector.py`) on `elspider_air_rough_raycast`; `--python-loop` collects the
   same rows with a plain loop over `env.step` (the checker).
 
-    python tools/train_estimator.py --iters 50 --envs 1024 [--policy walk_policy.pt] [--out run.json]
+    python tools/train_estimator.py --iters 50 --envs 1024 [--policy walk_policy.pt] [--out run.json] [--update native]
 """
 import argparse
 import json
@@ -204,11 +206,15 @@ def collect_python_loop(env, policy, num_steps):
 
 
 def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr=1e-3, gradient_length=15, out=None, log=print, small_terrain=False, update_device=None,
-          eval_precision="fp32"):
+          eval_precision="fp32", update="torch"):
     """update_device: where the torch update runs (default: the env's device).  "cpu" makes the update reproducible bit for bit -- the GPU's
     convolution backward is not -- which is what a comparison of two collections needs.  eval_precision: the encoder mode ("fp32" | "bf16") of the
-    native estimator that plays the trained module over the closing evaluation steps; training itself stays fp32 torch."""
-    from extended_legged_gym_amd.rl import NativeActorCritic, NativeTerrainEstimator, collect_estimation
+    native estimator that plays the trained module over the closing evaluation steps; training itself is fp32.  update: "torch" (`estimator_update`
+    on a `TerrainEstimatorTorch`) or "native" (`rl.NativeEstimatorDistillation`: the update on the device, the weights trained in place in an fp32
+    `NativeTerrainEstimator`; update_device does not apply)."""
+    from extended_legged_gym_amd.rl import NativeActorCritic, NativeEstimatorDistillation, NativeTerrainEstimator, collect_estimation
+    if update not in ("torch", "native"):
+        raise ValueError(f"update {update!r}: must be torch or native")
     torch.manual_seed(seed)
     env = make_env(envs, seed, small_terrain=small_terrain)
     policy = None
@@ -221,14 +227,27 @@ def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr
     model = TerrainEstimatorTorch(shape, 6, R).to(udev)
     opt = torch.optim.Adam(model.parameters(), lr=lr)
     hidden, curve = None, []
+    trained = alg = None
+    if update == "native":
+        start = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+        trained = NativeTerrainEstimator(start, shape, 6, device=str(env.device))
+        alg = NativeEstimatorDistillation(trained, start, gradient_length=gradient_length, learning_rate=lr)
     for it in range(iters):
         with torch.inference_mode():
             rows = collect_python_loop(env, policy, steps) if python_loop else collect_estimation(env, policy, steps)
-        rows = {k: v.to(udev, copy=True) for k, v in rows.items()}
-        loss, hidden = estimator_update(model, opt, rows, hidden, gradient_length)
+        if alg is not None:
+            loss = alg.update(rows)["estimation"]
+        else:
+            rows = {k: v.to(udev, copy=True) for k, v in rows.items()}
+            loss, hidden = estimator_update(model, opt, rows, hidden, gradient_length)
         curve.append(loss)
         log(f"iter {it:4d}  estimation loss {loss:.6f}")
-    state = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    if alg is not None:
+        state = alg.state_dict()
+        alg.close()
+        trained.close()
+    else:
+        state = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     native = NativeTerrainEstimator(state, shape, 6, device=str(env.device), encoder_precision=eval_precision)          # the file below is one it loads
     with torch.inference_mode():
         ev = collect_estimation(env, policy, steps, estimator=native)
@@ -254,8 +273,9 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="write the loss curve here (JSON) and the trained module next to it (_model.pt)")
     ap.add_argument("--small-terrain", action="store_true", help="2 x 3 terrain tiles (quick runs)")
     ap.add_argument("--eval-precision", choices=("fp32", "bf16"), default="fp32", help="encoder mode of the native estimator that plays the trained module at the end")
+    ap.add_argument("--update", choices=("torch", "native"), default="torch", help="where the gradient steps run: eager torch, or the library's kernels (rl.NativeEstimatorDistillation)")
     a = ap.parse_args(argv)
-    train(a.iters, a.envs, a.steps, a.seed, a.policy, a.python_loop, out=a.out, small_terrain=a.small_terrain, eval_precision=a.eval_precision)
+    train(a.iters, a.envs, a.steps, a.seed, a.policy, a.python_loop, out=a.out, small_terrain=a.small_terrain, eval_precision=a.eval_precision, update=a.update)
 
 
 if __name__ == "__main__":
