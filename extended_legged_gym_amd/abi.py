@@ -507,6 +507,66 @@ DISTILL_TRAIN_SYMBOLS = ["lg_distill_train_create", "lg_distill_train_destroy", 
                          "lg_distill_train_set_state", "lg_distill_train_set_learning_rate"]
 DISTILL_LOSSES = {"mse": 0, "huber": 1}          # enum lg_distill_loss
 
+
+class lg_distill_rtrain_params(C.Structure):
+    """include/lgdistill_recurrent.h: HOST pointers to the trained tensors (student.*, memory_s.*) in torch's layout."""
+    _fields_ = [(k, C.POINTER(C.POINTER(f32))) for k in ("student_weights", "student_biases", "memory_w_ih", "memory_w_hh", "memory_b_ih", "memory_b_hh")]
+
+
+class lg_distill_rtrain_stats(C.Structure):
+    """include/lgdistill_recurrent.h: what an update reports (float64, device memory)."""
+    _fields_ = [(k, C.c_double) for k in ("behavior", "optimizer_steps", "grad_norm", "memory_grad_norm")]
+
+
+def declare_distill_rtrain(lib):
+    """Prototypes of the recurrent student's distillation trainer (include/lgdistill_recurrent.h), same library."""
+    vp, i64 = C.c_void_p, C.c_int64
+    hp = C.POINTER(lg_distill_train_hyper)
+    lib.lg_distill_rtrain_create.argtypes = [vp, vp, C.POINTER(lg_distill_rtrain_params), C.c_double, i64]
+    lib.lg_distill_rtrain_create.restype = vp
+    lib.lg_distill_rtrain_destroy.argtypes = [vp]
+    lib.lg_distill_rtrain_destroy.restype = None
+    lib.lg_distill_rtrain_group.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, hp, vp]
+    lib.lg_distill_rtrain_group.restype = C.c_int
+    lib.lg_distill_rtrain_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, hp, vp, vp]
+    lib.lg_distill_rtrain_update.restype = C.c_int
+    lib.lg_distill_rtrain_parameter_count.argtypes = [vp]
+    lib.lg_distill_rtrain_parameter_count.restype = i64
+    lib.lg_distill_rtrain_student_parameter_count.argtypes = [vp]
+    lib.lg_distill_rtrain_student_parameter_count.restype = i64
+    lib.lg_distill_rtrain_workspace_bytes.argtypes = [vp]
+    lib.lg_distill_rtrain_workspace_bytes.restype = i64
+    lib.lg_distill_rtrain_gradients.argtypes = [vp, vp, vp, vp, i64, vp]
+    lib.lg_distill_rtrain_gradients.restype = C.c_int
+    lib.lg_distill_rtrain_forward_outputs.argtypes = [vp, vp, vp]
+    lib.lg_distill_rtrain_forward_outputs.restype = C.c_int
+    lib.lg_distill_rtrain_step_losses.argtypes = [vp, vp, i64, vp]
+    lib.lg_distill_rtrain_step_losses.restype = C.c_int
+    lib.lg_distill_rtrain_get_carry.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.lg_distill_rtrain_get_carry.restype = i64
+    lib.lg_distill_rtrain_set_carry.argtypes = [vp, vp, vp, i64, vp]
+    lib.lg_distill_rtrain_set_carry.restype = C.c_int
+    lib.lg_distill_rtrain_reset_carry.argtypes = [vp, vp]
+    lib.lg_distill_rtrain_reset_carry.restype = C.c_int
+    lib.lg_distill_rtrain_get_parameters.argtypes = [vp, vp, vp]
+    lib.lg_distill_rtrain_get_parameters.restype = C.c_int
+    lib.lg_distill_rtrain_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
+    lib.lg_distill_rtrain_get_state.restype = C.c_int
+    lib.lg_distill_rtrain_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
+    lib.lg_distill_rtrain_set_state.restype = C.c_int
+    lib.lg_distill_rtrain_set_learning_rate.argtypes = [vp, C.c_double, vp]
+    lib.lg_distill_rtrain_set_learning_rate.restype = C.c_int
+    return lib
+
+
+DISTILL_RTRAIN_SYMBOLS = ["lg_distill_rtrain_create", "lg_distill_rtrain_destroy", "lg_distill_rtrain_group", "lg_distill_rtrain_update",
+                          "lg_distill_rtrain_parameter_count", "lg_distill_rtrain_student_parameter_count", "lg_distill_rtrain_workspace_bytes",
+                          "lg_distill_rtrain_gradients", "lg_distill_rtrain_forward_outputs", "lg_distill_rtrain_step_losses",
+                          "lg_distill_rtrain_get_carry", "lg_distill_rtrain_set_carry", "lg_distill_rtrain_reset_carry",
+                          "lg_distill_rtrain_get_parameters", "lg_distill_rtrain_get_state", "lg_distill_rtrain_set_state",
+                          "lg_distill_rtrain_set_learning_rate"]
+
+
 class lg_estimator_train_hyper(C.Structure):
     """include/lgestimator_train.h: the loss, the clip (max_grad_norm <= 0: no clip) and whether the rows' dones reset the memory."""
     _fields_ = [("loss_type", i32), ("max_grad_norm", f32), ("use_dones", i32)]

@@ -20,16 +20,13 @@
 #include "lg_device.h"
 #include "lg_policy_internal.h"
 #include "lg_train_internal.h"
+#include "lg_distill_train_internal.h"
 #include "../../include/lgdistill.h"
 
 #define DISTILL_LOSS_LANES 256
 #define DISTILL_MAX_STEPS 65535     // steps of one batch: blockIdx.y of the loss kernel
 
-struct DistillScalars {
-  double acc;                        // sum of the step losses since the last clear
-  int64_t steps;                     // steps in that sum
-  int64_t optimizer_steps;           // optimiser steps since the last clear
-};
+// DistillScalars: lg_distill_train_internal.h
 
 struct lg_distill_train : TrainCore {
   lg_mlp* student = nullptr;
@@ -108,6 +105,21 @@ __global__ void distill_stats_kernel(DistillScalars* __restrict__ ds, const Trai
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host side
+// ---- what the recurrent trainer shares (lg_distill_train_internal.h)
+size_t distill_loss_floats(int64_t max_rows, int A) { return (size_t)max_rows * A / DISTILL_LOSS_LANES + (size_t)max_rows + 1; }
+
+void distill_launch_rows(int64_t* rows, int64_t n, int64_t N, int64_t T, int64_t t0, hipStream_t st) {
+  hipLaunchKernelGGL(distill_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rows, n, N, T, t0);
+}
+
+void distill_launch_loss(const float* out, const float* tgt, int64_t N, int A, int64_t T, int64_t t0, int64_t nsteps, int loss_type, float* delta, float* loss_part,
+                         float* step_tmp, float* group_loss, float* seq_loss, DistillScalars* ds, int train, hipStream_t st) {
+  const int64_t NA = N * A;
+  const int nblocks = (int)((NA + DISTILL_LOSS_LANES - 1) / DISTILL_LOSS_LANES);
+  hipLaunchKernelGGL(distill_loss_kernel, dim3(nblocks, (unsigned)nsteps), dim3(DISTILL_LOSS_LANES), 0, st, out, tgt, NA, T, t0, loss_type, delta, loss_part);
+  hipLaunchKernelGGL(distill_loss_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)loss_part, nblocks, nsteps, NA, step_tmp, group_loss, seq_loss, ds, train);
+}
+
 static int distill_check_call(lg_distill_train* p, const float* obs, const float* tgt, int64_t T, int64_t N, const lg_distill_train_hyper* h) {
   if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
   if (!obs || !tgt || !h) return lg_policy_fail(LG_ERR_INVALID, "null observations, targets or hyper-parameters");

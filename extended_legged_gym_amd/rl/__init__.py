@@ -2,7 +2,8 @@
 (LSTM / GRU memory in front of each MLP), `compute_returns`, `collect_rollout`; teacher-student distillation: `NativeStudentTeacher`, `NativeStudentTeacherRecurrent`,
 `collect_distillation`, `obs_history_step`; the terrain estimator (depth image -> ray distances): `NativeTerrainEstimator`, `NativeConvEncoder`, `collect_estimation`;
 the training side: `NativePPO` (`PPO.update` on the device, include/lgtrain.h), `NativeRecurrentPPO` (the same through the LSTM / GRU memories,
-include/lgtrain_recurrent.h), `NativeDistillation` (`Distillation.update`, include/lgdistill.h) and `NativeEstimatorDistillation`
+include/lgtrain_recurrent.h), `NativeDistillation` (`Distillation.update`, include/lgdistill.h), `NativeRecurrentDistillation` (the same for the
+recurrent student: truncated BPTT through its memory, include/lgdistill_recurrent.h) and `NativeEstimatorDistillation`
 (`EstimatorDistillation.update`: the terrain estimator's conv backward, truncated BPTT and Adam, include/lgestimator_train.h)."""
 from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
                      NativeStudentTeacher, NativeStudentTeacherRecurrent)
@@ -12,4 +13,5 @@ from .estimator import NativeConvEncoder, NativeTerrainEstimator, parse_estimato
 from .ppo import NativePPO          # noqa: F401
 from .ppo_recurrent import NativeRecurrentPPO          # noqa: F401
 from .distillation import NativeDistillation          # noqa: F401
+from .distillation_recurrent import NativeRecurrentDistillation          # noqa: F401
 from .estimator_distillation import NativeEstimatorDistillation          # noqa: F401

@@ -11,7 +11,8 @@
  * may straddle an epoch boundary: one optimiser step on the gradient of the SUM of the group's losses, i.e. one batch of G * N rows.  The trailing
  * (E * T) mod G steps train nothing; they are run forward with the final weights and count in the reported mean.
  *
- * Not built, refused by the Python layer: a recurrent student (truncated BPTT), multi-GPU reduction.
+ * The recurrent student (StudentTeacherRecurrent: truncated BPTT through its memory) has a trainer of its own, lgdistill_recurrent.h.  Not built,
+ * refused by the Python layer: multi-GPU reduction.
  * Equal inputs give equal bits: no atomics anywhere; every sum has a fixed order (per step: block order; across steps: step order). */
 #ifndef LGDISTILL_H
 #define LGDISTILL_H

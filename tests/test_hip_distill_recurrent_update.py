@@ -1,0 +1,434 @@
+"""The native distillation update of the recurrent student (include/lgdistill_recurrent.h, `rl.NativeRecurrentDistillation`) on the GPU against
+tests/distill_recurrent_reference.py in float64.
+
+The bar is the one of tests/test_hip_ppo_update.py, measured and not guessed: torch's own fp32 CPU autograd on the same inputs deviates from float64
+by e32(t) per tensor (e(t) = max|t - t64| / max|t64|); the kernels may deviate by at most max(8 e32(t), 2e-5).  Every figure is printed before it is
+asserted.  tests/test_distill_recurrent_update_reference.py shows, without a GPU, that this bar sees the ways these kernels can go wrong."""
+import numpy as np
+import pytest
+import torch
+
+from tests import distill_recurrent_reference as ref
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+RNNS = ["lstm", "gru"]
+
+
+def _slab():
+    from extended_legged_gym_amd import abi
+    from extended_legged_gym_amd.rl.policy import _lib
+    return int(abi.declare_train(_lib()).lg_ppo_wgrad_slab_rows())
+
+
+def _full_state(case, state=None, teacher_recurrent=False, seed=5):
+    """A `StudentTeacherRecurrent` state dict around the case's trained tensors: a small seeded teacher (and its memory) and std."""
+    g = torch.Generator().manual_seed(seed + case.salt)
+    tin = case.H if teacher_recurrent else case.S
+    sd = dict(state if state is not None else case.state())
+    sd.update({"teacher.0.weight": 0.2 * torch.randn(24, tin, generator=g), "teacher.0.bias": 0.1 * torch.randn(24, generator=g),
+               "teacher.2.weight": 0.2 * torch.randn(case.A, 24, generator=g), "teacher.2.bias": 0.1 * torch.randn(case.A, generator=g),
+               "std": 0.1 * torch.ones(case.A)})
+    if teacher_recurrent:
+        cls = torch.nn.LSTM if case.rnn == "lstm" else torch.nn.GRU
+        torch.manual_seed(seed)
+        sd.update({"memory_t.rnn." + k: v.detach().clone() for k, v in cls(case.S, case.H, case.layers).state_dict().items()})
+    return sd
+
+
+def _policy(case, sd, teacher_recurrent=False):
+    from extended_legged_gym_amd.rl import NativeStudentTeacherRecurrent
+    return NativeStudentTeacherRecurrent(sd, activation=case.act, rnn_type=case.rnn, teacher_recurrent=teacher_recurrent, device=DEV, seed=11)
+
+
+def _build(case, state=None, teacher_recurrent=False, **kw):
+    from extended_legged_gym_amd.rl import NativeRecurrentDistillation
+    sd = _full_state(case, state, teacher_recurrent)
+    policy = _policy(case, sd, teacher_recurrent)
+    kw.setdefault("gradient_length", case.G)
+    kw.setdefault("loss_type", case.loss)
+    return policy, NativeRecurrentDistillation(policy, sd, **kw)
+
+
+def _cuda(rows):
+    return {k: v.to(DEV) for k, v in rows.items()}
+
+
+def _dev(state):
+    return tuple(s.to(DEV) for s in state) if isinstance(state, tuple) else state.to(DEV)
+
+
+def _within(name, e, e32):
+    bar = ref.bar(e32)
+    print(f"{name}: e {e:.3e}  e32 {e32:.3e}  e/e32 {e / max(e32, 1e-300):.2f}  bar {bar:.3e}")
+    return e <= bar
+
+
+def _rel(got, want):
+    return abs(float(got) - float(want)) / abs(float(want))
+
+
+def _state_err(got, want):
+    return max(ref.err(g, w) for g, w in zip(ref._each(got), ref._each(want)))
+
+
+def _states_equal(a, b):
+    for x, y in zip(ref._each(a), ref._each(b)):
+        assert torch.equal(x.cpu(), y.cpu())
+
+
+def _trained(sd):
+    return {k: v for k, v in sd.items() if k.startswith("student.") or k.startswith("memory_s.")}
+
+
+# ------------------------------------------------------------------------------------------------------------ 1. one group against float64
+@pytest.mark.parametrize("rnn", RNNS)
+@pytest.mark.parametrize("index", range(4), ids=["h40_n7_g3", "h16_n16_g1", "h40_slab_g7", "carry_dones"])
+def test_group_gradients_against_float64(index, rnn):
+    """Every tensor's gradient before the clip, both norms and each step loss within the bar; the trainer's forward outputs bit-equal to
+    `policy.act_inference` stepped over the same rows from the same state with `policy.reset(dones[t])` after each step.  The single-step case and
+    the carry case enter from a seeded non-zero state (so that weight_hh has a gradient in a group of one step)."""
+    case = ref.group_cases(_slab(), rnn)[index]
+    carry = ref.carry_of(case) if case.name.endswith(ref.CARRY_CASE) or case.G == 1 else None
+    rows = case.rows()
+    g64, n64, l64, a64, end64 = ref.group_gradients(case, torch.float64, carry=carry)
+    g32, n32, l32, _, end32 = ref.group_gradients(case, torch.float32, carry=carry)
+    assert all(float(g.abs().max()) > 0 for g in g64.values())
+    policy, alg = _build(case, max_grad_norm=ref.CLIP_SMALL)
+    if carry is not None:
+        alg.set_hidden_states(carry)
+    alg.group(_cuda(rows), 0, case.G)
+    grads, norms, losses = alg.gradients()
+    acts = alg.forward_outputs().view(case.G, case.N, case.A)
+    ok = True
+    for k in g64:
+        ok &= _within(f"{case.name} {k}", ref.err(grads[k], g64[k]), ref.err(g32[k], g64[k]))
+    ok &= _within(f"{case.name} student norm", _rel(norms[0], n64[0]), _rel(n32[0], n64[0]))
+    ok &= _within(f"{case.name} memory norm", _rel(norms[1], n64[1]), _rel(n32[1], n64[1]))
+    for s in range(case.G):
+        ok &= _within(f"{case.name} loss[{s}]", _rel(losses[s], l64[s]), _rel(l32[s], l64[s]))
+    ok &= _within(f"{case.name} running state", _state_err(alg.get_hidden_states(running=True), end64), _state_err(end32, end64))
+    print(f"{case.name} actions vs float64: {ref.err(acts, a64):.3e}")
+    # the same rows through the inference kernels of a second policy with the weights the group started from
+    live = _policy(case, _full_state(case))
+    if carry is not None:
+        live.reset(hidden_states=(_dev(carry), None))
+    crows = _cuda(rows)
+    for s in range(case.G):
+        out = live.act_inference(crows["observations"][s])
+        assert torch.equal(out.cpu(), acts[s]), f"step {s}: the trainer's forward is not act_inference's bit for bit"
+        live.reset(crows["dones"][s])
+    _states_equal(live.get_hidden_states()[0], alg.get_hidden_states(running=True))
+    alg.close()
+    assert ok
+
+
+@pytest.mark.parametrize("rnn", RNNS)
+def test_second_group_enters_with_the_running_state_as_a_constant(rnn):
+    """The update case's steps 0-2 forward only, then the group of steps 3-5 (dones at its first and last step): its gradients are those of the
+    float64 group entered from the state after steps 0-2 as a constant -- nothing crosses the group boundary."""
+    case = ref.update_case(rnn)
+    kw = dict(first_step=case.G, num_steps=case.G, pre_steps=case.G)
+    g64, n64, l64, _, _ = ref.group_gradients(case, torch.float64, **kw)
+    g32, n32, l32, _, _ = ref.group_gradients(case, torch.float32, **kw)
+    policy, alg = _build(case)
+    rows = _cuda(case.rows())
+    alg.group(rows, 0, case.G, train=False)
+    alg.group(rows, case.G, case.G)
+    grads, norms, losses = alg.gradients()
+    ok = True
+    for k in g64:
+        ok &= _within(f"{case.name} {k}", ref.err(grads[k], g64[k]), ref.err(g32[k], g64[k]))
+    for s in range(case.G):
+        ok &= _within(f"{case.name} loss[{s}]", _rel(losses[s], l64[s]), _rel(l32[s], l64[s]))
+    alg.close()
+    assert ok
+
+
+# ------------------------------------------------------------------------------------------------------------ 2. the optimiser step
+def _ulp(t):
+    t = t.double().abs()
+    return torch.where(t > 0, 2.0 ** (torch.floor(torch.log2(t.clamp_min(1e-300))) - 23), torch.full_like(t, 2.0 ** -149))
+
+
+@pytest.mark.parametrize("rnn", RNNS)
+@pytest.mark.parametrize("max_grad_norm", [ref.CLIP_SMALL, ref.CLIP_LARGE, None])
+def test_optimiser_step_on_the_kernels_own_gradients(max_grad_norm, rnn):
+    """`clip_and_adam` of tests/ppo_reference.py in float64 on the gradients the kernels produced, with the MLP-only clip rule, from loaded non-zero
+    moments at step 7: parameters within 1e-5 lr + 1 ulp, moments within 1e-6 relative (the figures of tests/test_hip_ppo_update.py).  One clip
+    that bites, one that does not, and no clip at all.  `memory_s.*` takes the unclipped step even when the clip bites."""
+    case = ref.group_cases(_slab(), rnn)[0]
+    lr, params = 2.5e-3, case.state()
+    policy, alg = _build(case, learning_rate=lr, max_grad_norm=max_grad_norm)
+    moments = ref.seeded_moments(params)
+    alg.load_optimizer_state(dict(parameters=params, learning_rate=lr, **moments))
+    back = alg.optimizer_state()
+    assert back["step"] == 7 and back["learning_rate"] == lr
+    for k in params:
+        assert torch.equal(back["exp_avg"][k], moments["exp_avg"][k]) and torch.equal(back["parameters"][k], params[k]), k
+        assert torch.equal(back["exp_avg_sq"][k], moments["exp_avg_sq"][k]), k
+    alg.group(_cuda(case.rows()), 0, case.G)
+    grads, norms, _ = alg.gradients()
+    print("student norm", norms[0], "memory norm", norms[1], "max_grad_norm", max_grad_norm)
+    assert ref.CLIP_SMALL < norms[0] < ref.CLIP_LARGE
+    want, wstate, used = ref.student_clip_and_adam(params, grads, moments, lr, max_grad_norm)
+    unclipped = ref.student_clip_and_adam(params, grads, moments, lr, None)[0]
+    after = alg.optimizer_state()
+    assert after["step"] == 8
+
+    def worst(target, keys):
+        return max(float(((after["parameters"][k].double() - target[k]).abs() / (1e-5 * lr + _ulp(target[k]))).max()) for k in keys)
+
+    for k in params:
+        for moment in ("exp_avg", "exp_avg_sq"):
+            assert float((after[moment][k].double() - wstate[moment][k]).abs().max()) <= 1e-6 * float(wstate[moment][k].abs().max()) + 1e-12, (moment, k)
+    memory = [k for k in params if k.startswith("memory_s.")]
+    student = [k for k in params if k.startswith("student.")]
+    print("largest |theta - theta64| / (1e-5 lr + 1 ulp):", worst(want, params), " memory_s.* against the unclipped step:", worst(unclipped, memory))
+    if max_grad_norm == ref.CLIP_SMALL:
+        print("student.* against the unclipped step (must be far):", worst(unclipped, student))
+        assert worst(unclipped, student) > 1.0
+    alg.close()
+    assert worst(want, params) <= 1.0 and worst(unclipped, memory) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------------------ 3. a whole update
+@pytest.mark.parametrize("rnn", RNNS)
+def test_whole_update_against_float64(rnn):
+    """E = 2, T = 7, G = 3: groups (0 1 2) (3 4 5) (6 0 1) (2 3 4), remainder (5 6); dones at groups' first and last steps and at T - 1; the clip
+    bites.  Step losses, the mean, both norms, the parameters and the carry; then a second update from the first one's carry on other rows."""
+    case = ref.update_case(rnn)
+    E, lr, clip = ref.UPDATE_E, ref.UPDATE_LR, ref.CLIP_SMALL
+    batches = [case.rows(), case.rows(salt=1)]
+    runs = {}
+    for dtype in (torch.float64, torch.float32):
+        model = opt = carry = None
+        trace = []
+        for b in batches:
+            r = ref.run_update(case, dtype, E=E, lr=lr, max_grad_norm=clip, carry=carry, model=model, optimizer=opt, rows=b)
+            model, opt, carry = r["model"], r["optimizer"], r["carry"]
+            trace.append(dict(r, params={k: v.detach().clone() for k, v in model.state_dict().items()}))
+        runs[dtype] = trace
+    policy, alg = _build(case, num_learning_epochs=E, learning_rate=lr, max_grad_norm=clip)
+    ok = True
+    for u, b in enumerate(batches):
+        out = alg.update(_cuda(b))
+        r64, r32 = runs[torch.float64][u], runs[torch.float32][u]
+        assert alg.optimizer_steps == r64["steps"] == 4
+        assert r64["grad_norm"] > clip
+        losses = alg.step_losses()
+        for s in range(E * case.T):
+            ok &= _within(f"update {u} loss[{s}]", _rel(losses[s], r64["losses"][s]), _rel(r32["losses"][s], r64["losses"][s]))
+        ok &= _within(f"update {u} mean", _rel(out["behavior"], r64["mean"]), _rel(r32["mean"], r64["mean"]))
+        ok &= _within(f"update {u} grad_norm", _rel(alg.grad_norm, r64["grad_norm"]), _rel(r32["grad_norm"], r64["grad_norm"]))
+        ok &= _within(f"update {u} memory_grad_norm", _rel(alg.memory_grad_norm, r64["memory_grad_norm"]), _rel(r32["memory_grad_norm"], r64["memory_grad_norm"]))
+        sd = alg.state_dict()
+        for k, v in r64["params"].items():
+            ok &= _within(f"update {u} {k}", ref.err(sd[k], v), ref.err(r32["params"][k], v))
+        ok &= _within(f"update {u} carry", _state_err(alg.get_hidden_states(), r64["carry"]), _state_err(r32["carry"], r64["carry"]))
+    assert alg.num_updates == 2
+    alg.close()
+    assert ok
+
+
+@pytest.mark.parametrize("name", sorted(ref.GOLDEN_CASES))
+def test_update_against_the_references_own(name):
+    """tests/golden/distillation_recurrent_update.npz: the reference's `Distillation` + `StudentTeacherRecurrent` on torch-CPU, two collect-and-update
+    rounds, in float64 (what the update is held to) and in float32 (whose gap to float64 is the e32 of the bar)."""
+    G, cfg, z = ref.GOLDEN, ref.GOLDEN_CASES[name], ref.golden(name)
+    from extended_legged_gym_amd.rl import NativeRecurrentDistillation, NativeStudentTeacherRecurrent
+    case = ref.Case(name, S=G["S"], H=G["H"], layers=G["layers"], mlp=G["mlp"], A=G["A"], N=G["N"], G=G["G"], T=G["T"], rnn=cfg["rnn"], loss=G["loss"])
+    sd0 = ref.golden_state(z)
+    policy = NativeStudentTeacherRecurrent(sd0, activation="elu", rnn_type=cfg["rnn"], teacher_recurrent=cfg["teacher_recurrent"], device=DEV, seed=3)
+    alg = NativeRecurrentDistillation(policy, sd0, num_learning_epochs=G["E"], gradient_length=G["G"], learning_rate=G["lr"], max_grad_norm=ref.CLIP_SMALL,
+                                      loss_type=G["loss"])
+    ok = True
+    for r in range(G["rounds"]):
+        rows = ref.golden_rows(z, r, "f32")
+        # the collection of the round, through the policy's own memories (the targets fed to the update are the record's, so that only the update is judged)
+        for t in range(G["T"]):
+            policy.act_and_teach(rows["observations"][t].to(DEV), rows["teacher_observations"][t].to(DEV))
+            policy.reset(rows["dones"][t].to(DEV))
+        out = alg.update(_cuda(rows))
+        w64 = {k[len(f"r{r}.f64."):]: v for k, v in z.items() if k.startswith(f"r{r}.f64.")}
+        w32 = {k[len(f"r{r}.f32."):]: v for k, v in z.items() if k.startswith(f"r{r}.f32.")}
+        losses = alg.step_losses()
+        for s in range(len(w64["step_losses"])):
+            ok &= _within(f"{name} round {r} loss[{s}]", _rel(losses[s], w64["step_losses"][s]), _rel(w32["step_losses"][s], w64["step_losses"][s]))
+        ok &= _within(f"{name} round {r} returned loss", _rel(out["behavior"], w64["loss"]), _rel(w32["loss"], w64["loss"]))
+        ok &= _within(f"{name} round {r} grad_norm", _rel(alg.grad_norm, w64["norms"][-1]), _rel(w32["norms"][-1], w64["norms"][-1]))
+        sd = alg.state_dict()
+        for k in _trained(sd):
+            ok &= _within(f"{name} round {r} {k}", ref.err(sd[k], w64["sd." + k]), ref.err(w32["sd." + k], w64["sd." + k]))
+        carry, live = ref.state_parts(alg.get_hidden_states()), policy.get_hidden_states()
+        for part, v in carry.items():
+            ok &= _within(f"{name} round {r} carry.{part}", ref.err(v, w64["carry." + part]), ref.err(w32["carry." + part], w64["carry." + part]))
+            ok &= _within(f"{name} round {r} hidden_s.{part}", ref.err(ref.state_parts(live[0])[part], w64["hidden_s." + part]),
+                          ref.err(w32["hidden_s." + part], w64["hidden_s." + part]))
+        assert live[1] is None and int(w64["hidden_t.present"]) == 0          # the teacher's memory is forgotten, as in the record
+        rest = {k: v for k, v in sd.items() if k not in _trained(sd)}
+        assert rest and all(torch.equal(v, sd0[k]) for k, v in rest.items())          # teacher.*, memory_t.*, std as given
+    alg.close()
+    assert ok
+
+
+# ------------------------------------------------------------------------------------------------------------ 4. the in-place contract
+@pytest.mark.parametrize("rnn,tr", [("lstm", True), ("gru", False)])
+def test_update_moves_the_live_policy_in_place(rnn, tr):
+    """After `update`, `policy.act_inference` on fresh rows is bit-equal to a new policy built from `alg.state_dict()` and given the same hidden
+    state; the student memory's live state is the trainer's carry; the teacher memory's is forgotten, so the next `evaluate` starts it from zeros."""
+    case = ref.update_case(rnn)
+    policy, alg = _build(case, teacher_recurrent=tr, num_learning_epochs=ref.UPDATE_E, learning_rate=ref.UPDATE_LR, max_grad_norm=ref.CLIP_SMALL)
+    rows = _cuda(case.rows())
+    for t in range(case.T):          # a lived rollout: both memories hold state before the update
+        policy.act_and_teach(rows["observations"][t], rows["observations"][t])
+        policy.reset(rows["dones"][t])
+    assert (policy.get_hidden_states()[1] is not None) == tr
+    handles = (policy.student.handle, policy.memory_s.handle)
+    alg.update(rows)
+    assert (policy.student.handle, policy.memory_s.handle) == handles          # nothing was rebuilt
+    carry = alg.get_hidden_states()
+    live_s, live_t = policy.get_hidden_states()
+    _states_equal(live_s, carry)
+    assert live_t is None and float(ref._each(carry)[0].abs().max()) > 0
+    sd = alg.state_dict()
+    fresh = _policy(case, sd, tr)
+    fresh.reset(hidden_states=(carry, None))
+    probe = _cuda(case.rows(salt=2))["observations"]
+    for t in range(3):
+        assert torch.equal(policy.act_inference(probe[t]), fresh.act_inference(probe[t])), t
+    old = _policy(case, _full_state(case, teacher_recurrent=tr), tr)
+    assert not torch.equal(_policy_probe(old, carry, probe[0]), _policy_probe(fresh, carry, probe[0]))          # the update moved the weights
+    # the teacher: its memory restarts from zeros, its weights are the given ones
+    zero = _policy(case, _full_state(case, teacher_recurrent=tr), tr)
+    assert torch.equal(policy.evaluate(probe[0]), zero.evaluate(probe[0]))
+    alg.close()
+
+
+def _policy_probe(policy, carry, obs):
+    policy.reset(hidden_states=(carry, None))
+    return policy.act_inference(obs)
+
+
+def test_collect_update_collect_without_a_rebuild():
+    """`collect_distillation` -> `update` -> `collect_distillation` at N = 16, T = 4 on `anymal_c_flat`'s 48 observations: the same policy object
+    and handles throughout; the second rollout was acted by the updated student from the carried state."""
+    from extended_legged_gym_amd.rl import collect_distillation
+    from tests.test_env_api import make
+    N, T = 16, 4
+    env = make("anymal_c_flat", N, seed=5)
+    case = ref.Case("flat", S=48, H=40, layers=2, mlp=(32, 16), A=12, N=N, G=3, T=T, rnn="lstm", salt=9)
+    policy, alg = _build(case, num_learning_epochs=2, learning_rate=1e-3, max_grad_norm=1.0)
+    handles = (policy.student.handle, policy.memory_s.handle)
+    env.reset()
+    rows1 = collect_distillation(env, policy, T)
+    loss1 = alg.update(rows1)
+    trainer = alg.handle
+    carry = alg.get_hidden_states()
+    sd1 = alg.state_dict()
+    rows2 = collect_distillation(env, policy, T)
+    _states_equal(rows2["hidden_states"][0], carry)          # the state before step 0 of the second rollout
+    fresh = _policy(case, sd1)          # the trained weights from the carried state over the second rollout's rows: the live memory's end state
+    fresh.reset(hidden_states=(carry, None))
+    for t in range(T):
+        fresh.act_inference(rows2["observations"][t])
+        fresh.reset(rows2["dones"][t])
+    _states_equal(fresh.get_hidden_states()[0], policy.get_hidden_states()[0])
+    loss2 = alg.update(rows2)
+    print("losses", loss1, loss2, "optimiser steps", alg.optimizer_steps, "norms", alg.grad_norm, alg.memory_grad_norm)
+    assert (policy.student.handle, policy.memory_s.handle) == handles and alg.handle == trainer
+    assert all(np.isfinite(x["behavior"]) for x in (loss1, loss2)) and alg.optimizer_steps == 2 and alg.optimizer_state()["step"] == 4
+    alg.close()
+    env.core.close()
+
+
+# ------------------------------------------------------------------------------------------------------------ 5. determinism and round trip
+def _state_equal(a, b):
+    assert a["step"] == b["step"] and a["learning_rate"] == b["learning_rate"]
+    for part in ("parameters", "exp_avg", "exp_avg_sq"):
+        for k in a[part]:
+            assert torch.equal(a[part][k], b[part][k]), (part, k)
+
+
+@pytest.mark.parametrize("rnn", RNNS)
+def test_update_is_deterministic_and_equals_the_loop_of_groups(rnn):
+    case = ref.update_case(rnn)
+    E, T, G, rows = ref.UPDATE_E, case.T, case.G, _cuda(case.rows())
+    kw = dict(num_learning_epochs=E, learning_rate=4e-3, max_grad_norm=ref.CLIP_SMALL)
+    (p1, one), (p2, two), (p3, loop) = (_build(case, **kw) for _ in range(3))
+    loss1, loss2 = one.update(rows), two.update(rows)
+    k = 0
+    while E * T - k >= G:
+        loop.group(rows, k, G)
+        k += G
+    loop.group(rows, k, E * T - k, train=False)
+    loop.set_hidden_states(loop.get_hidden_states(running=True))
+    assert loss1 == loss2
+    assert torch.equal(one.step_losses(), two.step_losses())
+    for other in (two, loop):
+        _state_equal(one.optimizer_state(), other.optimizer_state())
+        _states_equal(one.get_hidden_states(), other.get_hidden_states())
+    assert one.update(rows) == two.update(rows)          # a second update from the carried state, again bit for bit
+    _state_equal(one.optimizer_state(), two.optimizer_state())
+    _states_equal(one.get_hidden_states(), two.get_hidden_states())
+    # optimizer_state() -> load_optimizer_state() -> the same group: bit-equal gradients
+    state, carry = one.optimizer_state(), one.get_hidden_states()
+    one.group(rows, 0, G)
+    g1 = one.gradients()
+    p4, again = _build(case, **kw)
+    again.load_optimizer_state(state)
+    again.set_hidden_states(carry)
+    again.group(rows, 0, G)
+    g2 = again.gradients()
+    assert g1[1] == g2[1] and g1[2] == g2[2] and all(torch.equal(g1[0][k], g2[0][k]) for k in g1[0])
+    _state_equal(one.optimizer_state(), again.optimizer_state())
+    assert one.workspace_bytes() > 0
+    for part in (one, two, loop, again):
+        part.close()
+
+
+def test_carry_rules_and_live_refusals():
+    """An update with another N than the carry's is refused until the carry is reset; the carry can be read and set; a refusal names its entry
+    point and leaves the handle usable."""
+    case = ref.update_case("gru")
+    policy, alg = _build(case)
+    assert alg.get_hidden_states() is None
+    rows = _cuda(case.rows())
+    alg.update(rows)
+    h = alg.get_hidden_states()
+    assert h.shape == (case.layers, case.N, case.H) and float(h.abs().max()) > 0
+    fewer = {k: v[:, :2].contiguous() for k, v in rows.items()}
+    with pytest.raises(Exception, match="lg_distill_rtrain_update: N is not the carry's"):
+        alg.update(fewer)
+    with pytest.raises(Exception, match="lg_distill_rtrain_set_learning_rate: learning rate <= 0"):
+        alg.set_learning_rate(0.0)
+    alg.set_hidden_states(None)
+    alg.update(fewer)
+    assert alg.get_hidden_states().shape == (case.layers, 2, case.H)
+    alg.set_hidden_states(h)
+    assert torch.equal(alg.get_hidden_states(), h)
+    alg.close()
+
+
+# ------------------------------------------------------------------------------------------------------------ 6. the training tool
+@pytest.mark.parametrize("rnn", RNNS)
+def test_train_tool_native_update_follows_the_torch_update(rnn):
+    """`tools/train_distill.py --student recurrent`, `--update native` against `--update torch`, 64 envs, noise off, the same seed: iteration 0 runs
+    both updates from the same weights on the same rows, its loss within the bar's 2e-5 floor.  Later iterations are two closed loops: each starts
+    from weights its own fp32 Adam history produced (a first step is +-lr whatever the gradient's size, so a gradient near zero may move a weight by
+    2 lr on one side only) and collects its rows by acting with them.  That is no precision statement; they are only held to following each other
+    within a tenth."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import train_distill
+    from tests.test_hip_distillation import STUDENT_ENV
+    over = [f"{k}={v!r}" for k, v in dict(STUDENT_ENV, **{"noise.add_noise": False}).items()]
+    kw = dict(envs=64, iters=3, seed=3, overrides=over, log=lambda *a: None, student="recurrent", rnn_type=rnn, rnn_hidden=40, rnn_layers=2)
+    native, module = train_distill.run(update="native", **kw)
+    eager, _ = train_distill.run(update="torch", **kw)
+    print("behaviour loss, native update:", native, " torch update:", eager)
+    assert len(native) == 3 and all(np.isfinite(native)) and native[0] > 0
+    assert any(k.startswith("memory_s.rnn.") for k in module.state_dict())
+    assert _rel(native[0], eager[0]) <= 2e-5
+    assert all(_rel(a, b) <= 1e-1 for a, b in zip(native, eager))
