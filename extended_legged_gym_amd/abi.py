@@ -413,6 +413,59 @@ def declare_train(lib):
     return lib
 
 
+class lg_ppo_sym_tables(C.Structure):
+    """include/lgtrain_symmetry.h: HOST signed-permutation tables, (num_blocks, width) each."""
+    _fields_ = ([(k, i32) for k in ("num_blocks", "observation_width", "critic_observation_width", "action_width")] +
+                [(k, C.c_void_p) for k in ("observation_perm", "observation_sign", "critic_observation_perm", "critic_observation_sign", "action_perm",
+                                           "action_sign")])
+
+
+class lg_ppo_sym_config(C.Structure):
+    """include/lgtrain_symmetry.h: the symmetry option of PPO."""
+    _fields_ = [("use_data_augmentation", i32), ("use_mirror_loss", i32), ("mirror_loss_coeff", f32)]
+
+
+class lg_ppo_sym_stats(C.Structure):
+    """include/lgtrain_symmetry.h: lg_ppo_stats and the symmetry mean (float64, device memory)."""
+    _fields_ = [(k, C.c_double) for k in ("value_function", "surrogate", "entropy", "kl", "learning_rate", "symmetry")]
+
+
+SYMMETRY_MAX_BLOCKS = 4          # LG_PPO_SYM_MAX_BLOCKS
+
+
+def declare_train_symmetry(lib):
+    """Prototypes of the symmetric PPO trainer (include/lgtrain_symmetry.h), same library."""
+    vp, fpp, i64 = C.c_void_p, C.POINTER(C.POINTER(f32)), C.c_int64
+    lib.lg_ppo_sym_create.argtypes = [vp, vp, fpp, fpp, fpp, fpp, vp, i32, C.c_double, i64, vp, C.POINTER(lg_ppo_sym_tables), C.POINTER(lg_ppo_sym_config)]
+    lib.lg_ppo_sym_create.restype = vp
+    lib.lg_ppo_sym_destroy.argtypes = [vp]
+    lib.lg_ppo_sym_destroy.restype = None
+    lib.lg_ppo_sym_minibatch.argtypes = [vp, C.POINTER(lg_ppo_rows), vp, i64, C.POINTER(lg_ppo_hyper), vp]
+    lib.lg_ppo_sym_minibatch.restype = C.c_int
+    lib.lg_ppo_sym_update.argtypes = [vp, C.POINTER(lg_ppo_rows), i64, vp, i32, i32, C.POINTER(lg_ppo_hyper), vp, vp]
+    lib.lg_ppo_sym_update.restype = C.c_int
+    lib.lg_ppo_sym_parameter_count.argtypes = [vp]
+    lib.lg_ppo_sym_parameter_count.restype = i64
+    lib.lg_ppo_sym_gradients.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.lg_ppo_sym_gradients.restype = C.c_int
+    lib.lg_ppo_sym_forward_outputs.argtypes = [vp, vp, vp, vp]
+    lib.lg_ppo_sym_forward_outputs.restype = C.c_int
+    lib.lg_ppo_sym_get_parameters.argtypes = [vp, vp, vp]
+    lib.lg_ppo_sym_get_parameters.restype = C.c_int
+    lib.lg_ppo_sym_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
+    lib.lg_ppo_sym_get_state.restype = C.c_int
+    lib.lg_ppo_sym_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
+    lib.lg_ppo_sym_set_state.restype = C.c_int
+    lib.lg_ppo_sym_set_learning_rate.argtypes = [vp, C.c_double, vp]
+    lib.lg_ppo_sym_set_learning_rate.restype = C.c_int
+    return lib
+
+
+SYMMETRY_TRAIN_SYMBOLS = ["lg_ppo_sym_create", "lg_ppo_sym_destroy", "lg_ppo_sym_minibatch", "lg_ppo_sym_update", "lg_ppo_sym_parameter_count",
+                          "lg_ppo_sym_gradients", "lg_ppo_sym_forward_outputs", "lg_ppo_sym_get_parameters", "lg_ppo_sym_get_state", "lg_ppo_sym_set_state",
+                          "lg_ppo_sym_set_learning_rate"]
+
+
 class lg_ppo_recurrent_params(C.Structure):
     """include/lgtrain_recurrent.h: HOST parameters of an ActorCriticRecurrent in torch's layout, and the shapes they were taken from."""
     _fields_ = ([(k, i32) for k in ("rnn_type", "num_layers", "input_a", "hidden_a", "input_c", "hidden_c")] +

@@ -28,8 +28,6 @@
 #include "lg_train_internal.h"
 #include "../../include/lgtrain.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #define LOSS_ROWS 256         // rows per block of the loss kernel
 #define LOSS_SLOTS 36         // surrogate, value, (entropy), KL, then up to 32 sigma gradients
 
@@ -70,17 +68,6 @@ LG_DEV void stage_rows(const float* __restrict__ src, const int64_t* __restrict_
       const int e = base + u * MLP_THREADS + tid, r = e / Kp, k = e - r * Kp;
       if (e < MLP_ROWS * Kp) img[IMG(r, k)] = v[u];
     }
-  }
-}
-
-// one 16-column chunk over nblk blocks of 16 inputs: both row halves, k ascending (the chain order of mlp_tile)
-LG_DEV void chunk_chain(const float4* __restrict__ wc, const float4* ap, int nblk, f32x4& acc0, f32x4& acc1) {
-  for (int kb = 0; kb < nblk; ++kb) {
-    const float4 w = wc[(size_t)kb * 64], p = ap[kb * 128], q = ap[kb * 128 + 64];
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.x, w.x, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.x, w.x, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.y, w.y, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.y, w.y, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.z, w.z, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.z, w.z, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.w, w.w, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.w, w.w, acc1, 0, 0, 0);
   }
 }
 
@@ -478,6 +465,11 @@ void train_launch_backward(const TrainCore* c, int64_t n, hipStream_t st) {
   bool any = false;
   for (int k = 0; k < c->nnet; ++k) any |= c->net[k].L > 1;
   if (any) hipLaunchKernelGGL(ppo_backward_kernel, dim3(tiles, c->nnet), dim3(MLP_THREADS), 0, st, c->net[0], c->net[c->nnet - 1], n);
+}
+
+void train_launch_backward_net(const TrainCore* c, int k, int64_t n, hipStream_t st) {
+  const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
+  if (c->net[k].L > 1) hipLaunchKernelGGL(ppo_backward_kernel, dim3(tiles, 1), dim3(MLP_THREADS), 0, st, c->net[k], c->net[k], n);
 }
 
 int train_launch_optimise(TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, float max_grad_norm, int clip_on, hipStream_t st) {

@@ -1,5 +1,5 @@
 // lg_train_internal.h — what the trainers share (lg_train.hip: PPO over two networks; lg_distill_train.hip: distillation over one;
-// lg_train_recurrent.hip: PPO over two networks behind two memories): the
+// lg_train_recurrent.hip: PPO over two networks behind two memories; lg_train_symmetry.hip: PPO with symmetry tables, its own staging kernels): the
 // description of a network and of a (network, layer) segment as the kernels of lg_train.hip see them, the scalars the optimiser keeps on the
 // device, and the host calls that size the workspaces and launch those kernels.  The kernels themselves live in lg_train.hip only.
 #pragma once
@@ -71,6 +71,19 @@ LG_DEV float block_sum_256(float x, float* red) {
   return red[0];
 }
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// one 16-column chunk over nblk blocks of 16 inputs: both row halves, k ascending (the chain order of mlp_tile)
+LG_DEV void chunk_chain(const float4* __restrict__ wc, const float4* ap, int nblk, f32x4& acc0, f32x4& acc1) {
+  for (int kb = 0; kb < nblk; ++kb) {
+    const float4 w = wc[(size_t)kb * 64], p = ap[kb * 128], q = ap[kb * 128 + 64];
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.x, w.x, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.x, w.x, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.y, w.y, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.y, w.y, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.z, w.z, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.z, w.z, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p.w, w.w, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.w, w.w, acc1, 0, 0, 0);
+  }
+}
+
 // a device allocation the core owns (train_core_free releases it); NULL + message on failure
 void* train_alloc(TrainCore* c, size_t bytes, bool zero);
 // appends `net`: its transposed tilings, the activation / delta workspaces for c->max_rows rows, one segment per layer at offset *off of the flat
@@ -84,6 +97,8 @@ void train_core_free(TrainCore* c);
 // forward with saved activations over the rows obs[idx[0 .. n)] (cobs: the second network's rows), and the backward data pass from d[L - 1]
 void train_launch_forward(const TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, hipStream_t st);
 void train_launch_backward(const TrainCore* c, int64_t n, hipStream_t st);
+// the backward data pass of network k alone, for a trainer whose networks do not share a row count (lg_train_symmetry.hip)
+void train_launch_backward_net(const TrainCore* c, int k, int64_t n, hipStream_t st);
 // weight gradients by slabs, their reduction, the global norm (clip_on == 0: the norm is reported and the gradient passes unscaled), Adam and the
 // rewrite of the tilings.  idx must not be NULL.
 int train_launch_optimise(TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, float max_grad_norm, int clip_on, hipStream_t st);

@@ -2,7 +2,8 @@
 (LSTM / GRU memory in front of each MLP), `compute_returns`, `collect_rollout`; teacher-student distillation: `NativeStudentTeacher`, `NativeStudentTeacherRecurrent`,
 `collect_distillation`, `obs_history_step`; the terrain estimator (depth image -> ray distances): `NativeTerrainEstimator`, `NativeConvEncoder`, `collect_estimation`;
 the training side: `NativePPO` (`PPO.update` on the device, include/lgtrain.h), `NativeRecurrentPPO` (the same through the LSTM / GRU memories,
-include/lgtrain_recurrent.h), `NativeDistillation` (`Distillation.update`, include/lgdistill.h), `NativeRecurrentDistillation` (the same for the
+include/lgtrain_recurrent.h), `NativeSymmetricPPO` (`NativePPO` with `symmetry_cfg`: symmetric data augmentation and the mirror loss,
+include/lgtrain_symmetry.h; `signed_permutation_tables` turns a `data_augmentation_func` into its tables), `NativeDistillation` (`Distillation.update`, include/lgdistill.h), `NativeRecurrentDistillation` (the same for the
 recurrent student: truncated BPTT through its memory, include/lgdistill_recurrent.h) and `NativeEstimatorDistillation`
 (`EstimatorDistillation.update`: the terrain estimator's conv backward, truncated BPTT and Adam, include/lgestimator_train.h)."""
 from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
@@ -12,6 +13,8 @@ from .collector import collect_distillation, collect_estimation, collect_rollout
 from .estimator import NativeConvEncoder, NativeTerrainEstimator, parse_estimator_state          # noqa: F401
 from .ppo import NativePPO          # noqa: F401
 from .ppo_recurrent import NativeRecurrentPPO          # noqa: F401
+from .ppo_symmetry import NativeSymmetricPPO          # noqa: F401
+from .symmetry import signed_permutation_tables          # noqa: F401
 from .distillation import NativeDistillation          # noqa: F401
 from .distillation_recurrent import NativeRecurrentDistillation          # noqa: F401
 from .estimator_distillation import NativeEstimatorDistillation          # noqa: F401

@@ -45,7 +45,8 @@ class NativePPO(_NativeHandle):
         for name, value in (("normalize_advantage_per_mini_batch", normalize_advantage_per_mini_batch), ("rnd_cfg", rnd_cfg),
                             ("symmetry_cfg", symmetry_cfg), ("multi_gpu_cfg", multi_gpu_cfg)):
             if value:
-                raise NotImplementedError(f"{name} is not built in the native update")
+                hint = " (rl.NativeSymmetricPPO takes it)" if name == "symmetry_cfg" else ""
+                raise NotImplementedError(f"{name} is not built in the native update{hint}")
         if schedule not in abi.LR_SCHEDULES:
             raise ValueError(f"Unknown schedule: {schedule}. Should be 'fixed' or 'adaptive'")
         self._open(policy.device, "training")
@@ -134,7 +135,7 @@ class NativePPO(_NativeHandle):
                                        _ptr(self._stats), self._stream()), self._prefix + "update")
         st = self._stats.cpu().tolist()
         del keep
-        self.learning_rate, self.kl = st[4], st[3]
+        self.learning_rate, self.kl, self._last_stats = st[4], st[3], st
         return {"value_function": st[0], "surrogate": st[1], "entropy": st[2]}
 
     def set_learning_rate(self, learning_rate):

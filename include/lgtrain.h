@@ -6,7 +6,7 @@
  * 0 / negative status as in lgstep.h, and ONE error channel: every refusal leaves "<entry point>: <reason>" in the thread's message (read with the
  * last-error call of lgpolicy.h) and launches nothing.
  *
- * Not built, refused by the Python layer: recurrent policies, RND, symmetry augmentation, normalize_advantage_per_mini_batch, multi-GPU reduction.
+ * Not built here, refused by the Python layer: recurrent policies (lgtrain_recurrent.h), symmetry_cfg (lgtrain_symmetry.h), RND, normalize_advantage_per_mini_batch, multi-GPU reduction.
  * Equal inputs give equal bits: no atomics anywhere; every sum has a fixed order. */
 #ifndef LGTRAIN_H
 #define LGTRAIN_H
