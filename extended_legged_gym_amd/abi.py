@@ -713,3 +713,44 @@ PRODUCT_SYMBOLS = ["lg_abi_sizes", "lg_arena_bytes", "lg_create", "lg_get_tensor
                    "lg_destroy", "lg_set_extra_obs", "lg_mesh_create", "lg_mesh_destroy", "lg_mesh_info", "lg_mesh_ray_lattice", "lg_mesh_contact_lattice", "lg_mesh_last_error",
                    "lg_raycast_mesh", "lg_mesh_query_sdf", "lg_raycaster_update", "lg_depth_camera_update",
                    "lg_terrain_generate", "lg_heightfield_to_trimesh", "lg_pose_layer_step", "lg_set_reward_terms", "lg_set_async_gait", "lg_set_lattice_capsules", "lg_step_subset_physics", "lg_post_physics_subset", "lg_raycaster_update_subset", "lg_sdf_bodies_update", "lg_set_state_indexed", "lg_gather_step_rows", "lg_step_subset_rows", "lg_step_rollout", "lg_set_extra_termination", "lg_foottrack_stray", "lg_foottrack_layer_step"]
+
+
+class lg_runner_episode(C.Structure):
+    """include/lgrunner.h: device pointers of the runner's episode bookkeeping over one collection."""
+    _fields_ = [(k, C.c_void_p) for k in ("raw_rewards", "extras", "cur_reward_sum", "cur_episode_length", "ep_return", "ep_length")]
+
+
+class lg_runner_hooks(C.Structure):
+    """include/lgrunner.h: the two optional hooks of lg_runner_collect."""
+    _fields_ = [("normalizer", C.c_void_p), ("training", i32), ("episode", C.POINTER(lg_runner_episode))]
+
+
+def declare_runner(lib):
+    """Prototypes of the runner's device pieces (include/lgrunner.h), same library."""
+    vp, i64, u64 = C.c_void_p, C.c_int64, C.c_uint64
+    lib.lg_obsnorm_create.argtypes = [i32, f32, i64, C.c_int]
+    lib.lg_obsnorm_create.restype = vp
+    lib.lg_obsnorm_destroy.argtypes = [vp]
+    lib.lg_obsnorm_destroy.restype = None
+    lib.lg_obsnorm_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), vp]
+    lib.lg_obsnorm_get_state.restype = C.c_int
+    lib.lg_obsnorm_set_state.argtypes = [vp, vp, vp, vp, i64, vp]
+    lib.lg_obsnorm_set_state.restype = C.c_int
+    lib.lg_obsnorm_step.argtypes = [vp, vp, i64, i64, i32, vp, vp]
+    lib.lg_obsnorm_step.restype = C.c_int
+    lib.lg_obsnorm_inverse.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.lg_obsnorm_inverse.restype = C.c_int
+    lib.lg_obsnorm_carried.argtypes = [vp, vp, i64, vp]
+    lib.lg_obsnorm_carried.restype = C.c_int
+    lib.lg_obsnorm_forget_carried.argtypes = [vp]
+    lib.lg_obsnorm_forget_carried.restype = C.c_int
+    lib.lg_runner_collect.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, f32, f32, i32, C.POINTER(lg_rollout), C.POINTER(lg_rollout_hidden),
+                                      vp, vp, vp, vp, C.POINTER(lg_runner_hooks), vp]
+    lib.lg_runner_collect.restype = C.c_int
+    lib.lg_runner_episode_track.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, vp]
+    lib.lg_runner_episode_track.restype = C.c_int
+    return lib
+
+
+RUNNER_SYMBOLS = ["lg_obsnorm_create", "lg_obsnorm_destroy", "lg_obsnorm_get_state", "lg_obsnorm_set_state", "lg_obsnorm_step", "lg_obsnorm_inverse",
+                  "lg_obsnorm_carried", "lg_obsnorm_forget_carried", "lg_runner_collect", "lg_runner_episode_track"]

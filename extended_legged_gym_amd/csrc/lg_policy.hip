@@ -26,6 +26,7 @@
 #include "lg_policy_internal.h"
 #include "lg_rnn_tile.h"
 #include "../../include/lgpolicy.h"
+#include "../../include/lgrunner.h"
 #include "../../include/lgstep.h"
 
 // ---- the one error channel and the create functions' plumbing (lg_policy_internal.h)
@@ -581,10 +582,10 @@ int lg_policy_act_recurrent(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp*
 
 }  // extern "C"
 
-// both PPO collectors: mem_a NULL = the feed-forward ActorCritic (no memory state, no hidden-state rows)
-static int collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
-                           float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a, float* c_a,
-                           float* h_c, float* c_c, void* stream) {
+// both PPO collectors: mem_a NULL = the feed-forward ActorCritic (no memory state, no hidden-state rows); hooks: lg_policy_internal.h
+int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
+                              int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
+                              float* c_a, float* h_c, float* c_c, const CollectHooks* hooks, void* stream) {
   DeviceScope ds_(actor->device);
   if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
       !out->sigma || !out->last_values) return lg_policy_fail(LG_ERR_INVALID, "null output row");
@@ -600,9 +601,22 @@ static int collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* me
     return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (obs width, one action per DOF, scalar value)");
   hipStream_t st = (hipStream_t)stream;
   const size_t sa = mem_a ? (size_t)mem_a->num_layers * n * mem_a->hidden : 0, sc = mem_a ? (size_t)mem_c->num_layers * n * mem_c->hidden : 0;
+  // the runner's hooks: the normaliser's carried row (row 0 of this collection when it holds one, the normalised row after the last step when
+  // the loop is done), and the env's raw reward and episode-extras rows
+  lg_obsnorm* norm = hooks ? hooks->normalizer : nullptr;
+  float* carried = nullptr; bool carried_valid = false;
+  if (norm && (rc = lg_obsnorm_carried_begin(norm, n, O, &carried, &carried_valid)) != LG_OK) return rc;
+  const float* rew_buf = nullptr; const float* extras_buf = nullptr; int64_t K = 0;
+  if (hooks && (hooks->raw_rewards || hooks->extras)) {
+    void* p; int64_t shp[4]; int32_t nd, dt;
+    if (lg_get_tensor(env, LG_T_REW_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's reward rows: ") + lg_last_error(env));
+    rew_buf = (const float*)p;
+    if (lg_get_tensor(env, LG_T_EXTRAS_EPISODE, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's episode extras: ") + lg_last_error(env));
+    extras_buf = (const float*)p; K = shp[0];
+  }
   // the first observation row is copied from the env; every later one is written by the step itself (lg_step_transition),
   // as are the reward (with the time-out bootstrap) and done rows: three launches per step (act, physics, post-physics)
-  POLICY_TRY(hipMemcpyAsync(out->observations, obs, (size_t)n * O * 4, hipMemcpyDeviceToDevice, st));
+  POLICY_TRY(hipMemcpyAsync(out->observations, carried_valid ? carried : obs, (size_t)n * O * 4, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
   for (int t = 0; t < T; ++t) {
     float* obs_t = out->observations + (size_t)t * n * O;
@@ -621,9 +635,12 @@ static int collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* me
                          out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
     }
     if (rc != LG_OK) return rc;
-    rc = lg_step_transition(env, act_t, t + 1 < T ? out->observations + (size_t)(t + 1) * n * O : nullptr, out->values + (size_t)t * n, gamma,
-                            out->rewards + (size_t)t * n, dones_t, stream);
+    float* next = t + 1 < T ? out->observations + (size_t)(t + 1) * n * O : carried;
+    rc = lg_step_transition(env, act_t, next, out->values + (size_t)t * n, gamma, out->rewards + (size_t)t * n, dones_t, stream);
     if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
+    if (norm && (rc = lg_obsnorm_step(norm, next, n, O, hooks->update, next, stream)) != LG_OK) return rc;          // on_policy_runner.py:425-427
+    if (hooks && hooks->raw_rewards) POLICY_TRY(hipMemcpyAsync(hooks->raw_rewards + (size_t)t * n, rew_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (hooks && hooks->extras) POLICY_TRY(hipMemcpyAsync(hooks->extras + (size_t)t * K, extras_buf, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
     if (mem_a) {                                       // PPO.process_env_step ends with policy.reset(dones) (ppo.py:188)
       rc = lg_rnn_reset_rows(mem_a, h_a, c_a, dones_t, n, stream);
       if (rc == LG_OK) rc = lg_rnn_reset_rows(mem_c, h_c, c_c, dones_t, n, stream);
@@ -631,9 +648,9 @@ static int collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* me
     }
   }
   // last_values = critic(last obs) (ppo.py:186-192); a recurrent policy.evaluate goes through Memory.forward, so the critic memory advances once more
-  const float* last = obs;
+  const float* last = norm ? carried : obs;
   if (mem_a) {
-    rc = lg_rnn_step(mem_c, obs, n, h_c, c_c, nullptr, nullptr, stream);
+    rc = lg_rnn_step(mem_c, last, n, h_c, c_c, nullptr, nullptr, stream);
     if (rc != LG_OK) return rc;
     last = h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden;
   }
@@ -643,6 +660,7 @@ static int collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* me
                             out->advantages, stream);
   if (rc != LG_OK) return rc;
   POLICY_TRY(hipGetLastError());
+  if (norm) lg_obsnorm_carried_commit(norm);
   return LG_OK;
 }
 
@@ -652,8 +670,8 @@ int lg_collect_rollout(lg_ctx* env, lg_mlp* actor, lg_mlp* critic, const float* 
                        float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, void* stream) {
   POLICY_ENTRY;
   if (!env || !actor || !critic || !std || !out || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
-  return collect_rollout(env, nullptr, actor, nullptr, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, stream);
+  return lg_policy_collect_rollout(env, nullptr, actor, nullptr, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, nullptr, nullptr,
+                                   nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int lg_collect_rollout_recurrent(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
@@ -661,7 +679,8 @@ int lg_collect_rollout_recurrent(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_r
                                  float* h_a, float* c_a, float* h_c, float* c_c, void* stream) {
   POLICY_ENTRY;
   if (!env || !mem_a || !mem_c || !actor || !critic || !std || !out || !hid || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
-  return collect_rollout(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c, stream);
+  return lg_policy_collect_rollout(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c,
+                                   nullptr, stream);
 }
 
 }  // extern "C"

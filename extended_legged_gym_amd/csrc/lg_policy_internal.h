@@ -34,6 +34,23 @@ int lg_policy_device_of(const void* p);
 void lg_mlp_widths(const lg_mlp* m, int* layers, int* in, int* out, int* device);
 void lg_rnn_widths(const lg_rnn* m, int* type, int* input, int* hidden, int* device);
 
+// ---- both PPO collectors (lg_policy.hip; mem_a NULL = the feed-forward ActorCritic), shared with the runner's collector (lg_runner.hip), which
+// passes hooks.  hooks NULL: the loop of lg_collect_rollout / lg_collect_rollout_recurrent, launch for launch.
+struct lg_obsnorm;
+struct CollectHooks {
+  lg_obsnorm* normalizer = nullptr;  // every new observation row passes lg_obsnorm_step in place; the row after the last step is the handle's carried row
+  int update = 0;                    // the normaliser's training mode
+  float* raw_rewards = nullptr;      // (T, n): the env's rew_buf after each step
+  float* extras = nullptr;           // (T, K): the env's extras_episode after each step
+};
+int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
+                              int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
+                              float* c_a, float* h_c, float* c_c, const CollectHooks* hooks, void* stream);
+// the carried row of a normaliser (lg_runner.hip): begin returns the (n, O) buffer (allocated on first use) and whether it holds a row, and marks it
+// as not holding one; commit marks it as holding the row the collector left there
+int lg_obsnorm_carried_begin(lg_obsnorm* h, int64_t n, int64_t O, float** row, bool* valid);
+void lg_obsnorm_carried_commit(lg_obsnorm* h);
+
 // ---- the network handle, shared with the trainer (lg_train.hip), which rewrites the device buffers of an lg_mlp in place
 #define MLP_ROWS 32          // batch rows per workgroup
 #define MLP_THREADS 512      // eight waves: two per SIMD

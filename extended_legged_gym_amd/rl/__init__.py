@@ -5,11 +5,14 @@ the training side: `NativePPO` (`PPO.update` on the device, include/lgtrain.h), 
 include/lgtrain_recurrent.h), `NativeSymmetricPPO` (`NativePPO` with `symmetry_cfg`: symmetric data augmentation and the mirror loss,
 include/lgtrain_symmetry.h; `signed_permutation_tables` turns a `data_augmentation_func` into its tables), `NativeDistillation` (`Distillation.update`, include/lgdistill.h), `NativeRecurrentDistillation` (the same for the
 recurrent student: truncated BPTT through its memory, include/lgdistill_recurrent.h) and `NativeEstimatorDistillation`
-(`EstimatorDistillation.update`: the terrain estimator's conv backward, truncated BPTT and Adam, include/lgestimator_train.h)."""
+(`EstimatorDistillation.update`: the terrain estimator's conv backward, truncated BPTT and Adam, include/lgestimator_train.h); the runner:
+`NativeOnPolicyRunner` (rsl_rl's `OnPolicyRunner` surface over these pieces), `NativeEmpiricalNormalization` (`empirical_normalization` on the device) and
+`collect_rollout_tracked` / `EpisodeTracker` (the collection with the normaliser and the episode bookkeeping between its launches, include/lgrunner.h)."""
 from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
                      NativeStudentTeacher, NativeStudentTeacherRecurrent)
 from .storage import compute_returns                      # noqa: F401
-from .collector import collect_distillation, collect_estimation, collect_rollout, obs_history_step          # noqa: F401
+from .collector import (EpisodeTracker, collect_distillation, collect_estimation, collect_rollout, collect_rollout_tracked,          # noqa: F401
+                        obs_history_step)
 from .estimator import NativeConvEncoder, NativeTerrainEstimator, parse_estimator_state          # noqa: F401
 from .ppo import NativePPO          # noqa: F401
 from .ppo_recurrent import NativeRecurrentPPO          # noqa: F401
@@ -18,3 +21,5 @@ from .symmetry import signed_permutation_tables          # noqa: F401
 from .distillation import NativeDistillation          # noqa: F401
 from .distillation_recurrent import NativeRecurrentDistillation          # noqa: F401
 from .estimator_distillation import NativeEstimatorDistillation          # noqa: F401
+from .normalizer import NativeEmpiricalNormalization          # noqa: F401
+from .runner import NativeOnPolicyRunner          # noqa: F401

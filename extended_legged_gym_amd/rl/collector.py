@@ -57,6 +57,96 @@ def collect_rollout(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_adva
     return out
 
 
+class EpisodeTracker:
+    """The live sums of the runner's episode bookkeeping (`on_policy_runner.py:372-373`), (N) float32 on the device, and the two 100-deep buffers
+    (`:370-371`).  `collect_rollout_tracked(..., episode_tracker=...)` and `track` update the sums in place; `extend` takes a collection's finished
+    episodes in the reference's `extend` order ((t, env): `dones.nonzero()`), with one device-to-host copy."""
+
+    def __init__(self, num_envs, device="cuda:0", maxlen=100):
+        from collections import deque
+        self.device = torch.device(device)
+        self.cur_reward_sum = torch.zeros(int(num_envs), device=self.device)
+        self.cur_episode_length = torch.zeros(int(num_envs), device=self.device)
+        self.rewbuffer, self.lenbuffer = deque(maxlen=maxlen), deque(maxlen=maxlen)
+
+    def track(self, rewards, dones):
+        """`lg_runner_episode_track` (include/lgrunner.h) over (T, N) rows: per env `sum += r; len += 1; if done: emit and zero`.  Returns
+        (ep_return, ep_length), (T, N), defined where `dones > 0` (0 elsewhere)."""
+        from .normalizer import _runner_lib
+        r = rewards.to(self.device, torch.float32).reshape(rewards.shape[0], -1).contiguous()
+        d = dones.to(self.device, torch.float32).reshape(dones.shape[0], -1).contiguous()
+        assert r.shape == d.shape and r.shape[1] == self.cur_reward_sum.shape[0]
+        ep_return, ep_length = torch.empty_like(r), torch.empty_like(r)
+        _check(_runner_lib().lg_runner_episode_track(_ptr(r), _ptr(d), r.shape[0], r.shape[1], _ptr(self.cur_reward_sum), _ptr(self.cur_episode_length),
+                                                     _ptr(ep_return), _ptr(ep_length), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+               "lg_runner_episode_track")
+        return ep_return, ep_length
+
+    def extend(self, dones, ep_return, ep_length):
+        done = dones.reshape(ep_return.shape) > 0
+        both = torch.stack([ep_return[done], ep_length[done]]).cpu().numpy()
+        self.rewbuffer.extend(both[0].tolist())
+        self.lenbuffer.extend(both[1].tolist())
+
+
+def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_advantage=True, compute_returns=True, obs_normalizer=None,
+                            episode_tracker=None):
+    """`collect_rollout` through `lg_runner_collect` (include/lgrunner.h), with the runner's two device pieces between the launches of the one
+    call.  Same dict; both hooks None: the same rows, bit for bit.
+    obs_normalizer (`NativeEmpiricalNormalization`): every new observation row is normalised in place (and counted when the normaliser is in
+    training mode) before it is stored and before the next act (`on_policy_runner.py:425-427`); row 0 is the normaliser's carried row -- the
+    normalised row after the previous collection's last step -- or, when it holds none, the env's raw observation, as the first observation of
+    `learn()` (`:364-365`); `last_values` is evaluated on the new carried row.  `env.obs_buf` stays raw.
+    episode_tracker (`EpisodeTracker`): adds `raw_rewards` (T, N, 1), the env's reward without the time-out bootstrap `rewards` carries,
+    `episode_extras` (T, K), the env's `extras_episode` tensor after each step, and `ep_return` / `ep_length` (T, N, 1), defined where
+    `dones > 0`; the tracker's live sums advance in place (its buffers do not: `episode_tracker.extend(...)`)."""
+    from .normalizer import _runner_lib
+    lib = _runner_lib()
+    dev = policy.device
+    T, N, O, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
+
+    def z(*shape):
+        return torch.empty(*shape, device=dev, dtype=torch.float32)
+    out = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1),
+               actions_log_prob=z(T, N, 1), mu=z(T, N, A), sigma=z(T, N, A), last_values=z(N, 1))
+    if compute_returns:
+        out.update(returns=z(T, N, 1), advantages=z(T, N, 1))
+    rows = abi.lg_rollout(**{k: v.data_ptr() for k, v in out.items()})
+    hooks = abi.lg_runner_hooks(normalizer=obs_normalizer.handle if obs_normalizer is not None else None,
+                                training=int(obs_normalizer.training) if obs_normalizer is not None else 0)
+    if obs_normalizer is not None and obs_normalizer.num_features != O:
+        raise ValueError(f"the normaliser holds {obs_normalizer.num_features} columns, the env's observations {O}")
+    extra = {}
+    if episode_tracker is not None:
+        K = env.core.t["extras_episode"].numel()
+        assert episode_tracker.cur_reward_sum.shape == (N,) and episode_tracker.cur_reward_sum.device == out["dones"].device
+        extra = dict(raw_rewards=z(T, N, 1), episode_extras=z(T, K), ep_return=z(T, N, 1), ep_length=z(T, N, 1))
+        episode = abi.lg_runner_episode(raw_rewards=extra["raw_rewards"].data_ptr(), extras=extra["episode_extras"].data_ptr(),
+                                        cur_reward_sum=episode_tracker.cur_reward_sum.data_ptr(), cur_episode_length=episode_tracker.cur_episode_length.data_ptr(),
+                                        ep_return=extra["ep_return"].data_ptr(), ep_length=extra["ep_length"].data_ptr())
+        hooks.episode = C.pointer(episode)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    head = (_ptr(policy.std), policy.seed, policy._call + 1, T, float(gamma), float(lam), int(bool(normalize_advantage)), C.byref(rows))
+    if not getattr(policy, "is_recurrent", False):
+        _check(lib.lg_runner_collect(env.core.ctx, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None, C.byref(hooks),
+                                     stream), "lg_runner_collect")
+    else:
+        mems = (policy.memory_a, policy.memory_c)
+        stacks = []
+        for m in mems:
+            m.ensure_state(N)
+            stacks.append([torch.empty(T, m.num_layers, N, m.hidden_size, device=dev) for _ in range(2 if m.rnn_type == "lstm" else 1)])
+        ptr = [[s.data_ptr() for s in st] + [None] * (2 - len(st)) for st in stacks]
+        hidden = abi.lg_rollout_hidden(h_a=ptr[0][0], c_a=ptr[0][1], h_c=ptr[1][0], c_c=ptr[1][1])
+        _check(lib.lg_runner_collect(env.core.ctx, mems[0].handle, policy.actor.handle, mems[1].handle, policy.critic.handle, *head, C.byref(hidden),
+                                     *mems[0]._ptrs(), *mems[1]._ptrs(), C.byref(hooks), stream), "lg_runner_collect")
+        out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
+        out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
+    _advance(env, policy, T)
+    out.update(extra)
+    return out
+
+
 def obs_history_step(history, obs, dones=None, noise_scale=None, clip=float("inf"), noise_uniforms=None, seed=0, call=0):
     """`lg_obs_history_step` (include/lgpolicy.h): one step of an observation-history layer, `student_history_update` + clip
     (`envs/anymal_c/anymal.py`) in one launch.  history (N, H, W) float32 contiguous, updated IN PLACE; obs (N, >= W): its first W columns enter

@@ -1,0 +1,442 @@
+"""`NativeOnPolicyRunner`: the surface of rsl_rl's `OnPolicyRunner` (`runners/on_policy_runner.py`) over the native pieces -- the one-call
+collection with the runner's two device hooks (`collect_rollout_tracked`: observation normalisation, episode bookkeeping) and the native PPO
+updates (`NativePPO`, `NativeRecurrentPPO`, `NativeSymmetricPPO`).  It needs neither `rsl_rl` nor `tensorboard`; its checkpoints have rsl_rl's
+layout (`model_state_dict`, `optimizer_state_dict` as `torch.optim.Adam(policy.parameters()).state_dict()` holds it, `iter`, `infos`, and the two
+normaliser dicts), so either runner resumes what the other wrote.
+
+Refused by name (`NotImplementedError`): `Distillation` (tools/train_distill.py runs it), `rnd_cfg`, `multi_gpu_cfg`,
+`normalize_advantage_per_mini_batch`, policy classes other than `ActorCritic` / `ActorCriticRecurrent`, and an env whose privileged
+observations differ from its observations."""
+import json
+import os
+import statistics
+import time
+
+import torch
+
+from .collector import EpisodeTracker, collect_rollout_tracked
+from .normalizer import STATE_KEYS, NativeEmpiricalNormalization
+from .storage import compute_returns
+
+ACTIVATIONS = {"elu": torch.nn.ELU, "selu": torch.nn.SELU, "relu": torch.nn.ReLU, "lrelu": torch.nn.LeakyReLU, "tanh": torch.nn.Tanh}
+PPO_KEYS = ("num_learning_epochs", "num_mini_batches", "clip_param", "value_loss_coef", "entropy_coef", "learning_rate", "schedule", "desired_kl",
+            "max_grad_norm", "use_clipped_value_loss")
+REFUSED_ALGORITHM_OPTIONS = ("rnd_cfg", "multi_gpu_cfg", "normalize_advantage_per_mini_batch")
+
+
+# ---------------------------------------------------------------------------------------------------------------- initial weights
+def _mlp(dims, act):
+    layers = []
+    for i in range(len(dims) - 1):
+        layers.append(torch.nn.Linear(dims[i], dims[i + 1]))
+        if i < len(dims) - 2:
+            layers.append(act())
+    return torch.nn.Sequential(*layers)
+
+
+class _Memory(torch.nn.Module):
+    """`rsl_rl/networks/memory.py:16-33`: the nn.LSTM / nn.GRU under the name `rnn`."""
+
+    def __init__(self, input_size, rnn_type, hidden_size, num_layers):
+        super().__init__()
+        self.rnn = (torch.nn.GRU if rnn_type == "gru" else torch.nn.LSTM)(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
+
+
+class _ActorCritic(torch.nn.Module):
+    """The layer order and parameter names of `rsl_rl/modules/actor_critic.py:16-94` (actor, critic, then `std` / `log_std`) and, with a memory
+    in front of each MLP, of `modules/actor_critic_recurrent.py:16-60`.  Only its initial `state_dict()` is used."""
+
+    def __init__(self, num_obs, num_actions, actor_hidden_dims, critic_hidden_dims, activation, init_noise_std, noise_std_type, rnn=None):
+        super().__init__()
+        act = ACTIVATIONS[activation]
+        width = rnn["rnn_hidden_size"] if rnn else num_obs
+        self.actor = _mlp([width] + list(actor_hidden_dims) + [num_actions], act)
+        self.critic = _mlp([width] + list(critic_hidden_dims) + [1], act)
+        if noise_std_type == "scalar":
+            self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
+        elif noise_std_type == "log":
+            self.log_std = torch.nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
+        else:
+            raise ValueError(f"Unknown standard deviation type: {noise_std_type}. Should be 'scalar' or 'log'")
+        if rnn:
+            self.memory_a = _Memory(num_obs, rnn["rnn_type"], rnn["rnn_hidden_size"], rnn["rnn_num_layers"])
+            self.memory_c = _Memory(num_obs, rnn["rnn_type"], rnn["rnn_hidden_size"], rnn["rnn_num_layers"])
+
+
+def policy_noise_std_type(policy_class_name, policy_cfg):
+    """`ActorCriticRecurrent` does not hand `noise_std_type` on to `ActorCritic` (`actor_critic_recurrent.py:30-58`: an ignored argument): scalar."""
+    return "scalar" if policy_class_name == "ActorCriticRecurrent" else policy_cfg.get("noise_std_type", "scalar")
+
+
+def initial_state_dict(policy_class_name, num_obs, num_actions, policy_cfg, seed):
+    """The `state_dict()` of a freshly initialised `ActorCritic` / `ActorCriticRecurrent` (torch's default `nn.Linear` / `nn.LSTM` / `nn.GRU`
+    initialisation, drawn under `seed` without disturbing the global generator): keys `std` / `log_std`, `actor.N.*`, `critic.N.*`,
+    `memory_a.rnn.*`, `memory_c.rnn.*`, in the module's order."""
+    if policy_class_name not in ("ActorCritic", "ActorCriticRecurrent"):
+        raise NotImplementedError(f"policy_class_name {policy_class_name}: the native runner builds ActorCritic and ActorCriticRecurrent")
+    activation = policy_cfg.get("activation", "elu")
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"Unknown activation: {activation}")
+    rnn = None
+    if policy_class_name == "ActorCriticRecurrent":
+        rnn = dict(rnn_type=str(policy_cfg.get("rnn_type", "lstm")).lower(), rnn_hidden_size=int(policy_cfg.get("rnn_hidden_size", 256)),
+                   rnn_num_layers=int(policy_cfg.get("rnn_num_layers", 1)))
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(int(seed))
+        module = _ActorCritic(num_obs, num_actions, policy_cfg.get("actor_hidden_dims", [256, 256, 256]), policy_cfg.get("critic_hidden_dims", [256, 256, 256]),
+                              activation, float(policy_cfg.get("init_noise_std", 1.0)), policy_noise_std_type(policy_class_name, policy_cfg), rnn)
+    return {k: v.detach().clone() for k, v in module.state_dict().items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------- checkpoint layout (no GPU)
+def parameter_order(names):
+    """The order of `policy.parameters()` in the reference module, from any ordering of the state dict's names: the module's own parameter
+    (`std` / `log_std`) first, then `actor`, `critic`, `memory_a`, `memory_c` in registration order, each in its own order."""
+    names = list(names)
+    groups = [[n for n in names if n in ("std", "log_std")]] + [[n for n in names if n.startswith(p + ".")] for p in ("actor", "critic", "memory_a", "memory_c")]
+    ordered = [n for g in groups for n in g]
+    if sorted(ordered) != sorted(names):
+        raise KeyError(f"names outside an ActorCritic(Recurrent): {sorted(set(names) - set(ordered))}")
+    return ordered
+
+
+def _adam_group(learning_rate, count):
+    group = torch.optim.Adam([torch.nn.Parameter(torch.zeros(1))], lr=float(learning_rate)).state_dict()["param_groups"][0]
+    group["params"] = list(range(count))
+    return group
+
+
+def adam_state_dict(optimizer_state):
+    """`NativePPO.optimizer_state()` (dicts `exp_avg`, `exp_avg_sq`, `parameters` by name, `step`, `learning_rate`) -> what
+    `torch.optim.Adam(policy.parameters(), lr).state_dict()` holds: parameter i of `parameter_order`, per parameter `step` (float32 scalar),
+    `exp_avg`, `exp_avg_sq`; an optimiser that has not stepped holds no state."""
+    names = parameter_order(optimizer_state["exp_avg"].keys())
+    state = {}
+    if int(optimizer_state["step"]) > 0:
+        for i, n in enumerate(names):
+            state[i] = {"step": torch.tensor(float(optimizer_state["step"]), dtype=torch.float32),
+                        "exp_avg": optimizer_state["exp_avg"][n].detach().cpu().clone(), "exp_avg_sq": optimizer_state["exp_avg_sq"][n].detach().cpu().clone()}
+    return {"state": state, "param_groups": [_adam_group(optimizer_state["learning_rate"], len(names))]}
+
+
+def native_optimizer_state(model_state_dict, adam):
+    """The inverse: a checkpoint's `model_state_dict` and `optimizer_state_dict` -> the dict `NativePPO.load_optimizer_state` takes."""
+    names = parameter_order(model_state_dict.keys())
+    group = adam["param_groups"][0]
+    if len(adam["param_groups"]) != 1 or list(group["params"]) != list(range(len(names))):
+        raise ValueError("optimizer_state_dict: expected one parameter group over the policy's parameters in order")
+    params = {n: model_state_dict[n].detach().cpu() for n in names}
+    state, steps = adam["state"], set()
+    avg, sq = {}, {}
+    for i, n in enumerate(names):
+        entry = state.get(i)
+        if entry is None:
+            avg[n], sq[n] = torch.zeros_like(params[n]), torch.zeros_like(params[n])
+            steps.add(0)
+        else:
+            avg[n], sq[n] = entry["exp_avg"].detach().cpu().to(torch.float32), entry["exp_avg_sq"].detach().cpu().to(torch.float32)
+            steps.add(int(float(entry["step"])))
+            if avg[n].shape != params[n].shape:
+                raise ValueError(f"optimizer_state_dict: moment {i} has shape {tuple(avg[n].shape)}, parameter {n} {tuple(params[n].shape)}")
+    if len(steps) != 1:
+        raise ValueError(f"optimizer_state_dict: the parameters have different step counts {sorted(steps)}")
+    return dict(parameters=params, exp_avg=avg, exp_avg_sq=sq, step=steps.pop(), learning_rate=float(group["lr"]))
+
+
+# ---------------------------------------------------------------------------------------------------------------- logging
+class _JsonlWriter:
+    """`add_scalar` as `{"tag", "value", "step"}` lines in `log_dir/scalars.jsonl`: the writer when `tensorboard` is not importable."""
+
+    def __init__(self, log_dir):
+        os.makedirs(log_dir, exist_ok=True)
+        self.path = os.path.join(log_dir, "scalars.jsonl")
+        self._f = open(self.path, "a")
+
+    def add_scalar(self, tag, value, step):
+        self._f.write(json.dumps({"tag": tag, "value": float(value), "step": float(step) if isinstance(step, float) else int(step)}) + "\n")
+
+    def flush(self):
+        self._f.flush()
+
+    def close(self):
+        self._f.close()
+
+
+def _make_writer(log_dir):
+    try:
+        from torch.utils.tensorboard import SummaryWriter
+        return SummaryWriter(log_dir=log_dir, flush_secs=10)
+    except Exception:
+        return _JsonlWriter(log_dir)
+
+
+def _view_index(value, tensor):
+    """(True, k) when `value` is the 0-d view `tensor[k]` of a 1-d tensor, else (False, -1)."""
+    if not isinstance(value, torch.Tensor) or value.device != tensor.device or value.dim() != 0 or value.dtype != tensor.dtype:
+        return False, -1
+    k = (value.data_ptr() - tensor.data_ptr()) // tensor.element_size()
+    return (True, int(k)) if 0 <= k < tensor.numel() and (value.data_ptr() - tensor.data_ptr()) % tensor.element_size() == 0 else (False, -1)
+
+
+def steps_outside_the_library(env):
+    """True for an env class whose `step` is more than the library's one call: a device layer behind it (`_after_native`: `FootTrackElSpider`) or an
+    overridden `step` with host work around the native step (the ray caster and the depth camera between physics and post-physics, the pose layer,
+    the batch-rollout classes).  `lg_runner_collect` steps the library directly and would skip that work, so such envs collect through `env.step`."""
+    from extended_legged_gym_amd.envs.base.legged_robot import LeggedRobot
+    return hasattr(env, "_after_native") or getattr(type(env), "step", None) is not LeggedRobot.step
+
+
+# ---------------------------------------------------------------------------------------------------------------- the runner
+class NativeOnPolicyRunner:
+    def __init__(self, env, train_cfg, log_dir=None, device="cuda:0"):
+        from . import NativeActorCritic, NativeActorCriticRecurrent, NativePPO, NativeRecurrentPPO, NativeSymmetricPPO
+        self.cfg, self.alg_cfg, self.policy_cfg = dict(train_cfg["runner"]), dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
+        self.env, self.device, self.log_dir = env, torch.device(device), log_dir
+        alg_name = self.alg_cfg.pop("class_name", self.cfg.get("algorithm_class_name", "PPO"))
+        if alg_name == "Distillation":
+            raise NotImplementedError("Distillation is not run by the native runner: tools/train_distill.py drives rl.NativeDistillation")
+        if alg_name != "PPO":
+            raise NotImplementedError(f"algorithm_class_name {alg_name}: the native runner runs PPO")
+        for name in REFUSED_ALGORITHM_OPTIONS:
+            if self.alg_cfg.get(name):
+                raise NotImplementedError(f"{name} is not built in the native runner")
+        policy_name = self.policy_cfg.pop("class_name", self.cfg.get("policy_class_name", "ActorCritic"))
+        if policy_name not in ("ActorCritic", "ActorCriticRecurrent"):
+            raise NotImplementedError(f"policy_class_name {policy_name}: the native runner builds ActorCritic and ActorCriticRecurrent")
+        num_obs, num_priv = env.num_obs, getattr(env, "num_privileged_obs", None)
+        if num_priv is not None and (num_priv != num_obs or getattr(env, "get_privileged_observations", lambda: None)() is not None):
+            raise NotImplementedError("privileged observations (num_privileged_obs) that differ from the observations are not built in the native runner: one "
+                                      "normaliser and one observation row serve actor and critic")
+        recurrent = policy_name == "ActorCriticRecurrent"
+        symmetry_cfg = self.alg_cfg.get("symmetry_cfg")
+        if symmetry_cfg and recurrent:
+            raise NotImplementedError("symmetry_cfg with ActorCriticRecurrent is not built in the native update (rl.NativeSymmetricPPO is feed-forward)")
+        self.seed = int(train_cfg.get("seed", 1))
+        self.noise_std_type = policy_noise_std_type(policy_name, self.policy_cfg)
+        sd = initial_state_dict(policy_name, num_obs, env.num_actions, self.policy_cfg, self.seed)
+        activation = self.policy_cfg.get("activation", "elu")
+        if recurrent:
+            policy = NativeActorCriticRecurrent(sd, activation, str(self.policy_cfg.get("rnn_type", "lstm")).lower(), self.noise_std_type, device=str(self.device),
+                                                seed=self.seed)
+        else:
+            policy = NativeActorCritic(sd, activation, self.noise_std_type, device=str(self.device), seed=self.seed)
+        kw = {k: self.alg_cfg[k] for k in PPO_KEYS if k in self.alg_cfg}
+        if symmetry_cfg:
+            self.alg = NativeSymmetricPPO(policy, sd, symmetry_cfg=dict(symmetry_cfg, _env=env), **kw)
+        else:
+            self.alg = (NativeRecurrentPPO if recurrent else NativePPO)(policy, sd, **kw)
+        self.gamma, self.lam = float(self.alg_cfg.get("gamma", 0.998)), float(self.alg_cfg.get("lam", 0.95))
+        self.num_steps_per_env, self.save_interval = int(self.cfg["num_steps_per_env"]), int(self.cfg["save_interval"])
+        self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
+        self.obs_normalizer = NativeEmpiricalNormalization([num_obs], until=int(1.0e8), device=str(self.device)) if self.empirical_normalization else None
+        self.privileged_obs_normalizer = self.obs_normalizer          # one handle serves actor and critic
+        self.layered = steps_outside_the_library(env)          # env classes with host work around the native step: the collection loop runs on the host
+        self.writer, self.disable_logs = None, False
+        self.tot_timesteps, self.tot_time, self.current_learning_iteration = 0, 0.0, 0
+        self._host_obs, self._host_episode = None, None
+        self.env.reset()
+
+    # ---- modes (`:729-754`)
+    def train_mode(self):
+        if self.obs_normalizer is not None:
+            self.obs_normalizer.train()
+
+    def eval_mode(self):
+        if self.obs_normalizer is not None:
+            self.obs_normalizer.eval()
+
+    # ---- collection
+    def _collect(self, tracker):
+        """One collection of `num_steps_per_env` steps: the rollout dict of `collect_rollout_tracked`."""
+        T = self.num_steps_per_env
+        if not self.layered:
+            return collect_rollout_tracked(self.env, self.alg.policy, T, gamma=self.gamma, lam=self.lam, obs_normalizer=self.obs_normalizer, episode_tracker=tracker)
+        return self._collect_host(tracker, T)
+
+    def _collect_host(self, tracker, T):
+        """The same dict from a host loop, for env classes whose step is more than the native one."""
+        env, policy, norm = self.env, self.alg.policy, self.obs_normalizer
+        obs = self._host_obs if self._host_obs is not None else env.get_observations().to(self.device)
+        N, O, A, dev = env.num_envs, obs.shape[1], env.num_actions, self.device
+        ex = env.core.t["extras_episode"]
+
+        def z(*shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32)
+        d = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1), actions_log_prob=z(T, N, 1), mu=z(T, N, A),
+                 sigma=z(T, N, A), raw_rewards=z(T, N, 1), episode_extras=z(T, ex.numel()))
+        hid, self._host_episode = [[], []], []
+        for t in range(T):
+            if policy.is_recurrent:
+                for k, m in enumerate((policy.memory_a, policy.memory_c)):
+                    m.ensure_state(N)
+                    hs = m.hidden_states
+                    hid[k].append(tuple(h.clone() for h in hs) if isinstance(hs, tuple) else hs.clone())
+            actions, values, logp, mu, sigma = policy.act_and_evaluate(obs)
+            d["observations"][t], d["actions"][t], d["values"][t], d["actions_log_prob"][t, :, 0], d["mu"][t], d["sigma"][t] = obs, actions, values, logp, mu, sigma
+            obs, _, rew, dones, infos = env.step(actions)
+            obs = obs.to(dev)
+            if norm is not None:
+                obs = norm(obs)
+            time_outs = infos["time_outs"].to(dev, torch.float32) if "time_outs" in infos else torch.zeros(N, device=dev)
+            d["raw_rewards"][t, :, 0] = rew
+            d["rewards"][t, :, 0] = rew + self.gamma * values[:, 0] * time_outs
+            d["dones"][t, :, 0] = (dones != 0).float()
+            d["episode_extras"][t] = ex
+            # infos["episode"] of this step, for the entries that are not views of extras_episode (a layer's own means): on_policy_runner.py:511-512
+            self._host_episode.append({k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in infos.get("episode", {}).items()
+                                       if not _view_index(v, ex)[0]})
+            policy.reset(dones)
+        self._host_obs = obs.clone()
+        d["last_values"] = policy.evaluate(obs).clone()
+        d["returns"], d["advantages"] = compute_returns(d["rewards"], d["dones"], d["values"], d["last_values"], self.gamma, self.lam)
+        ep_return, ep_length = tracker.track(d["raw_rewards"], d["dones"])
+        d["ep_return"], d["ep_length"] = ep_return.reshape(T, N, 1), ep_length.reshape(T, N, 1)
+        if policy.is_recurrent:
+            for key, rows in (("hidden_states_a", hid[0]), ("hidden_states_c", hid[1])):
+                d[key] = tuple(torch.stack([r[j] for r in rows]) for j in range(2)) if isinstance(rows[0], tuple) else torch.stack(rows)
+        return d
+
+    def _episode_means(self, rollout):
+        """`Episode/<key>`: the mean over the T per-step values of `infos["episode"][key]`.  Entries that are views of the env's `extras_episode`
+        tensor come from the collected rows.  The others come from the host loop's per-step copies; the one-call collector has no host step, and
+        the envs it serves write such entries (`max_command_x`, `reward_stage`) outside the step only, so their current value is every step's."""
+        ex, rows = self.env.core.t["extras_episode"], rollout["episode_extras"].mean(dim=0).cpu().numpy()
+        out = {}
+        for key, value in self.env.extras.get("episode", {}).items():
+            is_view, k = _view_index(value, ex)
+            if is_view:
+                out[key] = float(rows[k])
+            elif self.layered and self._host_episode and all(key in step for step in self._host_episode):
+                out[key] = float(torch.stack([torch.as_tensor(step[key], dtype=torch.float32).reshape(-1).mean().cpu() for step in self._host_episode]).mean())
+            else:
+                out[key] = float(torch.as_tensor(value, dtype=torch.float32).mean())
+        return out
+
+    # ---- the loop (`:347-486`)
+    def learn(self, num_learning_iterations, init_at_random_ep_len=False):
+        env = self.env
+        if self.log_dir is not None and self.writer is None and not self.disable_logs:
+            self.writer = _make_writer(self.log_dir)
+        if init_at_random_ep_len:
+            env.episode_length_buf[:] = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
+        if self.obs_normalizer is not None:
+            self.obs_normalizer.forget_carried()
+        self._host_obs = None
+        self.train_mode()
+        tracker = EpisodeTracker(env.num_envs, self.device)
+        start_iter = self.current_learning_iteration
+        tot_iter = start_iter + int(num_learning_iterations)
+        for it in range(start_iter, tot_iter):
+            start = time.time()
+            rollout = self._collect(tracker)
+            tracker.extend(rollout["dones"], rollout["ep_return"], rollout["ep_length"])          # (the one device-to-host copy of the collection)
+            stop = time.time()
+            collection_time, start = stop - start, stop
+            loss_dict = self.alg.update(rollout)
+            stop = time.time()
+            learn_time = stop - start
+            self.current_learning_iteration = it
+            if self.log_dir is not None and not self.disable_logs:
+                self.log(dict(it=it, tot_iter=tot_iter, start_iter=start_iter, num_learning_iterations=int(num_learning_iterations), collection_time=collection_time,
+                              learn_time=learn_time, loss_dict=loss_dict, rewbuffer=tracker.rewbuffer, lenbuffer=tracker.lenbuffer,
+                              episode=self._episode_means(rollout)))
+                if it % self.save_interval == 0:
+                    self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
+            if self.cfg.get("multi_stage_rewards", False) and len(tracker.rewbuffer) > 0 and env.update_reward_scales(statistics.mean(tracker.rewbuffer)):
+                print("Updated reward scales to ", env.reward_scales_stage)
+                tracker.rewbuffer.clear()
+                tracker.cur_reward_sum.zero_()
+        if self.log_dir is not None and not self.disable_logs:
+            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+            if hasattr(self.writer, "flush"):
+                self.writer.flush()
+
+    def log(self, locs, width=80, pad=35):
+        collection_size = self.num_steps_per_env * self.env.num_envs
+        self.tot_timesteps += collection_size
+        iteration_time = locs["collection_time"] + locs["learn_time"]
+        self.tot_time += iteration_time
+        it, w = locs["it"], self.writer
+        ep_string = ""
+        for key, value in locs["episode"].items():
+            if "/" in key:
+                w.add_scalar(key, value, it)
+                ep_string += f"""{f'{key}:':>{pad}} {value:.4f}\n"""
+            else:
+                w.add_scalar("Episode/" + key, value, it)
+                ep_string += f"""{f'Mean episode {key}:':>{pad}} {value:.4f}\n"""
+        mean_std = float(self.alg.policy.std.mean())
+        fps = int(collection_size / iteration_time)
+        for key, value in locs["loss_dict"].items():
+            w.add_scalar(f"Loss/{key}", value, it)
+        w.add_scalar("Loss/learning_rate", self.alg.learning_rate, it)
+        w.add_scalar("Policy/mean_noise_std", mean_std, it)
+        w.add_scalar("Perf/total_fps", fps, it)
+        w.add_scalar("Perf/collection time", locs["collection_time"], it)
+        w.add_scalar("Perf/learning_time", locs["learn_time"], it)
+        have = len(locs["rewbuffer"]) > 0
+        if have:
+            w.add_scalar("Train/mean_reward", statistics.mean(locs["rewbuffer"]), it)
+            w.add_scalar("Train/mean_episode_length", statistics.mean(locs["lenbuffer"]), it)
+            w.add_scalar("Train/mean_reward/time", statistics.mean(locs["rewbuffer"]), self.tot_time)
+            w.add_scalar("Train/mean_episode_length/time", statistics.mean(locs["lenbuffer"]), self.tot_time)
+        head = f" \033[1m Learning iteration {it}/{locs['tot_iter']} \033[0m "
+        log_string = (f"""{'#' * width}\n"""
+                      f"""{head.center(width, ' ')}\n\n"""
+                      f"""{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)\n"""
+                      f"""{'Mean action noise std:':>{pad}} {mean_std:.2f}\n""")
+        for key, value in locs["loss_dict"].items():
+            log_string += f"""{f'Mean {key} loss:':>{pad}} {value:.4f}\n""" if have else f"""{f'{key}:':>{pad}} {value:.4f}\n"""
+        if have:
+            log_string += f"""{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"""
+            log_string += f"""{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n"""
+        log_string += ep_string
+        eta = self.tot_time / (it - locs["start_iter"] + 1) * (locs["start_iter"] + locs["num_learning_iterations"] - it)
+        log_string += (f"""{'-' * width}\n"""
+                       f"""{'Total timesteps:':>{pad}} {self.tot_timesteps}\n"""
+                       f"""{'Iteration time:':>{pad}} {iteration_time:.2f}s\n"""
+                       f"""{'Time elapsed:':>{pad}} {time.strftime("%H:%M:%S", time.gmtime(self.tot_time))}\n"""
+                       f"""{'ETA:':>{pad}} {time.strftime("%H:%M:%S", time.gmtime(eta))}\n""")
+        print(log_string)
+
+    # ---- checkpoints (`:662-715`)
+    def model_state_dict(self):
+        sd = self.alg.state_dict()
+        return {n: sd[n] for n in parameter_order(sd.keys())}
+
+    def save(self, path, infos=None):
+        saved = {"model_state_dict": self.model_state_dict(), "optimizer_state_dict": adam_state_dict(self.alg.optimizer_state()),
+                 "iter": self.current_learning_iteration, "infos": infos}
+        if self.empirical_normalization:
+            saved["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            saved["privileged_obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+        torch.save(saved, path)
+
+    def load(self, path, load_optimizer=True):
+        loaded = torch.load(path, map_location="cpu", weights_only=False)
+        model = loaded["model_state_dict"]
+        want = parameter_order(self.alg.state_dict().keys())
+        if sorted(model.keys()) != sorted(want):
+            raise KeyError(f"model_state_dict does not hold this policy's parameters: missing {sorted(set(want) - set(model))}, "
+                           f"unexpected {sorted(set(model) - set(want))}")
+        if self.empirical_normalization:
+            a, b = loaded["obs_norm_state_dict"], loaded["privileged_obs_norm_state_dict"]
+            if any(not torch.equal(a[k], b[k]) for k in STATE_KEYS):
+                raise NotImplementedError("obs_norm_state_dict and privileged_obs_norm_state_dict differ: separate actor and critic normalisers are not "
+                                          "built in the native runner")
+            self.obs_normalizer.load_state_dict(a)
+            self.obs_normalizer.forget_carried()
+        if load_optimizer and "optimizer_state_dict" in loaded:
+            self.alg.load_optimizer_state(native_optimizer_state(model, loaded["optimizer_state_dict"]))
+        else:
+            self.alg.load_state_dict(model)
+        self.current_learning_iteration = loaded["iter"]
+        return loaded.get("infos")
+
+    def get_inference_policy(self, device=None):
+        self.eval_mode()
+        policy = self.alg.policy.act_inference
+        if self.empirical_normalization:
+            norm = self.obs_normalizer
+            return lambda x: policy(norm(x))
+        return policy

@@ -4,7 +4,8 @@ by an inference policy for ten episodes.
 
 Where the policy comes from: with `--policy` a checkpoint written by rsl_rl's `OnPolicyRunner.save` (or any state dict with
 `actor.*` / `critic.*` / `std`) is evaluated by `NativeActorCritic` (the fused MFMA MLP, csrc/lg_policy.hip); without it the
-runner is built and resumed from the log directory exactly as the reference does, which needs the external `rsl_rl`.
+runner is built and resumed from the log directory exactly as the reference does: rsl_rl's (the external package) by default,
+`rl.NativeOnPolicyRunner` with `--runner native`; either resumes what the other saved.
 The viewer-only parts of the reference script (camera motion, frame recording, matplotlib logger) have no counterpart:
 there is no renderer behind this env.  `play()` returns the per-step statistics it printed."""
 import torch

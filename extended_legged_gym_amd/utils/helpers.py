@@ -127,6 +127,8 @@ def get_args(argv=None):
     p.add_argument("--seed", type=int)
     p.add_argument("--max_iterations", type=int)
     p.add_argument("--num_threads", type=int, default=0)
+    p.add_argument("--runner", type=str, choices=("rsl_rl", "native"), default="rsl_rl",
+                   help="rsl_rl: the external package's OnPolicyRunner; native: rl.NativeOnPolicyRunner (collection and PPO update on the library's kernels)")
     args = p.parse_args(argv)
     args.physics_engine = "native_hip"
     args.use_gpu_pipeline = True

@@ -1,6 +1,6 @@
 """Task registry with the reference's interface (`utils/task_registry.py:44-155`): `register`, `get_cfgs`, `make_env`,
-`make_alg_runner`.  The PPO runner is the external `rsl_rl` package (unchanged caller of this env); it is imported only
-when a runner is requested."""
+`make_alg_runner`.  The PPO runner is the external `rsl_rl` package (unchanged caller of this env; imported only when a runner is
+requested) or, with `--runner native`, `rl.NativeOnPolicyRunner`: the same surface over the native collection and PPO update."""
 import os
 from datetime import datetime
 from typing import Tuple
@@ -44,9 +44,16 @@ class TaskRegistry():
         return env, env_cfg
 
     def make_alg_runner(self, env, name=None, args=None, train_cfg=None, log_root="default"):
-        from rsl_rl.runners import OnPolicyRunner   # external package, drops in unchanged
         if args is None:
             args = get_args()
+        if getattr(args, "runner", "rsl_rl") == "native":
+            from extended_legged_gym_amd.rl import NativeOnPolicyRunner as OnPolicyRunner
+        else:
+            try:
+                from rsl_rl.runners import OnPolicyRunner   # external package, drops in unchanged
+            except ImportError as e:
+                raise ImportError(f"{e}: the rsl_rl package is not installed; `--runner native` trains and resumes with rl.NativeOnPolicyRunner, "
+                                  "which needs no external package") from e
         if train_cfg is None:
             if name is None:
                 raise ValueError("Either 'name' or 'train_cfg' must be not None")
