@@ -754,3 +754,23 @@ def declare_runner(lib):
 
 RUNNER_SYMBOLS = ["lg_obsnorm_create", "lg_obsnorm_destroy", "lg_obsnorm_get_state", "lg_obsnorm_set_state", "lg_obsnorm_step", "lg_obsnorm_inverse",
                   "lg_obsnorm_carried", "lg_obsnorm_forget_carried", "lg_runner_collect", "lg_runner_episode_track"]
+
+
+class lg_runner_privileged(C.Structure):
+    """include/lgrunner_privileged.h: what lg_runner_collect_privileged takes beyond lg_runner_collect."""
+    _fields_ = [("history", C.POINTER(lg_obs_history)), ("critic_normalizer", C.c_void_p), ("privileged_observations", C.c_void_p),
+                ("last_observations", C.c_void_p)]
+
+
+def declare_runner_privileged(lib):
+    """Prototypes of the collection with privileged critic observations (include/lgrunner_privileged.h), same library."""
+    vp, i64, u64 = C.c_void_p, C.c_int64, C.c_uint64
+    lib.lg_obsnorm_step_pair.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, i64, i32, vp]
+    lib.lg_obsnorm_step_pair.restype = C.c_int
+    lib.lg_runner_collect_privileged.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, f32, f32, i32, C.POINTER(lg_rollout), C.POINTER(lg_rollout_hidden),
+                                                 vp, vp, vp, vp, C.POINTER(lg_runner_hooks), C.POINTER(lg_runner_privileged), vp]
+    lib.lg_runner_collect_privileged.restype = C.c_int
+    return lib
+
+
+RUNNER_PRIVILEGED_SYMBOLS = ["lg_obsnorm_step_pair", "lg_runner_collect_privileged"]

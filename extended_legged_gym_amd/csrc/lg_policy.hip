@@ -27,6 +27,7 @@
 #include "lg_rnn_tile.h"
 #include "../../include/lgpolicy.h"
 #include "../../include/lgrunner.h"
+#include "../../include/lgrunner_privileged.h"
 #include "../../include/lgstep.h"
 
 // ---- the one error channel and the create functions' plumbing (lg_policy_internal.h)
@@ -874,3 +875,120 @@ int lg_collect_distillation_recurrent(lg_ctx* env, lg_rnn* mem_s, lg_mlp* studen
 }
 
 }  // extern "C"
+
+
+// ============================================================================================ privileged critic observations (lgrunner_privileged.h)
+// The PPO collector with two observation streams: the critic reads the env's row (O_c wide), the actor the history layer's row or a column prefix
+// (O_a wide), each stream with its own normaliser and carried row.  The launches of lg_policy_collect_rollout with, per step, the actor's row (one
+// launch) in front of the normaliser, and the paired normaliser step (three launches for both handles) in place of the single one.
+int lg_policy_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
+                                 int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
+                                 float* c_a, float* h_c, float* c_c, const PrivilegedHooks* ph, void* stream) {
+  DeviceScope ds_(actor->device);
+  if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
+      !out->sigma || !out->last_values) return lg_policy_fail(LG_ERR_INVALID, "null output row");
+  const bool lstm_a = mem_a && mem_a->type == LG_RNN_LSTM, lstm_c = mem_a && mem_c->type == LG_RNN_LSTM;
+  if (mem_a && (!hid->h_a || !hid->h_c || (lstm_a && !hid->c_a) || (lstm_c && !hid->c_c))) return lg_policy_fail(LG_ERR_INVALID, "null hidden-state row");
+  const float* env_obs; int64_t n, Oc, Aenv;
+  int rc = env_shape(env, &env_obs, &n, &Oc, &Aenv);
+  if (rc == LG_OK && mem_a) rc = rnn_check(mem_a, h_a, c_a, n);
+  if (rc == LG_OK && mem_a) rc = rnn_check(mem_c, h_c, c_c, n);
+  if (rc != LG_OK) return rc;
+  const int A = actor->h.dims[actor->h.L];
+  const int64_t Oa = mem_a ? mem_a->input : actor->h.dims[0];
+  if ((mem_a ? mem_c->input : critic->h.dims[0]) != Oc || critic->h.dims[critic->h.L] != 1 || A != Aenv)
+    return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (the critic reads the env's observation row, one action per DOF, scalar value)");
+  const lg_obs_history* hist = ph->history;
+  if (hist) {
+    if (!hist->history || hist->H < 1 || hist->W < 1 || hist->W > Oc || !(hist->clip > 0.f)) return lg_policy_fail(LG_ERR_INVALID, "bad history layer (pointer, H, W <= env row, clip > 0)");
+    if ((int64_t)hist->H * hist->W != Oa) return lg_policy_fail(LG_ERR_INVALID, "the actor's input width is not H x W of the history layer");
+  } else if (Oa > Oc) {
+    return lg_policy_fail(LG_ERR_INVALID, "without a history layer the actor reads a prefix of the env's observation row: its input is wider than that row");
+  }
+  lg_obsnorm *norm_a = ph->normalizer_a, *norm_c = ph->normalizer_c;
+  if (norm_a && lg_obsnorm_width(norm_a) != Oa) return lg_policy_fail(LG_ERR_INVALID, "the actor's normaliser does not have the actor's input width");
+  if (norm_c && lg_obsnorm_width(norm_c) != Oc) return lg_policy_fail(LG_ERR_INVALID, "the critic's normaliser does not have the env's observation width");
+  if (norm_a && norm_a == norm_c) return lg_policy_fail(LG_ERR_INVALID, "the actor and the critic need a normaliser each");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t sa = mem_a ? (size_t)mem_a->num_layers * n * mem_a->hidden : 0, sc = mem_a ? (size_t)mem_c->num_layers * n * mem_c->hidden : 0;
+  const size_t so = (size_t)n * Oa, sp = (size_t)n * Oc;
+  const float* rew_buf = nullptr; const float* extras_buf = nullptr; int64_t K = 0;
+  if (ph->raw_rewards || ph->extras) {
+    void* p; int64_t shp[4]; int32_t nd, dt;
+    if (lg_get_tensor(env, LG_T_REW_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's reward rows: ") + lg_last_error(env));
+    rew_buf = (const float*)p;
+    if (lg_get_tensor(env, LG_T_EXTRAS_EPISODE, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's episode extras: ") + lg_last_error(env));
+    extras_buf = (const float*)p; K = shp[0];
+  }
+  float *carried_a = nullptr, *carried_c = nullptr; bool valid_a = false, valid_c = false;
+  if (norm_a && (rc = lg_obsnorm_carried_begin(norm_a, n, Oa, &carried_a, &valid_a)) != LG_OK) return rc;
+  if (norm_c && (rc = lg_obsnorm_carried_begin(norm_c, n, Oc, &carried_c, &valid_c)) != LG_OK) return rc;
+  // the actor's row after a step: the history layer on the env's own raw row (never the stored critic row: that one is normalised in place), or
+  // the head of that row
+  auto actor_row = [&](int t, const float* dones_t, float* dst) -> int {
+    if (hist) return lg_obs_history_step(hist->history, n, hist->H, hist->W, env_obs, Oc, dones_t, hist->noise_scale,
+                                         hist->inject_u ? hist->inject_u + (size_t)t * so : nullptr, hist->noise_seed, first_call + (uint64_t)t, hist->clip, dst, stream);
+    if (dst) POLICY_TRY(hipMemcpy2DAsync(dst, (size_t)Oa * 4, env_obs, (size_t)Oc * 4, (size_t)Oa * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+    return LG_OK;
+  };
+  // row 0 of each stream: the carried row where one is held, else the clipped history (the column prefix) and the env's raw row
+  if (valid_a) POLICY_TRY(hipMemcpyAsync(out->observations, carried_a, so * 4, hipMemcpyDeviceToDevice, st));
+  else if (hist) hipLaunchKernelGGL(obs_clip_kernel, dim3((unsigned)((so + 255) / 256)), dim3(256), 0, st, hist->history, (int64_t)so, hist->clip, out->observations);
+  else POLICY_TRY(hipMemcpy2DAsync(out->observations, (size_t)Oa * 4, env_obs, (size_t)Oc * 4, (size_t)Oa * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+  POLICY_TRY(hipMemcpyAsync(ph->privileged_observations, valid_c ? carried_c : env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
+  for (int t = 0; t < T; ++t) {
+    const float* obs_t = out->observations + t * so;
+    const float* priv_t = ph->privileged_observations + t * sp;
+    float* act_t = out->actions + (size_t)t * n * A;
+    float* dones_t = out->dones + (size_t)t * n;
+    if (mem_a) {
+      POLICY_TRY(hipMemcpyAsync(hid->h_a + t * sa, h_a, sa * 4, hipMemcpyDeviceToDevice, st));
+      if (lstm_a) POLICY_TRY(hipMemcpyAsync(hid->c_a + t * sa, c_a, sa * 4, hipMemcpyDeviceToDevice, st));
+      POLICY_TRY(hipMemcpyAsync(hid->h_c + t * sc, h_c, sc * 4, hipMemcpyDeviceToDevice, st));
+      if (lstm_c) POLICY_TRY(hipMemcpyAsync(hid->c_c + t * sc, c_c, sc * 4, hipMemcpyDeviceToDevice, st));
+      rc = lg_policy_act_recurrent(mem_a, actor, mem_c, critic, obs_t, priv_t, n, std, seed, first_call + (uint64_t)t, 0, h_a, c_a, h_c, c_c, nullptr, act_t,
+                                   out->mu + (size_t)t * n * A, out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
+    } else {
+      rc = lg_policy_act(actor, critic, obs_t, priv_t, n, std, seed, first_call + (uint64_t)t, 0, act_t, out->mu + (size_t)t * n * A,
+                         out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
+    }
+    if (rc != LG_OK) return rc;
+    const bool more = t + 1 < T;
+    // the critic's next row, written by the step itself; after the last step into the critic normaliser's carried row (none: the env's own row serves)
+    float* next_c = more ? ph->privileged_observations + (t + 1) * sp : carried_c;
+    rc = lg_step_transition(env, act_t, next_c, out->values + (size_t)t * n, gamma, out->rewards + (size_t)t * n, dones_t, stream);
+    if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
+    // the actor's next row; after the last step the un-normalised row goes to last_observations and its normalised copy to the carried row
+    float* norm_out_a = more ? out->observations + (t + 1) * so : carried_a;
+    float* next_a = more ? norm_out_a : (ph->last_observations ? ph->last_observations : carried_a);
+    rc = actor_row(t, dones_t, next_a);
+    if (rc != LG_OK) return rc;
+    if (norm_a && norm_c) rc = lg_obsnorm_step_pair(norm_a, next_a, Oa, norm_out_a, norm_c, next_c, Oc, next_c, n, ph->update, stream);
+    else if (norm_a) rc = lg_obsnorm_step(norm_a, next_a, n, Oa, ph->update, norm_out_a, stream);
+    else if (norm_c) rc = lg_obsnorm_step(norm_c, next_c, n, Oc, ph->update, next_c, stream);
+    if (rc != LG_OK) return rc;
+    if (ph->raw_rewards) POLICY_TRY(hipMemcpyAsync(ph->raw_rewards + (size_t)t * n, rew_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (ph->extras) POLICY_TRY(hipMemcpyAsync(ph->extras + (size_t)t * K, extras_buf, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
+    if (mem_a) {
+      rc = lg_rnn_reset_rows(mem_a, h_a, c_a, dones_t, n, stream);
+      if (rc == LG_OK) rc = lg_rnn_reset_rows(mem_c, h_c, c_c, dones_t, n, stream);
+      if (rc != LG_OK) return rc;
+    }
+  }
+  const float* last = norm_c ? carried_c : env_obs;
+  if (mem_a) {
+    rc = lg_rnn_step(mem_c, last, n, h_c, c_c, nullptr, nullptr, stream);
+    if (rc != LG_OK) return rc;
+    last = h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden;
+  }
+  rc = lg_mlp_forward(critic, last, n, out->last_values, stream);
+  if (rc == LG_OK && out->returns && out->advantages)
+    rc = lg_compute_returns(out->rewards, out->dones, out->values, out->last_values, T, n, gamma, lam, normalize_advantage, out->returns,
+                            out->advantages, stream);
+  if (rc != LG_OK) return rc;
+  POLICY_TRY(hipGetLastError());
+  if (norm_a) lg_obsnorm_carried_commit(norm_a);
+  if (norm_c) lg_obsnorm_carried_commit(norm_c);
+  return LG_OK;
+}

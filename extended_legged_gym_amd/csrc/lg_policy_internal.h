@@ -50,6 +50,23 @@ int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn*
 // as not holding one; commit marks it as holding the row the collector left there
 int lg_obsnorm_carried_begin(lg_obsnorm* h, int64_t n, int64_t O, float** row, bool* valid);
 void lg_obsnorm_carried_commit(lg_obsnorm* h);
+int lg_obsnorm_width(const lg_obsnorm* h);
+
+// ---- the PPO collector with privileged critic observations (lg_policy.hip), behind lg_runner_collect_privileged (lg_runner_privileged.hip):
+// two observation streams, a normaliser and a carried row each.  lg_policy_collect_rollout and its three entry points are untouched by it.
+struct PrivilegedHooks {
+  const lg_obs_history* history = nullptr;      // the actor's layer; NULL: the actor reads a column prefix of the env's row
+  lg_obsnorm* normalizer_a = nullptr;           // the actor's, O_a wide
+  lg_obsnorm* normalizer_c = nullptr;           // the critic's, O_c wide
+  int update = 0;                               // the normalisers' training mode
+  float* privileged_observations = nullptr;     // (T, n, O_c)
+  float* last_observations = nullptr;           // (n, O_a) or NULL
+  float* raw_rewards = nullptr;                 // (T, n)
+  float* extras = nullptr;                      // (T, K)
+};
+int lg_policy_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
+                                 int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
+                                 float* c_a, float* h_c, float* c_c, const PrivilegedHooks* ph, void* stream);
 
 // ---- the network handle, shared with the trainer (lg_train.hip), which rewrites the device buffers of an lg_mlp in place
 #define MLP_ROWS 32          // batch rows per workgroup

@@ -70,6 +70,9 @@ class AnymalStudent(Anymal):
     launches per step, outside the fused kernel because it is this one task's bookkeeping).  One difference: the rows that enter
     the history come out of the kernel already clipped to +-`clip_observations` (100), the reference stores them unclipped."""
     proprio_obs_size = 48
+    # all this class does around the native step is the history layer, which the library also runs on the device (`lg_obs_history_step`): the
+    # native runner may collect with `lg_runner_collect_privileged` instead of a host loop over `step` (rl/runner.py)
+    privileged_native_collection = True
 
     def __init__(self, cfg, sim_params, physics_engine, sim_device, headless):
         self.history_length = getattr(cfg.env, 'history_length', 5)

@@ -7,7 +7,9 @@ include/lgtrain_symmetry.h; `signed_permutation_tables` turns a `data_augmentati
 recurrent student: truncated BPTT through its memory, include/lgdistill_recurrent.h) and `NativeEstimatorDistillation`
 (`EstimatorDistillation.update`: the terrain estimator's conv backward, truncated BPTT and Adam, include/lgestimator_train.h); the runner:
 `NativeOnPolicyRunner` (rsl_rl's `OnPolicyRunner` surface over these pieces), `NativeEmpiricalNormalization` (`empirical_normalization` on the device) and
-`collect_rollout_tracked` / `EpisodeTracker` (the collection with the normaliser and the episode bookkeeping between its launches, include/lgrunner.h)."""
+`collect_rollout_tracked` / `EpisodeTracker` (the collection with the normaliser and the episode bookkeeping between its launches, include/lgrunner.h;
+with privileged critic observations -- two observation streams, two normalisers, `NativeEmpiricalNormalization.step_pair` --
+include/lgrunner_privileged.h)."""
 from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
                      NativeStudentTeacher, NativeStudentTeacherRecurrent)
 from .storage import compute_returns                      # noqa: F401

@@ -90,7 +90,7 @@ class EpisodeTracker:
 
 
 def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_advantage=True, compute_returns=True, obs_normalizer=None,
-                            episode_tracker=None):
+                            episode_tracker=None, privileged_obs_normalizer=None, noise_uniforms=None, actor_columns=None):
     """`collect_rollout` through `lg_runner_collect` (include/lgrunner.h), with the runner's two device pieces between the launches of the one
     call.  Same dict; both hooks None: the same rows, bit for bit.
     obs_normalizer (`NativeEmpiricalNormalization`): every new observation row is normalised in place (and counted when the normaliser is in
@@ -99,11 +99,29 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
     `learn()` (`:364-365`); `last_values` is evaluated on the new carried row.  `env.obs_buf` stays raw.
     episode_tracker (`EpisodeTracker`): adds `raw_rewards` (T, N, 1), the env's reward without the time-out bootstrap `rewards` carries,
     `episode_extras` (T, K), the env's `extras_episode` tensor after each step, and `ep_return` / `ep_length` (T, N, 1), defined where
-    `dones > 0`; the tracker's live sums advance in place (its buffers do not: `episode_tracker.extend(...)`)."""
+    `dones > 0`; the tracker's live sums advance in place (its buffers do not: `episode_tracker.extend(...)`).
+
+    PRIVILEGED CRITIC OBSERVATIONS (`lg_runner_collect_privileged`, include/lgrunner_privileged.h): an env with an observation history
+    (`env.obs_history`, (N, H, W): `AnymalStudent`), or `actor_columns=k` on any env (the actor reads the first k columns of the env's row).  The
+    critic reads the env's own row (O_c wide), the actor the history's row (H * W) or the prefix; the dict then holds `observations` (T, N, O_a) and
+    also `privileged_observations` (T, N, O_c), `values` are the critic's on the privileged rows.  `obs_normalizer` is the ACTOR's,
+    `privileged_obs_normalizer` the critic's: each with its own carried row.  The history is stepped in place by the library and `env.obs_buf` is
+    left as the actor's un-normalised row after the last step, as `collect_distillation` does; noise follows `env.add_noise`, and `noise_uniforms`
+    (T, N, H * W) replaces the Philox draws.  For every other env the three arguments must stay None and the call is the one above."""
     from .normalizer import _runner_lib
     lib = _runner_lib()
     dev = policy.device
     T, N, O, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
+    hist = getattr(env, "obs_history", None)
+    privileged = hist is not None or actor_columns is not None
+    if not privileged and (privileged_obs_normalizer is not None or noise_uniforms is not None):
+        raise ValueError("privileged_obs_normalizer / noise_uniforms need an env with an observation history, or actor_columns")
+    O_c = O
+    if privileged:
+        rec = getattr(policy, "is_recurrent", False)
+        O = policy.memory_a.input_size if rec else policy.actor.dims[0]
+        if actor_columns is not None and (hist is not None or int(actor_columns) != O):
+            raise ValueError(f"actor_columns = {actor_columns}: the actor reads {O} columns" + (", and the env has an observation history" if hist is not None else ""))
 
     def z(*shape):
         return torch.empty(*shape, device=dev, dtype=torch.float32)
@@ -127,6 +145,8 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
         hooks.episode = C.pointer(episode)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     head = (_ptr(policy.std), policy.seed, policy._call + 1, T, float(gamma), float(lam), int(bool(normalize_advantage)), C.byref(rows))
+    if privileged:
+        return _collect_privileged(lib, env, policy, T, N, O, O_c, out, extra, head, hooks, hist, privileged_obs_normalizer, noise_uniforms, stream)
     if not getattr(policy, "is_recurrent", False):
         _check(lib.lg_runner_collect(env.core.ctx, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None, C.byref(hooks),
                                      stream), "lg_runner_collect")
@@ -143,6 +163,65 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
         out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
         out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
     _advance(env, policy, T)
+    out.update(extra)
+    return out
+
+
+def _history_layer(env, policy, hist, T, N, noise_uniforms):
+    """`abi.lg_obs_history` over `env.obs_history` as `collect_distillation` and the privileged collector hand it to the library, and the tensors
+    it points into (keep them alive until the call returns)."""
+    dev = policy.device
+    if not (hist.is_contiguous() and hist.dtype == torch.float32 and hist.shape[0] == N):
+        raise ValueError("env.obs_history must be a contiguous float32 (N, H, W) tensor")
+    H, W = hist.shape[1], hist.shape[2]
+    scale = env.noise_scale_vec[:H * W].to(dev, torch.float32).contiguous() if getattr(env, "add_noise", False) else None
+    if noise_uniforms is not None:
+        noise_uniforms = noise_uniforms.to(dev, torch.float32).contiguous()
+        assert noise_uniforms.shape == (T, N, H * W)
+    layer = abi.lg_obs_history(history=hist.data_ptr(), H=H, W=W, noise_scale=scale.data_ptr() if scale is not None else None,
+                               clip=float(env.cfg.normalization.clip_observations), noise_seed=(policy.seed ^ 0x5DEECE66D) & (2 ** 64 - 1),
+                               inject_u=noise_uniforms.data_ptr() if noise_uniforms is not None else None)
+    return layer, [scale, noise_uniforms]
+
+
+def _collect_privileged(lib, env, policy, T, N, O_a, O_c, out, extra, head, hooks, hist, critic_normalizer, noise_uniforms, stream):
+    """The tail of `collect_rollout_tracked` for the two-stream collection: `lg_runner_collect_privileged`."""
+    dev = policy.device
+    if critic_normalizer is not None:          # (its width is the library's to check, with every other width of the call)
+        if not hooks.normalizer:
+            hooks.training = int(critic_normalizer.training)          # (one mode for both handles: the critic's when it is the only one)
+        elif bool(critic_normalizer.training) != bool(hooks.training):
+            raise ValueError("obs_normalizer and privileged_obs_normalizer are in different modes")
+    out["privileged_observations"] = torch.empty(T, N, O_c, device=dev, dtype=torch.float32)
+    last = torch.empty(N, O_a, device=dev, dtype=torch.float32) if hist is not None else None
+    layer, keep = (None, [])
+    if hist is not None:
+        layer, keep = _history_layer(env, policy, hist, T, N, noise_uniforms)
+    elif noise_uniforms is not None:
+        raise ValueError("noise_uniforms needs an env with an observation history")
+    priv = abi.lg_runner_privileged(history=C.pointer(layer) if layer is not None else None,
+                                    critic_normalizer=critic_normalizer.handle if critic_normalizer is not None else None,
+                                    privileged_observations=out["privileged_observations"].data_ptr(), last_observations=last.data_ptr() if last is not None else None)
+    if not getattr(policy, "is_recurrent", False):
+        rc = lib.lg_runner_collect_privileged(env.core.ctx, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None,
+                                              C.byref(hooks), C.byref(priv), stream)
+    else:
+        mems = (policy.memory_a, policy.memory_c)
+        stacks = []
+        for m in mems:
+            m.ensure_state(N)
+            stacks.append([torch.empty(T, m.num_layers, N, m.hidden_size, device=dev) for _ in range(2 if m.rnn_type == "lstm" else 1)])
+        ptr = [[s.data_ptr() for s in st] + [None] * (2 - len(st)) for st in stacks]
+        hidden = abi.lg_rollout_hidden(h_a=ptr[0][0], c_a=ptr[0][1], h_c=ptr[1][0], c_c=ptr[1][1])
+        rc = lib.lg_runner_collect_privileged(env.core.ctx, mems[0].handle, policy.actor.handle, mems[1].handle, policy.critic.handle, *head, C.byref(hidden),
+                                              *mems[0]._ptrs(), *mems[1]._ptrs(), C.byref(hooks), C.byref(priv), stream)
+        out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
+        out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
+    _check(rc, "lg_runner_collect_privileged")
+    del keep
+    _advance(env, policy, T)
+    if hist is not None:
+        env.obs_buf = last
     out.update(extra)
     return out
 
@@ -202,17 +281,7 @@ def collect_distillation(env, policy, num_steps, noise_uniforms=None):
     hist = getattr(env, "obs_history", None)
     layer, keep = None, []
     if hist is not None:
-        if not (hist.is_contiguous() and hist.dtype == torch.float32 and hist.shape[0] == N):
-            raise ValueError("env.obs_history must be a contiguous float32 (N, H, W) tensor")
-        H, W = hist.shape[1], hist.shape[2]
-        scale = env.noise_scale_vec[:H * W].to(dev, torch.float32).contiguous() if getattr(env, "add_noise", False) else None
-        if noise_uniforms is not None:
-            noise_uniforms = noise_uniforms.to(dev, torch.float32).contiguous()
-            assert noise_uniforms.shape == (T, N, H * W)
-        keep = [scale, noise_uniforms]
-        layer = abi.lg_obs_history(history=hist.data_ptr(), H=H, W=W, noise_scale=scale.data_ptr() if scale is not None else None,
-                                   clip=float(env.cfg.normalization.clip_observations), noise_seed=(policy.seed ^ 0x5DEECE66D) & (2 ** 64 - 1),
-                                   inject_u=noise_uniforms.data_ptr() if noise_uniforms is not None else None)
+        layer, keep = _history_layer(env, policy, hist, T, N, noise_uniforms)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     lp = C.byref(layer) if layer is not None else None
     if rec:

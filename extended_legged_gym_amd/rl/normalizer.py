@@ -15,6 +15,7 @@ def _runner_lib():
     lib = _lib()
     if not getattr(lib, "_runner_declared", False):
         abi.declare_runner(lib)
+        abi.declare_runner_privileged(lib)
         lib._runner_declared = True
     return lib
 
@@ -86,6 +87,28 @@ class NativeEmpiricalNormalization(_NativeHandle):
 
     def update(self, x):
         self._step(x, True, None)
+
+    def step_pair(self, other, x, x_other, inplace=False):
+        """`self(x)` and `other(x_other)` over the same number of rows in one call (`lg_obsnorm_step_pair`, include/lgrunner_privileged.h): three
+        launches for both handles instead of six, the bits of the two single calls.  Both handles must be in the same mode (the runner switches them
+        together); each one's `until` freezes its own statistics.  Returns the two normalised tensors; `inplace`: the inputs themselves, under the
+        conditions of `normalize_`."""
+        if self.training != other.training:
+            raise ValueError("step_pair: the two normalisers are in different modes")
+        if inplace:
+            for norm, t in ((self, x), (other, x_other)):
+                if not (isinstance(t, torch.Tensor) and t.device.type == "cuda" and t.dtype == torch.float32 and t.dim() == 2 and
+                        (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= norm.num_features)):
+                    raise ValueError("step_pair(inplace=True) takes float32 tensors of rows on the normalisers' device with unit column stride")
+        (xa, sa), (xc, sc) = self._rows(x), other._rows(x_other)
+        if xa.shape[0] != xc.shape[0]:
+            raise ValueError(f"step_pair: {xa.shape[0]} and {xc.shape[0]} rows")
+        outs = []
+        for t, stride in ((xa, sa), (xc, sc)):
+            outs.append(t if inplace else (torch.empty_strided(t.shape, (stride, 1), device=self.device, dtype=torch.float32) if t.shape[0] else torch.empty_like(t)))
+        self._check(self.lib.lg_obsnorm_step_pair(self.handle, _ptr(xa), sa, _ptr(outs[0]), other.handle, _ptr(xc), sc, _ptr(outs[1]), xa.shape[0],
+                                                  int(self.training), self._stream()), "lg_obsnorm_step_pair")
+        return outs[0], outs[1]
 
     def inverse(self, y):
         y, stride = self._rows(y)

@@ -5,8 +5,13 @@ layout (`model_state_dict`, `optimizer_state_dict` as `torch.optim.Adam(policy.p
 normaliser dicts), so either runner resumes what the other wrote.
 
 Refused by name (`NotImplementedError`): `Distillation` (tools/train_distill.py runs it), `rnd_cfg`, `multi_gpu_cfg`,
-`normalize_advantage_per_mini_batch`, policy classes other than `ActorCritic` / `ActorCriticRecurrent`, and an env whose privileged
-observations differ from its observations."""
+`normalize_advantage_per_mini_batch`, policy classes other than `ActorCritic` / `ActorCriticRecurrent`, and an env that declares a
+`num_privileged_obs` other than `num_obs` without returning privileged observations.
+
+Privileged critic observations (`env.num_privileged_obs` with `get_privileged_observations()` returning that tensor; `on_policy_runner.py:161-215`):
+the critic's first layer / `memory_c` is `num_privileged_obs` wide, there are two normalisers, the rollout holds `privileged_observations`, and the
+collection is the one-call two-stream collector (`lg_runner_collect_privileged`) for an env the library can run whole (`collects_privileged_natively`),
+the host loop for any other."""
 import json
 import os
 import statistics
@@ -46,12 +51,12 @@ class _ActorCritic(torch.nn.Module):
     """The layer order and parameter names of `rsl_rl/modules/actor_critic.py:16-94` (actor, critic, then `std` / `log_std`) and, with a memory
     in front of each MLP, of `modules/actor_critic_recurrent.py:16-60`.  Only its initial `state_dict()` is used."""
 
-    def __init__(self, num_obs, num_actions, actor_hidden_dims, critic_hidden_dims, activation, init_noise_std, noise_std_type, rnn=None):
+    def __init__(self, num_obs, num_actions, actor_hidden_dims, critic_hidden_dims, activation, init_noise_std, noise_std_type, rnn=None, num_critic_obs=None):
         super().__init__()
         act = ACTIVATIONS[activation]
-        width = rnn["rnn_hidden_size"] if rnn else num_obs
-        self.actor = _mlp([width] + list(actor_hidden_dims) + [num_actions], act)
-        self.critic = _mlp([width] + list(critic_hidden_dims) + [1], act)
+        num_critic_obs = num_obs if num_critic_obs is None else num_critic_obs
+        self.actor = _mlp([rnn["rnn_hidden_size"] if rnn else num_obs] + list(actor_hidden_dims) + [num_actions], act)
+        self.critic = _mlp([rnn["rnn_hidden_size"] if rnn else num_critic_obs] + list(critic_hidden_dims) + [1], act)
         if noise_std_type == "scalar":
             self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
         elif noise_std_type == "log":
@@ -60,7 +65,7 @@ class _ActorCritic(torch.nn.Module):
             raise ValueError(f"Unknown standard deviation type: {noise_std_type}. Should be 'scalar' or 'log'")
         if rnn:
             self.memory_a = _Memory(num_obs, rnn["rnn_type"], rnn["rnn_hidden_size"], rnn["rnn_num_layers"])
-            self.memory_c = _Memory(num_obs, rnn["rnn_type"], rnn["rnn_hidden_size"], rnn["rnn_num_layers"])
+            self.memory_c = _Memory(num_critic_obs, rnn["rnn_type"], rnn["rnn_hidden_size"], rnn["rnn_num_layers"])
 
 
 def policy_noise_std_type(policy_class_name, policy_cfg):
@@ -68,10 +73,11 @@ def policy_noise_std_type(policy_class_name, policy_cfg):
     return "scalar" if policy_class_name == "ActorCriticRecurrent" else policy_cfg.get("noise_std_type", "scalar")
 
 
-def initial_state_dict(policy_class_name, num_obs, num_actions, policy_cfg, seed):
+def initial_state_dict(policy_class_name, num_obs, num_actions, policy_cfg, seed, num_critic_obs=None):
     """The `state_dict()` of a freshly initialised `ActorCritic` / `ActorCriticRecurrent` (torch's default `nn.Linear` / `nn.LSTM` / `nn.GRU`
     initialisation, drawn under `seed` without disturbing the global generator): keys `std` / `log_std`, `actor.N.*`, `critic.N.*`,
-    `memory_a.rnn.*`, `memory_c.rnn.*`, in the module's order."""
+    `memory_a.rnn.*`, `memory_c.rnn.*`, in the module's order.  `num_critic_obs`: the input width of the critic's first layer / of `memory_c`
+    (`num_privileged_obs`); None or `num_obs`: the same draws, the same bits as without it."""
     if policy_class_name not in ("ActorCritic", "ActorCriticRecurrent"):
         raise NotImplementedError(f"policy_class_name {policy_class_name}: the native runner builds ActorCritic and ActorCriticRecurrent")
     activation = policy_cfg.get("activation", "elu")
@@ -84,7 +90,8 @@ def initial_state_dict(policy_class_name, num_obs, num_actions, policy_cfg, seed
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(int(seed))
         module = _ActorCritic(num_obs, num_actions, policy_cfg.get("actor_hidden_dims", [256, 256, 256]), policy_cfg.get("critic_hidden_dims", [256, 256, 256]),
-                              activation, float(policy_cfg.get("init_noise_std", 1.0)), policy_noise_std_type(policy_class_name, policy_cfg), rnn)
+                              activation, float(policy_cfg.get("init_noise_std", 1.0)), policy_noise_std_type(policy_class_name, policy_cfg), rnn,
+                              None if num_critic_obs is None else int(num_critic_obs))
     return {k: v.detach().clone() for k, v in module.state_dict().items()}
 
 
@@ -178,6 +185,14 @@ def _view_index(value, tensor):
     return (True, int(k)) if 0 <= k < tensor.numel() and (value.data_ptr() - tensor.data_ptr()) % tensor.element_size() == 0 else (False, -1)
 
 
+def collects_privileged_natively(env):
+    """True for an env with privileged observations whose only work around the native step is the observation-history layer the library runs
+    itself (`lg_obs_history_step`).  The env class declares it: `privileged_native_collection = True` (`AnymalStudent`).  Such an env collects
+    through `lg_runner_collect_privileged`; every other env with privileged observations through the host loop.  `steps_outside_the_library` is
+    True for `AnymalStudent` too (its `step` is overridden) and stays the rule for envs without privileged observations."""
+    return bool(getattr(type(env), "privileged_native_collection", False))
+
+
 def steps_outside_the_library(env):
     """True for an env class whose `step` is more than the library's one call: a device layer behind it (`_after_native`: `FootTrackElSpider`) or an
     overridden `step` with host work around the native step (the ray caster and the depth camera between physics and post-physics, the pose layer,
@@ -204,16 +219,21 @@ class NativeOnPolicyRunner:
         if policy_name not in ("ActorCritic", "ActorCriticRecurrent"):
             raise NotImplementedError(f"policy_class_name {policy_name}: the native runner builds ActorCritic and ActorCriticRecurrent")
         num_obs, num_priv = env.num_obs, getattr(env, "num_privileged_obs", None)
-        if num_priv is not None and (num_priv != num_obs or getattr(env, "get_privileged_observations", lambda: None)() is not None):
-            raise NotImplementedError("privileged observations (num_privileged_obs) that differ from the observations are not built in the native runner: one "
-                                      "normaliser and one observation row serve actor and critic")
+        priv_obs = getattr(env, "get_privileged_observations", lambda: None)() if num_priv is not None else None
+        if num_priv is not None and priv_obs is None and num_priv != num_obs:
+            raise NotImplementedError(f"num_privileged_obs = {num_priv} differs from num_obs = {num_obs}, but get_privileged_observations() returns None: "
+                                      "the critic would have no row of that width")
+        if priv_obs is not None and (priv_obs.dim() != 2 or priv_obs.shape[1] != num_priv):
+            raise ValueError(f"get_privileged_observations() returns {tuple(priv_obs.shape)}, num_privileged_obs is {num_priv}")
+        self.privileged = priv_obs is not None          # the critic reads its own row (on_policy_runner.py:161-215)
+        num_critic_obs = int(num_priv) if self.privileged else None
         recurrent = policy_name == "ActorCriticRecurrent"
         symmetry_cfg = self.alg_cfg.get("symmetry_cfg")
         if symmetry_cfg and recurrent:
             raise NotImplementedError("symmetry_cfg with ActorCriticRecurrent is not built in the native update (rl.NativeSymmetricPPO is feed-forward)")
         self.seed = int(train_cfg.get("seed", 1))
         self.noise_std_type = policy_noise_std_type(policy_name, self.policy_cfg)
-        sd = initial_state_dict(policy_name, num_obs, env.num_actions, self.policy_cfg, self.seed)
+        sd = initial_state_dict(policy_name, num_obs, env.num_actions, self.policy_cfg, self.seed, num_critic_obs=num_critic_obs)
         activation = self.policy_cfg.get("activation", "elu")
         if recurrent:
             policy = NativeActorCriticRecurrent(sd, activation, str(self.policy_cfg.get("rnn_type", "lstm")).lower(), self.noise_std_type, device=str(self.device),
@@ -229,34 +249,52 @@ class NativeOnPolicyRunner:
         self.num_steps_per_env, self.save_interval = int(self.cfg["num_steps_per_env"]), int(self.cfg["save_interval"])
         self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
         self.obs_normalizer = NativeEmpiricalNormalization([num_obs], until=int(1.0e8), device=str(self.device)) if self.empirical_normalization else None
-        self.privileged_obs_normalizer = self.obs_normalizer          # one handle serves actor and critic
-        self.layered = steps_outside_the_library(env)          # env classes with host work around the native step: the collection loop runs on the host
+        self.privileged_obs_normalizer = self.obs_normalizer          # without privileged observations one handle serves actor and critic
+        if self.privileged and self.empirical_normalization:
+            self.privileged_obs_normalizer = NativeEmpiricalNormalization([num_critic_obs], until=int(1.0e8), device=str(self.device))
+        # env classes with host work around the native step: the collection loop runs on the host.  With privileged observations the rule is the
+        # env class's own declaration: the one-call two-stream collector, or the host loop
+        self.layered = not collects_privileged_natively(env) if self.privileged else steps_outside_the_library(env)
         self.writer, self.disable_logs = None, False
         self.tot_timesteps, self.tot_time, self.current_learning_iteration = 0, 0.0, 0
-        self._host_obs, self._host_episode = None, None
+        self._host_obs, self._host_priv, self._host_episode = None, None, None
         self.env.reset()
 
     # ---- modes (`:729-754`)
+    def _normalizers(self):
+        """The actor's handle and, where the critic has its own, the critic's."""
+        both = (self.obs_normalizer, self.privileged_obs_normalizer if self.privileged else None)
+        return [n for n in both if n is not None]
+
     def train_mode(self):
-        if self.obs_normalizer is not None:
-            self.obs_normalizer.train()
+        for norm in self._normalizers():
+            norm.train()
 
     def eval_mode(self):
-        if self.obs_normalizer is not None:
-            self.obs_normalizer.eval()
+        for norm in self._normalizers():
+            norm.eval()
+
+    def forget_carried(self):
+        for norm in self._normalizers():
+            norm.forget_carried()
 
     # ---- collection
     def _collect(self, tracker):
         """One collection of `num_steps_per_env` steps: the rollout dict of `collect_rollout_tracked`."""
         T = self.num_steps_per_env
         if not self.layered:
-            return collect_rollout_tracked(self.env, self.alg.policy, T, gamma=self.gamma, lam=self.lam, obs_normalizer=self.obs_normalizer, episode_tracker=tracker)
+            return collect_rollout_tracked(self.env, self.alg.policy, T, gamma=self.gamma, lam=self.lam, obs_normalizer=self.obs_normalizer, episode_tracker=tracker,
+                                           privileged_obs_normalizer=self.privileged_obs_normalizer if self.privileged else None)
         return self._collect_host(tracker, T)
 
     def _collect_host(self, tracker, T):
         """The same dict from a host loop, for env classes whose step is more than the native one."""
         env, policy, norm = self.env, self.alg.policy, self.obs_normalizer
+        pnorm = self.privileged_obs_normalizer if self.privileged else None
         obs = self._host_obs if self._host_obs is not None else env.get_observations().to(self.device)
+        priv = None
+        if self.privileged:          # (the first rows of learn() pass no normaliser: on_policy_runner.py:364-366)
+            priv = self._host_priv if self._host_priv is not None else env.get_privileged_observations().to(self.device)
         N, O, A, dev = env.num_envs, obs.shape[1], env.num_actions, self.device
         ex = env.core.t["extras_episode"]
 
@@ -264,6 +302,8 @@ class NativeOnPolicyRunner:
             return torch.empty(*shape, device=dev, dtype=torch.float32)
         d = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1), actions_log_prob=z(T, N, 1), mu=z(T, N, A),
                  sigma=z(T, N, A), raw_rewards=z(T, N, 1), episode_extras=z(T, ex.numel()))
+        if self.privileged:
+            d["privileged_observations"] = z(T, N, priv.shape[1])
         hid, self._host_episode = [[], []], []
         for t in range(T):
             if policy.is_recurrent:
@@ -271,11 +311,22 @@ class NativeOnPolicyRunner:
                     m.ensure_state(N)
                     hs = m.hidden_states
                     hid[k].append(tuple(h.clone() for h in hs) if isinstance(hs, tuple) else hs.clone())
-            actions, values, logp, mu, sigma = policy.act_and_evaluate(obs)
+            actions, values, logp, mu, sigma = policy.act_and_evaluate(obs, priv)
             d["observations"][t], d["actions"][t], d["values"][t], d["actions_log_prob"][t, :, 0], d["mu"][t], d["sigma"][t] = obs, actions, values, logp, mu, sigma
-            obs, _, rew, dones, infos = env.step(actions)
+            if self.privileged:
+                d["privileged_observations"][t] = priv
+            obs, priv, rew, dones, infos = env.step(actions)
             obs = obs.to(dev)
-            if norm is not None:
+            if self.privileged:          # on_policy_runner.py:403-412: the step's second value, else the getter, else the observations
+                if priv is None:
+                    priv = env.get_privileged_observations()
+                priv = (obs if priv is None else priv).to(dev)
+                if norm is not None and pnorm is not None:
+                    obs, priv = norm.step_pair(pnorm, obs, priv)
+                else:
+                    obs = norm(obs) if norm is not None else obs
+                    priv = pnorm(priv) if pnorm is not None else priv.clone()          # (the env's own buffer: the next step overwrites it)
+            elif norm is not None:
                 obs = norm(obs)
             time_outs = infos["time_outs"].to(dev, torch.float32) if "time_outs" in infos else torch.zeros(N, device=dev)
             d["raw_rewards"][t, :, 0] = rew
@@ -287,7 +338,8 @@ class NativeOnPolicyRunner:
                                        if not _view_index(v, ex)[0]})
             policy.reset(dones)
         self._host_obs = obs.clone()
-        d["last_values"] = policy.evaluate(obs).clone()
+        self._host_priv = priv.clone() if self.privileged else None
+        d["last_values"] = policy.evaluate(priv if self.privileged else obs).clone()
         d["returns"], d["advantages"] = compute_returns(d["rewards"], d["dones"], d["values"], d["last_values"], self.gamma, self.lam)
         ep_return, ep_length = tracker.track(d["raw_rewards"], d["dones"])
         d["ep_return"], d["ep_length"] = ep_return.reshape(T, N, 1), ep_length.reshape(T, N, 1)
@@ -319,9 +371,8 @@ class NativeOnPolicyRunner:
             self.writer = _make_writer(self.log_dir)
         if init_at_random_ep_len:
             env.episode_length_buf[:] = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
-        if self.obs_normalizer is not None:
-            self.obs_normalizer.forget_carried()
-        self._host_obs = None
+        self.forget_carried()
+        self._host_obs = self._host_priv = None
         self.train_mode()
         tracker = EpisodeTracker(env.num_envs, self.device)
         start_iter = self.current_learning_iteration
@@ -409,7 +460,7 @@ class NativeOnPolicyRunner:
                  "iter": self.current_learning_iteration, "infos": infos}
         if self.empirical_normalization:
             saved["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
-            saved["privileged_obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            saved["privileged_obs_norm_state_dict"] = self.privileged_obs_normalizer.state_dict()
         torch.save(saved, path)
 
     def load(self, path, load_optimizer=True):
@@ -421,11 +472,17 @@ class NativeOnPolicyRunner:
                            f"unexpected {sorted(set(model) - set(want))}")
         if self.empirical_normalization:
             a, b = loaded["obs_norm_state_dict"], loaded["privileged_obs_norm_state_dict"]
-            if any(not torch.equal(a[k], b[k]) for k in STATE_KEYS):
-                raise NotImplementedError("obs_norm_state_dict and privileged_obs_norm_state_dict differ: separate actor and critic normalisers are not "
-                                          "built in the native runner")
-            self.obs_normalizer.load_state_dict(a)
-            self.obs_normalizer.forget_carried()
+            if self.privileged:
+                for name, norm, state in (("obs_norm_state_dict", self.obs_normalizer, a), ("privileged_obs_norm_state_dict", self.privileged_obs_normalizer, b)):
+                    if state["_mean"].numel() != norm.num_features:
+                        raise ValueError(f"{name} holds {state['_mean'].numel()} columns, this env's rows {norm.num_features}")
+                    norm.load_state_dict(state)
+            else:
+                if any(not torch.equal(a[k], b[k]) for k in STATE_KEYS):
+                    raise NotImplementedError("obs_norm_state_dict and privileged_obs_norm_state_dict differ: separate actor and critic normalisers are not "
+                                              "built in the native runner")
+                self.obs_normalizer.load_state_dict(a)
+            self.forget_carried()
         if load_optimizer and "optimizer_state_dict" in loaded:
             self.alg.load_optimizer_state(native_optimizer_state(model, loaded["optimizer_state_dict"]))
         else:

@@ -62,7 +62,8 @@ typedef struct lg_runner_hooks {
  * normalizer: row 0 is the handle's carried row when it holds one of n rows, else the env's raw observation, neither normalised nor counted
  * (the first observation of learn(), on_policy_runner.py:364-365, never passes the normaliser).  After every step the new raw row is
  * normalised in place by lg_obsnorm_step(update = training) -- the row after the last step too, which becomes the carried row: T steps, T
- * updates.  last_values is evaluated on the carried row.  The env's own obs_buf stays raw.  One handle serves actor and critic.
+ * updates.  last_values is evaluated on the carried row.  The env's own obs_buf stays raw.  One handle serves actor and critic here; a critic
+ * with privileged observations of its own, and a normaliser of its own, is lgrunner_privileged.h (lg_runner_collect_privileged).
  * episode: raw_rewards[t] and extras[t] are copied after step t; after the loop one kernel, one thread per env, walks the T steps:
  * sum += r; len += 1; if dones[t] > 0: emit and zero.  The host takes dones.nonzero() once: its (t, env) order is the reference's. */
 int lg_runner_collect(struct lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed,
