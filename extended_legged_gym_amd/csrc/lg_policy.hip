@@ -581,92 +581,7 @@ int lg_policy_act_recurrent(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp*
   return lg_policy_act(actor, critic, top_a, top_c, n, std_, seed, call, deterministic, actions, action_mean, actions_log_prob, values, stream);
 }
 
-}  // extern "C"
-
-// both PPO collectors: mem_a NULL = the feed-forward ActorCritic (no memory state, no hidden-state rows); hooks: lg_policy_internal.h
-int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
-                              int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
-                              float* c_a, float* h_c, float* c_c, const CollectHooks* hooks, void* stream) {
-  DeviceScope ds_(actor->device);
-  if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
-      !out->sigma || !out->last_values) return lg_policy_fail(LG_ERR_INVALID, "null output row");
-  const bool lstm_a = mem_a && mem_a->type == LG_RNN_LSTM, lstm_c = mem_a && mem_c->type == LG_RNN_LSTM;
-  if (mem_a && (!hid->h_a || !hid->h_c || (lstm_a && !hid->c_a) || (lstm_c && !hid->c_c))) return lg_policy_fail(LG_ERR_INVALID, "null hidden-state row");
-  const float* obs; int64_t n, O, Aenv;
-  int rc = env_shape(env, &obs, &n, &O, &Aenv);
-  if (rc == LG_OK && mem_a) rc = rnn_check(mem_a, h_a, c_a, n);
-  if (rc == LG_OK && mem_a) rc = rnn_check(mem_c, h_c, c_c, n);
-  if (rc != LG_OK) return rc;
-  const int A = actor->h.dims[actor->h.L];
-  if ((mem_a ? mem_a->input : actor->h.dims[0]) != O || (mem_a ? mem_c->input : critic->h.dims[0]) != O || critic->h.dims[critic->h.L] != 1 || A != Aenv)
-    return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (obs width, one action per DOF, scalar value)");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t sa = mem_a ? (size_t)mem_a->num_layers * n * mem_a->hidden : 0, sc = mem_a ? (size_t)mem_c->num_layers * n * mem_c->hidden : 0;
-  // the runner's hooks: the normaliser's carried row (row 0 of this collection when it holds one, the normalised row after the last step when
-  // the loop is done), and the env's raw reward and episode-extras rows
-  lg_obsnorm* norm = hooks ? hooks->normalizer : nullptr;
-  float* carried = nullptr; bool carried_valid = false;
-  if (norm && (rc = lg_obsnorm_carried_begin(norm, n, O, &carried, &carried_valid)) != LG_OK) return rc;
-  const float* rew_buf = nullptr; const float* extras_buf = nullptr; int64_t K = 0;
-  if (hooks && (hooks->raw_rewards || hooks->extras)) {
-    void* p; int64_t shp[4]; int32_t nd, dt;
-    if (lg_get_tensor(env, LG_T_REW_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's reward rows: ") + lg_last_error(env));
-    rew_buf = (const float*)p;
-    if (lg_get_tensor(env, LG_T_EXTRAS_EPISODE, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's episode extras: ") + lg_last_error(env));
-    extras_buf = (const float*)p; K = shp[0];
-  }
-  // the first observation row is copied from the env; every later one is written by the step itself (lg_step_transition),
-  // as are the reward (with the time-out bootstrap) and done rows: three launches per step (act, physics, post-physics)
-  POLICY_TRY(hipMemcpyAsync(out->observations, carried_valid ? carried : obs, (size_t)n * O * 4, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
-  for (int t = 0; t < T; ++t) {
-    float* obs_t = out->observations + (size_t)t * n * O;
-    float* act_t = out->actions + (size_t)t * n * A;
-    float* dones_t = out->dones + (size_t)t * n;
-    if (mem_a) {
-      // RolloutStorage._save_hidden_states (rollout_storage.py:123-140): the state BEFORE this step's act (ppo.py:148-149)
-      POLICY_TRY(hipMemcpyAsync(hid->h_a + t * sa, h_a, sa * 4, hipMemcpyDeviceToDevice, st));
-      if (lstm_a) POLICY_TRY(hipMemcpyAsync(hid->c_a + t * sa, c_a, sa * 4, hipMemcpyDeviceToDevice, st));
-      POLICY_TRY(hipMemcpyAsync(hid->h_c + t * sc, h_c, sc * 4, hipMemcpyDeviceToDevice, st));
-      if (lstm_c) POLICY_TRY(hipMemcpyAsync(hid->c_c + t * sc, c_c, sc * 4, hipMemcpyDeviceToDevice, st));
-      rc = lg_policy_act_recurrent(mem_a, actor, mem_c, critic, obs_t, obs_t, n, std, seed, first_call + (uint64_t)t, 0, h_a, c_a, h_c, c_c, nullptr, act_t,
-                                   out->mu + (size_t)t * n * A, out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
-    } else {
-      rc = lg_policy_act(actor, critic, obs_t, obs_t, n, std, seed, first_call + (uint64_t)t, 0, act_t, out->mu + (size_t)t * n * A,
-                         out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
-    }
-    if (rc != LG_OK) return rc;
-    float* next = t + 1 < T ? out->observations + (size_t)(t + 1) * n * O : carried;
-    rc = lg_step_transition(env, act_t, next, out->values + (size_t)t * n, gamma, out->rewards + (size_t)t * n, dones_t, stream);
-    if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
-    if (norm && (rc = lg_obsnorm_step(norm, next, n, O, hooks->update, next, stream)) != LG_OK) return rc;          // on_policy_runner.py:425-427
-    if (hooks && hooks->raw_rewards) POLICY_TRY(hipMemcpyAsync(hooks->raw_rewards + (size_t)t * n, rew_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    if (hooks && hooks->extras) POLICY_TRY(hipMemcpyAsync(hooks->extras + (size_t)t * K, extras_buf, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
-    if (mem_a) {                                       // PPO.process_env_step ends with policy.reset(dones) (ppo.py:188)
-      rc = lg_rnn_reset_rows(mem_a, h_a, c_a, dones_t, n, stream);
-      if (rc == LG_OK) rc = lg_rnn_reset_rows(mem_c, h_c, c_c, dones_t, n, stream);
-      if (rc != LG_OK) return rc;
-    }
-  }
-  // last_values = critic(last obs) (ppo.py:186-192); a recurrent policy.evaluate goes through Memory.forward, so the critic memory advances once more
-  const float* last = norm ? carried : obs;
-  if (mem_a) {
-    rc = lg_rnn_step(mem_c, last, n, h_c, c_c, nullptr, nullptr, stream);
-    if (rc != LG_OK) return rc;
-    last = h_c + (size_t)(mem_c->num_layers - 1) * n * mem_c->hidden;
-  }
-  rc = lg_mlp_forward(critic, last, n, out->last_values, stream);
-  if (rc == LG_OK && out->returns && out->advantages)
-    rc = lg_compute_returns(out->rewards, out->dones, out->values, out->last_values, T, n, gamma, lam, normalize_advantage, out->returns,
-                            out->advantages, stream);
-  if (rc != LG_OK) return rc;
-  POLICY_TRY(hipGetLastError());
-  if (norm) lg_obsnorm_carried_commit(norm);
-  return LG_OK;
-}
-
-extern "C" {
-
+// both PPO collectors: the loop is lg_policy_collect_rollout, at the end of this file (behind the history layer it shares with the distillation collector)
 int lg_collect_rollout(lg_ctx* env, lg_mlp* actor, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
                        float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, void* stream) {
   POLICY_ENTRY;
@@ -739,6 +654,36 @@ static int distill_widths(lg_mlp* student, lg_mlp* teacher) {
   return LG_OK;
 }
 
+// ---- the row a reader (the student; the actor of the two-stream PPO collection) derives from the env's raw row: the history layer's, or the
+// first `width` columns.  `who` names the reader in the refusals, `wider` ends the last of them.
+static int derived_row_check(const lg_obs_history* hist, int64_t width, int64_t env_width, const char* who, const char* wider) {
+  if (hist) {
+    if (!hist->history || hist->H < 1 || hist->W < 1 || hist->W > env_width || !(hist->clip > 0.f)) return lg_policy_fail(LG_ERR_INVALID, "bad history layer (pointer, H, W <= env row, clip > 0)");
+    if ((int64_t)hist->H * hist->W != width) return lg_policy_fail(LG_ERR_INVALID, std::string("the ") + who + "'s input width is not H x W of the history layer");
+  } else if (width > env_width) {
+    return lg_policy_fail(LG_ERR_INVALID, std::string("without a history layer the ") + who + " reads a prefix of the env's observation row" + wider);
+  }
+  return LG_OK;
+}
+
+struct DerivedRow { const lg_obs_history* hist; const float* env_obs; int64_t n, env_width, width; uint64_t first_call; void* stream; };
+
+// t >= 0: the row after step t -- the layer steps in place on the env's own raw row (dst NULL: it steps and writes no row out); t < 0: row 0 of
+// a collection, the clipped history as it stands.  Without a layer both are the 2-D copy of the prefix.  One launch or one copy.
+static int derived_row(const DerivedRow& r, int t, const float* dones_t, float* dst) {
+  const lg_obs_history* hist = r.hist;
+  hipStream_t st = (hipStream_t)r.stream;
+  const size_t count = (size_t)r.n * r.width;
+  if (hist && t < 0) {
+    hipLaunchKernelGGL(obs_clip_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, hist->history, (int64_t)count, hist->clip, dst);
+    return LG_OK;
+  }
+  if (hist) return lg_obs_history_step(hist->history, r.n, hist->H, hist->W, r.env_obs, r.env_width, dones_t, hist->noise_scale,
+                                       hist->inject_u ? hist->inject_u + (size_t)t * count : nullptr, hist->noise_seed, r.first_call + (uint64_t)t, hist->clip, dst, r.stream);
+  if (dst) POLICY_TRY(hipMemcpy2DAsync(dst, (size_t)r.width * 4, r.env_obs, (size_t)r.env_width * 4, (size_t)r.width * 4, (size_t)r.n, hipMemcpyDeviceToDevice, st));
+  return LG_OK;
+}
+
 extern "C" {
 
 int lg_obs_history_step(float* history, int64_t n, int32_t H, int32_t W, const float* obs, int64_t obs_stride, const float* dones,
@@ -807,24 +752,12 @@ static int collect_distillation(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_
     return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (the teacher reads the env's observation row, one action per DOF)");
   if (mem_s && (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden)))
     return lg_policy_fail(LG_ERR_INVALID, "an MLP's input width is not its memory's hidden width");
-  if (hist) {
-    if (!hist->history || hist->H < 1 || hist->W < 1 || hist->W > Ot || !(hist->clip > 0.f)) return lg_policy_fail(LG_ERR_INVALID, "bad history layer (pointer, H, W <= env row, clip > 0)");
-    if ((int64_t)hist->H * hist->W != Os) return lg_policy_fail(LG_ERR_INVALID, "the student's input width is not H x W of the history layer");
-  } else if (Os > Ot) {
-    return lg_policy_fail(LG_ERR_INVALID, "without a history layer the student reads a prefix of the env's observation row");
-  }
+  if ((rc = derived_row_check(hist, Os, Ot, "student", "")) != LG_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t so = (size_t)n * Os, sp = (size_t)n * Ot, sa = (size_t)n * A;
-  // the student's row after a step: the history layer, or the head of the teacher's row
-  auto student_row = [&](int t, const float* dones_t, float* dst) -> int {
-    if (hist) return lg_obs_history_step(hist->history, n, hist->H, hist->W, env_obs, Ot, dones_t, hist->noise_scale,
-                                         hist->inject_u ? hist->inject_u + (size_t)t * so : nullptr, hist->noise_seed, first_call + (uint64_t)t, hist->clip, dst, stream);
-    if (dst) POLICY_TRY(hipMemcpy2DAsync(dst, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
-    return LG_OK;
-  };
+  const DerivedRow student_row{hist, env_obs, n, Ot, Os, first_call, stream};          // the history layer, or the head of the teacher's row
   POLICY_TRY(hipMemcpyAsync(out->privileged_observations, env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
-  if (hist) hipLaunchKernelGGL(obs_clip_kernel, dim3((unsigned)((so + 255) / 256)), dim3(256), 0, st, hist->history, (int64_t)so, hist->clip, out->observations);
-  else POLICY_TRY(hipMemcpy2DAsync(out->observations, (size_t)Os * 4, env_obs, (size_t)Ot * 4, (size_t)Os * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+  if ((rc = derived_row(student_row, -1, nullptr, out->observations)) != LG_OK) return rc;
   for (int t = 0; t < T; ++t) {
     float* act_t = out->actions + t * sa;
     float* dones_t = out->dones + (size_t)t * n;
@@ -836,7 +769,7 @@ static int collect_distillation(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_
     // Distillation.process_env_step (distillation.py:98-101) stores the env's reward as it is: no value row, no time-out bootstrap
     rc = lg_step_transition(env, act_t, t + 1 < T ? out->privileged_observations + (t + 1) * sp : nullptr, nullptr, 0.f, out->rewards + (size_t)t * n, dones_t, stream);
     if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
-    rc = student_row(t, dones_t, t + 1 < T ? out->observations + (t + 1) * so : out->last_observations);
+    rc = derived_row(student_row, t, dones_t, t + 1 < T ? out->observations + (t + 1) * so : out->last_observations);
     if (rc == LG_OK && mem_s) {                        // policy.reset(dones) (distillation.py:105)
       rc = lg_rnn_reset_rows(mem_s, h_s, c_s, dones_t, n, stream);
       if (rc == LG_OK && mem_t) rc = lg_rnn_reset_rows(mem_t, h_t, c_t, dones_t, n, stream);
@@ -877,13 +810,24 @@ int lg_collect_distillation_recurrent(lg_ctx* env, lg_rnn* mem_s, lg_mlp* studen
 }  // extern "C"
 
 
-// ============================================================================================ privileged critic observations (lgrunner_privileged.h)
-// The PPO collector with two observation streams: the critic reads the env's row (O_c wide), the actor the history layer's row or a column prefix
-// (O_a wide), each stream with its own normaliser and carried row.  The launches of lg_policy_collect_rollout with, per step, the actor's row (one
-// launch) in front of the normaliser, and the paired normaliser step (three launches for both handles) in place of the single one.
-int lg_policy_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
-                                 int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
-                                 float* c_a, float* h_c, float* c_c, const PrivilegedHooks* ph, void* stream) {
+// ============================================================================================ the PPO collection loop (lgpolicy.h, lgrunner.h, lgrunner_privileged.h)
+int lg_policy_reward_rows(lg_ctx* env, EnvRewardRows* rows) {
+  void* p; int64_t shp[4]; int32_t nd, dt;
+  if (lg_get_tensor(env, LG_T_REW_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's reward rows: ") + lg_last_error(env));
+  rows->rew = (const float*)p; rows->n = shp[0];
+  if (lg_get_tensor(env, LG_T_EXTRAS_EPISODE, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's episode extras: ") + lg_last_error(env));
+  rows->extras = (const float*)p; rows->K = shp[0];
+  return LG_OK;
+}
+
+// The one loop of every PPO collector; mem_a NULL = the feed-forward ActorCritic (no memory state, no hidden-state rows); hooks and the two modes:
+// lg_policy_internal.h.  The step itself (lg_step_transition) writes the critic's stream: the env's row, O_c wide, stored in crit_rows and
+// normalised in place by norm_c.  With one stream that is out->observations and the actor reads it too; with two it is the privileged rows, and
+// the actor's row (O_a wide, out->observations, norm_a) is derived after each step from the env's own raw row, never from the stored one.
+// Per step: act, physics, post-physics, [the actor's row: one launch or copy], [the normaliser step: paired, three launches, for two handles].
+int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
+                              int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
+                              float* c_a, float* h_c, float* c_c, const CollectHooks* hooks, void* stream) {
   DeviceScope ds_(actor->device);
   if (!out->observations || !out->actions || !out->rewards || !out->dones || !out->values || !out->actions_log_prob || !out->mu ||
       !out->sigma || !out->last_values) return lg_policy_fail(LG_ERR_INVALID, "null output row");
@@ -894,88 +838,82 @@ int lg_policy_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_r
   if (rc == LG_OK && mem_a) rc = rnn_check(mem_a, h_a, c_a, n);
   if (rc == LG_OK && mem_a) rc = rnn_check(mem_c, h_c, c_c, n);
   if (rc != LG_OK) return rc;
+  const CollectHooks hk = hooks ? *hooks : CollectHooks();
+  const bool two = hk.privileged_observations != nullptr;
   const int A = actor->h.dims[actor->h.L];
   const int64_t Oa = mem_a ? mem_a->input : actor->h.dims[0];
-  if ((mem_a ? mem_c->input : critic->h.dims[0]) != Oc || critic->h.dims[critic->h.L] != 1 || A != Aenv)
-    return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (the critic reads the env's observation row, one action per DOF, scalar value)");
-  const lg_obs_history* hist = ph->history;
-  if (hist) {
-    if (!hist->history || hist->H < 1 || hist->W < 1 || hist->W > Oc || !(hist->clip > 0.f)) return lg_policy_fail(LG_ERR_INVALID, "bad history layer (pointer, H, W <= env row, clip > 0)");
-    if ((int64_t)hist->H * hist->W != Oa) return lg_policy_fail(LG_ERR_INVALID, "the actor's input width is not H x W of the history layer");
-  } else if (Oa > Oc) {
-    return lg_policy_fail(LG_ERR_INVALID, "without a history layer the actor reads a prefix of the env's observation row: its input is wider than that row");
+  if ((!two && Oa != Oc) || (mem_a ? mem_c->input : critic->h.dims[0]) != Oc || critic->h.dims[critic->h.L] != 1 || A != Aenv)
+    return lg_policy_fail(LG_ERR_INVALID, two ? "network widths do not match the env (the critic reads the env's observation row, one action per DOF, scalar value)"
+                                              : "network widths do not match the env (obs width, one action per DOF, scalar value)");
+  lg_obsnorm *norm_a = two ? hk.normalizer : nullptr, *norm_c = two ? hk.normalizer_c : hk.normalizer;
+  if (two) {
+    if ((rc = derived_row_check(hk.history, Oa, Oc, "actor", ": its input is wider than that row")) != LG_OK) return rc;
+    if (norm_a && lg_obsnorm_width(norm_a) != Oa) return lg_policy_fail(LG_ERR_INVALID, "the actor's normaliser does not have the actor's input width");
+    if (norm_c && lg_obsnorm_width(norm_c) != Oc) return lg_policy_fail(LG_ERR_INVALID, "the critic's normaliser does not have the env's observation width");
+    if (norm_a && norm_a == norm_c) return lg_policy_fail(LG_ERR_INVALID, "the actor and the critic need a normaliser each");
   }
-  lg_obsnorm *norm_a = ph->normalizer_a, *norm_c = ph->normalizer_c;
-  if (norm_a && lg_obsnorm_width(norm_a) != Oa) return lg_policy_fail(LG_ERR_INVALID, "the actor's normaliser does not have the actor's input width");
-  if (norm_c && lg_obsnorm_width(norm_c) != Oc) return lg_policy_fail(LG_ERR_INVALID, "the critic's normaliser does not have the env's observation width");
-  if (norm_a && norm_a == norm_c) return lg_policy_fail(LG_ERR_INVALID, "the actor and the critic need a normaliser each");
   hipStream_t st = (hipStream_t)stream;
   const size_t sa = mem_a ? (size_t)mem_a->num_layers * n * mem_a->hidden : 0, sc = mem_a ? (size_t)mem_c->num_layers * n * mem_c->hidden : 0;
   const size_t so = (size_t)n * Oa, sp = (size_t)n * Oc;
-  const float* rew_buf = nullptr; const float* extras_buf = nullptr; int64_t K = 0;
-  if (ph->raw_rewards || ph->extras) {
-    void* p; int64_t shp[4]; int32_t nd, dt;
-    if (lg_get_tensor(env, LG_T_REW_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's reward rows: ") + lg_last_error(env));
-    rew_buf = (const float*)p;
-    if (lg_get_tensor(env, LG_T_EXTRAS_EPISODE, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's episode extras: ") + lg_last_error(env));
-    extras_buf = (const float*)p; K = shp[0];
-  }
+  EnvRewardRows env_rows;
+  if ((hk.raw_rewards || hk.extras) && (rc = lg_policy_reward_rows(env, &env_rows)) != LG_OK) return rc;
+  // a normaliser's carried row: row 0 of this collection when it holds one, the normalised row after the last step when the loop is done
   float *carried_a = nullptr, *carried_c = nullptr; bool valid_a = false, valid_c = false;
   if (norm_a && (rc = lg_obsnorm_carried_begin(norm_a, n, Oa, &carried_a, &valid_a)) != LG_OK) return rc;
   if (norm_c && (rc = lg_obsnorm_carried_begin(norm_c, n, Oc, &carried_c, &valid_c)) != LG_OK) return rc;
-  // the actor's row after a step: the history layer on the env's own raw row (never the stored critic row: that one is normalised in place), or
-  // the head of that row
-  auto actor_row = [&](int t, const float* dones_t, float* dst) -> int {
-    if (hist) return lg_obs_history_step(hist->history, n, hist->H, hist->W, env_obs, Oc, dones_t, hist->noise_scale,
-                                         hist->inject_u ? hist->inject_u + (size_t)t * so : nullptr, hist->noise_seed, first_call + (uint64_t)t, hist->clip, dst, stream);
-    if (dst) POLICY_TRY(hipMemcpy2DAsync(dst, (size_t)Oa * 4, env_obs, (size_t)Oc * 4, (size_t)Oa * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
-    return LG_OK;
-  };
-  // row 0 of each stream: the carried row where one is held, else the clipped history (the column prefix) and the env's raw row
-  if (valid_a) POLICY_TRY(hipMemcpyAsync(out->observations, carried_a, so * 4, hipMemcpyDeviceToDevice, st));
-  else if (hist) hipLaunchKernelGGL(obs_clip_kernel, dim3((unsigned)((so + 255) / 256)), dim3(256), 0, st, hist->history, (int64_t)so, hist->clip, out->observations);
-  else POLICY_TRY(hipMemcpy2DAsync(out->observations, (size_t)Oa * 4, env_obs, (size_t)Oc * 4, (size_t)Oa * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
-  POLICY_TRY(hipMemcpyAsync(ph->privileged_observations, valid_c ? carried_c : env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
+  float* crit_rows = two ? hk.privileged_observations : out->observations;
+  const DerivedRow actor_row{hk.history, env_obs, n, Oc, Oa, first_call, stream};
+  // row 0 of each stream: the carried row where one is held, else the clipped history (the column prefix) for the actor and the env's raw row.
+  // Every later row of the critic's stream is written by the step itself, as are the reward (with the time-out bootstrap) and done rows
+  if (two) {
+    if (valid_a) POLICY_TRY(hipMemcpyAsync(out->observations, carried_a, so * 4, hipMemcpyDeviceToDevice, st));
+    else if ((rc = derived_row(actor_row, -1, nullptr, out->observations)) != LG_OK) return rc;
+  }
+  POLICY_TRY(hipMemcpyAsync(crit_rows, valid_c ? carried_c : env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(fill_sigma_kernel, dim3((unsigned)(((int64_t)T * n * A + 255) / 256)), dim3(256), 0, st, (int64_t)T * n, A, std, out->sigma);
   for (int t = 0; t < T; ++t) {
     const float* obs_t = out->observations + t * so;
-    const float* priv_t = ph->privileged_observations + t * sp;
+    const float* crit_t = crit_rows + t * sp;
     float* act_t = out->actions + (size_t)t * n * A;
     float* dones_t = out->dones + (size_t)t * n;
     if (mem_a) {
+      // RolloutStorage._save_hidden_states (rollout_storage.py:123-140): the state BEFORE this step's act (ppo.py:148-149)
       POLICY_TRY(hipMemcpyAsync(hid->h_a + t * sa, h_a, sa * 4, hipMemcpyDeviceToDevice, st));
       if (lstm_a) POLICY_TRY(hipMemcpyAsync(hid->c_a + t * sa, c_a, sa * 4, hipMemcpyDeviceToDevice, st));
       POLICY_TRY(hipMemcpyAsync(hid->h_c + t * sc, h_c, sc * 4, hipMemcpyDeviceToDevice, st));
       if (lstm_c) POLICY_TRY(hipMemcpyAsync(hid->c_c + t * sc, c_c, sc * 4, hipMemcpyDeviceToDevice, st));
-      rc = lg_policy_act_recurrent(mem_a, actor, mem_c, critic, obs_t, priv_t, n, std, seed, first_call + (uint64_t)t, 0, h_a, c_a, h_c, c_c, nullptr, act_t,
+      rc = lg_policy_act_recurrent(mem_a, actor, mem_c, critic, obs_t, crit_t, n, std, seed, first_call + (uint64_t)t, 0, h_a, c_a, h_c, c_c, nullptr, act_t,
                                    out->mu + (size_t)t * n * A, out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
     } else {
-      rc = lg_policy_act(actor, critic, obs_t, priv_t, n, std, seed, first_call + (uint64_t)t, 0, act_t, out->mu + (size_t)t * n * A,
+      rc = lg_policy_act(actor, critic, obs_t, crit_t, n, std, seed, first_call + (uint64_t)t, 0, act_t, out->mu + (size_t)t * n * A,
                          out->actions_log_prob + (size_t)t * n, out->values + (size_t)t * n, stream);
     }
     if (rc != LG_OK) return rc;
     const bool more = t + 1 < T;
-    // the critic's next row, written by the step itself; after the last step into the critic normaliser's carried row (none: the env's own row serves)
-    float* next_c = more ? ph->privileged_observations + (t + 1) * sp : carried_c;
+    // the critic's next row; after the last step into its normaliser's carried row (none: the env's own row serves)
+    float* next_c = more ? crit_rows + (t + 1) * sp : carried_c;
     rc = lg_step_transition(env, act_t, next_c, out->values + (size_t)t * n, gamma, out->rewards + (size_t)t * n, dones_t, stream);
     if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
-    // the actor's next row; after the last step the un-normalised row goes to last_observations and its normalised copy to the carried row
-    float* norm_out_a = more ? out->observations + (t + 1) * so : carried_a;
-    float* next_a = more ? norm_out_a : (ph->last_observations ? ph->last_observations : carried_a);
-    rc = actor_row(t, dones_t, next_a);
+    // two streams: the actor's next row; after the last step the un-normalised row goes to last_observations and its normalised copy to the carried row
+    float *norm_out_a = nullptr, *next_a = nullptr;
+    if (two) {
+      norm_out_a = more ? out->observations + (t + 1) * so : carried_a;
+      next_a = more ? norm_out_a : (hk.last_observations ? hk.last_observations : carried_a);
+      if ((rc = derived_row(actor_row, t, dones_t, next_a)) != LG_OK) return rc;
+    }
+    if (norm_a && norm_c) rc = lg_obsnorm_step_pair(norm_a, next_a, Oa, norm_out_a, norm_c, next_c, Oc, next_c, n, hk.update, stream);
+    else if (norm_a) rc = lg_obsnorm_step(norm_a, next_a, n, Oa, hk.update, norm_out_a, stream);
+    else if (norm_c) rc = lg_obsnorm_step(norm_c, next_c, n, Oc, hk.update, next_c, stream);          // on_policy_runner.py:425-427
     if (rc != LG_OK) return rc;
-    if (norm_a && norm_c) rc = lg_obsnorm_step_pair(norm_a, next_a, Oa, norm_out_a, norm_c, next_c, Oc, next_c, n, ph->update, stream);
-    else if (norm_a) rc = lg_obsnorm_step(norm_a, next_a, n, Oa, ph->update, norm_out_a, stream);
-    else if (norm_c) rc = lg_obsnorm_step(norm_c, next_c, n, Oc, ph->update, next_c, stream);
-    if (rc != LG_OK) return rc;
-    if (ph->raw_rewards) POLICY_TRY(hipMemcpyAsync(ph->raw_rewards + (size_t)t * n, rew_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    if (ph->extras) POLICY_TRY(hipMemcpyAsync(ph->extras + (size_t)t * K, extras_buf, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
-    if (mem_a) {
+    if (hk.raw_rewards) POLICY_TRY(hipMemcpyAsync(hk.raw_rewards + (size_t)t * n, env_rows.rew, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (hk.extras) POLICY_TRY(hipMemcpyAsync(hk.extras + (size_t)t * env_rows.K, env_rows.extras, (size_t)env_rows.K * 4, hipMemcpyDeviceToDevice, st));
+    if (mem_a) {                                       // PPO.process_env_step ends with policy.reset(dones) (ppo.py:188)
       rc = lg_rnn_reset_rows(mem_a, h_a, c_a, dones_t, n, stream);
       if (rc == LG_OK) rc = lg_rnn_reset_rows(mem_c, h_c, c_c, dones_t, n, stream);
       if (rc != LG_OK) return rc;
     }
   }
+  // last_values = critic(last obs) (ppo.py:186-192); a recurrent policy.evaluate goes through Memory.forward, so the critic memory advances once more
   const float* last = norm_c ? carried_c : env_obs;
   if (mem_a) {
     rc = lg_rnn_step(mem_c, last, n, h_c, c_c, nullptr, nullptr, stream);
@@ -992,3 +930,4 @@ int lg_policy_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_r
   if (norm_c) lg_obsnorm_carried_commit(norm_c);
   return LG_OK;
 }
+

@@ -34,39 +34,35 @@ int lg_policy_device_of(const void* p);
 void lg_mlp_widths(const lg_mlp* m, int* layers, int* in, int* out, int* device);
 void lg_rnn_widths(const lg_rnn* m, int* type, int* input, int* hidden, int* device);
 
-// ---- both PPO collectors (lg_policy.hip; mem_a NULL = the feed-forward ActorCritic), shared with the runner's collector (lg_runner.hip), which
-// passes hooks.  hooks NULL: the loop of lg_collect_rollout / lg_collect_rollout_recurrent, launch for launch.
+// ---- the PPO collection loop (lg_policy.hip; mem_a NULL = the feed-forward ActorCritic): the one loop behind lg_collect_rollout,
+// lg_collect_rollout_recurrent, lg_runner_collect and lg_runner_collect_privileged.  hooks NULL = a CollectHooks with nothing set.  Two modes:
+//   one stream  (privileged_observations NULL): actor and critic read the same stored row, the env's (out->observations, O wide); `normalizer`
+//               serves that row.  history, normalizer_c and last_observations are not read.
+//   two streams (privileged_observations set): the critic reads the env's row (stored there, O_c wide, `normalizer_c`), the actor the history
+//               layer's row or a column prefix of the env's raw row (out->observations, O_a wide, `normalizer`); a carried row each.
 struct lg_obsnorm;
 struct CollectHooks {
-  lg_obsnorm* normalizer = nullptr;  // every new observation row passes lg_obsnorm_step in place; the row after the last step is the handle's carried row
-  int update = 0;                    // the normaliser's training mode
-  float* raw_rewards = nullptr;      // (T, n): the env's rew_buf after each step
-  float* extras = nullptr;           // (T, K): the env's extras_episode after each step
+  lg_obsnorm* normalizer = nullptr;             // the actor's: every new row of its stream passes lg_obsnorm_step before it is stored and read; the row
+                                                // after the last step is the handle's carried row, row 0 of the next collection
+  lg_obsnorm* normalizer_c = nullptr;           // the critic's (two streams); both set: the paired step
+  int update = 0;                               // the normalisers' training mode
+  float* raw_rewards = nullptr;                 // (T, n): the env's rew_buf after each step
+  float* extras = nullptr;                      // (T, K): the env's extras_episode after each step
+  const lg_obs_history* history = nullptr;      // the actor's layer (two streams); NULL: the actor reads a column prefix of the env's row
+  float* privileged_observations = nullptr;     // (T, n, O_c): selects the two-stream mode
+  float* last_observations = nullptr;           // (n, O_a) or NULL: the actor's un-normalised row after the last step (two streams)
 };
 int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
                               int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
                               float* c_a, float* h_c, float* c_c, const CollectHooks* hooks, void* stream);
+// the env's raw reward row (n) and episode-extras row (K): what the loop copies after each step, and the n of the runner's episode tail
+struct EnvRewardRows { const float* rew = nullptr; const float* extras = nullptr; int64_t n = 0, K = 0; };
+int lg_policy_reward_rows(lg_ctx* env, EnvRewardRows* rows);
 // the carried row of a normaliser (lg_runner.hip): begin returns the (n, O) buffer (allocated on first use) and whether it holds a row, and marks it
 // as not holding one; commit marks it as holding the row the collector left there
 int lg_obsnorm_carried_begin(lg_obsnorm* h, int64_t n, int64_t O, float** row, bool* valid);
 void lg_obsnorm_carried_commit(lg_obsnorm* h);
 int lg_obsnorm_width(const lg_obsnorm* h);
-
-// ---- the PPO collector with privileged critic observations (lg_policy.hip), behind lg_runner_collect_privileged (lg_runner_privileged.hip):
-// two observation streams, a normaliser and a carried row each.  lg_policy_collect_rollout and its three entry points are untouched by it.
-struct PrivilegedHooks {
-  const lg_obs_history* history = nullptr;      // the actor's layer; NULL: the actor reads a column prefix of the env's row
-  lg_obsnorm* normalizer_a = nullptr;           // the actor's, O_a wide
-  lg_obsnorm* normalizer_c = nullptr;           // the critic's, O_c wide
-  int update = 0;                               // the normalisers' training mode
-  float* privileged_observations = nullptr;     // (T, n, O_c)
-  float* last_observations = nullptr;           // (n, O_a) or NULL
-  float* raw_rewards = nullptr;                 // (T, n)
-  float* extras = nullptr;                      // (T, K)
-};
-int lg_policy_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
-                                 int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
-                                 float* c_a, float* h_c, float* c_c, const PrivilegedHooks* ph, void* stream);
 
 // ---- the network handle, shared with the trainer (lg_train.hip), which rewrites the device buffers of an lg_mlp in place
 #define MLP_ROWS 32          // batch rows per workgroup

@@ -207,26 +207,39 @@ int lg_runner_episode_track(const float* rewards, const float* dones, int32_t T,
   return LG_OK;
 }
 
-int lg_runner_collect(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
-                      float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a, float* c_a, float* h_c,
-                      float* c_c, const lg_runner_hooks* hooks, void* stream) {
-  POLICY_ENTRY;
+}  // extern "C"
+
+// lg_runner_collect (priv NULL) and lg_runner_collect_privileged: the runner's structs become the loop's hooks, the loop runs (lg_policy.hip), and the
+// episode bookkeeping follows it on the same stream.  The message prefix is the caller's: each entry point opens its own POLICY_ENTRY.
+int lg_runner_collect_both(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
+                           float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a, float* c_a, float* h_c,
+                           float* c_c, const lg_runner_hooks* hooks, const lg_runner_privileged* priv, void* stream) {
   if (!env || !actor || !critic || !std || !out || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
   if ((mem_a != nullptr) != (mem_c != nullptr) || (mem_a && !hid)) return lg_policy_fail(LG_ERR_INVALID, "a recurrent policy needs both memories and the hidden-state rows");
   CollectHooks ch;
   const lg_runner_episode* ep = hooks ? hooks->episode : nullptr;
   if (hooks) { ch.normalizer = hooks->normalizer; ch.update = hooks->training != 0; }
+  if (priv) {
+    ch.history = priv->history; ch.normalizer_c = priv->critic_normalizer;
+    ch.privileged_observations = priv->privileged_observations; ch.last_observations = priv->last_observations;
+  }
   if (ep) {
     if (!ep->raw_rewards || !ep->extras || !ep->cur_reward_sum || !ep->cur_episode_length || !ep->ep_return || !ep->ep_length)
       return lg_policy_fail(LG_ERR_INVALID, "null episode row");
     ch.raw_rewards = ep->raw_rewards; ch.extras = ep->extras;
   }
-  int rc = lg_policy_collect_rollout(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c,
-                                     ch.normalizer || ep ? &ch : nullptr, stream);
+  int rc = lg_policy_collect_rollout(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c, &ch,
+                                     stream);
   if (rc != LG_OK || !ep) return rc;
-  void* p; int64_t shp[4]; int32_t nd, dt;
-  if (lg_get_tensor(env, LG_T_REW_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's reward rows: ") + lg_last_error(env));
-  return lg_runner_episode_track(ep->raw_rewards, out->dones, T, shp[0], ep->cur_reward_sum, ep->cur_episode_length, ep->ep_return, ep->ep_length, stream);
+  EnvRewardRows rows;
+  if ((rc = lg_policy_reward_rows(env, &rows)) != LG_OK) return rc;
+  return lg_runner_episode_track(ep->raw_rewards, out->dones, T, rows.n, ep->cur_reward_sum, ep->cur_episode_length, ep->ep_return, ep->ep_length, stream);
 }
 
-}  // extern "C"
+extern "C" int lg_runner_collect(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
+                                 float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a, float* c_a,
+                                 float* h_c, float* c_c, const lg_runner_hooks* hooks, void* stream) {
+  POLICY_ENTRY;
+  return lg_runner_collect_both(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c, hooks, nullptr,
+                                stream);
+}

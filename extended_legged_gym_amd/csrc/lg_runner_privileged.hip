@@ -1,5 +1,6 @@
 // lg_runner_privileged.hip — the runner's collection with privileged critic observations (include/lgrunner_privileged.h): the paired normaliser
-// step and the entry point of the two-stream collector (its loop: lg_policy.hip, lg_policy_collect_privileged).
+// step and the entry point of the two-stream collection (the one PPO loop in its two-stream mode: lg_policy.hip, lg_policy_collect_rollout; the
+// entry body it shares with lg_runner_collect: lg_runner.hip).
 //
 // With two normalisers the collection loop would run lg_obsnorm_step twice per env step: six launches of a few microseconds each on a step of
 // about a hundred.  The paired step runs each of the three phases as one launch over both handles: the grid's last index selects the handle, and
@@ -97,25 +98,9 @@ int lg_runner_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_r
                                  int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
                                  float* c_a, float* h_c, float* c_c, const lg_runner_hooks* hooks, const lg_runner_privileged* priv, void* stream) {
   POLICY_ENTRY;
-  if (!env || !actor || !critic || !std || !out || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
   if (!priv || !priv->privileged_observations) return lg_policy_fail(LG_ERR_INVALID, "null privileged struct or null privileged_observations rows");
-  if ((mem_a != nullptr) != (mem_c != nullptr) || (mem_a && !hid)) return lg_policy_fail(LG_ERR_INVALID, "a recurrent policy needs both memories and the hidden-state rows");
-  PrivilegedHooks ph;
-  ph.history = priv->history; ph.normalizer_c = priv->critic_normalizer;
-  ph.privileged_observations = priv->privileged_observations; ph.last_observations = priv->last_observations;
-  const lg_runner_episode* ep = hooks ? hooks->episode : nullptr;
-  if (hooks) { ph.normalizer_a = hooks->normalizer; ph.update = hooks->training != 0; }
-  if (ep) {
-    if (!ep->raw_rewards || !ep->extras || !ep->cur_reward_sum || !ep->cur_episode_length || !ep->ep_return || !ep->ep_length)
-      return lg_policy_fail(LG_ERR_INVALID, "null episode row");
-    ph.raw_rewards = ep->raw_rewards; ph.extras = ep->extras;
-  }
-  int rc = lg_policy_collect_privileged(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c,
-                                        &ph, stream);
-  if (rc != LG_OK || !ep) return rc;
-  void* p; int64_t shp[4]; int32_t nd, dt;
-  if (lg_get_tensor(env, LG_T_REW_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's reward rows: ") + lg_last_error(env));
-  return lg_runner_episode_track(ep->raw_rewards, out->dones, T, shp[0], ep->cur_reward_sum, ep->cur_episode_length, ep->ep_return, ep->ep_length, stream);
+  return lg_runner_collect_both(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c, hooks, priv,
+                                stream);
 }
 
 }  // extern "C"

@@ -28,33 +28,43 @@ def collect_rollout(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_adva
     lib = _lib()
     dev = policy.device
     T, N, O, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
-
-    def z(*shape):
-        return torch.empty(*shape, device=dev, dtype=torch.float32)
-    out = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1),
-               actions_log_prob=z(T, N, 1), mu=z(T, N, A), sigma=z(T, N, A), last_values=z(N, 1))
-    if compute_returns:
-        out.update(returns=z(T, N, 1), advantages=z(T, N, 1))
-    rows = abi.lg_rollout(**{k: v.data_ptr() for k, v in out.items()})
+    out, rows = rollout_rows(T, N, O, A, dev, compute_returns)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     head = (_ptr(policy.std), policy.seed, policy._call + 1, T, float(gamma), float(lam), int(bool(normalize_advantage)), C.byref(rows))
     if not getattr(policy, "is_recurrent", False):
         _check(lib.lg_collect_rollout(env.core.ctx, policy.actor.handle, policy.critic.handle, *head, stream), "lg_collect_rollout")
-        _advance(env, policy, T)
-        return out
+    else:
+        mems, hidden, state, stacks = _hidden_rows(policy, T, N)
+        _check(lib.lg_collect_rollout_recurrent(env.core.ctx, mems[0], policy.actor.handle, mems[1], policy.critic.handle, *head, C.byref(hidden), *state, stream),
+               "lg_collect_rollout_recurrent")
+        out.update(stacks)
+    _advance(env, policy, T)
+    return out
+
+
+def rollout_rows(T, N, O, A, device, compute_returns=True):
+    """The (T, N, .) tensors of one PPO collection (`observations` O wide) and the `abi.lg_rollout` over them."""
+    def z(*shape):
+        return torch.empty(*shape, device=device, dtype=torch.float32)
+    out = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1),
+               actions_log_prob=z(T, N, 1), mu=z(T, N, A), sigma=z(T, N, A), last_values=z(N, 1))
+    if compute_returns:
+        out.update(returns=z(T, N, 1), advantages=z(T, N, 1))
+    return out, abi.lg_rollout(**{k: v.data_ptr() for k, v in out.items()})
+
+
+def _hidden_rows(policy, T, N):
+    """What a recurrent collection passes beyond a feed-forward one: the two memory handles, the `abi.lg_rollout_hidden` over fresh (T, L, N, H)
+    stacks, the live state pointers (h_a, c_a, h_c, c_c), and the stacks as the dict's `hidden_states_a` / `hidden_states_c` (`(h, c)` for an LSTM)."""
     mems = (policy.memory_a, policy.memory_c)
     stacks = []
     for m in mems:
         m.ensure_state(N)
-        stacks.append([torch.empty(T, m.num_layers, N, m.hidden_size, device=dev) for _ in range(2 if m.rnn_type == "lstm" else 1)])
+        stacks.append([torch.empty(T, m.num_layers, N, m.hidden_size, device=policy.device) for _ in range(2 if m.rnn_type == "lstm" else 1)])
     ptr = [[s.data_ptr() for s in st] + [None] * (2 - len(st)) for st in stacks]
     hidden = abi.lg_rollout_hidden(h_a=ptr[0][0], c_a=ptr[0][1], h_c=ptr[1][0], c_c=ptr[1][1])
-    _check(lib.lg_collect_rollout_recurrent(env.core.ctx, mems[0].handle, policy.actor.handle, mems[1].handle, policy.critic.handle, *head, C.byref(hidden),
-                                            *mems[0]._ptrs(), *mems[1]._ptrs(), stream), "lg_collect_rollout_recurrent")
-    _advance(env, policy, T)
-    out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
-    out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
-    return out
+    keys = {"hidden_states_" + k: tuple(st) if len(st) == 2 else st[0] for k, st in zip("ac", stacks)}
+    return (mems[0].handle, mems[1].handle), hidden, (*mems[0]._ptrs(), *mems[1]._ptrs()), keys
 
 
 class EpisodeTracker:
@@ -101,7 +111,8 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
     `episode_extras` (T, K), the env's `extras_episode` tensor after each step, and `ep_return` / `ep_length` (T, N, 1), defined where
     `dones > 0`; the tracker's live sums advance in place (its buffers do not: `episode_tracker.extend(...)`).
 
-    PRIVILEGED CRITIC OBSERVATIONS (`lg_runner_collect_privileged`, include/lgrunner_privileged.h): an env with an observation history
+    PRIVILEGED CRITIC OBSERVATIONS (`lg_runner_collect_privileged`, include/lgrunner_privileged.h: the library's one PPO collection loop in its
+    two-stream mode; everything above holds, per stream): an env with an observation history
     (`env.obs_history`, (N, H, W): `AnymalStudent`), or `actor_columns=k` on any env (the actor reads the first k columns of the env's row).  The
     critic reads the env's own row (O_c wide), the actor the history's row (H * W) or the prefix; the dict then holds `observations` (T, N, O_a) and
     also `privileged_observations` (T, N, O_c), `values` are the critic's on the privileged rows.  `obs_normalizer` is the ACTOR's,
@@ -125,11 +136,7 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
 
     def z(*shape):
         return torch.empty(*shape, device=dev, dtype=torch.float32)
-    out = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1),
-               actions_log_prob=z(T, N, 1), mu=z(T, N, A), sigma=z(T, N, A), last_values=z(N, 1))
-    if compute_returns:
-        out.update(returns=z(T, N, 1), advantages=z(T, N, 1))
-    rows = abi.lg_rollout(**{k: v.data_ptr() for k, v in out.items()})
+    out, rows = rollout_rows(T, N, O, A, dev, compute_returns)
     hooks = abi.lg_runner_hooks(normalizer=obs_normalizer.handle if obs_normalizer is not None else None,
                                 training=int(obs_normalizer.training) if obs_normalizer is not None else 0)
     if obs_normalizer is not None and obs_normalizer.num_features != O:
@@ -145,24 +152,35 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
         hooks.episode = C.pointer(episode)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     head = (_ptr(policy.std), policy.seed, policy._call + 1, T, float(gamma), float(lam), int(bool(normalize_advantage)), C.byref(rows))
-    if privileged:
-        return _collect_privileged(lib, env, policy, T, N, O, O_c, out, extra, head, hooks, hist, privileged_obs_normalizer, noise_uniforms, stream)
+    call, name, tail, last, keep = lib.lg_runner_collect, "lg_runner_collect", (), None, []
+    if privileged:          # the second stream: its rows, the actor's layer and the critic's normaliser ride in one more struct
+        crit = privileged_obs_normalizer
+        if crit is not None:          # (its width is the library's to check, with every other width of the call)
+            if not hooks.normalizer:
+                hooks.training = int(crit.training)          # (one mode for both handles: the critic's when it is the only one)
+            elif bool(crit.training) != bool(hooks.training):
+                raise ValueError("obs_normalizer and privileged_obs_normalizer are in different modes")
+        out["privileged_observations"] = z(T, N, O_c)
+        layer = None
+        if hist is not None:
+            last = z(N, O)
+            layer, keep = _history_layer(env, policy, hist, T, N, noise_uniforms)
+        elif noise_uniforms is not None:
+            raise ValueError("noise_uniforms needs an env with an observation history")
+        priv = abi.lg_runner_privileged(history=C.pointer(layer) if layer is not None else None, critic_normalizer=crit.handle if crit is not None else None,
+                                        privileged_observations=out["privileged_observations"].data_ptr(), last_observations=last.data_ptr() if last is not None else None)
+        call, name, tail = lib.lg_runner_collect_privileged, "lg_runner_collect_privileged", (C.byref(priv),)
     if not getattr(policy, "is_recurrent", False):
-        _check(lib.lg_runner_collect(env.core.ctx, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None, C.byref(hooks),
-                                     stream), "lg_runner_collect")
+        rc = call(env.core.ctx, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None, C.byref(hooks), *tail, stream)
     else:
-        mems = (policy.memory_a, policy.memory_c)
-        stacks = []
-        for m in mems:
-            m.ensure_state(N)
-            stacks.append([torch.empty(T, m.num_layers, N, m.hidden_size, device=dev) for _ in range(2 if m.rnn_type == "lstm" else 1)])
-        ptr = [[s.data_ptr() for s in st] + [None] * (2 - len(st)) for st in stacks]
-        hidden = abi.lg_rollout_hidden(h_a=ptr[0][0], c_a=ptr[0][1], h_c=ptr[1][0], c_c=ptr[1][1])
-        _check(lib.lg_runner_collect(env.core.ctx, mems[0].handle, policy.actor.handle, mems[1].handle, policy.critic.handle, *head, C.byref(hidden),
-                                     *mems[0]._ptrs(), *mems[1]._ptrs(), C.byref(hooks), stream), "lg_runner_collect")
-        out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
-        out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
+        mems, hidden, state, stacks = _hidden_rows(policy, T, N)
+        rc = call(env.core.ctx, mems[0], policy.actor.handle, mems[1], policy.critic.handle, *head, C.byref(hidden), *state, C.byref(hooks), *tail, stream)
+        out.update(stacks)
+    _check(rc, name)
+    del keep
     _advance(env, policy, T)
+    if last is not None:
+        env.obs_buf = last
     out.update(extra)
     return out
 
@@ -182,48 +200,6 @@ def _history_layer(env, policy, hist, T, N, noise_uniforms):
                                clip=float(env.cfg.normalization.clip_observations), noise_seed=(policy.seed ^ 0x5DEECE66D) & (2 ** 64 - 1),
                                inject_u=noise_uniforms.data_ptr() if noise_uniforms is not None else None)
     return layer, [scale, noise_uniforms]
-
-
-def _collect_privileged(lib, env, policy, T, N, O_a, O_c, out, extra, head, hooks, hist, critic_normalizer, noise_uniforms, stream):
-    """The tail of `collect_rollout_tracked` for the two-stream collection: `lg_runner_collect_privileged`."""
-    dev = policy.device
-    if critic_normalizer is not None:          # (its width is the library's to check, with every other width of the call)
-        if not hooks.normalizer:
-            hooks.training = int(critic_normalizer.training)          # (one mode for both handles: the critic's when it is the only one)
-        elif bool(critic_normalizer.training) != bool(hooks.training):
-            raise ValueError("obs_normalizer and privileged_obs_normalizer are in different modes")
-    out["privileged_observations"] = torch.empty(T, N, O_c, device=dev, dtype=torch.float32)
-    last = torch.empty(N, O_a, device=dev, dtype=torch.float32) if hist is not None else None
-    layer, keep = (None, [])
-    if hist is not None:
-        layer, keep = _history_layer(env, policy, hist, T, N, noise_uniforms)
-    elif noise_uniforms is not None:
-        raise ValueError("noise_uniforms needs an env with an observation history")
-    priv = abi.lg_runner_privileged(history=C.pointer(layer) if layer is not None else None,
-                                    critic_normalizer=critic_normalizer.handle if critic_normalizer is not None else None,
-                                    privileged_observations=out["privileged_observations"].data_ptr(), last_observations=last.data_ptr() if last is not None else None)
-    if not getattr(policy, "is_recurrent", False):
-        rc = lib.lg_runner_collect_privileged(env.core.ctx, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None,
-                                              C.byref(hooks), C.byref(priv), stream)
-    else:
-        mems = (policy.memory_a, policy.memory_c)
-        stacks = []
-        for m in mems:
-            m.ensure_state(N)
-            stacks.append([torch.empty(T, m.num_layers, N, m.hidden_size, device=dev) for _ in range(2 if m.rnn_type == "lstm" else 1)])
-        ptr = [[s.data_ptr() for s in st] + [None] * (2 - len(st)) for st in stacks]
-        hidden = abi.lg_rollout_hidden(h_a=ptr[0][0], c_a=ptr[0][1], h_c=ptr[1][0], c_c=ptr[1][1])
-        rc = lib.lg_runner_collect_privileged(env.core.ctx, mems[0].handle, policy.actor.handle, mems[1].handle, policy.critic.handle, *head, C.byref(hidden),
-                                              *mems[0]._ptrs(), *mems[1]._ptrs(), C.byref(hooks), C.byref(priv), stream)
-        out["hidden_states_a"] = tuple(stacks[0]) if len(stacks[0]) == 2 else stacks[0][0]
-        out["hidden_states_c"] = tuple(stacks[1]) if len(stacks[1]) == 2 else stacks[1][0]
-    _check(rc, "lg_runner_collect_privileged")
-    del keep
-    _advance(env, policy, T)
-    if hist is not None:
-        env.obs_buf = last
-    out.update(extra)
-    return out
 
 
 def obs_history_step(history, obs, dones=None, noise_scale=None, clip=float("inf"), noise_uniforms=None, seed=0, call=0):

@@ -19,7 +19,7 @@ import time
 
 import torch
 
-from .collector import EpisodeTracker, collect_rollout_tracked
+from .collector import EpisodeTracker, collect_rollout_tracked, rollout_rows
 from .normalizer import STATE_KEYS, NativeEmpiricalNormalization
 from .storage import compute_returns
 
@@ -300,8 +300,8 @@ class NativeOnPolicyRunner:
 
         def z(*shape):
             return torch.empty(*shape, device=dev, dtype=torch.float32)
-        d = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1), actions_log_prob=z(T, N, 1), mu=z(T, N, A),
-                 sigma=z(T, N, A), raw_rewards=z(T, N, 1), episode_extras=z(T, ex.numel()))
+        d = rollout_rows(T, N, O, A, dev, compute_returns=False)[0]          # (last_values, returns and advantages are assigned below)
+        d.update(raw_rewards=z(T, N, 1), episode_extras=z(T, ex.numel()))
         if self.privileged:
             d["privileged_observations"] = z(T, N, priv.shape[1])
         hid, self._host_episode = [[], []], []

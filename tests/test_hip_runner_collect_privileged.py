@@ -196,6 +196,19 @@ def test_prefix_mode_on_an_env_without_a_history():
     assert torch.equal(norms[1][0].carried_row(N), last_a) and torch.equal(norms[1][1].carried_row(N), last_c)
 
 
+def test_whole_row_prefix_is_the_single_stream_collection():
+    """`actor_columns=48` on the 48-wide `anymal_c_flat`: the prefix is the whole row, so the two-stream mode of the collection loop must give the
+    rows of its one-stream mode (`collect_rollout`), bit for bit, across a reset."""
+    from extended_legged_gym_amd.rl import collect_rollout, collect_rollout_tracked
+    envs, T = twins(task="anymal_c_flat"), 5
+    pols = [policy(False, 48, 48) for _ in range(2)]
+    ref = collect_rollout(envs[0], pols[0], T, GAMMA, LAM)
+    out = collect_rollout_tracked(envs[1], pols[1], T, GAMMA, LAM, actor_columns=48)
+    same(ref, out, ROWS + ("last_values", "returns", "advantages"))
+    assert torch.equal(out["privileged_observations"], out["observations"])
+    assert float(out["dones"].sum()) > 0
+
+
 def test_refusals_carry_their_reason():
     from extended_legged_gym_amd.rl import NativeEmpiricalNormalization, collect_rollout_tracked
     student, flat = twins()[0], twins(task="anymal_c_flat")[0]
