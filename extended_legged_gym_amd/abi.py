@@ -774,3 +774,23 @@ def declare_runner_privileged(lib):
 
 
 RUNNER_PRIVILEGED_SYMBOLS = ["lg_obsnorm_step_pair", "lg_runner_collect_privileged"]
+
+
+class lg_runner_distill(C.Structure):
+    """include/lgrunner_distill.h: the hooks of lg_runner_collect_distillation(_recurrent)."""
+    _fields_ = [("student_normalizer", C.c_void_p), ("teacher_normalizer", C.c_void_p), ("training", i32), ("episode", C.POINTER(lg_runner_episode))]
+
+
+def declare_runner_distill(lib):
+    """Prototypes of the runner's distillation collection (include/lgrunner_distill.h), same library."""
+    vp, u64 = C.c_void_p, C.c_uint64
+    lib.lg_runner_collect_distillation.argtypes = [vp, vp, vp, vp, u64, u64, i32, C.POINTER(lg_obs_history), C.POINTER(lg_distill_rollout),
+                                                   C.POINTER(lg_runner_distill), vp]
+    lib.lg_runner_collect_distillation.restype = C.c_int
+    lib.lg_runner_collect_distillation_recurrent.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, C.POINTER(lg_obs_history), C.POINTER(lg_distill_rollout)] + \
+        [vp] * 8 + [C.POINTER(lg_runner_distill), vp]
+    lib.lg_runner_collect_distillation_recurrent.restype = C.c_int
+    return lib
+
+
+RUNNER_DISTILL_SYMBOLS = ["lg_runner_collect_distillation", "lg_runner_collect_distillation_recurrent"]

@@ -736,75 +736,20 @@ int lg_distill_act_recurrent(lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_m
   return lg_distill_act(student, teacher, top_s, top_t, n, std_, seed, call, deterministic, actions, action_mean, teacher_actions, stream);
 }
 
-// both collectors: mem_s NULL = the feed-forward StudentTeacher
-static int collect_distillation(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed, uint64_t first_call,
-                                int32_t T, const lg_obs_history* hist, const lg_distill_rollout* out, float* h_s, float* c_s, float* h_t, float* c_t, void* stream) {
-  DeviceScope ds_(student->device);
-  if (!out->observations || !out->privileged_observations || !out->actions || !out->privileged_actions || !out->rewards || !out->dones)
-    return lg_policy_fail(LG_ERR_INVALID, "null output row");
-  const float* env_obs; int64_t n, Ot, Aenv;
-  int rc = env_shape(env, &env_obs, &n, &Ot, &Aenv);
-  if (rc == LG_OK) rc = distill_widths(student, teacher);
-  if (rc != LG_OK) return rc;
-  const int A = student->h.dims[student->h.L];
-  const int64_t Os = mem_s ? mem_s->input : student->h.dims[0];
-  if ((mem_t ? mem_t->input : teacher->h.dims[0]) != Ot || A != Aenv)
-    return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (the teacher reads the env's observation row, one action per DOF)");
-  if (mem_s && (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden)))
-    return lg_policy_fail(LG_ERR_INVALID, "an MLP's input width is not its memory's hidden width");
-  if ((rc = derived_row_check(hist, Os, Ot, "student", "")) != LG_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t so = (size_t)n * Os, sp = (size_t)n * Ot, sa = (size_t)n * A;
-  const DerivedRow student_row{hist, env_obs, n, Ot, Os, first_call, stream};          // the history layer, or the head of the teacher's row
-  POLICY_TRY(hipMemcpyAsync(out->privileged_observations, env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
-  if ((rc = derived_row(student_row, -1, nullptr, out->observations)) != LG_OK) return rc;
-  for (int t = 0; t < T; ++t) {
-    float* act_t = out->actions + t * sa;
-    float* dones_t = out->dones + (size_t)t * n;
-    if (mem_s) rc = lg_distill_act_recurrent(mem_s, student, mem_t, teacher, out->observations + t * so, out->privileged_observations + t * sp, n, std, seed,
-                                             first_call + (uint64_t)t, 0, h_s, c_s, h_t, c_t, nullptr, act_t, nullptr, out->privileged_actions + t * sa, stream);
-    else rc = lg_distill_act(student, teacher, out->observations + t * so, out->privileged_observations + t * sp, n, std, seed, first_call + (uint64_t)t, 0, act_t,
-                             nullptr, out->privileged_actions + t * sa, stream);
-    if (rc != LG_OK) return rc;
-    // Distillation.process_env_step (distillation.py:98-101) stores the env's reward as it is: no value row, no time-out bootstrap
-    rc = lg_step_transition(env, act_t, t + 1 < T ? out->privileged_observations + (t + 1) * sp : nullptr, nullptr, 0.f, out->rewards + (size_t)t * n, dones_t, stream);
-    if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
-    rc = derived_row(student_row, t, dones_t, t + 1 < T ? out->observations + (t + 1) * so : out->last_observations);
-    if (rc == LG_OK && mem_s) {                        // policy.reset(dones) (distillation.py:105)
-      rc = lg_rnn_reset_rows(mem_s, h_s, c_s, dones_t, n, stream);
-      if (rc == LG_OK && mem_t) rc = lg_rnn_reset_rows(mem_t, h_t, c_t, dones_t, n, stream);
-    }
-    if (rc != LG_OK) return rc;
-  }
-  POLICY_TRY(hipGetLastError());
-  return LG_OK;
-}
-
+// both collectors: the loop is lg_policy_collect_distillation, at the end of this file
 int lg_collect_distillation(lg_ctx* env, lg_mlp* student, lg_mlp* teacher, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
                             const lg_obs_history* history, const lg_distill_rollout* rows, void* stream) {
   POLICY_ENTRY;
-  if (!env || !student || !teacher || !std || !rows || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
-  return collect_distillation(env, nullptr, student, nullptr, teacher, std, seed, first_call, T, history, rows, nullptr, nullptr, nullptr, nullptr, stream);
+  return lg_policy_collect_distillation(env, 0, nullptr, student, nullptr, teacher, std, seed, first_call, T, history, rows, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                        nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int lg_collect_distillation_recurrent(lg_ctx* env, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed,
                                       uint64_t first_call, int32_t T, const lg_obs_history* history, const lg_distill_rollout* rows, float* h_s0, float* c_s0,
                                       float* h_t0, float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, void* stream) {
   POLICY_ENTRY;
-  if (!env || !mem_s || !student || !teacher || !std || !rows || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
-  const float* env_obs; int64_t n, Ot, Aenv;
-  int rc = env_shape(env, &env_obs, &n, &Ot, &Aenv);
-  if (rc == LG_OK) rc = rnn_check(mem_s, h_s, c_s, n);
-  if (rc == LG_OK && mem_t) rc = rnn_check(mem_t, h_t, c_t, n);
-  if (rc != LG_OK) return rc;
-  DeviceScope ds_(student->device);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t ss = (size_t)mem_s->num_layers * n * mem_s->hidden * 4, stt = mem_t ? (size_t)mem_t->num_layers * n * mem_t->hidden * 4 : 0;
-  if (h_s0) POLICY_TRY(hipMemcpyAsync(h_s0, h_s, ss, hipMemcpyDeviceToDevice, st));
-  if (c_s0 && mem_s->type == LG_RNN_LSTM) POLICY_TRY(hipMemcpyAsync(c_s0, c_s, ss, hipMemcpyDeviceToDevice, st));
-  if (mem_t && h_t0) POLICY_TRY(hipMemcpyAsync(h_t0, h_t, stt, hipMemcpyDeviceToDevice, st));
-  if (mem_t && c_t0 && mem_t->type == LG_RNN_LSTM) POLICY_TRY(hipMemcpyAsync(c_t0, c_t, stt, hipMemcpyDeviceToDevice, st));
-  return collect_distillation(env, mem_s, student, mem_t, teacher, std, seed, first_call, T, history, rows, h_s, c_s, h_t, c_t, stream);
+  return lg_policy_collect_distillation(env, 1, mem_s, student, mem_t, teacher, std, seed, first_call, T, history, rows, h_s0, c_s0, h_t0, c_t0, h_s, c_s, h_t, c_t,
+                                        nullptr, stream);
 }
 
 }  // extern "C"
@@ -931,3 +876,89 @@ int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn*
   return LG_OK;
 }
 
+
+// ============================================================================================ the distillation collection loop (lgpolicy.h, lgrunner_distill.h)
+// The one loop of every distillation collector; recurrent = 0: the feed-forward StudentTeacher (no memory, no state pointers); hooks:
+// lg_policy_internal.h.  The step itself (lg_step_transition) writes the teacher's stream: the env's row, O_t wide, normalised in place by
+// normalizer_t.  The student's row (O_s wide, normalizer_s) is derived after each step from the env's own raw row, never from the stored one.
+// Per step: act, physics, post-physics, the student's row (one launch or copy), [the normaliser step: paired, three launches, for two handles].
+int lg_policy_collect_distillation(lg_ctx* env, int recurrent, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed,
+                                   uint64_t first_call, int32_t T, const lg_obs_history* hist, const lg_distill_rollout* out, float* h_s0, float* c_s0, float* h_t0,
+                                   float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, const DistillHooks* hooks, void* stream) {
+  if (!env || (recurrent && !mem_s) || !student || !teacher || !std || !out || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
+  const float* env_obs; int64_t n, Ot, Aenv;
+  int rc = env_shape(env, &env_obs, &n, &Ot, &Aenv);
+  if (rc == LG_OK && mem_s) rc = rnn_check(mem_s, h_s, c_s, n);
+  if (rc == LG_OK && mem_s && mem_t) rc = rnn_check(mem_t, h_t, c_t, n);
+  if (rc != LG_OK) return rc;
+  DeviceScope ds_(student->device);
+  if (!out->observations || !out->privileged_observations || !out->actions || !out->privileged_actions || !out->rewards || !out->dones)
+    return lg_policy_fail(LG_ERR_INVALID, "null output row");
+  if ((rc = distill_widths(student, teacher)) != LG_OK) return rc;
+  const int A = student->h.dims[student->h.L];
+  const int64_t Os = mem_s ? mem_s->input : student->h.dims[0];
+  if ((mem_t ? mem_t->input : teacher->h.dims[0]) != Ot || A != Aenv)
+    return lg_policy_fail(LG_ERR_INVALID, "network widths do not match the env (the teacher reads the env's observation row, one action per DOF)");
+  if (mem_s && (student->h.dims[0] != mem_s->hidden || (mem_t && teacher->h.dims[0] != mem_t->hidden)))
+    return lg_policy_fail(LG_ERR_INVALID, "an MLP's input width is not its memory's hidden width");
+  if ((rc = derived_row_check(hist, Os, Ot, "student", "")) != LG_OK) return rc;
+  const DistillHooks hk = hooks ? *hooks : DistillHooks();
+  lg_obsnorm *norm_s = hk.normalizer_s, *norm_t = hk.normalizer_t;
+  if (norm_s && lg_obsnorm_width(norm_s) != Os) return lg_policy_fail(LG_ERR_INVALID, "the student's normaliser does not have the student's input width");
+  if (norm_t && lg_obsnorm_width(norm_t) != Ot) return lg_policy_fail(LG_ERR_INVALID, "the teacher's normaliser does not have the env's observation width");
+  if (norm_s && norm_s == norm_t) return lg_policy_fail(LG_ERR_INVALID, "the student and the teacher need a normaliser each");
+  hipStream_t st = (hipStream_t)stream;
+  EnvRewardRows env_rows;
+  if ((hk.raw_rewards || hk.extras) && (rc = lg_policy_reward_rows(env, &env_rows)) != LG_OK) return rc;
+  // a normaliser's carried row: row 0 of this collection when it holds one, the normalised row after the last step when the loop is done
+  float *carried_s = nullptr, *carried_t = nullptr; bool valid_s = false, valid_t = false;
+  if (norm_s && (rc = lg_obsnorm_carried_begin(norm_s, n, Os, &carried_s, &valid_s)) != LG_OK) return rc;
+  if (norm_t && (rc = lg_obsnorm_carried_begin(norm_t, n, Ot, &carried_t, &valid_t)) != LG_OK) return rc;
+  if (mem_s) {          // the state BEFORE step 0: what seeds policy.reset(hidden_states=...) of the update
+    const size_t ss = (size_t)mem_s->num_layers * n * mem_s->hidden * 4, stt = mem_t ? (size_t)mem_t->num_layers * n * mem_t->hidden * 4 : 0;
+    if (h_s0) POLICY_TRY(hipMemcpyAsync(h_s0, h_s, ss, hipMemcpyDeviceToDevice, st));
+    if (c_s0 && mem_s->type == LG_RNN_LSTM) POLICY_TRY(hipMemcpyAsync(c_s0, c_s, ss, hipMemcpyDeviceToDevice, st));
+    if (mem_t && h_t0) POLICY_TRY(hipMemcpyAsync(h_t0, h_t, stt, hipMemcpyDeviceToDevice, st));
+    if (mem_t && c_t0 && mem_t->type == LG_RNN_LSTM) POLICY_TRY(hipMemcpyAsync(c_t0, c_t, stt, hipMemcpyDeviceToDevice, st));
+  }
+  const size_t so = (size_t)n * Os, sp = (size_t)n * Ot, sa = (size_t)n * A;
+  const DerivedRow student_row{hist, env_obs, n, Ot, Os, first_call, stream};          // the history layer, or the head of the teacher's row
+  // row 0 of each stream: the carried row where one is held, else the env's raw row for the teacher and the clipped history (the column prefix)
+  POLICY_TRY(hipMemcpyAsync(out->privileged_observations, valid_t ? carried_t : env_obs, sp * 4, hipMemcpyDeviceToDevice, st));
+  if (valid_s) POLICY_TRY(hipMemcpyAsync(out->observations, carried_s, so * 4, hipMemcpyDeviceToDevice, st));
+  else if ((rc = derived_row(student_row, -1, nullptr, out->observations)) != LG_OK) return rc;
+  for (int t = 0; t < T; ++t) {
+    float* act_t = out->actions + t * sa;
+    float* dones_t = out->dones + (size_t)t * n;
+    if (mem_s) rc = lg_distill_act_recurrent(mem_s, student, mem_t, teacher, out->observations + t * so, out->privileged_observations + t * sp, n, std, seed,
+                                             first_call + (uint64_t)t, 0, h_s, c_s, h_t, c_t, nullptr, act_t, nullptr, out->privileged_actions + t * sa, stream);
+    else rc = lg_distill_act(student, teacher, out->observations + t * so, out->privileged_observations + t * sp, n, std, seed, first_call + (uint64_t)t, 0, act_t,
+                             nullptr, out->privileged_actions + t * sa, stream);
+    if (rc != LG_OK) return rc;
+    const bool more = t + 1 < T;
+    // the teacher's next row; after the last step into its normaliser's carried row (none: the env's own row serves).
+    // Distillation.process_env_step (distillation.py:98-101) stores the env's reward as it is: no value row, no time-out bootstrap
+    float* next_t = more ? out->privileged_observations + (t + 1) * sp : carried_t;
+    rc = lg_step_transition(env, act_t, next_t, nullptr, 0.f, out->rewards + (size_t)t * n, dones_t, stream);
+    if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
+    // the student's next row; after the last step the un-normalised row goes to last_observations and its normalised copy to the carried row
+    float* norm_out_s = more ? out->observations + (t + 1) * so : carried_s;
+    float* next_s = more ? norm_out_s : (out->last_observations ? out->last_observations : carried_s);
+    if ((rc = derived_row(student_row, t, dones_t, next_s)) != LG_OK) return rc;
+    if (norm_s && norm_t) rc = lg_obsnorm_step_pair(norm_s, next_s, Os, norm_out_s, norm_t, next_t, Ot, next_t, n, hk.update, stream);
+    else if (norm_s) rc = lg_obsnorm_step(norm_s, next_s, n, Os, hk.update, norm_out_s, stream);
+    else if (norm_t) rc = lg_obsnorm_step(norm_t, next_t, n, Ot, hk.update, next_t, stream);          // on_policy_runner.py:425-427
+    if (rc != LG_OK) return rc;
+    if (hk.raw_rewards) POLICY_TRY(hipMemcpyAsync(hk.raw_rewards + (size_t)t * n, env_rows.rew, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (hk.extras) POLICY_TRY(hipMemcpyAsync(hk.extras + (size_t)t * env_rows.K, env_rows.extras, (size_t)env_rows.K * 4, hipMemcpyDeviceToDevice, st));
+    if (mem_s) {                                       // policy.reset(dones) (distillation.py:105)
+      rc = lg_rnn_reset_rows(mem_s, h_s, c_s, dones_t, n, stream);
+      if (rc == LG_OK && mem_t) rc = lg_rnn_reset_rows(mem_t, h_t, c_t, dones_t, n, stream);
+      if (rc != LG_OK) return rc;
+    }
+  }
+  POLICY_TRY(hipGetLastError());
+  if (norm_s) lg_obsnorm_carried_commit(norm_s);
+  if (norm_t) lg_obsnorm_carried_commit(norm_t);
+  return LG_OK;
+}

@@ -55,6 +55,22 @@ struct CollectHooks {
 int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
                               int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,
                               float* c_a, float* h_c, float* c_c, const CollectHooks* hooks, void* stream);
+// ---- the distillation collection loop (lg_policy.hip; recurrent = 0: the feed-forward StudentTeacher): the one loop behind
+// lg_collect_distillation, lg_collect_distillation_recurrent, lg_runner_collect_distillation and lg_runner_collect_distillation_recurrent.
+// hooks NULL = a DistillHooks with nothing set: the rows of the two plain collectors, launch for launch.  The teacher reads the env's row
+// (out->privileged_observations, O_t wide, `normalizer_t`), the student the history layer's row or a column prefix of the env's raw row
+// (out->observations, O_s wide, `normalizer_s`); a carried row each.  The four `*0` pointers take the memories' state before step 0.
+struct DistillHooks {
+  lg_obsnorm* normalizer_s = nullptr;           // the student's: every new row of its stream passes lg_obsnorm_step before it is stored and read; the row
+                                                // after the last step is the handle's carried row, row 0 of the next collection
+  lg_obsnorm* normalizer_t = nullptr;           // the teacher's; both set: the paired step
+  int update = 0;                               // the normalisers' training mode
+  float* raw_rewards = nullptr;                 // (T, n): the env's rew_buf after each step
+  float* extras = nullptr;                      // (T, K): the env's extras_episode after each step
+};
+int lg_policy_collect_distillation(lg_ctx* env, int recurrent, lg_rnn* mem_s, lg_mlp* student, lg_rnn* mem_t, lg_mlp* teacher, const float* std, uint64_t seed,
+                                   uint64_t first_call, int32_t T, const lg_obs_history* hist, const lg_distill_rollout* out, float* h_s0, float* c_s0, float* h_t0,
+                                   float* c_t0, float* h_s, float* c_s, float* h_t, float* c_t, const DistillHooks* hooks, void* stream);
 // the env's raw reward row (n) and episode-extras row (K): what the loop copies after each step, and the n of the runner's episode tail
 struct EnvRewardRows { const float* rew = nullptr; const float* extras = nullptr; int64_t n = 0, K = 0; };
 int lg_policy_reward_rows(lg_ctx* env, EnvRewardRows* rows);

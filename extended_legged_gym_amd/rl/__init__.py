@@ -9,12 +9,13 @@ recurrent student: truncated BPTT through its memory, include/lgdistill_recurren
 `NativeOnPolicyRunner` (rsl_rl's `OnPolicyRunner` surface over these pieces), `NativeEmpiricalNormalization` (`empirical_normalization` on the device) and
 `collect_rollout_tracked` / `EpisodeTracker` (the collection with the normaliser and the episode bookkeeping between its launches, include/lgrunner.h;
 with privileged critic observations -- two observation streams, two normalisers, `NativeEmpiricalNormalization.step_pair` --
-include/lgrunner_privileged.h)."""
+include/lgrunner_privileged.h); `NativeDistillationRunner` (the same surface for `Distillation`: the teacher from the PPO runner's checkpoint, two
+normalisers) over `collect_distillation_tracked` (include/lgrunner_distill.h)."""
 from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
                      NativeStudentTeacher, NativeStudentTeacherRecurrent)
 from .storage import compute_returns                      # noqa: F401
-from .collector import (EpisodeTracker, collect_distillation, collect_estimation, collect_rollout, collect_rollout_tracked,          # noqa: F401
-                        obs_history_step)
+from .collector import (EpisodeTracker, collect_distillation, collect_distillation_tracked, collect_estimation, collect_rollout,          # noqa: F401
+                        collect_rollout_tracked, obs_history_step)
 from .estimator import NativeConvEncoder, NativeTerrainEstimator, parse_estimator_state          # noqa: F401
 from .ppo import NativePPO          # noqa: F401
 from .ppo_recurrent import NativeRecurrentPPO          # noqa: F401
@@ -25,3 +26,4 @@ from .distillation_recurrent import NativeRecurrentDistillation          # noqa:
 from .estimator_distillation import NativeEstimatorDistillation          # noqa: F401
 from .normalizer import NativeEmpiricalNormalization          # noqa: F401
 from .runner import NativeOnPolicyRunner          # noqa: F401
+from .distillation_runner import NativeDistillationRunner          # noqa: F401

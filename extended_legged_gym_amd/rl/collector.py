@@ -242,7 +242,17 @@ def collect_distillation(env, policy, num_steps, noise_uniforms=None):
     sampling call); `noise_uniforms` (T, N, H * 48) replaces the draws (the checker mode).  Any other env: the student reads the first columns of
     the env's observation row.  Recurrent policy: also `hidden_states`, the `(memory_s, memory_t)` state BEFORE step 0 in `get_hidden_states()` form --
     distillation keeps no per-step hidden rows; this seeds `policy.reset(hidden_states=...)` of the update."""
+    return _collect_distillation(env, policy, num_steps, noise_uniforms)
+
+
+def _collect_distillation(env, policy, num_steps, noise_uniforms, hooks=None):
+    """The body of `collect_distillation` (hooks None: `lg_collect_distillation*`) and of `collect_distillation_tracked` (an
+    `abi.lg_runner_distill`: `lg_runner_collect_distillation*`, include/lgrunner_distill.h)."""
     lib = _lib()
+    name = "lg_collect_distillation"
+    if hooks is not None:
+        from .normalizer import _runner_lib
+        lib, name = _runner_lib(), "lg_runner_collect_distillation"
     dev = policy.device
     rec = getattr(policy, "is_recurrent", False)
     T, N, Ot, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
@@ -260,6 +270,7 @@ def collect_distillation(env, policy, num_steps, noise_uniforms=None):
         layer, keep = _history_layer(env, policy, hist, T, N, noise_uniforms)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     lp = C.byref(layer) if layer is not None else None
+    tail = () if hooks is None else (C.byref(hooks),)
     if rec:
         mems = (policy.memory_s, policy.memory_t)
         before = []
@@ -269,18 +280,55 @@ def collect_distillation(env, policy, num_steps, noise_uniforms=None):
             before.append(None if m is None else [torch.empty_like(m.h)] + ([torch.empty_like(m.c)] if m.rnn_type == "lstm" else []))
         p0 = [[_ptr(b) for b in bs] + [None] * (2 - len(bs)) if bs is not None else [None, None] for bs in before]
         live = [m._ptrs() if m is not None else (None, None) for m in mems]
-        rc = lib.lg_collect_distillation_recurrent(env.core.ctx, mems[0].handle, policy.student.handle, mems[1].handle if mems[1] is not None else None,
-                                                   policy.teacher.handle, _ptr(policy.std), policy.seed, policy._call + 1, T, lp, C.byref(rows),
-                                                   *p0[0], *p0[1], *live[0], *live[1], stream)
+        call = lib.lg_collect_distillation_recurrent if hooks is None else lib.lg_runner_collect_distillation_recurrent
+        rc = call(env.core.ctx, mems[0].handle, policy.student.handle, mems[1].handle if mems[1] is not None else None,
+                  policy.teacher.handle, _ptr(policy.std), policy.seed, policy._call + 1, T, lp, C.byref(rows),
+                  *p0[0], *p0[1], *live[0], *live[1], *tail, stream)
         out["hidden_states"] = tuple(None if bs is None else (tuple(bs) if len(bs) == 2 else bs[0]) for bs in before)
     else:
-        rc = lib.lg_collect_distillation(env.core.ctx, policy.student.handle, policy.teacher.handle, _ptr(policy.std), policy.seed, policy._call + 1, T, lp,
-                                         C.byref(rows), stream)
-    _check(rc, "lg_collect_distillation")
+        call = lib.lg_collect_distillation if hooks is None else lib.lg_runner_collect_distillation
+        rc = call(env.core.ctx, policy.student.handle, policy.teacher.handle, _ptr(policy.std), policy.seed, policy._call + 1, T, lp,
+                  C.byref(rows), *tail, stream)
+    _check(rc, name)
     del keep
     _advance(env, policy, T)
     if hist is not None:
         env.obs_buf = last
+    return out
+
+
+def collect_distillation_tracked(env, policy, num_steps, obs_normalizer=None, privileged_obs_normalizer=None, episode_tracker=None, noise_uniforms=None):
+    """`collect_distillation` through `lg_runner_collect_distillation` / `lg_runner_collect_distillation_recurrent` (include/lgrunner_distill.h),
+    with the runner's device pieces between the launches of the one call.  Same dict; nothing given: the same rows, bit for bit.
+    obs_normalizer (`NativeEmpiricalNormalization`, the student's width) and privileged_obs_normalizer (the teacher's, the env's row): every new
+    row of a stream is normalised (and counted in training mode; one mode for both, `ValueError` otherwise) before it is stored and before the next
+    act (`on_policy_runner.py:425-427`); row 0 is the normaliser's carried row -- the normalised row after the previous collection's last step --
+    or, when it holds none, the raw one, as the first observations of `learn()` (`:364-366`).  A stream without a normaliser stays raw.
+    `env.obs_buf` is left as the student's un-normalised row after the last step, and the env's privileged row stays raw.
+    episode_tracker (`EpisodeTracker`): adds `raw_rewards` (T, N, 1) (equal to `rewards`: distillation stores the env's reward as it is),
+    `episode_extras` (T, K), and `ep_return` / `ep_length` (T, N, 1), defined where `dones > 0`, as `collect_rollout_tracked` returns them; the
+    tracker's live sums advance in place."""
+    dev = policy.device
+    T, N = int(num_steps), env.core.t["obs_buf"].shape[0]
+    norms = [n for n in (obs_normalizer, privileged_obs_normalizer) if n is not None]
+    if len(norms) == 2 and bool(norms[0].training) != bool(norms[1].training):
+        raise ValueError("obs_normalizer and privileged_obs_normalizer are in different modes")
+    hooks = abi.lg_runner_distill(student_normalizer=obs_normalizer.handle if obs_normalizer is not None else None,
+                                  teacher_normalizer=privileged_obs_normalizer.handle if privileged_obs_normalizer is not None else None,
+                                  training=int(bool(norms[0].training)) if norms else 0)
+    extra = {}
+    if episode_tracker is not None:
+        def z(*shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32)
+        K = env.core.t["extras_episode"].numel()
+        assert episode_tracker.cur_reward_sum.shape == (N,) and episode_tracker.cur_reward_sum.device == policy.std.device
+        extra = dict(raw_rewards=z(T, N, 1), episode_extras=z(T, K), ep_return=z(T, N, 1), ep_length=z(T, N, 1))
+        episode = abi.lg_runner_episode(raw_rewards=extra["raw_rewards"].data_ptr(), extras=extra["episode_extras"].data_ptr(),
+                                        cur_reward_sum=episode_tracker.cur_reward_sum.data_ptr(), cur_episode_length=episode_tracker.cur_episode_length.data_ptr(),
+                                        ep_return=extra["ep_return"].data_ptr(), ep_length=extra["ep_length"].data_ptr())
+        hooks.episode = C.pointer(episode)
+    out = _collect_distillation(env, policy, T, noise_uniforms, hooks)
+    out.update(extra)
     return out
 
 

@@ -178,6 +178,11 @@ class NativeDistillation(_NativeHandle):
                                                         self._stream()), "lg_distill_train_set_state")
         self.learning_rate = float(state["learning_rate"])
 
+    def load_teacher(self, state_dict):
+        """Swaps the teacher (`policy.load_teacher`: `actor.*` of a PPO checkpoint or `teacher.*`) in the policy's image and in the `teacher.*`
+        entries `state_dict()` returns; nothing that is trained moves."""
+        self._rest.update(self.policy.load_teacher(state_dict))
+
     def load_state_dict(self, state_dict):
         """New student parameters (`student.*` of a `StudentTeacher` state dict); the moments, the step count and the learning rate stay."""
         state = self.optimizer_state()

@@ -16,6 +16,7 @@ def _runner_lib():
     if not getattr(lib, "_runner_declared", False):
         abi.declare_runner(lib)
         abi.declare_runner_privileged(lib)
+        abi.declare_runner_distill(lib)
         lib._runner_declared = True
     return lib
 

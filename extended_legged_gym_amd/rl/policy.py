@@ -367,6 +367,7 @@ class NativeStudentTeacher(_GaussianPolicy):
         self.device = torch.device(device)
         tsd, ssd, tprefix, self.resumed = _split_distillation_state(state_dict, student_state_dict)
         self._check_teacher_memory(tprefix)
+        self._activation = activation
         self.teacher = NativeMLP.from_sequential_state(tsd, tprefix, activation, device)
         self.student = NativeMLP.from_sequential_state(ssd, "student", activation, device)
         self.loaded_teacher = True
@@ -380,6 +381,23 @@ class NativeStudentTeacher(_GaussianPolicy):
 
     def _check_teacher_memory(self, tprefix):
         pass
+
+    def load_teacher(self, state_dict):
+        """A new teacher image from a PPO state dict (`actor.*`) or a distillation one (`teacher.*`): the teacher half of
+        `StudentTeacher.load_state_dict` (`student_teacher.py:125-144`).  The student, `std` and the call counter stay.  Returns the `teacher.*`
+        entries it loaded (the trainers keep them for `state_dict()`)."""
+        tprefix = "actor" if any("actor" in k for k in state_dict) else "teacher"
+        self._check_teacher_memory(tprefix)
+        entries = {"teacher." + k[len(tprefix) + 1:]: v.detach().clone() for k, v in state_dict.items() if k.startswith(tprefix + ".")}
+        if not entries:
+            raise ValueError("state_dict does not contain student or teacher parameters")
+        teacher = NativeMLP.from_sequential_state(entries, "teacher", self._activation, str(self.device))
+        if teacher.dims != self.teacher.dims:
+            raise ValueError(f"the loaded teacher has layer widths {teacher.dims}, this policy's teacher {self.teacher.dims}")
+        torch.cuda.synchronize(self.device)          # (the old image may still be read by a launch in flight)
+        self.teacher = teacher
+        self.loaded_teacher = True
+        return entries
 
     def reset(self, dones=None, hidden_states=None):
         pass

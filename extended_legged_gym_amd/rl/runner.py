@@ -4,7 +4,7 @@ updates (`NativePPO`, `NativeRecurrentPPO`, `NativeSymmetricPPO`).  It needs nei
 layout (`model_state_dict`, `optimizer_state_dict` as `torch.optim.Adam(policy.parameters()).state_dict()` holds it, `iter`, `infos`, and the two
 normaliser dicts), so either runner resumes what the other wrote.
 
-Refused by name (`NotImplementedError`): `Distillation` (tools/train_distill.py runs it), `rnd_cfg`, `multi_gpu_cfg`,
+Refused by name (`NotImplementedError`): `Distillation` (`rl.NativeDistillationRunner` runs it), `rnd_cfg`, `multi_gpu_cfg`,
 `normalize_advantage_per_mini_batch`, policy classes other than `ActorCritic` / `ActorCriticRecurrent`, and an env that declares a
 `num_privileged_obs` other than `num_obs` without returning privileged observations.
 
@@ -202,14 +202,88 @@ def steps_outside_the_library(env):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the runner
-class NativeOnPolicyRunner:
+class RunnerLogging:
+    """What the native runners share around their loops (`NativeOnPolicyRunner`, `NativeDistillationRunner`): the writer, the per-iteration `log`
+    (`on_policy_runner.py:488-660`) and the `Episode/*` means.  A runner provides `env`, `alg`, `num_steps_per_env`, `writer`, `log_dir`,
+    `disable_logs`, `tot_timesteps`, `tot_time`, `layered` and `_host_episode`."""
+
+    def _open_writer(self):
+        if self.log_dir is not None and self.writer is None and not self.disable_logs:
+            self.writer = _make_writer(self.log_dir)
+
+    def _episode_means(self, rollout):
+        """`Episode/<key>`: the mean over the T per-step values of `infos["episode"][key]`.  Entries that are views of the env's `extras_episode`
+        tensor come from the collected rows.  The others come from the host loop's per-step copies; the one-call collector has no host step, and
+        the envs it serves write such entries (`max_command_x`, `reward_stage`) outside the step only, so their current value is every step's."""
+        ex, rows = self.env.core.t["extras_episode"], rollout["episode_extras"].mean(dim=0).cpu().numpy()
+        out = {}
+        for key, value in self.env.extras.get("episode", {}).items():
+            is_view, k = _view_index(value, ex)
+            if is_view:
+                out[key] = float(rows[k])
+            elif self.layered and self._host_episode and all(key in step for step in self._host_episode):
+                out[key] = float(torch.stack([torch.as_tensor(step[key], dtype=torch.float32).reshape(-1).mean().cpu() for step in self._host_episode]).mean())
+            else:
+                out[key] = float(torch.as_tensor(value, dtype=torch.float32).mean())
+        return out
+
+    def log(self, locs, width=80, pad=35):
+        collection_size = self.num_steps_per_env * self.env.num_envs
+        self.tot_timesteps += collection_size
+        iteration_time = locs["collection_time"] + locs["learn_time"]
+        self.tot_time += iteration_time
+        it, w = locs["it"], self.writer
+        ep_string = ""
+        for key, value in locs["episode"].items():
+            if "/" in key:
+                w.add_scalar(key, value, it)
+                ep_string += f"""{f'{key}:':>{pad}} {value:.4f}\n"""
+            else:
+                w.add_scalar("Episode/" + key, value, it)
+                ep_string += f"""{f'Mean episode {key}:':>{pad}} {value:.4f}\n"""
+        mean_std = float(self.alg.policy.std.mean())
+        fps = int(collection_size / iteration_time)
+        for key, value in locs["loss_dict"].items():
+            w.add_scalar(f"Loss/{key}", value, it)
+        w.add_scalar("Loss/learning_rate", self.alg.learning_rate, it)
+        w.add_scalar("Policy/mean_noise_std", mean_std, it)
+        w.add_scalar("Perf/total_fps", fps, it)
+        w.add_scalar("Perf/collection time", locs["collection_time"], it)
+        w.add_scalar("Perf/learning_time", locs["learn_time"], it)
+        have = len(locs["rewbuffer"]) > 0
+        if have:
+            w.add_scalar("Train/mean_reward", statistics.mean(locs["rewbuffer"]), it)
+            w.add_scalar("Train/mean_episode_length", statistics.mean(locs["lenbuffer"]), it)
+            w.add_scalar("Train/mean_reward/time", statistics.mean(locs["rewbuffer"]), self.tot_time)
+            w.add_scalar("Train/mean_episode_length/time", statistics.mean(locs["lenbuffer"]), self.tot_time)
+        head = f" \033[1m Learning iteration {it}/{locs['tot_iter']} \033[0m "
+        log_string = (f"""{'#' * width}\n"""
+                      f"""{head.center(width, ' ')}\n\n"""
+                      f"""{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)\n"""
+                      f"""{'Mean action noise std:':>{pad}} {mean_std:.2f}\n""")
+        for key, value in locs["loss_dict"].items():
+            log_string += f"""{f'Mean {key} loss:':>{pad}} {value:.4f}\n""" if have else f"""{f'{key}:':>{pad}} {value:.4f}\n"""
+        if have:
+            log_string += f"""{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"""
+            log_string += f"""{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n"""
+        log_string += ep_string
+        eta = self.tot_time / (it - locs["start_iter"] + 1) * (locs["start_iter"] + locs["num_learning_iterations"] - it)
+        log_string += (f"""{'-' * width}\n"""
+                       f"""{'Total timesteps:':>{pad}} {self.tot_timesteps}\n"""
+                       f"""{'Iteration time:':>{pad}} {iteration_time:.2f}s\n"""
+                       f"""{'Time elapsed:':>{pad}} {time.strftime("%H:%M:%S", time.gmtime(self.tot_time))}\n"""
+                       f"""{'ETA:':>{pad}} {time.strftime("%H:%M:%S", time.gmtime(eta))}\n""")
+        print(log_string)
+
+
+class NativeOnPolicyRunner(RunnerLogging):
     def __init__(self, env, train_cfg, log_dir=None, device="cuda:0"):
         from . import NativeActorCritic, NativeActorCriticRecurrent, NativePPO, NativeRecurrentPPO, NativeSymmetricPPO
         self.cfg, self.alg_cfg, self.policy_cfg = dict(train_cfg["runner"]), dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
         self.env, self.device, self.log_dir = env, torch.device(device), log_dir
         alg_name = self.alg_cfg.pop("class_name", self.cfg.get("algorithm_class_name", "PPO"))
         if alg_name == "Distillation":
-            raise NotImplementedError("Distillation is not run by the native runner: tools/train_distill.py drives rl.NativeDistillation")
+            raise NotImplementedError("Distillation is not run by the native runner: tools/train_distill.py drives rl.NativeDistillation, and rl.NativeDistillationRunner runs it")
         if alg_name != "PPO":
             raise NotImplementedError(f"algorithm_class_name {alg_name}: the native runner runs PPO")
         for name in REFUSED_ALGORITHM_OPTIONS:
@@ -348,27 +422,10 @@ class NativeOnPolicyRunner:
                 d[key] = tuple(torch.stack([r[j] for r in rows]) for j in range(2)) if isinstance(rows[0], tuple) else torch.stack(rows)
         return d
 
-    def _episode_means(self, rollout):
-        """`Episode/<key>`: the mean over the T per-step values of `infos["episode"][key]`.  Entries that are views of the env's `extras_episode`
-        tensor come from the collected rows.  The others come from the host loop's per-step copies; the one-call collector has no host step, and
-        the envs it serves write such entries (`max_command_x`, `reward_stage`) outside the step only, so their current value is every step's."""
-        ex, rows = self.env.core.t["extras_episode"], rollout["episode_extras"].mean(dim=0).cpu().numpy()
-        out = {}
-        for key, value in self.env.extras.get("episode", {}).items():
-            is_view, k = _view_index(value, ex)
-            if is_view:
-                out[key] = float(rows[k])
-            elif self.layered and self._host_episode and all(key in step for step in self._host_episode):
-                out[key] = float(torch.stack([torch.as_tensor(step[key], dtype=torch.float32).reshape(-1).mean().cpu() for step in self._host_episode]).mean())
-            else:
-                out[key] = float(torch.as_tensor(value, dtype=torch.float32).mean())
-        return out
-
     # ---- the loop (`:347-486`)
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
         env = self.env
-        if self.log_dir is not None and self.writer is None and not self.disable_logs:
-            self.writer = _make_writer(self.log_dir)
+        self._open_writer()
         if init_at_random_ep_len:
             env.episode_length_buf[:] = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
         self.forget_carried()
@@ -401,54 +458,6 @@ class NativeOnPolicyRunner:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
             if hasattr(self.writer, "flush"):
                 self.writer.flush()
-
-    def log(self, locs, width=80, pad=35):
-        collection_size = self.num_steps_per_env * self.env.num_envs
-        self.tot_timesteps += collection_size
-        iteration_time = locs["collection_time"] + locs["learn_time"]
-        self.tot_time += iteration_time
-        it, w = locs["it"], self.writer
-        ep_string = ""
-        for key, value in locs["episode"].items():
-            if "/" in key:
-                w.add_scalar(key, value, it)
-                ep_string += f"""{f'{key}:':>{pad}} {value:.4f}\n"""
-            else:
-                w.add_scalar("Episode/" + key, value, it)
-                ep_string += f"""{f'Mean episode {key}:':>{pad}} {value:.4f}\n"""
-        mean_std = float(self.alg.policy.std.mean())
-        fps = int(collection_size / iteration_time)
-        for key, value in locs["loss_dict"].items():
-            w.add_scalar(f"Loss/{key}", value, it)
-        w.add_scalar("Loss/learning_rate", self.alg.learning_rate, it)
-        w.add_scalar("Policy/mean_noise_std", mean_std, it)
-        w.add_scalar("Perf/total_fps", fps, it)
-        w.add_scalar("Perf/collection time", locs["collection_time"], it)
-        w.add_scalar("Perf/learning_time", locs["learn_time"], it)
-        have = len(locs["rewbuffer"]) > 0
-        if have:
-            w.add_scalar("Train/mean_reward", statistics.mean(locs["rewbuffer"]), it)
-            w.add_scalar("Train/mean_episode_length", statistics.mean(locs["lenbuffer"]), it)
-            w.add_scalar("Train/mean_reward/time", statistics.mean(locs["rewbuffer"]), self.tot_time)
-            w.add_scalar("Train/mean_episode_length/time", statistics.mean(locs["lenbuffer"]), self.tot_time)
-        head = f" \033[1m Learning iteration {it}/{locs['tot_iter']} \033[0m "
-        log_string = (f"""{'#' * width}\n"""
-                      f"""{head.center(width, ' ')}\n\n"""
-                      f"""{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)\n"""
-                      f"""{'Mean action noise std:':>{pad}} {mean_std:.2f}\n""")
-        for key, value in locs["loss_dict"].items():
-            log_string += f"""{f'Mean {key} loss:':>{pad}} {value:.4f}\n""" if have else f"""{f'{key}:':>{pad}} {value:.4f}\n"""
-        if have:
-            log_string += f"""{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"""
-            log_string += f"""{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n"""
-        log_string += ep_string
-        eta = self.tot_time / (it - locs["start_iter"] + 1) * (locs["start_iter"] + locs["num_learning_iterations"] - it)
-        log_string += (f"""{'-' * width}\n"""
-                       f"""{'Total timesteps:':>{pad}} {self.tot_timesteps}\n"""
-                       f"""{'Iteration time:':>{pad}} {iteration_time:.2f}s\n"""
-                       f"""{'Time elapsed:':>{pad}} {time.strftime("%H:%M:%S", time.gmtime(self.tot_time))}\n"""
-                       f"""{'ETA:':>{pad}} {time.strftime("%H:%M:%S", time.gmtime(eta))}\n""")
-        print(log_string)
 
     # ---- checkpoints (`:662-715`)
     def model_state_dict(self):

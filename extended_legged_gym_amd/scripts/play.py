@@ -3,9 +3,11 @@ the env with the play overrides (<= 50 envs, 5 x 5 terrain, no curriculum / nois
 by an inference policy for ten episodes.
 
 Where the policy comes from: with `--policy` a checkpoint written by rsl_rl's `OnPolicyRunner.save` (or any state dict with
-`actor.*` / `critic.*` / `std`) is evaluated by `NativeActorCritic` (the fused MFMA MLP, csrc/lg_policy.hip); without it the
+`actor.*` / `critic.*` / `std`) is evaluated by `NativeActorCritic` (the fused MFMA MLP, csrc/lg_policy.hip), a distillation checkpoint
+(`student.*` / `teacher.*` / `std`) by the student of `NativeStudentTeacher`; without it the
 runner is built and resumed from the log directory exactly as the reference does: rsl_rl's (the external package) by default,
-`rl.NativeOnPolicyRunner` with `--runner native`; either resumes what the other saved.
+`rl.NativeOnPolicyRunner` with `--runner native` (`rl.NativeDistillationRunner` for a distillation task, which also needs
+`--teacher_model_path`, as the reference's runner does); either resumes what the other saved.
 The viewer-only parts of the reference script (camera motion, frame recording, matplotlib logger) have no counterpart:
 there is no renderer behind this env.  `play()` returns the per-step statistics it printed."""
 import torch
@@ -29,10 +31,17 @@ def play(args, policy_path=None, num_steps=None):
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     obs = env.get_observations()
     if policy_path is not None:
-        from extended_legged_gym_amd.rl.policy import NativeActorCritic
+        from extended_legged_gym_amd.rl.policy import NativeActorCritic, NativeStudentTeacher, NativeStudentTeacherRecurrent
         ck = torch.load(policy_path, map_location="cpu", weights_only=False)
         sd = ck.get("model_state_dict", ck)
-        policy = NativeActorCritic(sd, activation=train_cfg.policy.activation, device=str(env.device)).act_inference
+        kw = dict(activation=train_cfg.policy.activation, device=str(env.device))
+        if "memory_s.rnn.weight_hh_l0" in sd:          # a distillation checkpoint: the student acts, behind its memory where it has one
+            gates, hidden = sd["memory_s.rnn.weight_hh_l0"].shape
+            policy = NativeStudentTeacherRecurrent(sd, rnn_type="lstm" if gates == 4 * hidden else "gru", **kw).act_inference
+        elif any(k.startswith("student.") for k in sd):
+            policy = NativeStudentTeacher(sd, **kw).act_inference
+        else:
+            policy = NativeActorCritic(sd, **kw).act_inference
     else:
         train_cfg.runner.resume = True
         ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg)

@@ -108,6 +108,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
                 setattr(cfg_train.runner, tgt, getattr(args, a))
         if getattr(args, "resume", False):
             cfg_train.runner.resume = args.resume
+        if getattr(args, "teacher_model_path", None) is not None:          # distillation: the checkpoint that fills the teacher (on_policy_runner.py:132-141)
+            cfg_train.runner.teacher_model_path = args.teacher_model_path
     return env_cfg, cfg_train
 
 
@@ -129,6 +131,8 @@ def get_args(argv=None):
     p.add_argument("--num_threads", type=int, default=0)
     p.add_argument("--runner", type=str, choices=("rsl_rl", "native"), default="rsl_rl",
                    help="rsl_rl: the external package's OnPolicyRunner; native: rl.NativeOnPolicyRunner (collection and PPO update on the library's kernels)")
+    p.add_argument("--teacher_model_path", type=str,
+                   help="distillation tasks: the checkpoint of the teacher's PPO run (or of a distillation run), runner.teacher_model_path of the train config")
     args = p.parse_args(argv)
     args.physics_engine = "native_hip"
     args.use_gpu_pipeline = True

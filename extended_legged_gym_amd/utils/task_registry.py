@@ -1,6 +1,7 @@
 """Task registry with the reference's interface (`utils/task_registry.py:44-155`): `register`, `get_cfgs`, `make_env`,
 `make_alg_runner`.  The PPO runner is the external `rsl_rl` package (unchanged caller of this env; imported only when a runner is
-requested) or, with `--runner native`, `rl.NativeOnPolicyRunner`: the same surface over the native collection and PPO update."""
+requested) or, with `--runner native`, `rl.NativeOnPolicyRunner`: the same surface over the native collection and PPO update
+(`rl.NativeDistillationRunner` where the train config's algorithm is `Distillation`)."""
 import os
 from datetime import datetime
 from typing import Tuple
@@ -46,7 +47,8 @@ class TaskRegistry():
     def make_alg_runner(self, env, name=None, args=None, train_cfg=None, log_root="default"):
         if args is None:
             args = get_args()
-        if getattr(args, "runner", "rsl_rl") == "native":
+        native = getattr(args, "runner", "rsl_rl") == "native"
+        if native:
             from extended_legged_gym_amd.rl import NativeOnPolicyRunner as OnPolicyRunner
         else:
             try:
@@ -61,6 +63,8 @@ class TaskRegistry():
         elif name is not None:
             print(f"'train_cfg' provided -> Ignoring 'name={name}'")
         _, train_cfg = update_cfg_from_args(None, train_cfg, args)
+        if native and algorithm_class_name(train_cfg) == "Distillation":
+            from extended_legged_gym_amd.rl import NativeDistillationRunner as OnPolicyRunner
         if log_root == "default":
             log_root = os.path.join(LEGGED_GYM_ROOT_DIR, 'logs', train_cfg.runner.experiment_name)
             log_dir = os.path.join(log_root, datetime.now().strftime('%b%d_%H-%M-%S') + '_' + train_cfg.runner.run_name)
@@ -74,6 +78,11 @@ class TaskRegistry():
             print(f"Loading model from: {resume_path}")
             runner.load(resume_path)
         return runner, train_cfg
+
+
+def algorithm_class_name(train_cfg):
+    """The algorithm a train config names: `algorithm.class_name` where it has one, else `runner.algorithm_class_name` (PPO when neither is set)."""
+    return getattr(train_cfg.algorithm, "class_name", None) or getattr(train_cfg.runner, "algorithm_class_name", "PPO")
 
 
 task_registry = TaskRegistry()

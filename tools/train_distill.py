@@ -17,6 +17,8 @@ MLP; feed-forward teacher) collected by `lg_collect_distillation_recurrent`.  `-
 `--update native` is `rl.NativeRecurrentDistillation` (include/lgdistill_recurrent.h).  Either way the student memory continues from the end state of
 the replay.  The default, `feedforward`, is everything above.
 
+Training the registered task goes through `scripts/train.py --runner native` (`rl.NativeDistillationRunner`); this tool stays as the checker and the bench driver.
+
 usage: python tools/train_distill.py [--teacher train_acceptance_model.pt] [--out distill.json] [--iters 100] [--envs 4096] [--python-loop]
                                      [--update {torch,native}] [--student {feedforward,recurrent}]
 """
