@@ -383,6 +383,30 @@ class lg_ppo_stats(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("value_function", "surrogate", "entropy", "kl", "learning_rate")]
 
 
+def _declare_trainer_group(lib, prefix, carry=False, workspace=False, step_losses=False):
+    """The prototypes every native trainer exports under its own prefix: the parameter count, the checkpoint calls and the learning rate; optionally the
+    workspace size, the step losses of the last update and the carried memory state."""
+    vp, i64 = C.c_void_p, C.c_int64
+
+    def declare(name, argtypes, restype=C.c_int):
+        fn = getattr(lib, "%s_%s" % (prefix, name))
+        fn.argtypes, fn.restype = argtypes, restype
+
+    declare("parameter_count", [vp], i64)
+    declare("get_parameters", [vp, vp, vp])
+    declare("get_state", [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp])
+    declare("set_state", [vp, vp, vp, vp, i64, C.c_double, vp])
+    declare("set_learning_rate", [vp, C.c_double, vp])
+    if workspace:
+        declare("workspace_bytes", [vp], i64)
+    if step_losses:
+        declare("step_losses", [vp, vp, i64, vp])
+    if carry:
+        declare("get_carry", [vp, vp, vp, i64, i32, vp], i64)
+        declare("set_carry", [vp, vp, vp, i64, vp])
+        declare("reset_carry", [vp, vp])
+
+
 def declare_train(lib):
     """Prototypes of the training entry points (include/lgtrain.h), same library."""
     vp, fpp = C.c_void_p, C.POINTER(C.POINTER(f32))
@@ -394,22 +418,13 @@ def declare_train(lib):
     lib.lg_ppo_minibatch.restype = C.c_int
     lib.lg_ppo_update.argtypes = [vp, C.POINTER(lg_ppo_rows), C.c_int64, vp, i32, i32, C.POINTER(lg_ppo_hyper), vp, vp]
     lib.lg_ppo_update.restype = C.c_int
-    lib.lg_ppo_parameter_count.argtypes = [vp]
-    lib.lg_ppo_parameter_count.restype = C.c_int64
     lib.lg_ppo_gradients.argtypes = [vp, vp, vp, vp, vp]
     lib.lg_ppo_gradients.restype = C.c_int
     lib.lg_ppo_forward_outputs.argtypes = [vp, vp, vp, vp]
     lib.lg_ppo_forward_outputs.restype = C.c_int
-    lib.lg_ppo_get_parameters.argtypes = [vp, vp, vp]
-    lib.lg_ppo_get_parameters.restype = C.c_int
-    lib.lg_ppo_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), vp]
-    lib.lg_ppo_get_state.restype = C.c_int
-    lib.lg_ppo_set_state.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, vp]
-    lib.lg_ppo_set_state.restype = C.c_int
-    lib.lg_ppo_set_learning_rate.argtypes = [vp, C.c_double, vp]
-    lib.lg_ppo_set_learning_rate.restype = C.c_int
     lib.lg_ppo_wgrad_slab_rows.argtypes = []
     lib.lg_ppo_wgrad_slab_rows.restype = i32
+    _declare_trainer_group(lib, "lg_ppo")
     return lib
 
 
@@ -444,20 +459,11 @@ def declare_train_symmetry(lib):
     lib.lg_ppo_sym_minibatch.restype = C.c_int
     lib.lg_ppo_sym_update.argtypes = [vp, C.POINTER(lg_ppo_rows), i64, vp, i32, i32, C.POINTER(lg_ppo_hyper), vp, vp]
     lib.lg_ppo_sym_update.restype = C.c_int
-    lib.lg_ppo_sym_parameter_count.argtypes = [vp]
-    lib.lg_ppo_sym_parameter_count.restype = i64
     lib.lg_ppo_sym_gradients.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.lg_ppo_sym_gradients.restype = C.c_int
     lib.lg_ppo_sym_forward_outputs.argtypes = [vp, vp, vp, vp]
     lib.lg_ppo_sym_forward_outputs.restype = C.c_int
-    lib.lg_ppo_sym_get_parameters.argtypes = [vp, vp, vp]
-    lib.lg_ppo_sym_get_parameters.restype = C.c_int
-    lib.lg_ppo_sym_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
-    lib.lg_ppo_sym_get_state.restype = C.c_int
-    lib.lg_ppo_sym_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
-    lib.lg_ppo_sym_set_state.restype = C.c_int
-    lib.lg_ppo_sym_set_learning_rate.argtypes = [vp, C.c_double, vp]
-    lib.lg_ppo_sym_set_learning_rate.restype = C.c_int
+    _declare_trainer_group(lib, "lg_ppo_sym")
     return lib
 
 
@@ -486,24 +492,13 @@ def declare_train_recurrent(lib):
     lib.lg_ppo_recurrent_minibatch.restype = C.c_int
     lib.lg_ppo_recurrent_update.argtypes = [vp, rows, hid, vp, i32, i64, i32, i32, hyp, vp, vp]
     lib.lg_ppo_recurrent_update.restype = C.c_int
-    lib.lg_ppo_recurrent_parameter_count.argtypes = [vp]
-    lib.lg_ppo_recurrent_parameter_count.restype = i64
-    lib.lg_ppo_recurrent_workspace_bytes.argtypes = [vp]
-    lib.lg_ppo_recurrent_workspace_bytes.restype = i64
     lib.lg_ppo_recurrent_gradients.argtypes = [vp, vp, vp, vp, vp]
     lib.lg_ppo_recurrent_gradients.restype = C.c_int
     lib.lg_ppo_recurrent_forward_outputs.argtypes = [vp, vp, vp, vp]
     lib.lg_ppo_recurrent_forward_outputs.restype = C.c_int
-    lib.lg_ppo_recurrent_get_parameters.argtypes = [vp, vp, vp]
-    lib.lg_ppo_recurrent_get_parameters.restype = C.c_int
-    lib.lg_ppo_recurrent_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
-    lib.lg_ppo_recurrent_get_state.restype = C.c_int
-    lib.lg_ppo_recurrent_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
-    lib.lg_ppo_recurrent_set_state.restype = C.c_int
-    lib.lg_ppo_recurrent_set_learning_rate.argtypes = [vp, C.c_double, vp]
-    lib.lg_ppo_recurrent_set_learning_rate.restype = C.c_int
     lib.lg_ppo_recurrent_get_images.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.lg_ppo_recurrent_get_images.restype = C.c_int
+    _declare_trainer_group(lib, "lg_ppo_recurrent", workspace=True)
     return lib
 
 
@@ -535,22 +530,11 @@ def declare_distill_train(lib):
     lib.lg_distill_train_group.restype = C.c_int
     lib.lg_distill_train_update.argtypes = [vp, vp, vp, i64, i64, i32, i32, hp, vp, vp]
     lib.lg_distill_train_update.restype = C.c_int
-    lib.lg_distill_train_parameter_count.argtypes = [vp]
-    lib.lg_distill_train_parameter_count.restype = i64
     lib.lg_distill_train_gradients.argtypes = [vp, vp, vp, vp, i64, vp]
     lib.lg_distill_train_gradients.restype = C.c_int
     lib.lg_distill_train_forward_outputs.argtypes = [vp, vp, vp]
     lib.lg_distill_train_forward_outputs.restype = C.c_int
-    lib.lg_distill_train_step_losses.argtypes = [vp, vp, i64, vp]
-    lib.lg_distill_train_step_losses.restype = C.c_int
-    lib.lg_distill_train_get_parameters.argtypes = [vp, vp, vp]
-    lib.lg_distill_train_get_parameters.restype = C.c_int
-    lib.lg_distill_train_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
-    lib.lg_distill_train_get_state.restype = C.c_int
-    lib.lg_distill_train_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
-    lib.lg_distill_train_set_state.restype = C.c_int
-    lib.lg_distill_train_set_learning_rate.argtypes = [vp, C.c_double, vp]
-    lib.lg_distill_train_set_learning_rate.restype = C.c_int
+    _declare_trainer_group(lib, "lg_distill_train", step_losses=True)
     return lib
 
 
@@ -583,32 +567,13 @@ def declare_distill_rtrain(lib):
     lib.lg_distill_rtrain_group.restype = C.c_int
     lib.lg_distill_rtrain_update.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, hp, vp, vp]
     lib.lg_distill_rtrain_update.restype = C.c_int
-    lib.lg_distill_rtrain_parameter_count.argtypes = [vp]
-    lib.lg_distill_rtrain_parameter_count.restype = i64
     lib.lg_distill_rtrain_student_parameter_count.argtypes = [vp]
     lib.lg_distill_rtrain_student_parameter_count.restype = i64
-    lib.lg_distill_rtrain_workspace_bytes.argtypes = [vp]
-    lib.lg_distill_rtrain_workspace_bytes.restype = i64
     lib.lg_distill_rtrain_gradients.argtypes = [vp, vp, vp, vp, i64, vp]
     lib.lg_distill_rtrain_gradients.restype = C.c_int
     lib.lg_distill_rtrain_forward_outputs.argtypes = [vp, vp, vp]
     lib.lg_distill_rtrain_forward_outputs.restype = C.c_int
-    lib.lg_distill_rtrain_step_losses.argtypes = [vp, vp, i64, vp]
-    lib.lg_distill_rtrain_step_losses.restype = C.c_int
-    lib.lg_distill_rtrain_get_carry.argtypes = [vp, vp, vp, i64, i32, vp]
-    lib.lg_distill_rtrain_get_carry.restype = i64
-    lib.lg_distill_rtrain_set_carry.argtypes = [vp, vp, vp, i64, vp]
-    lib.lg_distill_rtrain_set_carry.restype = C.c_int
-    lib.lg_distill_rtrain_reset_carry.argtypes = [vp, vp]
-    lib.lg_distill_rtrain_reset_carry.restype = C.c_int
-    lib.lg_distill_rtrain_get_parameters.argtypes = [vp, vp, vp]
-    lib.lg_distill_rtrain_get_parameters.restype = C.c_int
-    lib.lg_distill_rtrain_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
-    lib.lg_distill_rtrain_get_state.restype = C.c_int
-    lib.lg_distill_rtrain_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
-    lib.lg_distill_rtrain_set_state.restype = C.c_int
-    lib.lg_distill_rtrain_set_learning_rate.argtypes = [vp, C.c_double, vp]
-    lib.lg_distill_rtrain_set_learning_rate.restype = C.c_int
+    _declare_trainer_group(lib, "lg_distill_rtrain", carry=True, workspace=True, step_losses=True)
     return lib
 
 
@@ -649,32 +614,13 @@ def declare_estimator_train(lib):
     lib.lg_estimator_train_group.restype = C.c_int
     lib.lg_estimator_train_update.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, hp, vp, vp]
     lib.lg_estimator_train_update.restype = C.c_int
-    lib.lg_estimator_train_parameter_count.argtypes = [vp]
-    lib.lg_estimator_train_parameter_count.restype = i64
-    lib.lg_estimator_train_workspace_bytes.argtypes = [vp]
-    lib.lg_estimator_train_workspace_bytes.restype = i64
     lib.lg_estimator_train_wgrad_slab_rows.argtypes = []
     lib.lg_estimator_train_wgrad_slab_rows.restype = i32
     lib.lg_estimator_train_gradients.argtypes = [vp, vp, vp, vp, i64, vp]
     lib.lg_estimator_train_gradients.restype = C.c_int
     lib.lg_estimator_train_forward_outputs.argtypes = [vp, vp, vp]
     lib.lg_estimator_train_forward_outputs.restype = C.c_int
-    lib.lg_estimator_train_step_losses.argtypes = [vp, vp, i64, vp]
-    lib.lg_estimator_train_step_losses.restype = C.c_int
-    lib.lg_estimator_train_get_carry.argtypes = [vp, vp, vp, i64, i32, vp]
-    lib.lg_estimator_train_get_carry.restype = i64
-    lib.lg_estimator_train_set_carry.argtypes = [vp, vp, vp, i64, vp]
-    lib.lg_estimator_train_set_carry.restype = C.c_int
-    lib.lg_estimator_train_reset_carry.argtypes = [vp, vp]
-    lib.lg_estimator_train_reset_carry.restype = C.c_int
-    lib.lg_estimator_train_get_parameters.argtypes = [vp, vp, vp]
-    lib.lg_estimator_train_get_parameters.restype = C.c_int
-    lib.lg_estimator_train_get_state.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp]
-    lib.lg_estimator_train_get_state.restype = C.c_int
-    lib.lg_estimator_train_set_state.argtypes = [vp, vp, vp, vp, i64, C.c_double, vp]
-    lib.lg_estimator_train_set_state.restype = C.c_int
-    lib.lg_estimator_train_set_learning_rate.argtypes = [vp, C.c_double, vp]
-    lib.lg_estimator_train_set_learning_rate.restype = C.c_int
+    _declare_trainer_group(lib, "lg_estimator_train", carry=True, workspace=True, step_losses=True)
     return lib
 
 

@@ -31,12 +31,10 @@
 struct lg_distill_train : TrainCore {
   lg_mlp* student = nullptr;
   int A = 0;
-  int64_t last_steps = 0, last_update_steps = 0, seq_cap = 0;
+  int64_t seq_cap = 0;               // last_steps, last_update_steps, group_loss (max_rows) and seq_loss (seq_cap) are the core's
   int64_t* rows = nullptr;           // (max_rows) the group's row index
   float* loss_part = nullptr;        // [step][block]
   float* step_tmp = nullptr;         // (max_rows) the means of the steps in flight
-  float* group_loss = nullptr;       // (max_rows) the last group's
-  float* seq_loss = nullptr;         // (seq_cap) the last update's
   DistillScalars* ds = nullptr;
 };
 
@@ -235,20 +233,12 @@ int lg_distill_train_update(lg_distill_train* p, const float* obs, const float* 
 
 int64_t lg_distill_train_parameter_count(lg_distill_train* p) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  return p->P;
+  return train_api_parameter_count(p);
 }
 
 int lg_distill_train_gradients(lg_distill_train* p, float* g, float* norm, float* losses, int64_t capacity, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  if (losses && capacity < p->last_steps) return lg_policy_fail(LG_ERR_INVALID, "the last group had more steps than the buffer holds");
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  if (g) POLICY_TRY(hipMemcpy(g, p->G, (size_t)p->P * sizeof(float), hipMemcpyDeviceToHost));
-  if (norm) POLICY_TRY(hipMemcpy(norm, &p->sc->norm, sizeof(float), hipMemcpyDeviceToHost));
-  if (losses && p->last_steps > 0) POLICY_TRY(hipMemcpy(losses, p->group_loss, (size_t)p->last_steps * sizeof(float), hipMemcpyDeviceToHost));
-  return LG_OK;
+  return train_api_group_gradients(p, g, norm, losses, capacity, stream);
 }
 
 int lg_distill_train_forward_outputs(lg_distill_train* p, float* actions, void* stream) {
@@ -264,41 +254,27 @@ int lg_distill_train_forward_outputs(lg_distill_train* p, float* actions, void* 
 
 int lg_distill_train_step_losses(lg_distill_train* p, float* losses, int64_t count, void* stream) {
   POLICY_ENTRY;
-  if (!p || !losses) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (count < 0 || count > p->last_update_steps) return lg_policy_fail(LG_ERR_INVALID, "count exceeds the steps of the last update");
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  if (count > 0) POLICY_TRY(hipMemcpy(losses, p->seq_loss, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-  return LG_OK;
+  return train_api_step_losses(p, losses, count, stream);
 }
 
 int lg_distill_train_get_state(lg_distill_train* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  DeviceScope ds_(p->device);
-  return train_core_get_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_get_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_distill_train_get_parameters(lg_distill_train* p, float* params, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  return lg_distill_train_get_state(p, params, nullptr, nullptr, nullptr, nullptr, stream);
+  return train_api_get_parameters(p, params, stream);
 }
 
 int lg_distill_train_set_state(lg_distill_train* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params || !exp_avg || !exp_avg_sq) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (step < 0 || !(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "step < 0 or learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_set_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_distill_train_set_learning_rate(lg_distill_train* p, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  if (!(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_learning_rate(p, lr, (hipStream_t)stream);
+  return train_api_set_learning_rate(p, lr, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // lg_distill_train_internal.h -- the behaviour-loss kernels of lg_distill_train.hip (the group's row index, the element losses with their seed
 // gradient, the per-step means and the update's sums) as host launch functions: the recurrent student's trainer (lg_distill_train_recurrent.hip)
-// runs its MLP stage through them.  The kernels themselves live in lg_distill_train.hip only.
+// runs its MLP stage through them.  The kernels live in lg_distill_train.hip only; both trainers' checkpoint entry points are lg_train.hip's train_api_*.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

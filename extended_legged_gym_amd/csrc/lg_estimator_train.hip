@@ -357,36 +357,29 @@ __global__ void est_stats_kernel(EstScalars* __restrict__ es, const TrainScalars
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host side
-struct EstMemLayer {
-  float *gate[4], *hin, *cin, *cnew, *hnew, *dup, *Dih, *Dhh, *dh[2], *dc[2];
-  float *wtx, *wth;
-};
-
 struct lg_estimator_train : TrainCore {
-  lg_conv_encoder* enc = nullptr; lg_mlp* combine = nullptr; lg_rnn* mem = nullptr; lg_mlp* decoder = nullptr;
-  int F = 0, P_in = 0, cat_w = 0, Fc = 0, H = 0, Gates = 0, ML = 0, R_out = 0, act = 0;
+  lg_conv_encoder* enc = nullptr; lg_mlp* combine = nullptr; lg_mlp* decoder = nullptr;
+  TrainMem tm;                                 // the memory, its workspaces and carried state (lg_train_recurrent_internal.h)
+  int F = 0, P_in = 0, cat_w = 0, Fc = 0, R_out = 0, act = 0;
   int nd = 0;                                  // dense segments [0, nd): decoder, depth_encoder.10 / .12, combination_mlp.0, the memory's; then conv 1-4
   int64_t map_floats[4] = {0, 0, 0, 0};
   float* map[4] = {nullptr, nullptr, nullptr, nullptr};
   float *pool = nullptr, *y5 = nullptr, *cat = nullptr, *comb = nullptr;
   float *dA = nullptr, *dB = nullptr, *dpool = nullptr, *d5 = nullptr, *d6 = nullptr, *dcomb = nullptr;
-  EstMemLayer layer[RNN_MAX_LAYERS];
-  float *zero_state = nullptr, *zero_n = nullptr;
-  float *carry_h = nullptr, *carry_c = nullptr, *cur_h = nullptr, *cur_c = nullptr;          // (ML, max_rows, H)
-  int64_t carry_n = 0;
   DgradLayer dg_comb, dg_l12, dg_l10, dg_conv[4][4];       // dg_conv[l][parity class]: conv l + 1 (index 0 unused); a stride-1 layer has class 0 only (Hc == 0: no launch)
   ConvRetile* d_cretile = nullptr; int64_t cretile_big = 0;
-  RnnRetile* d_rretile = nullptr; int64_t rretile_big = 0;
-  int64_t last_steps = 0, last_update_steps = 0, seq_cap = 0;
-  float *loss_part = nullptr, *step_tmp = nullptr, *group_loss = nullptr, *seq_loss = nullptr;
+  int64_t seq_cap = 0;
+  float *loss_part = nullptr, *step_tmp = nullptr;
   EstScalars* es = nullptr;
 };
 
-static int est_retile(lg_estimator_train* p, hipStream_t st) {
+static TrainMem* est_mem(lg_estimator_train* p) { return p ? &p->tm : nullptr; }
+
+// the masters -> the convolutions' and the memory's images (the dense layers' are the Adam kernel's / train_core_retile's)
+static int est_retile(TrainCore* c, hipStream_t st) {
+  lg_estimator_train* p = static_cast<lg_estimator_train*>(c);
   hipLaunchKernelGGL(est_conv_retile_kernel, dim3((unsigned)((p->cretile_big + 255) / 256), 4), dim3(256), 0, st, (const ConvRetile*)p->d_cretile, (const float*)p->theta);
-  rec_launch_retile(p->d_rretile, p->ML, p->rretile_big, p->theta, st);
-  POLICY_TRY(hipGetLastError());
-  return LG_OK;
+  return mem_retile(&p->tm, p->theta, st);
 }
 
 static void est_launch_dgrad(const DgradLayer& L, const float* D, int64_t d_estride, int64_t n, const float* ysrc, int64_t y_estride, float* out, int64_t out_estride,
@@ -420,19 +413,7 @@ static int est_check_call(lg_estimator_train* p, const float* depth, const float
   if (h->loss_type != LG_EST_LOSS_MSE && h->loss_type != LG_EST_LOSS_HUBER && h->loss_type != LG_EST_LOSS_L1)
     return lg_policy_fail(LG_ERR_INVALID, "unknown loss type (mse | huber | l1)");
   if (h->use_dones && !dones) return lg_policy_fail(LG_ERR_INVALID, "use_dones without dones");
-  if (p->carry_n != 0 && p->carry_n != N) return lg_policy_fail(LG_ERR_INVALID, "N is not the carry's number of rows (reset the carry first)");
-  return LG_OK;
-}
-
-// the first call after a reset: zero carry and running state for N rows
-static int est_open_carry(lg_estimator_train* p, int64_t N, hipStream_t st) {
-  if (p->carry_n == N) return LG_OK;
-  const size_t bytes = (size_t)p->ML * p->max_rows * p->H * sizeof(float);
-  POLICY_TRY(hipMemsetAsync(p->carry_h, 0, bytes, st));
-  POLICY_TRY(hipMemsetAsync(p->cur_h, 0, bytes, st));
-  if (p->carry_c) { POLICY_TRY(hipMemsetAsync(p->carry_c, 0, bytes, st)); POLICY_TRY(hipMemsetAsync(p->cur_c, 0, bytes, st)); }
-  p->carry_n = N;
-  return LG_OK;
+  return mem_check_rows(&p->tm, N);
 }
 
 // steps [first, first + nsteps) of the sequence as one batch; train: an optimiser step, else forward and loss only.  seq_loss: where the update keeps
@@ -440,10 +421,11 @@ static int est_open_carry(lg_estimator_train* p, int64_t N, hipStream_t st) {
 static int est_steps(lg_estimator_train* p, const float* depth, const float* proprio, const float* tgt, const float* dones, int64_t T, int64_t N, int64_t first,
                      int64_t nsteps, const lg_estimator_train_hyper* h, bool train, float* seq_loss, hipStream_t st) {
   const int64_t n = nsteps * N, NR = N * p->R_out, t0 = first % T;
-  const int H = p->H, L = p->ML, hw = p->enc->H * p->enc->W;
-  const bool lstm = p->Gates == 4, use_dones = h->use_dones != 0;
-  const size_t lstride = (size_t)p->max_rows * H;
-  int rc = est_open_carry(p, N, st);
+  const int hw = p->enc->H * p->enc->W;
+  const bool use_dones = h->use_dones != 0;
+  TrainMem* M = &p->tm;
+  const MemSpan W{T, N, t0, nsteps, use_dones ? dones : nullptr};
+  int rc = mem_open_carry(M, N, st);
   if (rc != LG_OK) return rc;
   p->last_rows = n;
   p->last_steps = nsteps;
@@ -458,33 +440,10 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
     s += len;
   }
   if ((rc = lg_mlp_forward(p->combine, p->cat, n, p->comb, st)) != LG_OK) return rc;
-  // ---- the memory through time.  A step with time index 0 enters with the carry, the batch's first step otherwise with the running state, both as
-  // constants (dprev NULL: every row reads the saved row); every other step with the step before's state, zero where use_dones ended the episode
-  auto saved_entry = [&](int64_t s) { return s == 0 || (t0 + s) % T == 0; };
-  auto prev_dones = [&](int64_t s) -> const float* { return use_dones ? dones + ((t0 + s - 1) % T) * N : p->zero_n; };
-  for (int64_t s = 0; s < nsteps; ++s)
-    for (int l = 0; l < L; ++l) {
-      const EstMemLayer& Y = p->layer[l];
-      const size_t at = (size_t)s * N * H, before = s > 0 ? (size_t)(s - 1) * N * H : 0;
-      const bool epoch = (t0 + s) % T == 0;
-      RnnStepArgs S{}; RnnSaveArgs V{};
-      S.L = p->mem->layer[l];
-      S.x = l == 0 ? p->comb + (size_t)s * N * p->Fc : p->layer[l - 1].hnew + at;
-      if (saved_entry(s)) {
-        V.hs = (epoch ? p->carry_h : p->cur_h) + l * lstride; V.cs = lstm ? (epoch ? p->carry_c : p->cur_c) + l * lstride : nullptr;
-        V.hprev = nullptr; V.cprev = nullptr; V.dprev = nullptr;
-      } else {
-        V.hs = p->zero_state; V.cs = lstm ? p->zero_state : nullptr;
-        V.hprev = Y.hnew + before; V.cprev = lstm ? Y.cnew + before : nullptr; V.dprev = prev_dones(s);
-      }
-      for (int g = 0; g < 4; ++g) V.gate[g] = Y.gate[g] + at;
-      V.hin = Y.hin + at; V.hnew = Y.hnew + at;
-      V.cin = lstm ? Y.cin + at : nullptr; V.cnew = lstm ? Y.cnew + at : nullptr;
-      rec_launch_forward_one(S, V, N, st);
-    }
+  mem_forward(M, W, p->comb, false, st);
   // ---- the decoder on the memory's outputs, the losses
   const TrainNet& Dn = p->net[0];
-  const float* top = p->layer[L - 1].hnew;
+  const float* top = M->layer[M->ML - 1].hnew;
   train_launch_forward(p, top, top, nullptr, n, st);
   const int nblocks = (int)((NR + EST_LOSS_LANES - 1) / EST_LOSS_LANES);
   hipLaunchKernelGGL(est_loss_kernel, dim3(nblocks, (unsigned)nsteps), dim3(EST_LOSS_LANES), 0, st, (const float*)Dn.a[Dn.L], tgt, NR, T, t0, h->loss_type,
@@ -492,33 +451,10 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
   hipLaunchKernelGGL(est_loss_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)p->loss_part, nblocks, nsteps, NR, p->step_tmp, p->group_loss, seq_loss, p->es,
                      train ? 1 : 0);
   if (train) {
-    // ---- the decoder backwards and dL/d(its input)
+    // ---- the decoder backwards and dL/d(its input); then backwards through time: layer 0 propagates into the combination layer's output
     train_launch_backward(p, n, st);
-    {
-      RowsMatArgs M;
-      M.A = Dn.d[0]; M.K = Dn.dims[1]; M.nbk = Dn.bkpad[0] / 16; M.wt = Dn.bw[0]; M.nout = H; M.nch = (H + 15) / 16; M.out = p->layer[L - 1].dup;
-      rec_launch_rows_matmul_one(M, n, st);
-    }
-    // ---- backwards through time; layer 0 propagates into the combination layer's output
-    for (int64_t s = nsteps - 1; s >= 0; --s)
-      for (int l = L - 1; l >= 0; --l) {
-        const EstMemLayer& Y = p->layer[l];
-        const size_t at = (size_t)s * N * H;
-        const int Il = l == 0 ? p->Fc : H;
-        RnnBackArgs b{};
-        b.gru = lstm ? 0 : 1; b.I = Il; b.H = H; b.K = p->Gates * H; b.nbk = (b.K + 15) / 16;
-        b.nchx = (Il + 15) / 16; b.nchh = (H + 15) / 16;
-        b.wtx = Y.wtx; b.wth = Y.wth;
-        for (int g = 0; g < 4; ++g) b.gate[g] = Y.gate[g] + at;
-        b.hin = Y.hin + at; b.cin = lstm ? Y.cin + at : nullptr; b.cnew = lstm ? Y.cnew + at : nullptr;
-        b.dup = Y.dup + at;
-        b.dh_in = s + 1 < nsteps ? Y.dh[(s + 1) & 1] : nullptr; b.dc_in = (s + 1 < nsteps && lstm) ? Y.dc[(s + 1) & 1] : nullptr;
-        b.dprev = saved_entry(s) ? nullptr : prev_dones(s);
-        b.dh_out = Y.dh[s & 1]; b.dc_out = lstm ? Y.dc[s & 1] : nullptr;
-        b.dx = l > 0 ? p->layer[l - 1].dup + at : p->dcomb + (size_t)s * N * p->Fc;
-        b.Dih = Y.Dih + (size_t)s * N * b.K; b.Dhh = Y.Dhh + (size_t)s * N * b.K;
-        rec_launch_backward_one(b, N, st);
-      }
+    mem_top_matmul(M, Dn, n, st);
+    mem_backward(M, W, p->dcomb, st);
     // ---- the combination layer and the encoder backwards; each convolution's weight gradient as soon as its delta stands (two delta buffers ping-pong)
     hipLaunchKernelGGL(est_act_delta_kernel, dim3((unsigned)((n * p->Fc + 255) / 256)), dim3(256), 0, st, p->dcomb, (const float*)p->comb, n * p->Fc, p->act);
     est_launch_dgrad(p->dg_comb, p->dcomb, p->Fc, n, p->cat, p->cat_w, p->d6, p->F, st);
@@ -543,15 +479,12 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
     if ((rc = est_retile(p, st)) != LG_OK) return rc;
   }
   // ---- the running state: the memory after the last step
-  for (int l = 0; l < L; ++l) {
-    const size_t last = (size_t)(nsteps - 1) * N * H, bytes = (size_t)N * H * sizeof(float);
-    POLICY_TRY(hipMemcpyAsync(p->cur_h + l * lstride, p->layer[l].hnew + last, bytes, hipMemcpyDeviceToDevice, st));
-    if (lstm) POLICY_TRY(hipMemcpyAsync(p->cur_c + l * lstride, p->layer[l].cnew + last, bytes, hipMemcpyDeviceToDevice, st));
-  }
+  if ((rc = mem_keep_running(M, W, st)) != LG_OK) return rc;
   if (use_dones) {
     const float* dl = dones + ((t0 + nsteps - 1) % T) * N;
-    hipLaunchKernelGGL(est_mask_rows_kernel, dim3((unsigned)((N * H + 255) / 256)), dim3(256), 0, st, p->cur_h, dl, N, H, (int64_t)lstride, L);
-    if (lstm) hipLaunchKernelGGL(est_mask_rows_kernel, dim3((unsigned)((N * H + 255) / 256)), dim3(256), 0, st, p->cur_c, dl, N, H, (int64_t)lstride, L);
+    const int64_t lstride = M->max_rows * M->H;
+    hipLaunchKernelGGL(est_mask_rows_kernel, dim3((unsigned)((N * M->H + 255) / 256)), dim3(256), 0, st, M->cur_h, dl, N, M->H, lstride, M->ML);
+    if (M->cur_c) hipLaunchKernelGGL(est_mask_rows_kernel, dim3((unsigned)((N * M->H + 255) / 256)), dim3(256), 0, st, M->cur_c, dl, N, M->H, lstride, M->ML);
   }
   POLICY_TRY(hipGetLastError());
   return LG_OK;
@@ -623,22 +556,21 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   DeviceScope ds_(enc->device);
   if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_estimator_train* p = new lg_estimator_train();
-  p->enc = enc; p->combine = combine; p->mem = mem; p->decoder = decoder; p->device = enc->device; p->max_rows = max_rows;
-  p->F = F; p->cat_w = cat_w; p->P_in = cat_w - F; p->Fc = Fc; p->H = H; p->ML = ML; p->Gates = mem->type == LG_RNN_GRU ? 3 : 4; p->act = enc->act;
+  p->enc = enc; p->combine = combine; p->decoder = decoder; p->device = enc->device; p->max_rows = max_rows;
+  p->F = F; p->cat_w = cat_w; p->P_in = cat_w - F; p->Fc = Fc; p->act = enc->act;
   p->R_out = decoder->h.dims[decoder->h.L];
+  p->retile_own = est_retile;
+  TrainMem* M = &p->tm;
   bool ok = true;
   auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(p, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
   const size_t R = (size_t)max_rows;
-  const int slabs_max = (int)((max_rows + WGRAD_SLAB - 1) / WGRAD_SLAB);
-  const int K = p->Gates * H, nbk = (K + 15) / 16;
   // ---- workspaces
   for (int l = 0; l < 4; ++l) { p->map_floats[l] = (int64_t)enc->layer[l].Hout * enc->layer[l].Wout * enc->layer[l].Cout; p->map[l] = alloc(R * p->map_floats[l], false); }
   p->pool = alloc(R * 1024, false); p->y5 = alloc(R * 128, false); p->cat = alloc(R * cat_w, false); p->comb = alloc(R * Fc, false);
   p->dA = alloc(R * std::max(p->map_floats[0], p->map_floats[2]), false); p->dB = alloc(R * std::max(p->map_floats[1], p->map_floats[3]), false);
   p->dpool = alloc(R * 1024, false); p->d5 = alloc(R * 128, false); p->d6 = alloc(R * F, false); p->dcomb = alloc(R * Fc, false);
-  p->zero_state = alloc(R * H, true); p->zero_n = alloc(R, true);
-  p->carry_h = alloc(ML * R * H, true); p->cur_h = alloc(ML * R * H, true);
-  if (p->Gates == 4) { p->carry_c = alloc(ML * R * H, true); p->cur_c = alloc(ML * R * H, true); }
+  ok = ok && mem_alloc(p, M, mem);
+  const int K = M->Gates * H, nbk = (K + 15) / 16;
   // ---- segments: the decoder's (net 0), then the dense ones by hand, then the convolutions.  Layer ids behind the decoder's index the host tables.
   int64_t off = 0;
   ok = ok && train_core_add_net(p, decoder, &off);
@@ -647,15 +579,7 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   const float* wtab[ID_COUNT] = {}; const float* btab[ID_COUNT] = {};
   for (int l = 0; l < Ld; ++l) { wtab[l] = q->decoder_weights[l]; btab[l] = q->decoder_biases[l]; }
   auto dense_seg = [&](int id, int dO, int dI, const float* Dp, const float* Ain, float* fw, float* fb, int f_nb, float* bw, int b_nb) -> TrainSeg& {
-    TrainSeg& S = p->seg[p->nseg++];
-    S.net = 0; S.layer = id; S.dO = dO; S.dI = dI; S.f_nb = f_nb; S.b_nb = b_nb; S.woff = 0; S.boff = 0;
-    S.D = Dp; S.Ain = Ain; S.partial = alloc((size_t)slabs_max * dO * (dI + 1), false);
-    S.fw = fw; S.fb = fb; S.bw = bw;
-    const int64_t cnt = (int64_t)dO * (dI + 1);
-    if (cnt > p->big) p->big = cnt;
-    const int tiles = ((dO + 31) / 32) * ((dI + 1 + 63) / 64);
-    if ((tiles + 3) / 4 > p->wgrad_blocks) p->wgrad_blocks = (tiles + 3) / 4;
-    return S;
+    return train_core_add_seg(p, 0, id, dO, dI, Dp, Ain, fw, fb, f_nb, bw, b_nb, &ok);
   };
   // a transposed image the data-gradient kernel reads: chunks of 16 inputs padded to 64 columns, K = dO padded to 64
   auto transposed = [&](int dO, int dI) -> float* { return alloc((size_t)(((dI + 63) & ~63) / 16) * (((dO + 63) & ~63) / 16) * 256, true); };
@@ -670,17 +594,9 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   wtab[ID_COMB] = q->combine_weight; btab[ID_COMB] = q->combine_bias;
   const int seg_mem = p->nseg;
   for (int l = 0; l < ML && ok; ++l) {
-    EstMemLayer& Y = p->layer[l];
+    const MemLayer& Y = M->layer[l];
     const int I = l == 0 ? Fc : H;
-    const bool lstm = p->Gates == 4;
-    for (int g = 0; g < 4; ++g) Y.gate[g] = alloc(R * H, false);
-    Y.hin = alloc(R * H, false); Y.hnew = alloc(R * H, false); Y.dup = alloc(R * H, false);
-    Y.cin = lstm ? alloc(R * H, false) : nullptr; Y.cnew = lstm ? alloc(R * H, false) : nullptr;
-    Y.Dih = alloc(R * K, false); Y.Dhh = lstm ? Y.Dih : alloc(R * K, false);
-    for (int s = 0; s < 2; ++s) { Y.dh[s] = alloc(R * H, true); Y.dc[s] = lstm ? alloc(R * H, true) : nullptr; }
-    Y.wtx = alloc((size_t)((I + 15) / 16) * nbk * 256, true);
-    Y.wth = alloc((size_t)((H + 15) / 16) * nbk * 256, true);
-    dense_seg(ID_MEM + 2 * l, K, I, Y.Dih, l == 0 ? p->comb : p->layer[l - 1].hnew, nullptr, nullptr, 0, Y.wtx, nbk);
+    dense_seg(ID_MEM + 2 * l, K, I, Y.Dih, l == 0 ? p->comb : M->layer[l - 1].hnew, nullptr, nullptr, 0, Y.wtx, nbk);
     dense_seg(ID_MEM + 2 * l + 1, K, H, Y.Dhh, Y.hin, nullptr, nullptr, 0, Y.wth, nbk);
     wtab[ID_MEM + 2 * l] = q->memory_w_ih[l]; btab[ID_MEM + 2 * l] = q->memory_b_ih[l];
     wtab[ID_MEM + 2 * l + 1] = q->memory_w_hh[l]; btab[ID_MEM + 2 * l + 1] = q->memory_b_hh[l];
@@ -690,7 +606,7 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   {
     TrainNet& Nn = p->net[0];
     float* bw0 = alloc((size_t)Nn.bnch[0] * (Nn.bkpad[0] / 16) * 256, true);
-    Nn.bw[0] = bw0; p->seg[dec_first].bw = bw0; p->seg[dec_first].Ain = p->layer[ML - 1].hnew;
+    Nn.bw[0] = bw0; p->seg[dec_first].bw = bw0; p->seg[dec_first].Ain = M->layer[ML - 1].hnew;
   }
   float* conv_bw[4] = {nullptr, nullptr, nullptr, nullptr};
   for (int l = 0; l < 4 && ok; ++l) {          // the partials are est_conv_wgrad_kernel's; Adam writes no image (fw, fb, bw NULL): est_conv_retile_kernel does
@@ -711,21 +627,7 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   off = 0;
   for (int l = 0; l < 4; ++l) place(p->seg[p->nd + l]);
   place(p->seg[seg_l10]); place(p->seg[seg_l10 + 1]); place(p->seg[seg_l10 + 2]);
-  std::vector<RnnRetile> rret;
-  for (int l = 0; l < ML; ++l) {
-    TrainSeg &Si = p->seg[seg_mem + 2 * l], &Sh = p->seg[seg_mem + 2 * l + 1];
-    Si.woff = off; off += (int64_t)Si.dO * Si.dI;
-    Sh.woff = off; off += (int64_t)Sh.dO * Sh.dI;
-    Si.boff = off; off += Si.dO;
-    Sh.boff = off; off += Sh.dO;
-    const RnnLayerDev& D = mem->layer[l];
-    RnnRetile rt;
-    rt.w = const_cast<float*>(D.w); rt.b = const_cast<float*>(D.b); rt.G = p->Gates; rt.I = D.I; rt.H = D.H; rt.Ip = D.Ip; rt.nb = D.nb; rt.nch = D.nch;
-    rt.wih = Si.woff; rt.whh = Sh.woff; rt.bih = Si.boff; rt.bhh = Sh.boff;
-    rret.push_back(rt);
-    const int64_t cnt = (int64_t)D.nch * (D.nb + 1) * rt.G * 256 + 4 * 16 * D.nch;
-    if (cnt > p->rretile_big) p->rretile_big = cnt;
-  }
+  for (int l = 0; l < ML; ++l) mem_place_layer(M, l, p->seg[seg_mem + 2 * l], p->seg[seg_mem + 2 * l + 1], &off);
   for (int l = 0; l < Ld; ++l) place(p->seg[dec_first + l]);
   std::vector<ConvRetile> cret(4);
   for (int l = 0; l < 4; ++l) {
@@ -766,13 +668,12 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   p->seq_loss = (float*)zalloc((size_t)p->seq_cap * sizeof(float));
   p->es = (EstScalars*)zalloc(sizeof(EstScalars));
   p->d_cretile = (ConvRetile*)zalloc(sizeof(ConvRetile) * 4);
-  p->d_rretile = (RnnRetile*)zalloc(sizeof(RnnRetile) * (rret.size() + 1));
+  ok = ok && mem_upload_retile(p, M);
   const float* const* ws[1] = {wtab};
   const float* const* bs[1] = {btab};
   if (!ok || train_core_finish(p, off, ws, bs, nullptr, learning_rate) != LG_OK ||
       hipMemcpy(p->d_cretile, cret.data(), sizeof(ConvRetile) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(p->d_rretile, rret.data(), sizeof(RnnRetile) * rret.size(), hipMemcpyHostToDevice) != hipSuccess || est_retile(p, nullptr) != LG_OK ||
-      hipDeviceSynchronize() != hipSuccess) {
+      est_retile(p, nullptr) != LG_OK || hipDeviceSynchronize() != hipSuccess) {
     lg_estimator_train_destroy(p);
     return nullptr;
   }
@@ -818,9 +719,8 @@ int lg_estimator_train_update(lg_estimator_train* p, const float* depth, const f
     const int r2 = est_steps(p, depth, proprio, tgt, dones, T, N, k, total - k, hyper, false, p->seq_loss + k, st);
     if (r2 != LG_OK) return r2;
   }
-  const size_t bytes = (size_t)p->ML * p->max_rows * p->H * sizeof(float);
-  POLICY_TRY(hipMemcpyAsync(p->carry_h, p->cur_h, bytes, hipMemcpyDeviceToDevice, st));
-  if (p->carry_c) POLICY_TRY(hipMemcpyAsync(p->carry_c, p->cur_c, bytes, hipMemcpyDeviceToDevice, st));
+  const int r3 = mem_keep_carry(&p->tm, st);
+  if (r3 != LG_OK) return r3;
   if (stats) hipLaunchKernelGGL(est_stats_kernel, dim3(1), dim3(1), 0, st, p->es, (const TrainScalars*)p->sc, stats, 1);
   POLICY_TRY(hipGetLastError());
   return LG_OK;
@@ -828,32 +728,17 @@ int lg_estimator_train_update(lg_estimator_train* p, const float* depth, const f
 
 int64_t lg_estimator_train_parameter_count(lg_estimator_train* p) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  return p->P;
+  return train_api_parameter_count(p);
 }
 
 int64_t lg_estimator_train_workspace_bytes(lg_estimator_train* p) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  DeviceScope ds_(p->device);
-  int64_t total = 0;
-  for (void* d : p->allocs) {
-    size_t bytes = 0;
-    if (hipMemPtrGetInfo(d, &bytes) == hipSuccess) total += (int64_t)bytes;
-  }
-  return total;
+  return train_api_workspace_bytes(p);
 }
 
 int lg_estimator_train_gradients(lg_estimator_train* p, float* g, float* norm, float* losses, int64_t capacity, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  if (losses && capacity < p->last_steps) return lg_policy_fail(LG_ERR_INVALID, "the last group had more steps than the buffer holds");
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  if (g) POLICY_TRY(hipMemcpy(g, p->G, (size_t)p->P * sizeof(float), hipMemcpyDeviceToHost));
-  if (norm) POLICY_TRY(hipMemcpy(norm, &p->sc->norm, sizeof(float), hipMemcpyDeviceToHost));
-  if (losses && p->last_steps > 0) POLICY_TRY(hipMemcpy(losses, p->group_loss, (size_t)p->last_steps * sizeof(float), hipMemcpyDeviceToHost));
-  return LG_OK;
+  return train_api_group_gradients(p, g, norm, losses, capacity, stream);
 }
 
 int lg_estimator_train_forward_outputs(lg_estimator_train* p, float* predictions, void* stream) {
@@ -869,87 +754,43 @@ int lg_estimator_train_forward_outputs(lg_estimator_train* p, float* predictions
 
 int lg_estimator_train_step_losses(lg_estimator_train* p, float* losses, int64_t count, void* stream) {
   POLICY_ENTRY;
-  if (!p || !losses) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (count < 0 || count > p->last_update_steps) return lg_policy_fail(LG_ERR_INVALID, "count exceeds the steps of the last update");
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  if (count > 0) POLICY_TRY(hipMemcpy(losses, p->seq_loss, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-  return LG_OK;
+  return train_api_step_losses(p, losses, count, stream);
 }
 
+// the caller's h / c are HOST arrays
 int64_t lg_estimator_train_get_carry(lg_estimator_train* p, float* h, float* c, int64_t capacity_rows, int32_t running, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  const int64_t N = p->carry_n;
-  if (!h || N == 0 || capacity_rows < N) return N;
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  const size_t lstride = (size_t)p->max_rows * p->H, row = (size_t)N * p->H;
-  for (int l = 0; l < p->ML; ++l) {
-    POLICY_TRY(hipMemcpy(h + l * row, (running ? p->cur_h : p->carry_h) + l * lstride, row * sizeof(float), hipMemcpyDeviceToHost));
-    if (c && p->carry_c) POLICY_TRY(hipMemcpy(c + l * row, (running ? p->cur_c : p->carry_c) + l * lstride, row * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  return N;
+  return mem_get_carry(est_mem(p), h, c, capacity_rows, running, hipMemcpyDeviceToHost, stream);
 }
 
 int lg_estimator_train_set_carry(lg_estimator_train* p, const float* h, const float* c, int64_t N, void* stream) {
   POLICY_ENTRY;
-  if (!p || !h) return lg_policy_fail(LG_ERR_INVALID, "null trainer or state");
-  if (p->carry_c && !c) return lg_policy_fail(LG_ERR_INVALID, "an LSTM needs its cell state");
-  if (N < 1 || N > p->max_rows) return lg_policy_fail(LG_ERR_INVALID, "N < 1 or N > max_rows of the trainer");
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  const size_t lstride = (size_t)p->max_rows * p->H, row = (size_t)N * p->H;
-  for (int l = 0; l < p->ML; ++l) {
-    POLICY_TRY(hipMemcpy(p->carry_h + l * lstride, h + l * row, row * sizeof(float), hipMemcpyHostToDevice));
-    POLICY_TRY(hipMemcpy(p->cur_h + l * lstride, h + l * row, row * sizeof(float), hipMemcpyHostToDevice));
-    if (p->carry_c) {
-      POLICY_TRY(hipMemcpy(p->carry_c + l * lstride, c + l * row, row * sizeof(float), hipMemcpyHostToDevice));
-      POLICY_TRY(hipMemcpy(p->cur_c + l * lstride, c + l * row, row * sizeof(float), hipMemcpyHostToDevice));
-    }
-  }
-  p->carry_n = N;
-  return LG_OK;
+  return mem_set_carry(est_mem(p), h, c, N, hipMemcpyHostToDevice, stream);
 }
 
 int lg_estimator_train_reset_carry(lg_estimator_train* p, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  p->carry_n = 0;
-  return LG_OK;
+  return mem_reset_carry(est_mem(p));
 }
 
 int lg_estimator_train_get_state(lg_estimator_train* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  DeviceScope ds_(p->device);
-  return train_core_get_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_get_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_estimator_train_get_parameters(lg_estimator_train* p, float* params, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  return lg_estimator_train_get_state(p, params, nullptr, nullptr, nullptr, nullptr, stream);
+  return train_api_get_parameters(p, params, stream);
 }
 
 int lg_estimator_train_set_state(lg_estimator_train* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params || !exp_avg || !exp_avg_sq) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (step < 0 || !(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "step < 0 or learning rate <= 0");
-  DeviceScope ds_(p->device);
-  int rc = train_core_set_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
-  if (rc == LG_OK) rc = est_retile(p, (hipStream_t)stream);
-  if (rc != LG_OK) return rc;
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return LG_OK;
+  return train_api_set_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_estimator_train_set_learning_rate(lg_estimator_train* p, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  if (!(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_learning_rate(p, lr, (hipStream_t)stream);
+  return train_api_set_learning_rate(p, lr, stream);
 }
 
 }  // extern "C"

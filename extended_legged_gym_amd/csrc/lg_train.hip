@@ -414,6 +414,21 @@ bool train_core_add_net(TrainCore* c, const lg_mlp* net, int64_t* off) {
   return ok;
 }
 
+TrainSeg& train_core_add_seg(TrainCore* c, int net, int layer_id, int dO, int dI, const float* D, const float* Ain, float* fw, float* fb, int f_nb, float* bw, int b_nb,
+                             bool* ok) {
+  const int slabs_max = (int)((c->max_rows + WGRAD_SLAB - 1) / WGRAD_SLAB);
+  TrainSeg& S = c->seg[c->nseg++];
+  S.net = net; S.layer = layer_id; S.dO = dO; S.dI = dI; S.f_nb = f_nb; S.b_nb = b_nb; S.woff = 0; S.boff = 0;
+  S.D = D; S.Ain = Ain; S.fw = fw; S.fb = fb; S.bw = bw;
+  S.partial = *ok ? (float*)train_alloc(c, (size_t)slabs_max * dO * (dI + 1) * sizeof(float), false) : nullptr;
+  if (!S.partial) *ok = false;
+  const int64_t cnt = (int64_t)dO * (dI + 1);
+  if (cnt > c->big) c->big = cnt;
+  const int tiles = ((dO + 31) / 32) * ((dI + 1 + 63) / 64);
+  if ((tiles + 3) / 4 > c->wgrad_blocks) c->wgrad_blocks = (tiles + 3) / 4;
+  return S;
+}
+
 static int train_core_retile_or_step(TrainCore* p, hipStream_t st, bool step) {
   hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((p->big + 255) / 256), p->nseg + (p->nstd > 0 ? 1 : 0)), dim3(256), 0, st, p->d_seg, p->nseg, p->std_off,
                      p->nstd, p->std_type, p->std_dev, p->theta, p->m, p->v, p->G, p->sc, step ? 0 : 1);
@@ -499,7 +514,24 @@ int train_launch_norm_adam(TrainCore* c, float max_grad_norm, int clip_on, hipSt
   return train_core_retile_or_step(c, st, true);
 }
 
-int train_core_get_state(TrainCore* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, hipStream_t st) {
+// ---- the entry points every trainer exports under its own prefix (lg_train_internal.h)
+int64_t train_api_parameter_count(TrainCore* p) {
+  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
+  return p->P;
+}
+
+int64_t train_api_workspace_bytes(TrainCore* p) {
+  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
+  DeviceScope ds_(p->device);
+  int64_t total = 0;
+  for (void* d : p->allocs) {
+    size_t bytes = 0;
+    if (hipMemPtrGetInfo(d, &bytes) == hipSuccess) total += (int64_t)bytes;
+  }
+  return total;
+}
+
+static int train_core_get_state(TrainCore* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, hipStream_t st) {
   POLICY_TRY(hipStreamSynchronize(st));
   const size_t bytes = (size_t)p->P * sizeof(float);
   if (params) POLICY_TRY(hipMemcpy(params, p->theta, bytes, hipMemcpyDeviceToHost));
@@ -512,7 +544,7 @@ int train_core_get_state(TrainCore* p, float* params, float* exp_avg, float* exp
   return LG_OK;
 }
 
-int train_core_set_state(TrainCore* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, hipStream_t st) {
+static int train_core_set_state(TrainCore* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, hipStream_t st) {
   POLICY_TRY(hipStreamSynchronize(st));
   const size_t bytes = (size_t)p->P * sizeof(float);
   POLICY_TRY(hipMemcpy(p->theta, params, bytes, hipMemcpyHostToDevice));
@@ -528,9 +560,55 @@ int train_core_set_state(TrainCore* p, const float* params, const float* exp_avg
   return LG_OK;
 }
 
-int train_core_set_learning_rate(TrainCore* p, double lr, hipStream_t st) {
+int train_api_get_state(TrainCore* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, void* stream) {
+  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
+  DeviceScope ds_(p->device);
+  return train_core_get_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+}
+
+int train_api_get_parameters(TrainCore* p, float* params, void* stream) {
+  if (!p || !params) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
+  return train_api_get_state(p, params, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int train_api_set_state(TrainCore* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, void* stream) {
+  if (!p || !params || !exp_avg || !exp_avg_sq) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
+  if (step < 0 || !(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "step < 0 or learning rate <= 0");
+  DeviceScope ds_(p->device);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = train_core_set_state(p, params, exp_avg, exp_avg_sq, step, lr, st);
+  if (rc != LG_OK || !p->retile_own) return rc;
+  if ((rc = p->retile_own(p, st)) != LG_OK) return rc;
   POLICY_TRY(hipStreamSynchronize(st));
+  return LG_OK;
+}
+
+int train_api_set_learning_rate(TrainCore* p, double lr, void* stream) {
+  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
+  if (!(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0");
+  DeviceScope ds_(p->device);
+  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
   POLICY_TRY(hipMemcpy(&p->sc->lr, &lr, sizeof(double), hipMemcpyHostToDevice));
+  return LG_OK;
+}
+
+int train_api_group_gradients(TrainCore* p, float* g, float* norm, float* losses, int64_t capacity, void* stream) {
+  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
+  if (losses && capacity < p->last_steps) return lg_policy_fail(LG_ERR_INVALID, "the last group had more steps than the buffer holds");
+  DeviceScope ds_(p->device);
+  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (g) POLICY_TRY(hipMemcpy(g, p->G, (size_t)p->P * sizeof(float), hipMemcpyDeviceToHost));
+  if (norm) POLICY_TRY(hipMemcpy(norm, &p->sc->norm, sizeof(float), hipMemcpyDeviceToHost));
+  if (losses && p->last_steps > 0) POLICY_TRY(hipMemcpy(losses, p->group_loss, (size_t)p->last_steps * sizeof(float), hipMemcpyDeviceToHost));
+  return LG_OK;
+}
+
+int train_api_step_losses(TrainCore* p, float* losses, int64_t count, void* stream) {
+  if (!p || !losses) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
+  if (count < 0 || count > p->last_update_steps) return lg_policy_fail(LG_ERR_INVALID, "count exceeds the steps of the last update");
+  DeviceScope ds_(p->device);
+  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (count > 0) POLICY_TRY(hipMemcpy(losses, p->seq_loss, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
   return LG_OK;
 }
 
@@ -650,8 +728,7 @@ int lg_ppo_update(lg_ppo* p, const lg_ppo_rows* rows, int64_t R, const int64_t* 
 
 int64_t lg_ppo_parameter_count(lg_ppo* p) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  return p->P;
+  return train_api_parameter_count(p);
 }
 
 int lg_ppo_gradients(lg_ppo* p, float* g, float* norm, float* means, void* stream) {
@@ -681,31 +758,22 @@ int lg_ppo_forward_outputs(lg_ppo* p, float* mean, float* values, void* stream) 
 
 int lg_ppo_get_state(lg_ppo* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  DeviceScope ds_(p->device);
-  return train_core_get_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_get_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_ppo_get_parameters(lg_ppo* p, float* params, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  return lg_ppo_get_state(p, params, nullptr, nullptr, nullptr, nullptr, stream);
+  return train_api_get_parameters(p, params, stream);
 }
 
 int lg_ppo_set_state(lg_ppo* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params || !exp_avg || !exp_avg_sq) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (step < 0 || !(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "step < 0 or learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_set_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_ppo_set_learning_rate(lg_ppo* p, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  if (!(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_learning_rate(p, lr, (hipStream_t)stream);
+  return train_api_set_learning_rate(p, lr, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // lg_train_internal.h — what the trainers share (lg_train.hip: PPO over two networks; lg_distill_train.hip: distillation over one;
 // lg_train_recurrent.hip: PPO over two networks behind two memories; lg_train_symmetry.hip: PPO with symmetry tables, its own staging kernels): the
 // description of a network and of a (network, layer) segment as the kernels of lg_train.hip see them, the scalars the optimiser keeps on the
-// device, and the host calls that size the workspaces and launch those kernels.  The kernels themselves live in lg_train.hip only.
+// device, and the host calls that size the workspaces and launch those kernels.  The kernels themselves live in lg_train.hip only.  So do the bodies
+// of the entry points every trainer exports under its own prefix (train_api_*, at the end of this file).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,6 +61,11 @@ struct TrainCore {
   float *theta = nullptr, *m = nullptr, *v = nullptr, *G = nullptr, *norm_part = nullptr, *std_dev = nullptr;
   TrainScalars* sc = nullptr;
   std::vector<void*> allocs;
+  // the trainers that run groups of steps: the step losses of the last group and of the last update (train_api_group_gradients / _step_losses)
+  int64_t last_steps = 0, last_update_steps = 0;
+  float *group_loss = nullptr, *seq_loss = nullptr;
+  // the owner's own images of the masters (a memory's, a convolution's), rewritten after set_state; NULL: the core's tilings are all there is
+  int (*retile_own)(TrainCore*, hipStream_t) = nullptr;
 };
 
 // fixed-order tree over the 256 lanes of a block
@@ -89,6 +95,10 @@ void* train_alloc(TrainCore* c, size_t bytes, bool zero);
 // appends `net`: its transposed tilings, the activation / delta workspaces for c->max_rows rows, one segment per layer at offset *off of the flat
 // vector (advanced).  false + message on failure.
 bool train_core_add_net(TrainCore* c, const lg_mlp* net, int64_t* off);
+// appends one dense segment that is no layer of an lg_mlp (a memory's weight_ih / weight_hh, a linear layer of another stage): its slab partials for
+// c->max_rows rows; the owner places it in the flat vector (woff / boff) itself.  *ok goes false (+ message) on failure.
+TrainSeg& train_core_add_seg(TrainCore* c, int net, int layer_id, int dO, int dI, const float* D, const float* Ain, float* fw, float* fb, int f_nb, float* bw, int b_nb,
+                             bool* ok);
 // after the networks: c->P = off + c->nstd; masters, moments, gradient, norm partials, scalars, the device copy of the segments; uploads the masters
 // from HOST weights / biases per network in torch's layout (+ tail: the nstd trailing floats) and writes every tiling from them.
 int train_core_finish(TrainCore* c, int64_t off, const float* const* const* weights, const float* const* const* biases, const float* tail, double learning_rate);
@@ -110,9 +120,19 @@ int train_launch_norm_adam(TrainCore* c, float max_grad_norm, int clip_on, hipSt
 // the masters -> the tilings (and std_dev), without a step
 int train_core_retile(TrainCore* c, hipStream_t st);
 
-int train_core_get_state(TrainCore* c, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, hipStream_t st);
-int train_core_set_state(TrainCore* c, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, hipStream_t st);
-int train_core_set_learning_rate(TrainCore* c, double lr, hipStream_t st);
+// The whole body of the entry points every trainer exports as <prefix>_parameter_count / _workspace_bytes / _get_state / _get_parameters / _set_state /
+// _set_learning_rate: the checks with their messages, the device scope, the copies and the final synchronise.  An exported function is POLICY_ENTRY
+// and one call, so a refusal names the entry point the caller called.  c may be NULL (refused).
+int64_t train_api_parameter_count(TrainCore* c);
+int64_t train_api_workspace_bytes(TrainCore* c);
+int train_api_get_state(TrainCore* c, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, void* stream);
+int train_api_get_parameters(TrainCore* c, float* params, void* stream);
+int train_api_set_state(TrainCore* c, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, void* stream);
+int train_api_set_learning_rate(TrainCore* c, double lr, void* stream);
+// <prefix>_gradients / _step_losses of the trainers that run groups of steps: the gradient, the norm the clip used and the last group's step losses
+// (last_steps of group_loss); the first `count` of the last update's last_update_steps losses in seq_loss
+int train_api_group_gradients(TrainCore* c, float* g, float* norm, float* losses, int64_t capacity, void* stream);
+int train_api_step_losses(TrainCore* c, float* losses, int64_t count, void* stream);
 
 // PPO's clipped losses on the mini-batch rows i (rollout rows idx[i]) from the forward outputs a[L] of networks 0 and 1: dL/dmu and dL/dvalue into
 // d[L - 1], the four loss means and the gradient of std / log_std (into G at std_off), the KL-adaptive learning rate.  loss_part: the caller's

@@ -208,15 +208,10 @@ __global__ __launch_bounds__(256) void rec_index_kernel(int64_t* __restrict__ id
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host side
-struct RecLayer {
-  float *gate[4], *hin, *cin, *cnew, *hnew, *dup, *Dih, *Dhh, *dh[2], *dc[2];
-  float *wtx, *wth;
-};
-
 struct RecMem {
   lg_rnn* m = nullptr;
   int G = 0, L = 0, I = 0, H = 0;
-  RecLayer layer[RNN_MAX_LAYERS];
+  MemLayer layer[RNN_MAX_LAYERS];
 };
 
 struct lg_ppo_recurrent : TrainCore {
@@ -228,7 +223,8 @@ struct lg_ppo_recurrent : TrainCore {
   RnnRetile* d_retile = nullptr;
 };
 
-static int rec_retile(lg_ppo_recurrent* p, hipStream_t st) {
+static int rec_retile(TrainCore* c, hipStream_t st) {
+  lg_ppo_recurrent* p = static_cast<lg_ppo_recurrent*>(c);
   hipLaunchKernelGGL(rnn_retile_kernel, dim3((unsigned)((p->retile_big + 255) / 256), p->nretile), dim3(256), 0, st, (const RnnRetile*)p->d_retile, (const float*)p->theta);
   POLICY_TRY(hipGetLastError());
   return LG_OK;
@@ -262,7 +258,7 @@ static int rec_step(lg_ppo_recurrent* p, const lg_ppo_rows* r, const lg_rollout_
       RnnStepArgs* S = P.S; RnnSaveArgs* V = P.V;
       for (int k = 0; k < 2; ++k) {
         const RecMem& M = p->mem[k];
-        const RecLayer& Y = M.layer[l];
+        const MemLayer& Y = M.layer[l];
         const size_t at = (size_t)t * mb * M.H, before = t > 0 ? (size_t)(t - 1) * mb * M.H : 0;
         const size_t saved = (((size_t)t * L + l) * N + env0) * M.H;
         S[k].L = M.m->layer[l];
@@ -297,7 +293,7 @@ static int rec_step(lg_ppo_recurrent* p, const lg_ppo_rows* r, const lg_rollout_
       RnnBackArgs* B = P.B;
       for (int k = 0; k < 2; ++k) {
         const RecMem& M = p->mem[k];
-        const RecLayer& Y = M.layer[l];
+        const MemLayer& Y = M.layer[l];
         const size_t at = (size_t)t * mb * M.H;
         const int Il = l == 0 ? M.I : M.H;
         RnnBackArgs& b = B[k];
@@ -375,12 +371,11 @@ lg_ppo_recurrent* lg_ppo_recurrent_create(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* 
   DeviceScope ds_(actor->device);
   if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_ppo_recurrent* p = new lg_ppo_recurrent();
-  p->device = actor->device; p->A = actor->h.dims[actor->h.L]; p->max_rows = max_rows;
+  p->device = actor->device; p->A = actor->h.dims[actor->h.L]; p->max_rows = max_rows; p->retile_own = rec_retile;
   p->nstd = p->A; p->std_type = noise_std_type; p->std_dev = std_device;
   bool ok = true;
   auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(p, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
   const size_t R = (size_t)max_rows;
-  const int slabs_max = (int)((max_rows + WGRAD_SLAB - 1) / WGRAD_SLAB);
   int64_t off = 0;
   int first_seg[2];
   for (int k = 0; k < 2 && ok; ++k) { first_seg[k] = p->nseg; ok = train_core_add_net(p, nets[k], &off); }
@@ -393,7 +388,7 @@ lg_ppo_recurrent* lg_ppo_recurrent_create(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* 
     TrainNet& Nn = p->net[k];
     TrainSeg& S0 = p->seg[first_seg[k]];
     for (int l = 0; l < M.L; ++l) {
-      RecLayer& Y = M.layer[l];
+      MemLayer& Y = M.layer[l];
       const int I = l == 0 ? M.I : H;
       for (int g = 0; g < 4; ++g) Y.gate[g] = alloc(R * H, false);
       Y.hin = alloc(R * H, false); Y.hnew = alloc(R * H, false); Y.dup = alloc(R * H, false);
@@ -402,18 +397,9 @@ lg_ppo_recurrent* lg_ppo_recurrent_create(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* 
       for (int s = 0; s < 2; ++s) { Y.dh[s] = alloc(R * H, true); Y.dc[s] = M.G == 4 ? alloc(R * H, true) : nullptr; }
       Y.wtx = l > 0 ? alloc((size_t)((I + 15) / 16) * nbk * 256, true) : nullptr;
       Y.wth = alloc((size_t)((H + 15) / 16) * nbk * 256, true);
-      for (int s = 0; s < 2; ++s) {                      // weight_ih + bias_ih with (D_ih, x); weight_hh + bias_hh with (D_hh, h_in)
-        TrainSeg& S = p->seg[p->nseg++];
-        S.net = k; S.layer = LG_MLP_MAX_LAYERS + 2 * l + s; S.dO = K; S.dI = s == 0 ? I : H; S.f_nb = 0; S.b_nb = nbk;
-        S.D = s == 0 ? Y.Dih : Y.Dhh;
-        S.Ain = s == 0 ? (l == 0 ? nullptr : M.layer[l - 1].hnew) : Y.hin;
-        S.partial = alloc((size_t)slabs_max * S.dO * (S.dI + 1), false);
-        S.fw = nullptr; S.fb = nullptr; S.bw = s == 0 ? Y.wtx : Y.wth;
-        const int64_t cnt = (int64_t)S.dO * (S.dI + 1);
-        if (cnt > p->big) p->big = cnt;
-        const int tiles = ((S.dO + 31) / 32) * ((S.dI + 1 + 63) / 64);
-        if ((tiles + 3) / 4 > p->wgrad_blocks) p->wgrad_blocks = (tiles + 3) / 4;
-      }
+      // weight_ih + bias_ih with (D_ih, x); weight_hh + bias_hh with (D_hh, h_in)
+      train_core_add_seg(p, k, LG_MLP_MAX_LAYERS + 2 * l, K, I, Y.Dih, l == 0 ? nullptr : M.layer[l - 1].hnew, nullptr, nullptr, 0, Y.wtx, nbk, &ok);
+      train_core_add_seg(p, k, LG_MLP_MAX_LAYERS + 2 * l + 1, K, H, Y.Dhh, Y.hin, nullptr, nullptr, 0, Y.wth, nbk, &ok);
     }
     float* bw0 = alloc((size_t)Nn.bnch[0] * (Nn.bkpad[0] / 16) * 256, true);
     Nn.bw[0] = bw0; S0.bw = bw0; S0.Ain = M.layer[M.L - 1].hnew;
@@ -487,20 +473,12 @@ int lg_ppo_recurrent_update(lg_ppo_recurrent* p, const lg_ppo_rows* rows, const 
 
 int64_t lg_ppo_recurrent_parameter_count(lg_ppo_recurrent* p) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  return p->P;
+  return train_api_parameter_count(p);
 }
 
 int64_t lg_ppo_recurrent_workspace_bytes(lg_ppo_recurrent* p) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  DeviceScope ds_(p->device);
-  int64_t total = 0;
-  for (void* d : p->allocs) {
-    size_t bytes = 0;
-    if (hipMemPtrGetInfo(d, &bytes) == hipSuccess) total += (int64_t)bytes;
-  }
-  return total;
+  return train_api_workspace_bytes(p);
 }
 
 int lg_ppo_recurrent_gradients(lg_ppo_recurrent* p, float* g, float* norm, float* means, void* stream) {
@@ -530,35 +508,22 @@ int lg_ppo_recurrent_forward_outputs(lg_ppo_recurrent* p, float* mean, float* va
 
 int lg_ppo_recurrent_get_state(lg_ppo_recurrent* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  DeviceScope ds_(p->device);
-  return train_core_get_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_get_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_ppo_recurrent_get_parameters(lg_ppo_recurrent* p, float* params, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  return lg_ppo_recurrent_get_state(p, params, nullptr, nullptr, nullptr, nullptr, stream);
+  return train_api_get_parameters(p, params, stream);
 }
 
 int lg_ppo_recurrent_set_state(lg_ppo_recurrent* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params || !exp_avg || !exp_avg_sq) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (step < 0 || !(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "step < 0 or learning rate <= 0");
-  DeviceScope ds_(p->device);
-  int rc = train_core_set_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
-  if (rc == LG_OK) rc = rec_retile(p, (hipStream_t)stream);
-  if (rc != LG_OK) return rc;
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return LG_OK;
+  return train_api_set_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_ppo_recurrent_set_learning_rate(lg_ppo_recurrent* p, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  if (!(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_learning_rate(p, lr, (hipStream_t)stream);
+  return train_api_set_learning_rate(p, lr, stream);
 }
 
 int lg_ppo_recurrent_get_images(lg_ppo_recurrent* p, int32_t memory, int32_t layer, float* tiled, float* bias, void* stream) {
@@ -595,4 +560,186 @@ void rec_launch_rows_matmul_one(const RowsMatArgs& M, int64_t n, hipStream_t st)
 
 void rec_launch_retile(const RnnRetile* tab, int count, int64_t big, const float* theta, hipStream_t st) {
   hipLaunchKernelGGL(rnn_retile_kernel, dim3((unsigned)((big + 255) / 256), count), dim3(256), 0, st, tab, theta);
+}
+
+// ---- one trained memory and its carried state (lg_train_recurrent_internal.h): truncated BPTT through the launches above
+bool mem_alloc(TrainCore* c, TrainMem* M, lg_rnn* rnn) {
+  bool ok = true;
+  auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(c, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
+  M->rnn = rnn; M->device = c->device; M->max_rows = c->max_rows;
+  M->I = rnn->input; M->H = rnn->hidden; M->ML = rnn->num_layers; M->Gates = rnn->type == LG_RNN_GRU ? 3 : 4;
+  const size_t R = (size_t)c->max_rows;
+  const int H = M->H, ML = M->ML, K = M->Gates * H, nbk = (K + 15) / 16;
+  const bool lstm = M->Gates == 4;
+  M->zero_state = alloc(R * H, true);
+  M->carry_h = alloc(ML * R * H, true); M->cur_h = alloc(ML * R * H, true);
+  if (lstm) { M->carry_c = alloc(ML * R * H, true); M->cur_c = alloc(ML * R * H, true); }
+  for (int l = 0; l < ML && ok; ++l) {
+    MemLayer& Y = M->layer[l];
+    const int I = l == 0 ? M->I : H;
+    for (int g = 0; g < 4; ++g) Y.gate[g] = alloc(R * H, false);
+    Y.hin = alloc(R * H, false); Y.hnew = alloc(R * H, false); Y.dup = alloc(R * H, false);
+    Y.cin = lstm ? alloc(R * H, false) : nullptr; Y.cnew = lstm ? alloc(R * H, false) : nullptr;
+    Y.Dih = alloc(R * K, false); Y.Dhh = lstm ? Y.Dih : alloc(R * K, false);
+    for (int s = 0; s < 2; ++s) { Y.dh[s] = alloc(R * H, true); Y.dc[s] = lstm ? alloc(R * H, true) : nullptr; }
+    Y.wtx = alloc((size_t)((I + 15) / 16) * nbk * 256, true);
+    Y.wth = alloc((size_t)((H + 15) / 16) * nbk * 256, true);
+  }
+  return ok;
+}
+
+void mem_place_layer(TrainMem* M, int l, TrainSeg& Si, TrainSeg& Sh, int64_t* off) {
+  Si.woff = *off; *off += (int64_t)Si.dO * Si.dI;
+  Sh.woff = *off; *off += (int64_t)Sh.dO * Sh.dI;
+  Si.boff = *off; *off += Si.dO;
+  Sh.boff = *off; *off += Sh.dO;
+  const RnnLayerDev& D = M->rnn->layer[l];
+  RnnRetile& rt = M->retile[l];
+  rt.w = const_cast<float*>(D.w); rt.b = const_cast<float*>(D.b); rt.G = M->Gates; rt.I = D.I; rt.H = D.H; rt.Ip = D.Ip; rt.nb = D.nb; rt.nch = D.nch;
+  rt.wih = Si.woff; rt.whh = Sh.woff; rt.bih = Si.boff; rt.bhh = Sh.boff;
+  const int64_t cnt = (int64_t)D.nch * (D.nb + 1) * rt.G * 256 + 4 * 16 * D.nch;
+  if (cnt > M->retile_big) M->retile_big = cnt;
+}
+
+bool mem_upload_retile(TrainCore* c, TrainMem* M) {
+  M->d_retile = (RnnRetile*)lg_policy_upload(M->retile, sizeof(RnnRetile) * (M->ML + 1), c->allocs);
+  return M->d_retile != nullptr;
+}
+
+int mem_retile(const TrainMem* M, const float* theta, hipStream_t st) {
+  rec_launch_retile(M->d_retile, M->ML, M->retile_big, theta, st);
+  POLICY_TRY(hipGetLastError());
+  return LG_OK;
+}
+
+int mem_check_rows(const TrainMem* M, int64_t N) {
+  if (M->carry_n != 0 && M->carry_n != N) return lg_policy_fail(LG_ERR_INVALID, "N is not the carry's number of rows (reset the carry first)");
+  return LG_OK;
+}
+
+int mem_open_carry(TrainMem* M, int64_t N, hipStream_t st) {
+  if (M->carry_n == N) return LG_OK;
+  const size_t bytes = (size_t)M->ML * M->max_rows * M->H * sizeof(float);
+  POLICY_TRY(hipMemsetAsync(M->carry_h, 0, bytes, st));
+  POLICY_TRY(hipMemsetAsync(M->cur_h, 0, bytes, st));
+  if (M->carry_c) { POLICY_TRY(hipMemsetAsync(M->carry_c, 0, bytes, st)); POLICY_TRY(hipMemsetAsync(M->cur_c, 0, bytes, st)); }
+  M->carry_n = N;
+  return LG_OK;
+}
+
+// step s of the span reads a saved row (the carry or the running state), not the step before
+static bool mem_saved_entry(const MemSpan& W, int64_t s) { return s == 0 || (W.t0 + s) % W.T == 0; }
+static const float* mem_prev_dones(const TrainMem* M, const MemSpan& W, int64_t s) { return W.dones ? W.dones + ((W.t0 + s - 1) % W.T) * W.N : M->zero_state; }
+
+void mem_forward(const TrainMem* M, const MemSpan& W, const float* x0, bool x0_by_time, hipStream_t st) {
+  const int H = M->H;
+  const int64_t N = W.N;
+  const bool lstm = M->Gates == 4;
+  const size_t lstride = (size_t)M->max_rows * H;
+  for (int64_t s = 0; s < W.nsteps; ++s)
+    for (int l = 0; l < M->ML; ++l) {
+      const MemLayer& Y = M->layer[l];
+      const size_t at = (size_t)s * N * H, before = s > 0 ? (size_t)(s - 1) * N * H : 0;
+      const bool epoch = (W.t0 + s) % W.T == 0;
+      RnnStepArgs S{}; RnnSaveArgs V{};
+      S.L = M->rnn->layer[l];
+      S.x = l == 0 ? x0 + (size_t)(x0_by_time ? (W.t0 + s) % W.T : s) * N * M->I : M->layer[l - 1].hnew + at;
+      if (mem_saved_entry(W, s)) {
+        V.hs = (epoch ? M->carry_h : M->cur_h) + l * lstride; V.cs = lstm ? (epoch ? M->carry_c : M->cur_c) + l * lstride : nullptr;
+        V.hprev = nullptr; V.cprev = nullptr; V.dprev = nullptr;
+      } else {
+        V.hs = M->zero_state; V.cs = lstm ? M->zero_state : nullptr;
+        V.hprev = Y.hnew + before; V.cprev = lstm ? Y.cnew + before : nullptr; V.dprev = mem_prev_dones(M, W, s);
+      }
+      for (int g = 0; g < 4; ++g) V.gate[g] = Y.gate[g] + at;
+      V.hin = Y.hin + at; V.hnew = Y.hnew + at;
+      V.cin = lstm ? Y.cin + at : nullptr; V.cnew = lstm ? Y.cnew + at : nullptr;
+      rec_launch_forward_one(S, V, N, st);
+    }
+}
+
+void mem_top_matmul(const TrainMem* M, const TrainNet& head, int64_t n, hipStream_t st) {
+  RowsMatArgs A;
+  A.A = head.d[0]; A.K = head.dims[1]; A.nbk = head.bkpad[0] / 16; A.wt = head.bw[0]; A.nout = M->H; A.nch = (M->H + 15) / 16; A.out = M->layer[M->ML - 1].dup;
+  rec_launch_rows_matmul_one(A, n, st);
+}
+
+void mem_backward(const TrainMem* M, const MemSpan& W, float* dx0, hipStream_t st) {
+  const int H = M->H;
+  const int64_t N = W.N, nsteps = W.nsteps;
+  const bool lstm = M->Gates == 4;
+  for (int64_t s = nsteps - 1; s >= 0; --s)
+    for (int l = M->ML - 1; l >= 0; --l) {
+      const MemLayer& Y = M->layer[l];
+      const size_t at = (size_t)s * N * H;
+      const int Il = l == 0 ? M->I : H;
+      RnnBackArgs b{};
+      b.gru = lstm ? 0 : 1; b.I = Il; b.H = H; b.K = M->Gates * H; b.nbk = (b.K + 15) / 16;
+      b.dx = l > 0 ? M->layer[l - 1].dup + at : (dx0 ? dx0 + (size_t)s * N * M->I : nullptr);
+      b.nchx = b.dx ? (Il + 15) / 16 : 0; b.nchh = (H + 15) / 16;
+      b.wtx = Y.wtx; b.wth = Y.wth;
+      for (int g = 0; g < 4; ++g) b.gate[g] = Y.gate[g] + at;
+      b.hin = Y.hin + at; b.cin = lstm ? Y.cin + at : nullptr; b.cnew = lstm ? Y.cnew + at : nullptr;
+      b.dup = Y.dup + at;
+      b.dh_in = s + 1 < nsteps ? Y.dh[(s + 1) & 1] : nullptr; b.dc_in = (s + 1 < nsteps && lstm) ? Y.dc[(s + 1) & 1] : nullptr;
+      b.dprev = mem_saved_entry(W, s) ? nullptr : mem_prev_dones(M, W, s);
+      b.dh_out = Y.dh[s & 1]; b.dc_out = lstm ? Y.dc[s & 1] : nullptr;
+      b.Dih = Y.Dih + (size_t)s * N * b.K; b.Dhh = Y.Dhh + (size_t)s * N * b.K;
+      rec_launch_backward_one(b, N, st);
+    }
+}
+
+int mem_keep_running(TrainMem* M, const MemSpan& W, hipStream_t st) {
+  const size_t lstride = (size_t)M->max_rows * M->H, last = (size_t)(W.nsteps - 1) * W.N * M->H, bytes = (size_t)W.N * M->H * sizeof(float);
+  for (int l = 0; l < M->ML; ++l) {
+    POLICY_TRY(hipMemcpyAsync(M->cur_h + l * lstride, M->layer[l].hnew + last, bytes, hipMemcpyDeviceToDevice, st));
+    if (M->cur_c) POLICY_TRY(hipMemcpyAsync(M->cur_c + l * lstride, M->layer[l].cnew + last, bytes, hipMemcpyDeviceToDevice, st));
+  }
+  return LG_OK;
+}
+
+int mem_keep_carry(TrainMem* M, hipStream_t st) {
+  const size_t bytes = (size_t)M->ML * M->max_rows * M->H * sizeof(float);
+  POLICY_TRY(hipMemcpyAsync(M->carry_h, M->cur_h, bytes, hipMemcpyDeviceToDevice, st));
+  if (M->carry_c) POLICY_TRY(hipMemcpyAsync(M->carry_c, M->cur_c, bytes, hipMemcpyDeviceToDevice, st));
+  return LG_OK;
+}
+
+int64_t mem_get_carry(TrainMem* M, float* h, float* c, int64_t capacity_rows, int32_t running, hipMemcpyKind kind, void* stream) {
+  if (!M) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
+  const int64_t N = M->carry_n;
+  if (!h || N == 0 || capacity_rows < N) return N;
+  DeviceScope ds_(M->device);
+  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
+  const size_t lstride = (size_t)M->max_rows * M->H, row = (size_t)N * M->H;
+  for (int l = 0; l < M->ML; ++l) {
+    POLICY_TRY(hipMemcpy(h + l * row, (running ? M->cur_h : M->carry_h) + l * lstride, row * sizeof(float), kind));
+    if (c && M->carry_c) POLICY_TRY(hipMemcpy(c + l * row, (running ? M->cur_c : M->carry_c) + l * lstride, row * sizeof(float), kind));
+  }
+  return N;
+}
+
+int mem_set_carry(TrainMem* M, const float* h, const float* c, int64_t N, hipMemcpyKind kind, void* stream) {
+  if (!M || !h) return lg_policy_fail(LG_ERR_INVALID, "null trainer or state");
+  if (M->carry_c && !c) return lg_policy_fail(LG_ERR_INVALID, "an LSTM needs its cell state");
+  if (N < 1 || N > M->max_rows) return lg_policy_fail(LG_ERR_INVALID, "N < 1 or N > max_rows of the trainer");
+  DeviceScope ds_(M->device);
+  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
+  const size_t lstride = (size_t)M->max_rows * M->H, row = (size_t)N * M->H;
+  for (int l = 0; l < M->ML; ++l) {
+    POLICY_TRY(hipMemcpy(M->carry_h + l * lstride, h + l * row, row * sizeof(float), kind));
+    POLICY_TRY(hipMemcpy(M->cur_h + l * lstride, h + l * row, row * sizeof(float), kind));
+    if (M->carry_c) {
+      POLICY_TRY(hipMemcpy(M->carry_c + l * lstride, c + l * row, row * sizeof(float), kind));
+      POLICY_TRY(hipMemcpy(M->cur_c + l * lstride, c + l * row, row * sizeof(float), kind));
+    }
+  }
+  M->carry_n = N;
+  return LG_OK;
+}
+
+int mem_reset_carry(TrainMem* M) {
+  if (!M) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
+  M->carry_n = 0;
+  return LG_OK;
 }

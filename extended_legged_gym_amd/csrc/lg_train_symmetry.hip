@@ -447,8 +447,7 @@ int lg_ppo_sym_update(lg_ppo_sym* p, const lg_ppo_rows* rows, int64_t R, const i
 
 int64_t lg_ppo_sym_parameter_count(lg_ppo_sym* p) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  return p->P;
+  return train_api_parameter_count(p);
 }
 
 int lg_ppo_sym_gradients(lg_ppo_sym* p, float* g, float* norm, float* means, float* symmetry, void* stream) {
@@ -481,31 +480,22 @@ int lg_ppo_sym_forward_outputs(lg_ppo_sym* p, float* mean, float* values, void* 
 
 int lg_ppo_sym_get_state(lg_ppo_sym* p, float* params, float* exp_avg, float* exp_avg_sq, int64_t* step, double* lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  DeviceScope ds_(p->device);
-  return train_core_get_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_get_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_ppo_sym_get_parameters(lg_ppo_sym* p, float* params, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  return lg_ppo_sym_get_state(p, params, nullptr, nullptr, nullptr, nullptr, stream);
+  return train_api_get_parameters(p, params, stream);
 }
 
 int lg_ppo_sym_set_state(lg_ppo_sym* p, const float* params, const float* exp_avg, const float* exp_avg_sq, int64_t step, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p || !params || !exp_avg || !exp_avg_sq) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (step < 0 || !(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "step < 0 or learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_state(p, params, exp_avg, exp_avg_sq, step, lr, (hipStream_t)stream);
+  return train_api_set_state(p, params, exp_avg, exp_avg_sq, step, lr, stream);
 }
 
 int lg_ppo_sym_set_learning_rate(lg_ppo_sym* p, double lr, void* stream) {
   POLICY_ENTRY;
-  if (!p) return lg_policy_fail(LG_ERR_INVALID, "null trainer");
-  if (!(lr > 0.0)) return lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0");
-  DeviceScope ds_(p->device);
-  return train_core_set_learning_rate(p, lr, (hipStream_t)stream);
+  return train_api_set_learning_rate(p, lr, stream);
 }
 
 }  // extern "C"

@@ -9,23 +9,18 @@ import numpy as np
 import torch
 
 from extended_legged_gym_amd import abi
-from .policy import NativeStudentTeacher, _NativeHandle, _lib, _ptr
+from .policy import NativeStudentTeacher, _ptr
 from .ppo import _sequential_layers
+from .trainer import _NativeTrainer
 
 
-def _distill_lib():
-    lib = _lib()
-    if not getattr(lib, "_distill_train_declared", False):
-        abi.declare_distill_train(lib)
-        lib._distill_train_declared = True
-    return lib
-
-
-class NativeDistillation(_NativeHandle):
+class NativeDistillation(_NativeTrainer):
     """rsl_rl's `Distillation` for a feed-forward `NativeStudentTeacher`, with its names and defaults.  `state_dict`: the `StudentTeacher` state dict
     `policy` was built from (`student.*`, `teacher.*`, `std`); `student.*` seeds the fp32 master parameters.  After `update`, the same `policy`
     object acts with the new student; nothing is rebuilt."""
     _destroy = "lg_distill_train_destroy"
+    _prefix = "lg_distill_train_"
+    _declare = staticmethod(abi.declare_distill_train)
 
     def __init__(self, policy, state_dict, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse",
                  multi_gpu_cfg=None, max_rows=None):
@@ -37,16 +32,16 @@ class NativeDistillation(_NativeHandle):
             raise NotImplementedError("multi_gpu_cfg is not built in the native update")
         if not isinstance(policy, NativeStudentTeacher):
             raise TypeError("NativeDistillation trains a NativeStudentTeacher")
-        self._open(policy.device, "training")
-        self.lib = _distill_lib()
+        self._open_trainer(policy.device)
         self.policy = policy
         self.num_learning_epochs, self.gradient_length = int(num_learning_epochs), int(gradient_length)
         self.learning_rate, self.max_grad_norm, self.loss_type = float(learning_rate), max_grad_norm, loss_type
         self.max_rows = max_rows
         self._idx, self._layers = _sequential_layers(state_dict, "student")
-        self._shapes = [(f"student.{i}", w.shape) for i, (w, _) in zip(self._idx, self._layers)]
+        self._shapes = []
+        for i, (w, b) in zip(self._idx, self._layers):
+            self._shapes += [(f"student.{i}.weight", w.shape), (f"student.{i}.bias", b.shape)]
         self._rest = {k: v.detach().clone() for k, v in state_dict.items() if not k.startswith("student.")}          # teacher.*, std: never written
-        self.handle = None
         self._stats = torch.zeros(3, dtype=torch.float64, device=self.device)
         self.num_updates = 0
         self._group_steps = self._last_steps = 0          # steps of the last group / of the last update
@@ -55,26 +50,11 @@ class NativeDistillation(_NativeHandle):
             self._create(int(max_rows))
 
     # ---- handle
-    def _create(self, max_rows):
+    def _make_handle(self, max_rows):
         fp = C.POINTER(C.c_float)
         ws = (fp * len(self._layers))(*[w.ctypes.data_as(fp) for w, _ in self._layers])
         bs = (fp * len(self._layers))(*[b.ctypes.data_as(fp) for _, b in self._layers])
-        state = self.optimizer_state() if self.handle else None
-        self.close()
-        torch.cuda.synchronize(self.device)
-        self._created(self.lib.lg_distill_train_create(self.policy.student.handle, ws, bs, self.learning_rate, max_rows), "lg_distill_train_create")
-        self.max_rows = max_rows
-        self.num_parameters = int(self.lib.lg_distill_train_parameter_count(self.handle))
-        if state is not None:
-            self.load_optimizer_state(state)
-
-    def _ensure(self, rows):
-        if self.handle is None or rows > self.max_rows:
-            self._create(rows)
-
-    def _need_handle(self):
-        if self.handle is None:
-            self._create(1)
+        return self._fn("create")(self.policy.student.handle, ws, bs, self.learning_rate, max_rows)
 
     def _hyper(self):
         return abi.lg_distill_train_hyper(abi.DISTILL_LOSSES[self.loss_type], float(self.max_grad_norm) if self.max_grad_norm else 0.0)
@@ -92,8 +72,7 @@ class NativeDistillation(_NativeHandle):
         obs, tgt, T, N = self._rows(rows)
         self._ensure(max(int(num_steps), 1) * N)
         hyper = self._hyper()
-        self._check(self.lib.lg_distill_train_group(self.handle, _ptr(obs), _ptr(tgt), T, N, int(first_step), int(num_steps), C.byref(hyper), self._stream()),
-                    "lg_distill_train_group")
+        self._call("group", _ptr(obs), _ptr(tgt), T, N, int(first_step), int(num_steps), C.byref(hyper))
         self._group_steps = int(num_steps)
 
     def update(self, rows):
@@ -103,8 +82,7 @@ class NativeDistillation(_NativeHandle):
         obs, tgt, T, N = self._rows(rows)
         self._ensure(self.gradient_length * N)
         hyper = self._hyper()
-        self._check(self.lib.lg_distill_train_update(self.handle, _ptr(obs), _ptr(tgt), T, N, self.num_learning_epochs, self.gradient_length, C.byref(hyper),
-                                                     _ptr(self._stats), self._stream()), "lg_distill_train_update")
+        self._call("update", _ptr(obs), _ptr(tgt), T, N, self.num_learning_epochs, self.gradient_length, C.byref(hyper), _ptr(self._stats))
         st = self._stats.cpu().tolist()
         self._last_steps = self.num_learning_epochs * T
         if self._last_steps >= self.gradient_length:
@@ -112,79 +90,23 @@ class NativeDistillation(_NativeHandle):
         self.optimizer_steps, self.grad_norm = int(st[1]), st[2]
         return {"behavior": st[0]}
 
-    def set_learning_rate(self, learning_rate):
-        self.learning_rate = float(learning_rate)
-        if self.handle:
-            self._check(self.lib.lg_distill_train_set_learning_rate(self.handle, self.learning_rate, self._stream()), "lg_distill_train_set_learning_rate")
-
-    # ---- what the device holds
-    def _split(self, flat):
-        out, off = {}, 0
-        for name, (o, i) in self._shapes:
-            out[name + ".weight"] = torch.from_numpy(flat[off:off + o * i].reshape(o, i).copy()); off += o * i
-            out[name + ".bias"] = torch.from_numpy(flat[off:off + o].copy()); off += o
-        return out
-
-    def _join(self, tensors):
-        parts = []
-        for name, _ in self._shapes:
-            parts += [tensors[name + ".weight"].detach().cpu().numpy().reshape(-1), tensors[name + ".bias"].detach().cpu().numpy().reshape(-1)]
-        flat = np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
-        assert flat.size == self.num_parameters
-        return flat
-
+    # ---- what the device holds (the checkpoint methods are `_NativeTrainer`'s; `state_dict()` is a `StudentTeacher` state dict: `student.*` as
+    # trained, `teacher.*` and `std` as given)
     def gradients(self):
         """The last group's gradients before the clip (dict in the state dict's names), the global norm, and its per-step losses."""
         self._need_handle()
         g, norm, losses = np.empty(self.num_parameters, np.float32), C.c_float(), np.empty(self._group_steps, np.float32)
-        self._check(self.lib.lg_distill_train_gradients(self.handle, g.ctypes.data, C.addressof(norm), losses.ctypes.data, losses.size, self._stream()),
-                    "lg_distill_train_gradients")
+        self._call("gradients", g.ctypes.data, C.addressof(norm), losses.ctypes.data, losses.size)
         return self._split(g), norm.value, [float(x) for x in losses]
 
     def forward_outputs(self, rows):
         """The student's outputs (rows, A) of the last group's forward pass, step-major."""
         self._need_handle()
         out = np.empty((rows, self.policy.num_actions), np.float32)
-        self._check(self.lib.lg_distill_train_forward_outputs(self.handle, out.ctypes.data, self._stream()), "lg_distill_train_forward_outputs")
+        self._call("forward_outputs", out.ctypes.data)
         return torch.from_numpy(out)
-
-    def step_losses(self):
-        """The E * T fp32 step losses of the last `update`."""
-        self._need_handle()
-        out = np.empty(self._last_steps, np.float32)
-        self._check(self.lib.lg_distill_train_step_losses(self.handle, out.ctypes.data, out.size, self._stream()), "lg_distill_train_step_losses")
-        return torch.from_numpy(out)
-
-    def state_dict(self):
-        """A `StudentTeacher` state dict: `student.*` as trained, `teacher.*` and `std` as given."""
-        self._need_handle()
-        flat = np.empty(self.num_parameters, np.float32)
-        self._check(self.lib.lg_distill_train_get_parameters(self.handle, flat.ctypes.data, self._stream()), "lg_distill_train_get_parameters")
-        return {**self._split(flat), **{k: v.clone() for k, v in self._rest.items()}}
-
-    def optimizer_state(self):
-        """Masters, both Adam moments, the step count and the learning rate."""
-        self._need_handle()
-        bufs = [np.empty(self.num_parameters, np.float32) for _ in range(3)]
-        step, lr = C.c_int64(), C.c_double()
-        self._check(self.lib.lg_distill_train_get_state(self.handle, *[b.ctypes.data for b in bufs], C.byref(step), C.byref(lr), self._stream()),
-                    "lg_distill_train_get_state")
-        return dict(parameters=self._split(bufs[0]), exp_avg=self._split(bufs[1]), exp_avg_sq=self._split(bufs[2]), step=step.value, learning_rate=lr.value)
-
-    def load_optimizer_state(self, state):
-        self._need_handle()
-        bufs = [self._join(state[k]) for k in ("parameters", "exp_avg", "exp_avg_sq")]
-        self._check(self.lib.lg_distill_train_set_state(self.handle, *[b.ctypes.data for b in bufs], int(state["step"]), float(state["learning_rate"]),
-                                                        self._stream()), "lg_distill_train_set_state")
-        self.learning_rate = float(state["learning_rate"])
 
     def load_teacher(self, state_dict):
         """Swaps the teacher (`policy.load_teacher`: `actor.*` of a PPO checkpoint or `teacher.*`) in the policy's image and in the `teacher.*`
         entries `state_dict()` returns; nothing that is trained moves."""
         self._rest.update(self.policy.load_teacher(state_dict))
-
-    def load_state_dict(self, state_dict):
-        """New student parameters (`student.*` of a `StudentTeacher` state dict); the moments, the step count and the learning rate stay."""
-        state = self.optimizer_state()
-        state["parameters"] = state_dict
-        self.load_optimizer_state(state)

@@ -10,27 +10,23 @@ import numpy as np
 import torch
 
 from extended_legged_gym_amd import abi
-from .policy import NativeStudentTeacherRecurrent, _NativeHandle, _lib, _ptr
+from .policy import NativeStudentTeacherRecurrent, _ptr
 from .ppo import _sequential_layers
+from .trainer import _NativeTrainer
 
 _MEMORY_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
 
-def _distill_rtrain_lib():
-    lib = _lib()
-    if not getattr(lib, "_distill_rtrain_declared", False):
-        abi.declare_distill_rtrain(lib)
-        lib._distill_rtrain_declared = True
-    return lib
-
-
-class NativeRecurrentDistillation(_NativeHandle):
+class NativeRecurrentDistillation(_NativeTrainer):
     """rsl_rl's `Distillation` for a `NativeStudentTeacherRecurrent`, with its names and defaults.  `state_dict`: the `StudentTeacherRecurrent`
     state dict `policy`'s student was built from (`student.*`, `memory_s.rnn.*`, and whatever else it holds); `student.*` and `memory_s.*` seed the
     fp32 master parameters.  After `update`, the same `policy` object acts with the new student and memory; nothing is rebuilt.  As the reference
     replays through the policy's own modules, `update` leaves the end state of the replay as the student memory's live state (it is also the state
     the next update's epochs start from) and forgets the teacher memory's."""
     _destroy = "lg_distill_rtrain_destroy"
+    _prefix = "lg_distill_rtrain_"
+    _declare = staticmethod(abi.declare_distill_rtrain)
+    _carry_on_device = True          # the carry calls take device tensors: the state never visits the host
 
     def __init__(self, policy, state_dict, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse",
                  multi_gpu_cfg=None, max_rows=None):
@@ -40,14 +36,14 @@ class NativeRecurrentDistillation(_NativeHandle):
             raise NotImplementedError("multi_gpu_cfg is not built in the native update")
         if not isinstance(policy, NativeStudentTeacherRecurrent):
             raise TypeError("NativeRecurrentDistillation trains a NativeStudentTeacherRecurrent")
-        self._open(policy.device, "training")
-        self.lib = _distill_rtrain_lib()
+        self._open_trainer(policy.device)
         self.policy = policy
         self.num_learning_epochs, self.gradient_length = int(num_learning_epochs), int(gradient_length)
         self.learning_rate, self.max_grad_norm, self.loss_type = float(learning_rate), max_grad_norm, loss_type
         self.max_rows = max_rows
         mem = policy.memory_s
-        self._L, self._H, self._lstm = mem.num_layers, mem.hidden_size, mem.rnn_type == "lstm"
+        self._L = mem.num_layers
+        self._carry = (mem.num_layers, mem.hidden_size, mem.rnn_type == "lstm")
         self._idx, self._layers = _sequential_layers(state_dict, "student")
         self._memory = [[np.ascontiguousarray(state_dict[f"memory_s.rnn.{name}_l{l}"].detach().cpu().numpy(), dtype=np.float32) for name in _MEMORY_NAMES]
                         for l in range(self._L)]
@@ -59,7 +55,6 @@ class NativeRecurrentDistillation(_NativeHandle):
             self._shapes += [(f"memory_s.rnn.{name}_l{l}", a.shape) for name, a in zip(_MEMORY_NAMES, self._memory[l])]
         trained = {name for name, _ in self._shapes}
         self._rest = {k: v.detach().clone() for k, v in state_dict.items() if k not in trained}          # teacher.*, memory_t.*, std: never written
-        self.handle = None
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self.num_updates = 0
         self._group_steps = self._last_steps = self._last_rows = 0
@@ -68,7 +63,7 @@ class NativeRecurrentDistillation(_NativeHandle):
             self._create(int(max_rows))
 
     # ---- handle
-    def _create(self, max_rows):
+    def _make_handle(self, max_rows):
         fp = C.POINTER(C.c_float)
 
         def plist(arrays):
@@ -76,26 +71,7 @@ class NativeRecurrentDistillation(_NativeHandle):
 
         q = abi.lg_distill_rtrain_params(plist([w for w, _ in self._layers]), plist([b for _, b in self._layers]),
                                          *[plist([m[j] for m in self._memory]) for j in range(4)])
-        state = self.optimizer_state() if self.handle else None
-        carry = self.get_hidden_states() if self.handle else None
-        self.close()
-        torch.cuda.synchronize(self.device)
-        self._created(self.lib.lg_distill_rtrain_create(self.policy.memory_s.handle, self.policy.student.handle, C.byref(q), self.learning_rate, max_rows),
-                      "lg_distill_rtrain_create")
-        self.max_rows = max_rows
-        self.num_parameters = int(self.lib.lg_distill_rtrain_parameter_count(self.handle))
-        if state is not None:
-            self.load_optimizer_state(state)
-        if carry is not None:
-            self.set_hidden_states(carry)
-
-    def _ensure(self, rows):
-        if self.handle is None or rows > self.max_rows:
-            self._create(rows)
-
-    def _need_handle(self):
-        if self.handle is None:
-            self._create(1)
+        return self._fn("create")(self.policy.memory_s.handle, self.policy.student.handle, C.byref(q), self.learning_rate, max_rows)
 
     def _hyper(self):
         return abi.lg_distill_train_hyper(abi.DISTILL_LOSSES[self.loss_type], float(self.max_grad_norm) if self.max_grad_norm else 0.0)
@@ -118,8 +94,7 @@ class NativeRecurrentDistillation(_NativeHandle):
         obs, tgt, dones, T, N = self._rows(rows)
         self._ensure(max(int(num_steps), 1) * N)
         hyper = self._hyper()
-        self._check(self.lib.lg_distill_rtrain_group(self.handle, _ptr(obs), _ptr(tgt), _ptr(dones), T, N, int(first_step), int(num_steps), 1 if train else 0,
-                                                     C.byref(hyper), self._stream()), "lg_distill_rtrain_group")
+        self._call("group", _ptr(obs), _ptr(tgt), _ptr(dones), T, N, int(first_step), int(num_steps), 1 if train else 0, C.byref(hyper))
         self._group_steps, self._last_rows = int(num_steps), int(num_steps) * N
 
     def update(self, rows):
@@ -131,8 +106,7 @@ class NativeRecurrentDistillation(_NativeHandle):
         obs, tgt, dones, T, N = self._rows(rows)
         self._ensure(self.gradient_length * N)
         hyper = self._hyper()
-        self._check(self.lib.lg_distill_rtrain_update(self.handle, _ptr(obs), _ptr(tgt), _ptr(dones), T, N, self.num_learning_epochs, self.gradient_length,
-                                                      C.byref(hyper), _ptr(self._stats), self._stream()), "lg_distill_rtrain_update")
+        self._call("update", _ptr(obs), _ptr(tgt), _ptr(dones), T, N, self.num_learning_epochs, self.gradient_length, C.byref(hyper), _ptr(self._stats))
         st = self._stats.cpu().tolist()
         self._last_steps = self.num_learning_epochs * T
         rem = self._last_steps % self.gradient_length
@@ -144,112 +118,24 @@ class NativeRecurrentDistillation(_NativeHandle):
         self.policy.reset(hidden_states=(self.get_hidden_states(), None))
         return {"behavior": st[0]}
 
-    def set_learning_rate(self, learning_rate):
-        self.learning_rate = float(learning_rate)
-        if self.handle:
-            self._check(self.lib.lg_distill_rtrain_set_learning_rate(self.handle, self.learning_rate, self._stream()), "lg_distill_rtrain_set_learning_rate")
-
-    def workspace_bytes(self):
-        self._need_handle()
-        return int(self.lib.lg_distill_rtrain_workspace_bytes(self.handle))
-
-    # ---- the carried state
-    def get_hidden_states(self, running=False):
-        """The state the next update's epochs start from (`last_hidden_states`): `h` (L, N, H) for a GRU, `(h, c)` for an LSTM, None before the
-        first update.  `running=True`: the state after the last step run instead (what a loop of `group` calls hands to `set_hidden_states`).
-        The copy stays on the device."""
-        if self.handle is None:
-            return None
-        N = int(self.lib.lg_distill_rtrain_get_carry(self.handle, None, None, 0, 0, self._stream()))
-        if N <= 0:
-            return None
-        h = torch.empty(self._L, N, self._H, device=self.device)
-        c = torch.empty_like(h) if self._lstm else None
-        got = self.lib.lg_distill_rtrain_get_carry(self.handle, _ptr(h), _ptr(c), N, 1 if running else 0, self._stream())
-        if got != N:
-            self._check(int(got), "lg_distill_rtrain_get_carry")
-        return (h, c) if self._lstm else h
-
-    def set_hidden_states(self, hidden_states):
-        """Installs the carried state (None: forgets it; the next update starts from zeros, with any number of rows)."""
-        self._need_handle()
-        if hidden_states is None:
-            self._check(self.lib.lg_distill_rtrain_reset_carry(self.handle, self._stream()), "lg_distill_rtrain_reset_carry")
-            return
-        parts = hidden_states if isinstance(hidden_states, (tuple, list)) else (hidden_states,)
-        parts = [p.detach().to(device=self.device, dtype=torch.float32).contiguous() for p in parts]
-        N = parts[0].shape[1]
-        assert all(tuple(p.shape) == (self._L, N, self._H) for p in parts) and len(parts) == (2 if self._lstm else 1)
-        self._ensure(N)
-        self._check(self.lib.lg_distill_rtrain_set_carry(self.handle, _ptr(parts[0]), _ptr(parts[1]) if self._lstm else None, N, self._stream()),
-                    "lg_distill_rtrain_set_carry")
-
-    # ---- what the device holds
-    def _split(self, flat):
-        out, off = {}, 0
-        for name, shape in self._shapes:
-            cnt = int(np.prod(shape))
-            out[name] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy()); off += cnt
-        return out
-
-    def _join(self, tensors):
-        flat = np.ascontiguousarray(np.concatenate([tensors[name].detach().cpu().numpy().reshape(-1) for name, _ in self._shapes]), dtype=np.float32)
-        assert flat.size == self.num_parameters
-        return flat
-
+    # ---- what the device holds (the checkpoint and carry methods are `_NativeTrainer`'s; `state_dict()` is a `StudentTeacherRecurrent` state dict:
+    # `student.*` and `memory_s.*` as trained, everything else as given; the carried state stays on the device)
     def gradients(self):
         """The last group's gradients before the clip (dict in the state dict's names), the two norms (over `student.*`, over `memory_s.*`), and
         its per-step losses."""
         self._need_handle()
         g, norms, losses = np.empty(self.num_parameters, np.float32), np.zeros(2, np.float32), np.empty(self._group_steps, np.float32)
-        self._check(self.lib.lg_distill_rtrain_gradients(self.handle, g.ctypes.data, norms.ctypes.data, losses.ctypes.data, losses.size, self._stream()),
-                    "lg_distill_rtrain_gradients")
+        self._call("gradients", g.ctypes.data, norms.ctypes.data, losses.ctypes.data, losses.size)
         return self._split(g), (float(norms[0]), float(norms[1])), [float(x) for x in losses]
 
     def forward_outputs(self):
         """The student's outputs (rows, A) of the last group's (or remainder's) forward pass, step-major."""
         self._need_handle()
         out = np.empty((self._last_rows, self.policy.num_actions), np.float32)
-        self._check(self.lib.lg_distill_rtrain_forward_outputs(self.handle, out.ctypes.data, self._stream()), "lg_distill_rtrain_forward_outputs")
+        self._call("forward_outputs", out.ctypes.data)
         return torch.from_numpy(out)
-
-    def step_losses(self):
-        """The E * T fp32 step losses of the last `update`."""
-        self._need_handle()
-        out = np.empty(self._last_steps, np.float32)
-        self._check(self.lib.lg_distill_rtrain_step_losses(self.handle, out.ctypes.data, out.size, self._stream()), "lg_distill_rtrain_step_losses")
-        return torch.from_numpy(out)
-
-    def state_dict(self):
-        """A `StudentTeacherRecurrent` state dict: `student.*` and `memory_s.*` as trained, everything else as given."""
-        self._need_handle()
-        flat = np.empty(self.num_parameters, np.float32)
-        self._check(self.lib.lg_distill_rtrain_get_parameters(self.handle, flat.ctypes.data, self._stream()), "lg_distill_rtrain_get_parameters")
-        return {**self._split(flat), **{k: v.clone() for k, v in self._rest.items()}}
-
-    def optimizer_state(self):
-        """Masters, both Adam moments, the step count and the learning rate."""
-        self._need_handle()
-        bufs = [np.empty(self.num_parameters, np.float32) for _ in range(3)]
-        step, lr = C.c_int64(), C.c_double()
-        self._check(self.lib.lg_distill_rtrain_get_state(self.handle, *[b.ctypes.data for b in bufs], C.byref(step), C.byref(lr), self._stream()),
-                    "lg_distill_rtrain_get_state")
-        return dict(parameters=self._split(bufs[0]), exp_avg=self._split(bufs[1]), exp_avg_sq=self._split(bufs[2]), step=step.value, learning_rate=lr.value)
-
-    def load_optimizer_state(self, state):
-        self._need_handle()
-        bufs = [self._join(state[k]) for k in ("parameters", "exp_avg", "exp_avg_sq")]
-        self._check(self.lib.lg_distill_rtrain_set_state(self.handle, *[b.ctypes.data for b in bufs], int(state["step"]), float(state["learning_rate"]),
-                                                         self._stream()), "lg_distill_rtrain_set_state")
-        self.learning_rate = float(state["learning_rate"])
 
     def load_teacher(self, state_dict):
         """Swaps the teacher (`policy.load_teacher`: `actor.*` of a PPO checkpoint or `teacher.*`) in the policy's image and in the `teacher.*`
         entries `state_dict()` returns; nothing that is trained moves."""
         self._rest.update(self.policy.load_teacher(state_dict))
-
-    def load_state_dict(self, state_dict):
-        """New parameters (`student.*`, `memory_s.*` of a `StudentTeacherRecurrent` state dict); the moments, the step count and the learning rate stay."""
-        state = self.optimizer_state()
-        state["parameters"] = state_dict
-        self.load_optimizer_state(state)

@@ -358,7 +358,7 @@ class NativeDistillationRunner(RunnerLogging):
         if rule["student"]:
             policy = self.alg.policy
             policy.std.copy_(model["std"].to(policy.std.device, torch.float32))
-            self.alg._rest["std"] = model["std"].detach().clone()
+            self.alg.set_untrained("std", model["std"])
             if load_optimizer and rule["optimizer"] and "optimizer_state_dict" in loaded:
                 self.alg.load_optimizer_state(native_distillation_optimizer_state(model, loaded["optimizer_state_dict"]))
             else:

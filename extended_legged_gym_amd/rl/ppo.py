@@ -8,15 +8,12 @@ import numpy as np
 import torch
 
 from extended_legged_gym_amd import abi
-from .policy import NativeActorCritic, _NativeHandle, _lib, _ptr
+from .policy import NativeActorCritic, _ptr
+from .trainer import _NativeTrainer, _declared
 
 
 def _train_lib():
-    lib = _lib()
-    if not getattr(lib, "_train_declared", False):
-        abi.declare_train(lib)
-        lib._train_declared = True
-    return lib
+    return _declared(abi.declare_train)
 
 
 def _sequential_layers(state_dict, prefix):
@@ -25,15 +22,13 @@ def _sequential_layers(state_dict, prefix):
                   np.ascontiguousarray(state_dict[f"{prefix}.{i}.bias"].detach().cpu().numpy(), dtype=np.float32)) for i in idx]
 
 
-class NativePPO(_NativeHandle):
+class NativePPO(_NativeTrainer):
     """rsl_rl's `PPO` for a feed-forward `NativeActorCritic`, with its names and defaults.  `state_dict`: the `ActorCritic` state dict `policy` was
     built from (`actor.*`, `critic.*`, `std` / `log_std`); it seeds the fp32 master parameters.  After `update`, the same `policy` object acts with
     the new weights; nothing is rebuilt."""
     _destroy = "lg_ppo_destroy"
-    _prefix = "lg_ppo_"          # the entry points of include/lgtrain.h; `NativeRecurrentPPO` shares the checkpoint and inspection methods
-
-    def _fn(self, name):
-        return getattr(self.lib, self._prefix + name)
+    _prefix = "lg_ppo_"          # the entry points of include/lgtrain.h
+    _declare = staticmethod(abi.declare_train)
 
     def __init__(self, policy, state_dict, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, schedule="fixed", desired_kl=0.01, max_grad_norm=1.0, use_clipped_value_loss=True, max_rows=None,
@@ -49,8 +44,7 @@ class NativePPO(_NativeHandle):
                 raise NotImplementedError(f"{name} is not built in the native update{hint}")
         if schedule not in abi.LR_SCHEDULES:
             raise ValueError(f"Unknown schedule: {schedule}. Should be 'fixed' or 'adaptive'")
-        self._open(policy.device, "training")
-        self.lib = _train_lib()
+        self._open_trainer(policy.device)
         self.policy = policy
         self.num_learning_epochs, self.num_mini_batches = int(num_learning_epochs), int(num_mini_batches)
         self.clip_param, self.value_loss_coef, self.entropy_coef = float(clip_param), float(value_loss_coef), float(entropy_coef)
@@ -62,35 +56,25 @@ class NativePPO(_NativeHandle):
         self._aidx, self._alayers = _sequential_layers(state_dict, "actor")
         self._cidx, self._clayers = _sequential_layers(state_dict, "critic")
         self._std0 = np.ascontiguousarray(state_dict[self.std_key].detach().cpu().numpy(), dtype=np.float32)
-        self._shapes = ([(f"actor.{i}", w.shape) for i, (w, _) in zip(self._aidx, self._alayers)] +
-                        [(f"critic.{i}", w.shape) for i, (w, _) in zip(self._cidx, self._clayers)])
-        self.handle = None
+        self._shapes = []
+        for prefix, idx, layers in (("actor", self._aidx, self._alayers), ("critic", self._cidx, self._clayers)):
+            for i, (w, b) in zip(idx, layers):
+                self._shapes += [(f"{prefix}.{i}.weight", w.shape), (f"{prefix}.{i}.bias", b.shape)]
+        self._shapes.append((self.std_key, self._std0.shape))
         self._stats = torch.zeros(5, dtype=torch.float64, device=self.device)
         if max_rows is not None:
             self._create(int(max_rows))
 
     # ---- handle
-    def _create(self, max_rows):
+    def _make_handle(self, max_rows):
         fp = C.POINTER(C.c_float)
 
         def lists(layers):
             return ((fp * len(layers))(*[w.ctypes.data_as(fp) for w, _ in layers]), (fp * len(layers))(*[b.ctypes.data_as(fp) for _, b in layers]))
         aw, ab = lists(self._alayers)
         cw, cb = lists(self._clayers)
-        state = self.optimizer_state() if self.handle else None
-        self.close()
-        torch.cuda.synchronize(self.device)
-        self._created(self._fn("create")(self.policy.actor.handle, self.policy.critic.handle, aw, ab, cw, cb, self._std0.ctypes.data,
-                                        abi.NOISE_STD_TYPES[self.policy.noise_std_type], self.learning_rate, max_rows, _ptr(self.policy.std)),
-                      self._prefix + "create")
-        self.max_rows = max_rows
-        self.num_parameters = int(self._fn("parameter_count")(self.handle))
-        if state is not None:
-            self.load_optimizer_state(state)
-
-    def _ensure(self, rows):
-        if self.handle is None or rows > self.max_rows:
-            self._create(rows)
+        return self._fn("create")(self.policy.actor.handle, self.policy.critic.handle, aw, ab, cw, cb, self._std0.ctypes.data,
+                                  abi.NOISE_STD_TYPES[self.policy.noise_std_type], self.learning_rate, max_rows, _ptr(self.policy.std))
 
     def _hyper(self):
         return abi.lg_ppo_hyper(self.clip_param, self.value_loss_coef, self.entropy_coef, int(self.use_clipped_value_loss), self.max_grad_norm,
@@ -117,7 +101,7 @@ class NativePPO(_NativeHandle):
         idx = indices.to(device=self.device, dtype=torch.int64).contiguous()
         self._ensure(idx.numel())
         hyper = self._hyper()
-        self._check(self._fn("minibatch")(self.handle, C.byref(rows), _ptr(idx), idx.numel(), C.byref(hyper), self._stream()), self._prefix + "minibatch")
+        self._call("minibatch", C.byref(rows), _ptr(idx), idx.numel(), C.byref(hyper))
         del keep
 
     def update(self, rollout, indices=None):
@@ -131,80 +115,24 @@ class NativePPO(_NativeHandle):
         assert idx.numel() >= (R // self.num_mini_batches) * self.num_mini_batches
         self._ensure(max(R // self.num_mini_batches, 1))
         hyper = self._hyper()
-        self._check(self._fn("update")(self.handle, C.byref(rows), R, _ptr(idx), self.num_mini_batches, self.num_learning_epochs, C.byref(hyper),
-                                       _ptr(self._stats), self._stream()), self._prefix + "update")
+        self._call("update", C.byref(rows), R, _ptr(idx), self.num_mini_batches, self.num_learning_epochs, C.byref(hyper), _ptr(self._stats))
         st = self._stats.cpu().tolist()
         del keep
         self.learning_rate, self.kl, self._last_stats = st[4], st[3], st
         return {"value_function": st[0], "surrogate": st[1], "entropy": st[2]}
 
-    def set_learning_rate(self, learning_rate):
-        self.learning_rate = float(learning_rate)
-        if self.handle:
-            self._check(self._fn("set_learning_rate")(self.handle, self.learning_rate, self._stream()), self._prefix + "set_learning_rate")
-
-    # ---- what the device holds
-    def _need_handle(self):
-        if self.handle is None:
-            self._create(1)
-
-    def _split(self, flat):
-        """A flat parameter-shaped vector -> dict in the state dict's names."""
-        out, off = {}, 0
-        for name, (o, i) in self._shapes:
-            out[name + ".weight"] = torch.from_numpy(flat[off:off + o * i].reshape(o, i).copy()); off += o * i
-            out[name + ".bias"] = torch.from_numpy(flat[off:off + o].copy()); off += o
-        out[self.std_key] = torch.from_numpy(flat[off:].copy())
-        return out
-
-    def _join(self, tensors):
-        parts = []
-        for name, _ in self._shapes:
-            parts += [tensors[name + ".weight"].detach().cpu().numpy().reshape(-1), tensors[name + ".bias"].detach().cpu().numpy().reshape(-1)]
-        parts.append(tensors[self.std_key].detach().cpu().numpy().reshape(-1))
-        flat = np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
-        assert flat.size == self.num_parameters
-        return flat
-
+    # ---- what the device holds (the checkpoint methods are `_NativeTrainer`'s; `state_dict()` is an `ActorCritic` state dict)
     def gradients(self):
         """The gradients of the last mini-batch before the norm clip (dict in the state dict's names), the global norm, and the four loss means
         (surrogate, value_function, entropy, kl)."""
         self._need_handle()
         g, norm, means = np.empty(self.num_parameters, np.float32), C.c_float(), (C.c_float * 4)()
-        self._check(self._fn("gradients")(self.handle, g.ctypes.data, C.byref(norm), means, self._stream()), self._prefix + "gradients")
+        self._call("gradients", g.ctypes.data, C.byref(norm), means)
         return self._split(g), norm.value, dict(zip(("surrogate", "value_function", "entropy", "kl"), [float(x) for x in means]))
 
     def forward_outputs(self, count):
         """The action means (count, A) and values (count, 1) the last mini-batch's forward pass computed, in mini-batch order."""
         self._need_handle()
         mu, val = np.empty((count, self.policy.num_actions), np.float32), np.empty((count, 1), np.float32)
-        self._check(self._fn("forward_outputs")(self.handle, mu.ctypes.data, val.ctypes.data, self._stream()), self._prefix + "forward_outputs")
+        self._call("forward_outputs", mu.ctypes.data, val.ctypes.data)
         return torch.from_numpy(mu), torch.from_numpy(val)
-
-    def state_dict(self):
-        """An `ActorCritic` state dict (`actor.*`, `critic.*`, `std` / `log_std`): rsl_rl and `NativeActorCritic(...)` both load it."""
-        self._need_handle()
-        flat = np.empty(self.num_parameters, np.float32)
-        self._check(self._fn("get_parameters")(self.handle, flat.ctypes.data, self._stream()), self._prefix + "get_parameters")
-        return self._split(flat)
-
-    def optimizer_state(self):
-        """Masters, both Adam moments, the step count and the learning rate."""
-        self._need_handle()
-        bufs = [np.empty(self.num_parameters, np.float32) for _ in range(3)]
-        step, lr = C.c_int64(), C.c_double()
-        self._check(self._fn("get_state")(self.handle, *[b.ctypes.data for b in bufs], C.byref(step), C.byref(lr), self._stream()), self._prefix + "get_state")
-        return dict(parameters=self._split(bufs[0]), exp_avg=self._split(bufs[1]), exp_avg_sq=self._split(bufs[2]), step=step.value, learning_rate=lr.value)
-
-    def load_optimizer_state(self, state):
-        self._need_handle()
-        bufs = [self._join(state[k]) for k in ("parameters", "exp_avg", "exp_avg_sq")]
-        self._check(self._fn("set_state")(self.handle, *[b.ctypes.data for b in bufs], int(state["step"]), float(state["learning_rate"]), self._stream()),
-                    self._prefix + "set_state")
-        self.learning_rate = float(state["learning_rate"])
-
-    def load_state_dict(self, state_dict):
-        """New parameters (an `ActorCritic` state dict); the moments, the step count and the learning rate stay."""
-        state = self.optimizer_state()
-        state["parameters"] = state_dict
-        self.load_optimizer_state(state)

@@ -9,18 +9,10 @@ import numpy as np
 import torch
 
 from extended_legged_gym_amd import abi
-from .policy import NativeActorCriticRecurrent, _lib, _ptr
+from .policy import NativeActorCriticRecurrent, _ptr
 from .ppo import NativePPO, _sequential_layers
 
 RNN_TENSORS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
-
-
-def _train_recurrent_lib():
-    lib = _lib()
-    if not getattr(lib, "_train_recurrent_declared", False):
-        abi.declare_train_recurrent(lib)
-        lib._train_recurrent_declared = True
-    return lib
 
 
 class NativeRecurrentPPO(NativePPO):
@@ -29,6 +21,7 @@ class NativeRecurrentPPO(NativePPO):
     the fp32 masters.  After `update`, the same `policy` object acts with the new weights; nothing is rebuilt."""
     _destroy = "lg_ppo_recurrent_destroy"
     _prefix = "lg_ppo_recurrent_"
+    _declare = staticmethod(abi.declare_train_recurrent)
 
     def __init__(self, policy, state_dict, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, schedule="fixed", desired_kl=0.01, max_grad_norm=1.0, use_clipped_value_loss=True, max_rows=None,
@@ -41,8 +34,7 @@ class NativeRecurrentPPO(NativePPO):
                 raise NotImplementedError(f"{name} is not built in the native update")
         if schedule not in abi.LR_SCHEDULES:
             raise ValueError(f"Unknown schedule: {schedule}. Should be 'fixed' or 'adaptive'")
-        self._open(policy.device, "training")
-        self.lib = _train_recurrent_lib()
+        self._open_trainer(policy.device)
         self.policy = policy
         self.num_learning_epochs, self.num_mini_batches = int(num_learning_epochs), int(num_mini_batches)
         self.clip_param, self.value_loss_coef, self.entropy_coef = float(clip_param), float(value_loss_coef), float(entropy_coef)
@@ -65,21 +57,20 @@ class NativeRecurrentPPO(NativePPO):
                                  f"({mem.num_layers} layers, {mem.input_size} -> {mem.hidden_size})")
             self._mem[prefix] = arrs
         # the flat order of include/lgtrain_recurrent.h: actor, critic, memory_a, memory_c (per layer weight_ih, weight_hh, bias_ih, bias_hh), std
-        self._tensors = []
+        self._shapes = []
         for prefix, idx, layers in (("actor", self._aidx, self._alayers), ("critic", self._cidx, self._clayers)):
             for i, (w, b) in zip(idx, layers):
-                self._tensors += [(f"{prefix}.{i}.weight", w.shape), (f"{prefix}.{i}.bias", b.shape)]
+                self._shapes += [(f"{prefix}.{i}.weight", w.shape), (f"{prefix}.{i}.bias", b.shape)]
         for prefix in ("memory_a", "memory_c"):
             for l, arr in enumerate(self._mem[prefix]):
-                self._tensors += [(f"{prefix}.rnn.{name}_l{l}", a.shape) for name, a in zip(RNN_TENSORS, arr)]
-        self._tensors.append((self.std_key, self._std0.shape))
-        self.handle = None
+                self._shapes += [(f"{prefix}.rnn.{name}_l{l}", a.shape) for name, a in zip(RNN_TENSORS, arr)]
+        self._shapes.append((self.std_key, self._std0.shape))
         self._stats = torch.zeros(5, dtype=torch.float64, device=self.device)
         if max_rows is not None:
             self._create(int(max_rows))
 
     # ---- handle
-    def _create(self, max_rows):
+    def _make_handle(self, max_rows):
         fp = C.POINTER(C.c_float)
 
         def plist(arrays):
@@ -95,20 +86,8 @@ class NativeRecurrentPPO(NativePPO):
                                              input_a=self._mem["memory_a"][0][0].shape[1], hidden_a=self._mem["memory_a"][0][1].shape[1],
                                              input_c=self._mem["memory_c"][0][0].shape[1], hidden_c=self._mem["memory_c"][0][1].shape[1],
                                              std=self._std0.ctypes.data, **lists)
-        state = self.optimizer_state() if self.handle else None
-        self.close()
-        torch.cuda.synchronize(self.device)
-        self._created(self.lib.lg_ppo_recurrent_create(pol.memory_a.handle, pol.actor.handle, pol.memory_c.handle, pol.critic.handle, C.byref(params),
-                                                       abi.NOISE_STD_TYPES[pol.noise_std_type], self.learning_rate, max_rows, _ptr(pol.std)),
-                      "lg_ppo_recurrent_create")
-        self.max_rows = max_rows
-        self.num_parameters = int(self.lib.lg_ppo_recurrent_parameter_count(self.handle))
-        if state is not None:
-            self.load_optimizer_state(state)
-
-    def workspace_bytes(self):
-        self._need_handle()
-        return int(self.lib.lg_ppo_recurrent_workspace_bytes(self.handle))
+        return self._fn("create")(pol.memory_a.handle, pol.actor.handle, pol.memory_c.handle, pol.critic.handle, C.byref(params),
+                                  abi.NOISE_STD_TYPES[pol.noise_std_type], self.learning_rate, max_rows, _ptr(pol.std))
 
     def _rollout(self, rollout):
         """The (T, N, .) tensors of a recurrent `collect_rollout` dict as the library takes them, kept alive by the returned list."""
@@ -148,8 +127,7 @@ class NativeRecurrentPPO(NativePPO):
         rows, hidden, dones, T, N, keep = self._rollout(rollout)
         self._ensure(T * int(count))
         hyper = self._hyper()
-        self._check(self.lib.lg_ppo_recurrent_minibatch(self.handle, C.byref(rows), C.byref(hidden), _ptr(dones), T, N, int(env0), int(count), C.byref(hyper),
-                                                        self._stream()), "lg_ppo_recurrent_minibatch")
+        self._call("minibatch", C.byref(rows), C.byref(hidden), _ptr(dones), T, N, int(env0), int(count), C.byref(hyper))
         del keep
 
     def update(self, rollout):
@@ -158,28 +136,13 @@ class NativeRecurrentPPO(NativePPO):
         rows, hidden, dones, T, N, keep = self._rollout(rollout)
         self._ensure(T * max(N // self.num_mini_batches, 1))
         hyper = self._hyper()
-        self._check(self.lib.lg_ppo_recurrent_update(self.handle, C.byref(rows), C.byref(hidden), _ptr(dones), T, N, self.num_mini_batches,
-                                                     self.num_learning_epochs, C.byref(hyper), _ptr(self._stats), self._stream()), "lg_ppo_recurrent_update")
+        self._call("update", C.byref(rows), C.byref(hidden), _ptr(dones), T, N, self.num_mini_batches, self.num_learning_epochs, C.byref(hyper), _ptr(self._stats))
         st = self._stats.cpu().tolist()
         del keep
         self.learning_rate, self.kl = st[4], st[3]
         return {"value_function": st[0], "surrogate": st[1], "entropy": st[2]}
 
     # ---- what the device holds
-    def _split(self, flat):
-        out, off = {}, 0
-        for name, shape in self._tensors:
-            size = int(np.prod(shape))
-            out[name] = torch.from_numpy(flat[off:off + size].reshape(shape).copy())
-            off += size
-        assert off == flat.size
-        return out
-
-    def _join(self, tensors):
-        flat = np.ascontiguousarray(np.concatenate([tensors[name].detach().cpu().numpy().reshape(-1) for name, _ in self._tensors]), dtype=np.float32)
-        assert flat.size == self.num_parameters
-        return flat
-
     def images(self, memory, layer):
         """The device images of one memory layer as the acts read them: (tiled weights, tiled bias), float32 numpy."""
         self._need_handle()
@@ -187,5 +150,5 @@ class NativeRecurrentPPO(NativePPO):
         G, H = (4 if mem.rnn_type == "lstm" else 3), mem.hidden_size
         count = int(self.lib.lg_rnn_tile_weights(abi.RNN_TYPES[mem.rnn_type], mem.input_size if layer == 0 else H, H, None, None, None))
         w, b = np.empty(count, np.float32), np.empty(4 * 16 * ((H + 15) // 16), np.float32)
-        self._check(self.lib.lg_ppo_recurrent_get_images(self.handle, memory, layer, w.ctypes.data, b.ctypes.data, self._stream()), "lg_ppo_recurrent_get_images")
+        self._call("get_images", memory, layer, w.ctypes.data, b.ctypes.data)
         return w, b

@@ -7,19 +7,11 @@ import numpy as np
 import torch
 
 from extended_legged_gym_amd import abi
-from .policy import _lib, _ptr
+from .policy import _ptr
 from .ppo import NativePPO
 from .symmetry import resolve_callable, signed_permutation_tables
 
 SYMMETRY_KEYS = ("use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff", "data_augmentation_func", "_env")
-
-
-def _train_symmetry_lib():
-    lib = _lib()
-    if not getattr(lib, "_train_symmetry_declared", False):
-        abi.declare_train_symmetry(lib)
-        lib._train_symmetry_declared = True
-    return lib
 
 
 class NativeSymmetricPPO(NativePPO):
@@ -28,6 +20,7 @@ class NativeSymmetricPPO(NativePPO):
     `"module:function"`), `_env` (passed to the function while it is probed)."""
     _destroy = "lg_ppo_sym_destroy"
     _prefix = "lg_ppo_sym_"
+    _declare = staticmethod(abi.declare_train_symmetry)
 
     def __init__(self, policy, state_dict, symmetry_cfg=None, **kw):
         if not symmetry_cfg:
@@ -58,8 +51,7 @@ class NativeSymmetricPPO(NativePPO):
             self._create(int(max_rows))
 
     # ---- handle
-    def _create(self, max_rows, tables=None):
-        self.lib = _train_symmetry_lib()
+    def _make_handle(self, max_rows, tables=None):
         fp = C.POINTER(C.c_float)
 
         def lists(layers):
@@ -70,16 +62,8 @@ class NativeSymmetricPPO(NativePPO):
         tab = abi.lg_ppo_sym_tables(op.shape[0], op.shape[1], cp.shape[1], ap.shape[1], op.ctypes.data, os_.ctypes.data, cp.ctypes.data, cs.ctypes.data,
                                     ap.ctypes.data, as_.ctypes.data)
         cfg = abi.lg_ppo_sym_config(int(self.use_data_augmentation), int(self.use_mirror_loss), self.mirror_loss_coeff)
-        state = self.optimizer_state() if self.handle else None
-        self.close()
-        torch.cuda.synchronize(self.device)
-        self._created(self.lib.lg_ppo_sym_create(self.policy.actor.handle, self.policy.critic.handle, aw, ab, cw, cb, self._std0.ctypes.data,
-                                                 abi.NOISE_STD_TYPES[self.policy.noise_std_type], self.learning_rate, max_rows, _ptr(self.policy.std),
-                                                 C.byref(tab), C.byref(cfg)), "lg_ppo_sym_create")
-        self.max_rows = max_rows
-        self.num_parameters = int(self.lib.lg_ppo_sym_parameter_count(self.handle))
-        if state is not None:
-            self.load_optimizer_state(state)
+        return self._fn("create")(self.policy.actor.handle, self.policy.critic.handle, aw, ab, cw, cb, self._std0.ctypes.data,
+                                  abi.NOISE_STD_TYPES[self.policy.noise_std_type], self.learning_rate, max_rows, _ptr(self.policy.std), C.byref(tab), C.byref(cfg))
 
     # ---- training
     def update(self, rollout, indices=None):
@@ -93,7 +77,7 @@ class NativeSymmetricPPO(NativePPO):
         """As `NativePPO.gradients`; the means also carry the mini-batch's `"symmetry"` loss."""
         self._need_handle()
         g, norm, means, sym = np.empty(self.num_parameters, np.float32), C.c_float(), (C.c_float * 4)(), C.c_float()
-        self._check(self.lib.lg_ppo_sym_gradients(self.handle, g.ctypes.data, C.byref(norm), means, C.byref(sym), self._stream()), "lg_ppo_sym_gradients")
+        self._call("gradients", g.ctypes.data, C.byref(norm), means, C.byref(sym))
         out = dict(zip(("surrogate", "value_function", "entropy", "kl"), [float(x) for x in means]))
         out["symmetry"] = float(sym.value)
         return self._split(g), norm.value, out
@@ -105,5 +89,5 @@ class NativeSymmetricPPO(NativePPO):
         K = self.num_blocks
         mu = np.empty((K * count, self.policy.num_actions), np.float32)
         val = np.empty(((K if self.use_data_augmentation else 1) * count, 1), np.float32)
-        self._check(self.lib.lg_ppo_sym_forward_outputs(self.handle, mu.ctypes.data, val.ctypes.data, self._stream()), "lg_ppo_sym_forward_outputs")
+        self._call("forward_outputs", mu.ctypes.data, val.ctypes.data)
         return torch.from_numpy(mu), torch.from_numpy(val)
