@@ -288,6 +288,13 @@ class lg_obs_history(C.Structure):
                 ("inject_u", C.c_void_p)]
 
 
+def declare_policy_wide(lib):
+    """Prototype of include/lgpolicy_wide.h: `lg_mlp_create` for an input row of up to MLP_MAX_INPUT columns."""
+    lib.lg_mlp_create_wide.argtypes = [i32, C.POINTER(i32), C.POINTER(C.POINTER(f32)), C.POINTER(C.POINTER(f32)), i32, C.c_int]
+    lib.lg_mlp_create_wide.restype = C.c_void_p
+    return lib
+
+
 def declare_policy(lib):
     """Prototypes of the rollout-collection entry points (include/lgpolicy.h), same library."""
     vp = C.c_void_p
@@ -651,6 +658,8 @@ LG_PREC_F32, LG_PREC_BF16 = 0, 1          # the encoder's precision modes (inclu
 ENCODER_PRECISIONS = {"fp32": LG_PREC_F32, "bf16": LG_PREC_BF16}
 ENCODER_MAX_SIDE, ENCODER_MIN_SIDE, ENCODER_MAX_OUT = 128, 8, 512          # limits of lg_conv_encoder_create
 MLP_MAX_WIDTH = 512          # widest layer of an lg_mlp, inputs included: MLP_MAXW of csrc/lg_policy.hip, held to it by tests/test_estimator_abi.py
+MLP_MAX_INPUT = 2048         # widest input row of lg_mlp_create_wide: LG_MLP_MAX_INPUT of include/lgpolicy_wide.h (the other widths stay within MLP_MAX_WIDTH)
+POLICY_WIDE_SYMBOLS = ["lg_mlp_create_wide"]
 RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2, "lrelu": 3, "selu": 4}
 

@@ -184,6 +184,11 @@ lg_distill_rtrain* lg_distill_rtrain_create(lg_rnn* mem, lg_mlp* student, const 
   if (max_rows < 1) { lg_policy_fail(LG_ERR_INVALID, "max_rows < 1"); return nullptr; }
   if (!(learning_rate > 0.0)) { lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0"); return nullptr; }
   if (student->h.act_out) { lg_policy_fail(LG_ERR_UNSUPPORTED, "a network with an output activation cannot be trained here"); return nullptr; }
+  if (mlp_is_wide(student)) {
+    lg_policy_fail(LG_ERR_UNSUPPORTED, "the student's first layer takes " + std::to_string(student->h.dims[0]) + " inputs: it reads the memory's hidden row of at most " +
+                                           std::to_string(MLP_MAXW) + " columns");
+    return nullptr;
+  }
   if (student->h.dims[0] != mem->hidden) { lg_policy_fail(LG_ERR_INVALID, "the MLP's input width is not the memory's hidden width"); return nullptr; }
   if (student->device != mem->device) { lg_policy_fail(LG_ERR_INVALID, "the memory and the network live on different devices"); return nullptr; }
   const int ML = mem->num_layers, Ls = student->h.L, H = mem->hidden;

@@ -539,6 +539,7 @@ int lg_estimator_step(lg_conv_encoder* e, lg_mlp* combine, lg_rnn* mem, lg_mlp* 
   lg_mlp_widths(combine, &cl, &cin, &cout, &cdev);
   lg_rnn_widths(mem, &rtype, &rin, &rhid, &rdev);
   lg_mlp_widths(decoder, &dl, &din, &dout, &ddev);
+  if (cin > MLP_MAXW) return lg_policy_fail(LG_ERR_UNSUPPORTED, "combine takes " + std::to_string(cin) + " inputs: the estimator's stages are at most " + std::to_string(MLP_MAXW) + " wide (a handle of lg_mlp_create_wide is refused)");
   const int P = cin - e->out_dim;
   if (cl != 1 || P < 0 || cout != rin || din != rhid)
     return lg_policy_fail(LG_ERR_INVALID, "stage widths do not chain (combine: one layer of encoder out_dim + proprio inputs; its outputs = the memory's input; decoder input = the memory's hidden width)");

@@ -59,28 +59,26 @@ const void* lg_policy_upload(const void* host, size_t bytes, std::vector<void*>&
   return d;
 }
 
-// 32 rows of x through the whole network; result rows (width dims[L], <= 16 * nchunks) left in `yrows` / written to `y_global`
-LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0, int64_t n, float* buf0, float* buf1, float* yrows /* [32][16*?] */,
-                     float* __restrict__ y_global) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  // stage the input tile: x (n, K0) row-major -> activation image.  Eight independent loads in flight per lane.
-  const int K0 = M.dims[0], K0p = M.kpad[0];
-  for (int base = 0; base < MLP_ROWS * K0p; base += 8 * MLP_THREADS) {
+// stage an input tile: columns [k0, k0 + Kp) of 32 rows of x (n, K0) row-major -> activation image of padded width Kp (zeros past column K0 and
+// past row n).  Eight independent loads in flight per lane.
+LG_DEV void mlp_stage(const float* __restrict__ x, int K0, int k0, int Kp, int64_t row0, int64_t n, float* img) {
+  const int tid = threadIdx.x;
+  for (int base = 0; base < MLP_ROWS * Kp; base += 8 * MLP_THREADS) {
     float v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const int idx = base + u * MLP_THREADS + tid, r = idx / K0p, k = idx - r * K0p;
+      const int idx = base + u * MLP_THREADS + tid, r = idx / Kp, k = idx - r * Kp;
       const int64_t row = row0 + r;
-      v[u] = (idx < MLP_ROWS * K0p && row < n && k < K0) ? x[row * K0 + k] : 0.f;
+      v[u] = (idx < MLP_ROWS * Kp && row < n && k0 + k < K0) ? x[row * K0 + k0 + k] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const int idx = base + u * MLP_THREADS + tid, r = idx / K0p, k = idx - r * K0p;
-      if (idx < MLP_ROWS * K0p) buf0[IMG(r, k)] = v[u];
+      const int idx = base + u * MLP_THREADS + tid, r = idx / Kp, k = idx - r * Kp;
+      if (idx < MLP_ROWS * Kp) img[IMG(r, k)] = v[u];
     }
   }
-  lds_barrier();
-  float* in = buf0; float* out = buf1;
+}
+
 // volatile asm keeps the two accumulator chains interleaved as written (the compiler otherwise issues the dependent MFMAs of one
 // accumulator back to back: 40-cycle dependent latency instead of the 32-cycle issue rate)
 #define MFMA_IN_ORDER(ACC, A, B) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(ACC) : "v"(A), "v"(B))
@@ -98,7 +96,103 @@ LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0,
         MFMA_IN_ORDER(acc0, A0.w, W.w); MFMA_IN_ORDER(acc1, A1.w, W.w);                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
       }
-  for (int l = 0; l < M.L; ++l) {
+
+// Layer 0 of a network whose input row is wider than one activation image (kpad[0] > MLP_MAXW; lg_mlp_create_wide): split-K.  The row is staged
+// into `img` in slabs of MLP_MAXW columns (the last one padded to 64 as any input is), and between slabs the workgroup barriers and restages.  A wave
+// keeps the accumulators of ALL its chunks (at most MLP_WIDE_CHUNKS, both row halves) live across the slabs, so every output element is still ONE
+// k-ascending MFMA chain from zero, the chain of the one-slab path: the result does not depend on where the slabs are cut, and columns whose weights
+// are zero change no bit.  Bias and activation follow the last slab; nothing is summed through LDS or memory.  Ends as a layer of mlp_tile ends:
+// the next layer's image in `out` (or the rows in `yrows` / `y_global` when the network has one layer), and a barrier.
+#define MLP_WIDE_CHUNKS (MLP_MAXW / 16 / (MLP_THREADS / 64))
+LG_DEV void mlp_wide_first_layer(const MlpDev& M, const float* __restrict__ x, int64_t row0, int64_t n, float* img, float* out, float* yrows,
+                                 float* __restrict__ y_global) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int K0 = M.dims[0], K0p = M.kpad[0], nblk0 = K0p >> 4, nch = M.nchunks[0], nout = M.dims[1];
+  const bool last = M.L == 1;
+  const float4* ap = reinterpret_cast<const float4*>(img) + (lane & 15) * 4 + (lane >> 4);
+  const float4* wl = reinterpret_cast<const float4*>(M.w[0]) + lane;
+  f32x4 acc[MLP_WIDE_CHUNKS][2];
+#pragma unroll
+  for (int ci = 0; ci < MLP_WIDE_CHUNKS; ++ci) { acc[ci][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[ci][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int k0 = 0; k0 < K0p; k0 += MLP_MAXW) {
+    const int Kp = K0p - k0 < MLP_MAXW ? K0p - k0 : MLP_MAXW, nblk = Kp >> 4;       // a multiple of 64 columns = of 4 blocks
+    if (k0) lds_barrier();                                                            // every wave has read the slab before
+    mlp_stage(x, K0, k0, Kp, row0, n, img);
+    lds_barrier();
+    const float4* ws = wl + (size_t)(k0 >> 4) * 64;                                   // the slab's first block within a chunk
+    float4 w0, w1, w2, w3, p0, p1, p2, p3, q0, q1, q2, q3;
+    if (wv < nch) {
+      const float4* wc = ws + (size_t)wv * nblk0 * 64;
+      w0 = wc[0]; p0 = ap[0]; q0 = ap[64];
+      w1 = wc[64]; p1 = ap[128]; q1 = ap[128 + 64];
+    }
+#pragma unroll
+    for (int ci = 0; ci < MLP_WIDE_CHUNKS; ++ci) {
+      const int c = wv + ci * (MLP_THREADS / 64);
+      if (c < nch) {
+        f32x4 acc0 = acc[ci][0], acc1 = acc[ci][1];
+        const float4* wc = ws + (size_t)c * nblk0 * 64;
+        const int cn = c + MLP_THREADS / 64 < nch ? c + MLP_THREADS / 64 : c;         // the wave's last chunk re-reads its own first blocks
+        const float4* wnext = ws + (size_t)cn * nblk0 * 64;
+        for (int kb = 0; kb < nblk; kb += 4) {
+          const bool more = kb + 4 < nblk;
+          MLP_BLOCK(w0, p0, q0, w2, p2, q2, wc + (size_t)(kb + 2) * 64, ap + (kb + 2) * 128)
+          MLP_BLOCK(w1, p1, q1, w3, p3, q3, wc + (size_t)(kb + 3) * 64, ap + (kb + 3) * 128)
+          MLP_BLOCK(w2, p2, q2, w0, p0, q0, more ? wc + (size_t)(kb + 4) * 64 : wnext, more ? ap + (kb + 4) * 128 : ap)
+          MLP_BLOCK(w3, p3, q3, w1, p1, q1, more ? wc + (size_t)(kb + 5) * 64 : wnext + 64, more ? ap + (kb + 5) * 128 : ap + 128)
+        }
+        // as in mlp_tile: the last MFMA's result latency, before anything the compiler schedules touches the accumulators
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+        acc[ci][0] = acc0; acc[ci][1] = acc1;
+      }
+    }
+  }
+#pragma unroll
+  for (int ci = 0; ci < MLP_WIDE_CHUNKS; ++ci) {
+    const int c = wv + ci * (MLP_THREADS / 64);
+    if (c < nch) {
+      const int col = c * 16 + (lane & 15);
+      const float bias = M.b[0][col];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = 4 * (lane >> 4) + i;
+        float v0 = acc[ci][0][i] + bias, v1 = acc[ci][1][i] + bias;
+        if (!last) {
+          v0 = apply_act(v0, M.act); v1 = apply_act(v1, M.act);
+          if (col >= nout) { v0 = 0.f; v1 = 0.f; }
+          out[IMG(m, col)] = v0;
+          out[IMG(m + 16, col)] = v1;
+        } else if (col < nout) {
+          if (M.act_out) { v0 = apply_act(v0, M.act); v1 = apply_act(v1, M.act); }
+          if (yrows) { yrows[m * 16 * nch + col] = v0; yrows[(m + 16) * 16 * nch + col] = v1; }
+          if (y_global) {
+            if (row0 + m < n) y_global[(row0 + m) * nout + col] = v0;
+            if (row0 + m + 16 < n) y_global[(row0 + m + 16) * nout + col] = v1;
+          }
+        }
+      }
+    }
+  }
+  lds_barrier();
+}
+
+// 32 rows of x through the whole network; result rows (width dims[L], <= 16 * nchunks) left in `yrows` / written to `y_global`.  WIDE: the instance
+// that also takes networks with more than MLP_MAXW inputs (a narrow network in the same launch runs the loop below from layer 0, as in the
+// narrow instance).
+template <bool WIDE>
+LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0, int64_t n, float* buf0, float* buf1, float* yrows /* [32][16*?] */,
+                     float* __restrict__ y_global) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float* in = buf0; float* out = buf1;
+  int l0 = 0;
+  if (WIDE && M.kpad[0] > MLP_MAXW) {
+    mlp_wide_first_layer(M, x, row0, n, buf0, buf1, yrows, y_global);
+    in = buf1; out = buf0; l0 = 1;
+  } else {
+    mlp_stage(x, M.dims[0], 0, M.kpad[0], row0, n, buf0);
+    lds_barrier();
+  }
+  for (int l = l0; l < M.L; ++l) {
     const int nblk = M.kpad[l] >> 4, nch = M.nchunks[l];          // blocks of 16 inputs per chunk: a multiple of 4
     const bool last = l == M.L - 1;
     const int nout = M.dims[l + 1];
@@ -158,12 +252,20 @@ LG_DEV void mlp_tile(const MlpDev& M, const float* __restrict__ x, int64_t row0,
 __global__ __launch_bounds__(MLP_THREADS) void mlp_forward_kernel(MlpDev M, const float* __restrict__ x, int64_t n, float* __restrict__ y) {
   __shared__ __attribute__((aligned(16))) float buf0[MLP_IMG];
   __shared__ __attribute__((aligned(16))) float buf1[MLP_IMG];
-  mlp_tile(M, x, (int64_t)blockIdx.x * MLP_ROWS, n, buf0, buf1, nullptr, y);
+  mlp_tile<false>(M, x, (int64_t)blockIdx.x * MLP_ROWS, n, buf0, buf1, nullptr, y);
+}
+
+// The *_wide_* kernels (this one and the two acts below) are the WIDE instances of the same bodies, for launches in which a network has more than
+// MLP_MAXW inputs; the host picks them from the handles (mlp_is_wide), and every other launch takes the kernels above, unchanged.
+__global__ __launch_bounds__(MLP_THREADS) void mlp_wide_forward_kernel(MlpDev M, const float* __restrict__ x, int64_t n, float* __restrict__ y) {
+  __shared__ __attribute__((aligned(16))) float buf0[MLP_IMG];
+  __shared__ __attribute__((aligned(16))) float buf1[MLP_IMG];
+  mlp_tile<true>(M, x, (int64_t)blockIdx.x * MLP_ROWS, n, buf0, buf1, nullptr, y);
 }
 
 // PPO.act: blockIdx.y = 0 actor (+ sampling, log-prob), 1 critic.  LOGP = false is Distillation.act (lg_distill_act): the second network is the teacher
 // (its whole output row goes to `values`), and no log-prob is kept (distillation.py:89-96 stores none).
-template <bool LOGP>
+template <bool LOGP, bool WIDE>
 LG_DEV void policy_act_body(const MlpDev& A, const MlpDev& Cr, const float* __restrict__ obs, const float* __restrict__ cobs, int64_t n,
                             const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi, uint32_t call_lo, uint32_t call_hi, int deterministic,
                             float* __restrict__ actions, float* __restrict__ mean, float* __restrict__ logp, float* __restrict__ values) {
@@ -172,9 +274,9 @@ LG_DEV void policy_act_body(const MlpDev& A, const MlpDev& Cr, const float* __re
   __shared__ float yrows[MLP_ROWS * 16 * 2];       // output rows of the actor (<= 32 actions)
   __shared__ float lp[LOGP ? MLP_ROWS : 1][32];
   const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
-  if (blockIdx.y == 1) { mlp_tile(Cr, cobs, row0, n, buf0, buf1, nullptr, values); return; }
+  if (blockIdx.y == 1) { mlp_tile<WIDE>(Cr, cobs, row0, n, buf0, buf1, nullptr, values); return; }
   const int na = A.dims[A.L], stride = 16 * A.nchunks[A.L - 1];
-  mlp_tile(A, obs, row0, n, buf0, buf1, yrows, mean);
+  mlp_tile<WIDE>(A, obs, row0, n, buf0, buf1, yrows, mean);
   // one lane per (row, action): z from Philox + Box-Muller, two normals per counter word pair
   const int tid = threadIdx.x;
   for (int idx = tid; idx < MLP_ROWS * 32; idx += MLP_THREADS) {
@@ -212,14 +314,28 @@ __global__ __launch_bounds__(MLP_THREADS) void policy_act_kernel(MlpDev A, MlpDe
                                                          int64_t n, const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi,
                                                          uint32_t call_lo, uint32_t call_hi, int deterministic, float* __restrict__ actions,
                                                          float* __restrict__ mean, float* __restrict__ logp, float* __restrict__ values) {
-  policy_act_body<true>(A, Cr, obs, cobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, logp, values);
+  policy_act_body<true, false>(A, Cr, obs, cobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, logp, values);
 }
 
 __global__ __launch_bounds__(MLP_THREADS) void distill_act_kernel(MlpDev S, MlpDev Te, const float* __restrict__ obs, const float* __restrict__ tobs,
                                                           int64_t n, const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi,
                                                           uint32_t call_lo, uint32_t call_hi, int deterministic, float* __restrict__ actions,
                                                           float* __restrict__ mean, float* __restrict__ teacher_actions) {
-  policy_act_body<false>(S, Te, obs, tobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, nullptr, teacher_actions);
+  policy_act_body<false, false>(S, Te, obs, tobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, nullptr, teacher_actions);
+}
+
+__global__ __launch_bounds__(MLP_THREADS) void policy_wide_act_kernel(MlpDev A, MlpDev Cr, const float* __restrict__ obs, const float* __restrict__ cobs,
+                                                              int64_t n, const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi,
+                                                              uint32_t call_lo, uint32_t call_hi, int deterministic, float* __restrict__ actions,
+                                                              float* __restrict__ mean, float* __restrict__ logp, float* __restrict__ values) {
+  policy_act_body<true, true>(A, Cr, obs, cobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, logp, values);
+}
+
+__global__ __launch_bounds__(MLP_THREADS) void distill_wide_act_kernel(MlpDev S, MlpDev Te, const float* __restrict__ obs, const float* __restrict__ tobs,
+                                                               int64_t n, const float* __restrict__ stdv, uint32_t seed_lo, uint32_t seed_hi,
+                                                               uint32_t call_lo, uint32_t call_hi, int deterministic, float* __restrict__ actions,
+                                                               float* __restrict__ mean, float* __restrict__ teacher_actions) {
+  policy_act_body<false, true>(S, Te, obs, tobs, n, stdv, seed_lo, seed_hi, call_lo, call_hi, deterministic, actions, mean, nullptr, teacher_actions);
 }
 
 // GAE (rollout_storage.py:145-160): one lane per env, the T-step recursion in registers
@@ -271,13 +387,24 @@ void lg_mlp_destroy(lg_mlp* m) {
   delete m;
 }
 
-lg_mlp* lg_mlp_create(int32_t L, const int32_t* dims, const float* const* weights, const float* const* biases, int32_t activation,
-                      int device_id) {
-  POLICY_ENTRY;
+// the body of both create functions; max_input: the widest dims[0] the caller's entry point takes
+static lg_mlp* mlp_create(int32_t L, const int32_t* dims, const float* const* weights, const float* const* biases, int32_t activation, int device_id,
+                          int max_input) {
   if (L <= 0 || L > LG_MLP_MAX_LAYERS || !dims || !weights || !biases) { lg_policy_fail(LG_ERR_INVALID, "bad layer list"); return nullptr; }
   if (activation < LG_ACT_ELU || activation > LG_ACT_SELU) { lg_policy_fail(LG_ERR_INVALID, "unknown activation"); return nullptr; }
   // (an output wider than 32 is fine for lg_mlp_forward; lg_policy_act checks its own limit)
-  for (int l = 0; l <= L; ++l) if (dims[l] <= 0 || dims[l] > MLP_MAXW) { lg_policy_fail(LG_ERR_INVALID, "layer width out of range (1..512)"); return nullptr; }
+  if (max_input == MLP_MAXW) {
+    for (int l = 0; l <= L; ++l) if (dims[l] <= 0 || dims[l] > MLP_MAXW) { lg_policy_fail(LG_ERR_INVALID, "layer width out of range (1..512)"); return nullptr; }
+  } else {
+    for (int l = 0; l <= L; ++l) {
+      const int most = l == 0 ? max_input : MLP_MAXW;
+      if (dims[l] >= 1 && dims[l] <= most) continue;
+      const std::string which = std::string(l == 0 ? "input" : (l == L ? "output" : "hidden")) + " width " + std::to_string(dims[l]) + " (dims[" + std::to_string(l) + "])";
+      lg_policy_fail(LG_ERR_INVALID, dims[l] < 1 ? which + " is below 1"
+                                                 : which + " is over " + std::to_string(most) + (l == 0 ? "" : ": only the input row may be wider than 512"));
+      return nullptr;
+    }
+  }
   if (!lg_policy_device_ok(device_id)) return nullptr;
   DeviceScope ds_(device_id);
   if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
@@ -307,6 +434,18 @@ lg_mlp* lg_mlp_create(int32_t L, const int32_t* dims, const float* const* weight
   return m;
 }
 
+lg_mlp* lg_mlp_create(int32_t L, const int32_t* dims, const float* const* weights, const float* const* biases, int32_t activation,
+                      int device_id) {
+  POLICY_ENTRY;
+  return mlp_create(L, dims, weights, biases, activation, device_id, MLP_MAXW);
+}
+
+lg_mlp* lg_mlp_create_wide(int32_t L, const int32_t* dims, const float* const* weights, const float* const* biases, int32_t activation,
+                           int device_id) {
+  POLICY_ENTRY;
+  return mlp_create(L, dims, weights, biases, activation, device_id, LG_MLP_MAX_INPUT);
+}
+
 int lg_mlp_set_output_activation(lg_mlp* m, int32_t enabled) {
   POLICY_ENTRY;
   if (!m) return lg_policy_fail(LG_ERR_INVALID, "null network");
@@ -319,7 +458,8 @@ int lg_mlp_forward(lg_mlp* m, const float* x, int64_t n, float* y, void* stream)
   if (!m || !x || !y || n < 0) return lg_policy_fail(LG_ERR_INVALID, "null network or row, or n < 0");
   DeviceScope ds_(m->device);
   if (n == 0) return LG_OK;
-  hipLaunchKernelGGL(mlp_forward_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS)), dim3(MLP_THREADS), 0, (hipStream_t)stream, m->h, x, n, y);
+  hipLaunchKernelGGL(mlp_is_wide(m) ? mlp_wide_forward_kernel : mlp_forward_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS)), dim3(MLP_THREADS), 0,
+                     (hipStream_t)stream, m->h, x, n, y);
   POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
@@ -332,7 +472,8 @@ int lg_policy_act(lg_mlp* actor, lg_mlp* critic, const float* obs, const float* 
   DeviceScope ds_(actor->device);
   if (actor->h.dims[actor->h.L] > 32) return lg_policy_fail(LG_ERR_UNSUPPORTED, "the actor ends in more than 32 actions");
   if (n == 0) return LG_OK;
-  hipLaunchKernelGGL(policy_act_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 2), dim3(MLP_THREADS), 0, (hipStream_t)stream, actor->h, critic->h,
+  hipLaunchKernelGGL(mlp_is_wide(actor) || mlp_is_wide(critic) ? policy_wide_act_kernel : policy_act_kernel,
+                     dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 2), dim3(MLP_THREADS), 0, (hipStream_t)stream, actor->h, critic->h,
                      obs, critic_obs, n, std_, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), deterministic,
                      actions, action_mean, logp, values);
   POLICY_TRY(hipGetLastError());
@@ -710,7 +851,8 @@ int lg_distill_act(lg_mlp* student, lg_mlp* teacher, const float* obs, const flo
   const int rc = distill_widths(student, teacher);
   if (rc != LG_OK || n == 0) return rc;
   DeviceScope ds_(student->device);
-  hipLaunchKernelGGL(distill_act_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 2), dim3(MLP_THREADS), 0, (hipStream_t)stream, student->h, teacher->h,
+  hipLaunchKernelGGL(mlp_is_wide(student) || mlp_is_wide(teacher) ? distill_wide_act_kernel : distill_act_kernel,
+                     dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), 2), dim3(MLP_THREADS), 0, (hipStream_t)stream, student->h, teacher->h,
                      obs, teacher_obs, n, std_, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)call, (uint32_t)(call >> 32), deterministic,
                      actions, action_mean, teacher_actions);
   POLICY_TRY(hipGetLastError());

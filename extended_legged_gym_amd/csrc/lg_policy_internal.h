@@ -7,6 +7,7 @@
 #include <vector>
 #include "lg_device.h"
 #include "../../include/lgpolicy.h"
+#include "../../include/lgpolicy_wide.h"
 
 // The exported entry point the caller called: the first line of every entry point that can fail is POLICY_ENTRY.  Entry points call each other
 // (a collector calls the acts); the outermost name stays, so a message always begins with the call the caller made.
@@ -83,7 +84,7 @@ int lg_obsnorm_width(const lg_obsnorm* h);
 // ---- the network handle, shared with the trainer (lg_train.hip), which rewrites the device buffers of an lg_mlp in place
 #define MLP_ROWS 32          // batch rows per workgroup
 #define MLP_THREADS 512      // eight waves: two per SIMD
-#define MLP_MAXW 512         // widest layer
+#define MLP_MAXW 512         // widest layer; an input row may be wider (lg_mlp_create_wide: up to LG_MLP_MAX_INPUT), staged in slabs of this width
 #define MLP_IMG (MLP_MAXW * MLP_ROWS)          // floats of one activation image
 // element (row m, input k) of the activation image
 #define IMG(m, k) (((((k) >> 4) * MLP_ROWS + (m)) * 4 + ((k) & 3)) * 4 + (((k) >> 2) & 3))
@@ -103,6 +104,8 @@ struct lg_mlp {
   int device = 0;
   std::vector<void*> allocs;
 };
+// a handle whose input row does not fit one activation image: its launches take the kernels' wide instances (split-K first layer)
+inline bool mlp_is_wide(const lg_mlp* m) { return m->h.kpad[0] > MLP_MAXW; }
 
 // the activations, shared so that the trainer's forward values are lg_mlp_forward's bit for bit
 LG_DEV float apply_act(float x, int act) {

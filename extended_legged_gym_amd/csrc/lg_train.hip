@@ -5,6 +5,8 @@
 //                           lg_policy.hip: same activation image in LDS, same tiled weights (the lg_mlp's own buffers), the same k-ordered MFMA chain
 //                           per accumulator, bias and apply_act -- so the values are lg_mlp_forward's bit for bit.  The rows are gathered through the
 //                           index vector while staging; every layer's post-activation output is also written to a workspace.
+//                           ppo_wide_forward_kernel: the same body (lg_train_forward_body.h) with a split-K first layer, for observation rows wider than
+//                           one activation image (lg_mlp_create_wide).
 //   ppo_loss_kernel         one lane per row: log-prob, ratio, both surrogate branches, the value loss, the KL term; dL/dmu, dL/dvalue, the row's
 //                           part of dL/dsigma; per-block sums in a fixed order.
 //   ppo_loss_finish_kernel  the block sums in block order -> the four loss means, the gradient of std / log_std, the KL-adaptive learning rate.
@@ -50,8 +52,8 @@ LG_DEV float act_grad_from_output(float a, int act) {
   return 1.f;
 }
 
-// rows of `src` (width K, optionally gathered through idx) -> activation image of padded width Kp
-LG_DEV void stage_rows(const float* __restrict__ src, const int64_t* __restrict__ idx, int K, int Kp, int64_t row0, int64_t n, float* img) {
+// columns [k0, k0 + Kp) of rows of `src` (width K, optionally gathered through idx) -> activation image of padded width Kp
+LG_DEV void stage_rows(const float* __restrict__ src, const int64_t* __restrict__ idx, int K, int Kp, int64_t row0, int64_t n, float* img, int k0 = 0) {
   const int tid = threadIdx.x;
   for (int base = 0; base < MLP_ROWS * Kp; base += 4 * MLP_THREADS) {
     float v[4];
@@ -60,7 +62,7 @@ LG_DEV void stage_rows(const float* __restrict__ src, const int64_t* __restrict_
       const int e = base + u * MLP_THREADS + tid, r = e / Kp, k = e - r * Kp;
       const int64_t row = row0 + r;
       float val = 0.f;
-      if (e < MLP_ROWS * Kp && row < n && k < K) val = src[(idx ? idx[row] : row) * K + k];
+      if (e < MLP_ROWS * Kp && row < n && k0 + k < K) val = src[(idx ? idx[row] : row) * K + k0 + k];
       v[u] = val;
     }
 #pragma unroll
@@ -71,46 +73,42 @@ LG_DEV void stage_rows(const float* __restrict__ src, const int64_t* __restrict_
   }
 }
 
+// the epilogue of chunk c of layer l of the training forward: bias, activation, the next layer's image, and the saved output a[l + 1]
+LG_DEV void forward_chunk_out(const float* __restrict__ fb, float* save, int nout, bool last, int act, int c, const f32x4& acc0, const f32x4& acc1, float* out,
+                              int64_t row0, int64_t n) {
+  const int lane = threadIdx.x & 63;
+  const int col = c * 16 + (lane & 15);
+  const float bias = fb[col];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = 4 * (lane >> 4) + i;
+    float v0 = acc0[i] + bias, v1 = acc1[i] + bias;
+    if (!last) {
+      v0 = apply_act(v0, act); v1 = apply_act(v1, act);
+      if (col >= nout) { v0 = 0.f; v1 = 0.f; }
+      out[IMG(m, col)] = v0;
+      out[IMG(m + 16, col)] = v1;
+    }
+    if (col < nout) {
+      if (row0 + m < n) save[(row0 + m) * nout + col] = v0;
+      if (row0 + m + 16 < n) save[(row0 + m + 16) * nout + col] = v1;
+    }
+  }
+}
+
+// the training forward (its body: lg_train_forward_body.h), and its instance for networks with more than MLP_MAXW inputs
 __global__ __launch_bounds__(MLP_THREADS) void ppo_forward_kernel(TrainNet NA, TrainNet NC, const float* __restrict__ obs, const float* __restrict__ cobs,
                                                                   const int64_t* __restrict__ idx, int64_t n) {
-  __shared__ __attribute__((aligned(16))) float buf0[MLP_IMG];
-  __shared__ __attribute__((aligned(16))) float buf1[MLP_IMG];
-  const TrainNet& M = blockIdx.y == 0 ? NA : NC;
-  const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  stage_rows(blockIdx.y == 0 ? obs : cobs, idx, M.dims[0], M.fkpad[0], row0, n, buf0);
-  lds_barrier();
-  float* in = buf0; float* out = buf1;
-  for (int l = 0; l < M.L; ++l) {
-    const int nblk = M.fkpad[l] >> 4, nch = M.fnch[l], nout = M.dims[l + 1];
-    const bool last = l == M.L - 1;
-    const float4* ap = reinterpret_cast<const float4*>(in) + (lane & 15) * 4 + (lane >> 4);
-    const float4* wl = reinterpret_cast<const float4*>(M.fw[l]) + lane;
-    float* save = M.a[l + 1];
-    for (int c = wv; c < nch; c += MLP_THREADS / 64) {
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      chunk_chain(wl + (size_t)c * nblk * 64, ap, nblk, acc0, acc1);
-      const int col = c * 16 + (lane & 15);
-      const float bias = M.fb[l][col];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = 4 * (lane >> 4) + i;
-        float v0 = acc0[i] + bias, v1 = acc1[i] + bias;
-        if (!last) {
-          v0 = apply_act(v0, M.act); v1 = apply_act(v1, M.act);
-          if (col >= nout) { v0 = 0.f; v1 = 0.f; }
-          out[IMG(m, col)] = v0;
-          out[IMG(m + 16, col)] = v1;
-        }
-        if (col < nout) {
-          if (row0 + m < n) save[(row0 + m) * nout + col] = v0;
-          if (row0 + m + 16 < n) save[(row0 + m + 16) * nout + col] = v1;
-        }
-      }
-    }
-    lds_barrier();
-    float* t = in; in = out; out = t;
-  }
+#define PPO_FORWARD_WIDE 0
+#include "lg_train_forward_body.h"
+#undef PPO_FORWARD_WIDE
+}
+
+__global__ __launch_bounds__(MLP_THREADS) void ppo_wide_forward_kernel(TrainNet NA, TrainNet NC, const float* __restrict__ obs, const float* __restrict__ cobs,
+                                                                       const int64_t* __restrict__ idx, int64_t n) {
+#define PPO_FORWARD_WIDE 1
+#include "lg_train_forward_body.h"
+#undef PPO_FORWARD_WIDE
 }
 
 __global__ __launch_bounds__(MLP_THREADS) void ppo_backward_kernel(TrainNet NA, TrainNet NC, int64_t n) {
@@ -472,7 +470,10 @@ int train_core_finish(TrainCore* c, int64_t off, const float* const* const* ws, 
 
 void train_launch_forward(const TrainCore* c, const float* obs, const float* cobs, const int64_t* idx, int64_t n, hipStream_t st) {
   const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
-  hipLaunchKernelGGL(ppo_forward_kernel, dim3(tiles, c->nnet), dim3(MLP_THREADS), 0, st, c->net[0], c->net[c->nnet - 1], obs, cobs, idx, n);
+  bool wide = false;
+  for (int k = 0; k < c->nnet; ++k) wide |= c->net[k].fkpad[0] > MLP_MAXW;
+  hipLaunchKernelGGL(wide ? ppo_wide_forward_kernel : ppo_forward_kernel, dim3(tiles, c->nnet), dim3(MLP_THREADS), 0, st, c->net[0], c->net[c->nnet - 1],
+                     obs, cobs, idx, n);
 }
 
 void train_launch_backward(const TrainCore* c, int64_t n, hipStream_t st) {

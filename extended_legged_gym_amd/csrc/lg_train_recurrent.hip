@@ -341,6 +341,12 @@ lg_ppo_recurrent* lg_ppo_recurrent_create(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* 
   if (q->rnn_type != mem_a->type) { lg_policy_fail(LG_ERR_INVALID, "the parameters' rnn_type is not the memory handles' (lstm against gru)"); return nullptr; }
   if (q->num_layers != mem_a->num_layers || q->input_a != mem_a->input || q->hidden_a != mem_a->hidden || q->input_c != mem_c->input || q->hidden_c != mem_c->hidden) {
     lg_policy_fail(LG_ERR_INVALID, "the parameters' depth or widths disagree with the memory handles"); return nullptr; }
+  for (const lg_mlp* head : {actor, critic})
+    if (mlp_is_wide(head)) {
+      lg_policy_fail(LG_ERR_UNSUPPORTED, "a head's first layer takes " + std::to_string(head->h.dims[0]) + " inputs: a head reads its memory's hidden row of at most " +
+                                             std::to_string(MLP_MAXW) + " columns");
+      return nullptr;
+    }
   if (actor->h.dims[0] != mem_a->hidden || critic->h.dims[0] != mem_c->hidden) { lg_policy_fail(LG_ERR_INVALID, "an MLP's input width is not its memory's hidden width"); return nullptr; }
   if (actor->device != critic->device || mem_a->device != actor->device || mem_c->device != actor->device) {
     lg_policy_fail(LG_ERR_INVALID, "the memories and the networks live on different devices"); return nullptr; }

@@ -383,6 +383,12 @@ lg_ppo_sym* lg_ppo_sym_create(lg_mlp* actor, lg_mlp* critic, const float* const*
   if (critic->h.dims[critic->h.L] != 1) { lg_policy_fail(LG_ERR_UNSUPPORTED, "the critic must end in 1 output"); return nullptr; }
   if (actor->h.dims[actor->h.L] > 32) { lg_policy_fail(LG_ERR_UNSUPPORTED, "the actor ends in more than 32 actions"); return nullptr; }
   const lg_mlp* nets[2] = {actor, critic};
+  for (int k = 0; k < 2; ++k)                                  // sym_fwd_kernel stages a whole mirrored row into one activation image
+    if (mlp_is_wide(nets[k])) {
+      lg_policy_fail(LG_ERR_UNSUPPORTED, std::string(k == 0 ? "the actor's" : "the critic's") + " first layer takes " + std::to_string(nets[k]->h.dims[0]) +
+                                             " inputs: the symmetric update stages rows of at most " + std::to_string(MLP_MAXW) + " columns");
+      return nullptr;
+    }
   const float* const* ws[2] = {aw, cw};
   const float* const* bs[2] = {ab, cb};
   for (int k = 0; k < 2; ++k)

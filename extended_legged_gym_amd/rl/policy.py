@@ -20,6 +20,7 @@ def _lib():
     lib = load_library()
     if not getattr(lib, "_policy_declared", False):
         abi.declare_policy(lib)
+        abi.declare_policy_wide(lib)
         lib._policy_declared = True
     return lib
 
@@ -93,7 +94,9 @@ class NativeMLP(_NativeHandle):
         wp = (fp * L)(*[w.ctypes.data_as(fp) for w in ws])
         bp = (fp * L)(*[b.ctypes.data_as(fp) for b in bs])
         self.dims = dims
-        self._created(self.lib.lg_mlp_create(L, (C.c_int32 * (L + 1))(*dims), wp, bp, abi.ACTIVATIONS[activation], index), "lg_mlp_create")
+        # an input row wider than one activation image (an observation that carries a sensor) takes the entry point with the split-K first layer
+        create = "lg_mlp_create_wide" if dims[0] > abi.MLP_MAX_WIDTH else "lg_mlp_create"
+        self._created(getattr(self.lib, create)(L, (C.c_int32 * (L + 1))(*dims), wp, bp, abi.ACTIVATIONS[activation], index), create)
 
     @classmethod
     def from_sequential_state(cls, state, prefix, activation="elu", device="cuda:0"):

@@ -25,6 +25,11 @@ class NativeSymmetricPPO(NativePPO):
     def __init__(self, policy, state_dict, symmetry_cfg=None, **kw):
         if not symmetry_cfg:
             raise ValueError("NativeSymmetricPPO needs a symmetry_cfg; NativePPO is the trainer without one")
+        for name in ("actor", "critic"):          # the symmetric forward stages a whole mirrored row at once: no split-K first layer there
+            width = getattr(policy, name).dims[0] if hasattr(policy, name) else 0
+            if width > abi.MLP_MAX_WIDTH:
+                raise NotImplementedError(f"NativeSymmetricPPO: the {name} reads rows of {width} columns; the symmetric update takes at most "
+                                          f"{abi.MLP_MAX_WIDTH} (NativePPO trains wide rows, without the symmetry terms)")
         unknown = set(symmetry_cfg) - set(SYMMETRY_KEYS)
         if unknown:
             raise ValueError(f"symmetry_cfg: unknown keys {sorted(unknown)} (known: {', '.join(SYMMETRY_KEYS)})")

@@ -20,7 +20,8 @@ typedef struct lg_mlp lg_mlp;
 
 /* One nn.Sequential(Linear, act, ..., Linear) (actor_critic.py:42-66).  dims[0 .. num_layers]: input width, hidden widths,
  * output width; weights[l] is Linear.weight of layer l, (dims[l+1], dims[l]) row-major, biases[l] (dims[l+1]) — HOST
- * pointers, re-tiled for the matrix cores and uploaded.  Widths up to 512 per hidden layer. */
+ * pointers, re-tiled for the matrix cores and uploaded.  Every width, the input's included, is 1..512; an input row of up to 2048
+ * columns: lg_mlp_create_wide of lgpolicy_wide.h, whose handles every entry point below that runs the MLP on the caller's row takes as they are. */
 lg_mlp* lg_mlp_create(int32_t num_layers, const int32_t* dims, const float* const* weights, const float* const* biases,
                       int32_t activation, int device_id);
 void lg_mlp_destroy(lg_mlp* mlp);
