@@ -1,15 +1,14 @@
 // lg_distill_train_recurrent.hip — Distillation.update (include/lgdistill_recurrent.h) for the recurrent student: a trainer over the student's memory
 // (lg_rnn) and MLP (lg_mlp).  A group of G steps is one batch of G * N rows, step-major.  Reused as they are: the memory's forward with saved gates /
 // backward step / rows x transposed tiling / retile (lg_train_recurrent_internal.h), the MLP's forward with saved activations, backward data pass,
-// slab weight gradients and reduction (lg_train_internal.h), the row index and the behaviour loss (lg_distill_train_internal.h).  New here:
+// slab weight gradients and reduction (lg_train_internal.h), the row index, the behaviour loss, the state mask after a group (Memory.reset(dones)) and
+// the update's loop (lg_train_sequence_internal.h).  New here:
 //
 //   rdistill_norm_kernel       TWO norms from the reduction's block sums, in block order: over the student's segments (the one the clip uses) and over
 //                              the memory's; the clip coefficient from the first alone; the step count and Adam's bias corrections.
 //   rdistill_adam_kernel       ppo_adam_kernel's arithmetic, with the clip coefficient applied to the first nclip segments only (student.*): the
 //                              gradients of memory_s.* enter Adam as they are.  The same lane rewrites the element in the MLP's forward tiling and in
 //                              the transposed tilings; the memory's forward images are rnn_retile_kernel's.
-//   rdistill_mask_rows_kernel  Memory.reset(dones): zero h (and c) in every layer for the rows whose episode ended.
-//   rdistill_stats_kernel      clears the update's sums / writes the stats.
 // No host synchronisation inside an update and no atomics: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -23,10 +22,8 @@
 #include "lg_policy_internal.h"
 #include "lg_train_internal.h"
 #include "lg_train_recurrent_internal.h"
-#include "lg_distill_train_internal.h"
+#include "lg_train_sequence_internal.h"
 #include "../../include/lgdistill_recurrent.h"
-
-#define RDISTILL_MAX_STEPS 65535    // steps of one batch: blockIdx.y of the loss kernel
 
 struct RDistillScalars {
   float memory_norm;                 // the norm over memory_s.* of the last optimiser step
@@ -77,37 +74,12 @@ __global__ __launch_bounds__(256) void rdistill_adam_kernel(const TrainSeg* __re
   if (S.bw) S.bw[((((size_t)(i >> 4) * S.b_nb + (o >> 4)) * 64) + ((i & 15) | ((o & 3) << 4))) * 4 + ((o >> 2) & 3)] = th;
 }
 
-// h, c (layers, cap, H) (c may be NULL): rows j < N of every layer with dones[j] != 0 -> 0
-__global__ __launch_bounds__(256) void rdistill_mask_rows_kernel(float* __restrict__ h, float* __restrict__ c, const float* __restrict__ dones, int64_t N, int H,
-                                                                 int64_t layer_stride, int layers) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= N * H) return;
-  if (dones[idx / H] != 0.f)
-    for (int l = 0; l < layers; ++l) { h[l * layer_stride + idx] = 0.f; if (c) c[l * layer_stride + idx] = 0.f; }
-}
-
-// mode 0: clear the update's sums; 1: write the stats
-__global__ void rdistill_stats_kernel(DistillScalars* __restrict__ ds, const TrainScalars* __restrict__ sc, const RDistillScalars* __restrict__ rs,
-                                      lg_distill_rtrain_stats* __restrict__ stats, int mode) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (mode == 0) { ds->acc = 0.0; ds->steps = 0; ds->optimizer_steps = 0; return; }
-  stats->behavior = ds->acc / (double)ds->steps;
-  stats->optimizer_steps = (double)ds->optimizer_steps;
-  stats->grad_norm = (double)sc->norm;
-  stats->memory_grad_norm = (double)rs->memory_norm;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------ host side
-struct lg_distill_rtrain : TrainCore {
+struct lg_distill_rtrain : SeqCore {
   lg_mlp* student = nullptr;
   TrainMem tm;                                 // the student's memory, its workspaces and carried state (lg_train_recurrent_internal.h)
-  int A = 0;
   int nstudent = 0;                            // segments [0, nstudent): student.*, the ones the clip covers; then weight_ih, weight_hh per memory layer
   int64_t student_floats = 0;
-  int64_t seq_cap = 0;
-  int64_t* rows = nullptr;
-  float *loss_part = nullptr, *step_tmp = nullptr;
-  DistillScalars* ds = nullptr;
   RDistillScalars* rs = nullptr;
 };
 
@@ -125,7 +97,8 @@ static int rdistill_check_call(lg_distill_rtrain* p, const float* obs, const flo
 }
 
 // steps [first, first + nsteps) of the sequence as one batch; train: an optimiser step, else forward and loss only.  seq_loss: where the update keeps
-// these steps' losses, or NULL (a group call: the losses go to group_loss either way).
+// these steps' losses, or NULL (a group call: the losses go to group_loss either way, so last_steps counts a standalone forward-only group too; the
+// update's forward-only remainder leaves both alone).
 static int rdistill_steps(lg_distill_rtrain* p, const float* obs, const float* tgt, const float* dones, int64_t T, int64_t N, int64_t first, int64_t nsteps,
                           const lg_distill_train_hyper* h, bool train, float* seq_loss, hipStream_t st) {
   const int64_t n = nsteps * N, t0 = first % T;
@@ -140,15 +113,15 @@ static int rdistill_steps(lg_distill_rtrain* p, const float* obs, const float* t
   const TrainNet& Sn = p->net[0];
   const float* top = M->layer[M->ML - 1].hnew;
   train_launch_forward(p, top, top, nullptr, n, st);
-  distill_launch_loss(Sn.a[Sn.L], tgt, N, p->A, T, t0, nsteps, h->loss_type, train ? Sn.d[Sn.L - 1] : (float*)nullptr, p->loss_part, p->step_tmp, p->group_loss,
-                      seq_loss ? seq_loss : (train ? (float*)nullptr : p->group_loss), p->ds, train ? 1 : 0, st);
+  seq_launch_loss(p, Sn.a[Sn.L], tgt, N, T, t0, nsteps, h->loss_type, train ? Sn.d[Sn.L - 1] : (float*)nullptr, train || !seq_loss ? p->group_loss : (float*)nullptr,
+                  seq_loss, train ? 1 : 0, st);
   if (train) {
     // ---- the student backwards and dL/d(its input); then backwards through time: nothing is propagated into the observations
     train_launch_backward(p, n, st);
     mem_top_matmul(M, Sn, n, st);
     mem_backward(M, W, nullptr, st);
     // ---- every weight gradient in one slab pass (weight_ih of layer 0 gathers its observation rows), the reduction, the two norms, Adam, the images
-    distill_launch_rows(p->rows, n, N, T, t0, st);
+    seq_launch_rows(p->rows, n, N, T, t0, st);
     train_launch_wgrad_range(p, 0, p->nseg, obs, obs, p->rows, n, st);
     train_launch_reduce_range(p, 0, p->nseg, (int)((n + WGRAD_SLAB - 1) / WGRAD_SLAB), st);
     hipLaunchKernelGGL(rdistill_norm_kernel, dim3(1), dim3(256), 0, st, (const float*)p->norm_part, p->red_blocks * p->nstudent, p->red_blocks * p->nseg, h->max_grad_norm,
@@ -159,8 +132,7 @@ static int rdistill_steps(lg_distill_rtrain* p, const float* obs, const float* t
   }
   // ---- the running state: the memory after the last step, its dones applied
   if ((rc = mem_keep_running(M, W, st)) != LG_OK) return rc;
-  hipLaunchKernelGGL(rdistill_mask_rows_kernel, dim3((unsigned)((N * M->H + 255) / 256)), dim3(256), 0, st, M->cur_h, M->cur_c,
-                     dones + ((t0 + nsteps - 1) % T) * N, N, M->H, M->max_rows * M->H, M->ML);
+  seq_launch_mask_rows(M->cur_h, M->cur_c, dones + ((t0 + nsteps - 1) % T) * N, N, M->H, M->max_rows * M->H, M->ML, st);
   POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
@@ -199,12 +171,11 @@ lg_distill_rtrain* lg_distill_rtrain_create(lg_rnn* mem, lg_mlp* student, const 
   DeviceScope ds_(student->device);
   if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_distill_rtrain* p = new lg_distill_rtrain();
-  p->student = student; p->device = student->device; p->max_rows = max_rows; p->A = student->h.dims[Ls];
+  p->student = student; p->device = student->device; p->max_rows = max_rows;
   p->retile_own = rdistill_retile;
   TrainMem* M = &p->tm;
   bool ok = true;
   auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(p, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
-  const size_t R = (size_t)max_rows;
   ok = mem_alloc(p, M, mem);
   const int K = M->Gates * H, nbk = (K + 15) / 16;
   // ---- segments: the student's (net 0, at the head of the flat vector), then weight_ih / weight_hh of every memory layer.  Layer ids behind the
@@ -230,15 +201,8 @@ lg_distill_rtrain* lg_distill_rtrain_create(lg_rnn* mem, lg_mlp* student, const 
     float* bw0 = alloc((size_t)Nn.bnch[0] * (Nn.bkpad[0] / 16) * 256, true);
     Nn.bw[0] = bw0; p->seg[0].bw = bw0; p->seg[0].Ain = M->layer[ML - 1].hnew;
   }
-  auto zalloc = [&](size_t bytes) -> void* { void* d = ok ? train_alloc(p, bytes, true) : nullptr; if (!d) ok = false; return d; };
-  p->loss_part = (float*)zalloc(distill_loss_floats(max_rows, p->A) * sizeof(float));
-  p->rows = (int64_t*)zalloc(R * sizeof(int64_t));
-  p->step_tmp = (float*)zalloc(R * sizeof(float));
-  p->group_loss = (float*)zalloc(R * sizeof(float));
-  p->seq_cap = 1024;
-  p->seq_loss = (float*)zalloc((size_t)p->seq_cap * sizeof(float));
-  p->ds = (DistillScalars*)zalloc(sizeof(DistillScalars));
-  p->rs = (RDistillScalars*)zalloc(sizeof(RDistillScalars));
+  ok = ok && seq_alloc(p, max_rows, student->h.dims[Ls], true);
+  p->rs = (RDistillScalars*)alloc(sizeof(RDistillScalars) / sizeof(float), true);
   ok = ok && mem_upload_retile(p, M);
   const float* const* ws[1] = {wtab};
   const float* const* bs[1] = {btab};
@@ -252,11 +216,9 @@ lg_distill_rtrain* lg_distill_rtrain_create(lg_rnn* mem, lg_mlp* student, const 
 int lg_distill_rtrain_group(lg_distill_rtrain* p, const float* obs, const float* tgt, const float* dones, int64_t T, int64_t N, int64_t first_step, int64_t num_steps,
                             int32_t train, const lg_distill_train_hyper* hyper, void* stream) {
   POLICY_ENTRY;
-  const int rc = rdistill_check_call(p, obs, tgt, dones, T, N, hyper);
+  int rc = rdistill_check_call(p, obs, tgt, dones, T, N, hyper);
   if (rc != LG_OK) return rc;
-  if (num_steps < 1 || first_step < 0) return lg_policy_fail(LG_ERR_INVALID, "num_steps < 1 or first_step < 0");
-  if (num_steps > RDISTILL_MAX_STEPS) return lg_policy_fail(LG_ERR_INVALID, "num_steps > 65535");
-  if (N > p->max_rows || num_steps > p->max_rows / N) return lg_policy_fail(LG_ERR_INVALID, "num_steps * N > max_rows of the trainer");
+  if ((rc = seq_check_group(p, N, first_step, num_steps)) != LG_OK) return rc;
   DeviceScope ds_(p->device);
   return rdistill_steps(p, obs, tgt, dones, T, N, first_step, num_steps, hyper, train != 0, nullptr, (hipStream_t)stream);
 }
@@ -266,33 +228,8 @@ int lg_distill_rtrain_update(lg_distill_rtrain* p, const float* obs, const float
   POLICY_ENTRY;
   const int rc = rdistill_check_call(p, obs, tgt, dones, T, N, hyper);
   if (rc != LG_OK) return rc;
-  if (E < 1 || G < 1) return lg_policy_fail(LG_ERR_INVALID, "num_learning_epochs < 1 or gradient_length < 1");
-  if (G > RDISTILL_MAX_STEPS) return lg_policy_fail(LG_ERR_INVALID, "gradient_length > 65535");
-  if (N > p->max_rows || G > p->max_rows / N) return lg_policy_fail(LG_ERR_INVALID, "gradient_length * N > max_rows of the trainer");
-  DeviceScope ds_(p->device);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t total = (int64_t)E * T;
-  if (total > p->seq_cap) {                                  // (the old vector stays with the trainer: kernels in flight may still write it)
-    float* grown = (float*)train_alloc(p, (size_t)total * sizeof(float), true);
-    if (!grown) return LG_ERR_HIP;
-    p->seq_loss = grown; p->seq_cap = total;
-  }
-  p->last_update_steps = total;
-  hipLaunchKernelGGL(rdistill_stats_kernel, dim3(1), dim3(1), 0, st, p->ds, (const TrainScalars*)p->sc, (const RDistillScalars*)p->rs, stats, 0);
-  int64_t k = 0;
-  for (; total - k >= G; k += G) {
-    const int r2 = rdistill_steps(p, obs, tgt, dones, T, N, k, G, hyper, true, p->seq_loss + k, st);
-    if (r2 != LG_OK) return r2;
-  }
-  if (k < total) {
-    const int r2 = rdistill_steps(p, obs, tgt, dones, T, N, k, total - k, hyper, false, p->seq_loss + k, st);
-    if (r2 != LG_OK) return r2;
-  }
-  const int r3 = mem_keep_carry(&p->tm, st);
-  if (r3 != LG_OK) return r3;
-  if (stats) hipLaunchKernelGGL(rdistill_stats_kernel, dim3(1), dim3(1), 0, st, p->ds, (const TrainScalars*)p->sc, (const RDistillScalars*)p->rs, stats, 1);
-  POLICY_TRY(hipGetLastError());
-  return LG_OK;
+  return seq_update(p, T, N, E, G, [&](int64_t first, int64_t nsteps, bool train, float* seq_loss, hipStream_t st) {
+    return rdistill_steps(p, obs, tgt, dones, T, N, first, nsteps, hyper, train, seq_loss, st); }, &p->tm, stats, &p->rs->memory_norm, stream);
 }
 
 int64_t lg_distill_rtrain_parameter_count(lg_distill_rtrain* p) {
@@ -322,13 +259,7 @@ int lg_distill_rtrain_gradients(lg_distill_rtrain* p, float* g, float* norms, fl
 
 int lg_distill_rtrain_forward_outputs(lg_distill_rtrain* p, float* actions, void* stream) {
   POLICY_ENTRY;
-  if (!p || !actions) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (p->last_rows <= 0) return lg_policy_fail(LG_ERR_INVALID, "no group has run yet");
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  const TrainNet& S = p->net[0];
-  POLICY_TRY(hipMemcpy(actions, S.a[S.L], (size_t)p->last_rows * p->A * sizeof(float), hipMemcpyDeviceToHost));
-  return LG_OK;
+  return seq_forward_outputs(p, actions, stream);
 }
 
 int lg_distill_rtrain_step_losses(lg_distill_rtrain* p, float* losses, int64_t count, void* stream) {

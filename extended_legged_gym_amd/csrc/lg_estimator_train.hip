@@ -2,7 +2,8 @@
 // an estimator (depth encoder, combination layer, memory, decoder).  A group of G steps is one batch of G * N rows.  Reused as they are: the
 // encoder's forward kernels onto trainer-owned maps (lg_estimator_internal.h), lg_mlp_forward for the combination layer, the memory's forward with
 // saved gates / backward step / retile (lg_train_recurrent_internal.h), and for every dense layer the forward with saved activations, the backward
-// data pass, the slab weight gradients, the reduction, the norm and Adam of lg_train.hip (lg_train_internal.h).  New here, all fp32 on
+// data pass, the slab weight gradients, the reduction, the norm and Adam of lg_train.hip (lg_train_internal.h), the loss (mse | huber | l1), the
+// use_dones state mask and the update's loop (lg_train_sequence_internal.h).  New here, all fp32 on
 // v_mfma_f32_16x16x4_f32, activations channel last (env, y, x, channel):
 //
 //   est_dgrad_kernel          the data gradient of a convolution (and, as the 1 x 1 convolution of a 1 x 1 image, of a linear layer) as an implicit
@@ -20,10 +21,8 @@
 //                             EST_WGRAD_SLAB rows (blockIdx.y); a wave owns a 32 x 64 tile of [C_out][K + 1] and reads both operands from the maps
 //                             (the tile of ppo_wgrad_kernel); partials in torch's (ci, ky, kx) order, reduced in slab order by ppo_grad_reduce_kernel.
 //   est_act_delta_kernel      d *= act'(y) for the combination layer, whose weight gradient needs its pre-activation delta as rows.
-//   est_loss_kernel / _finish mse | huber (delta 1) | l1 per step (blockIdx.y: the step), the seed gradient into the decoder's last delta.
 //   est_conv_retile_kernel    the masters -> the forward images of conv 1-4 (lg_conv_tile_weights' layout, bit for bit) with their bias rows, and the
 //                             transposed images of conv 2-4.
-//   est_mask_rows_kernel      use_dones: zero state for the rows whose episode ended.
 // No atomics: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -38,11 +37,10 @@
 #include "lg_estimator_internal.h"
 #include "lg_train_internal.h"
 #include "lg_train_recurrent_internal.h"
+#include "lg_train_sequence_internal.h"
 #include "../../include/lgestimator_train.h"
 
 #define EST_WGRAD_SLAB 8192         // rows (env, output pixel) per slab of a convolution's weight gradient
-#define EST_LOSS_LANES 256
-#define EST_MAX_STEPS 65535         // steps of one batch: blockIdx.y of the loss kernel
 #define EST_DENSE_EXTRA 3           // depth_encoder.10, depth_encoder.12, combination_mlp.0
 
 LG_DEV float est_act_grad(float y, int act) {
@@ -282,85 +280,11 @@ __global__ __launch_bounds__(256) void est_conv_retile_kernel(const ConvRetile* 
   if (e < ((R.Cout + 63) & ~63)) R.fb[e] = e < R.Cout ? theta[R.boff + e] : 0.f;
 }
 
-// state (L, cap, H): rows j < N of every layer with dones[j] != 0 -> 0
-__global__ __launch_bounds__(256) void est_mask_rows_kernel(float* __restrict__ h, const float* __restrict__ dones, int64_t N, int H, int64_t layer_stride, int layers) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= N * H) return;
-  if (dones[idx / H] != 0.f)
-    for (int l = 0; l < layers; ++l) h[l * layer_stride + idx] = 0.f;
-}
-
-struct EstScalars {
-  double acc;                        // sum of the step losses since the last clear
-  int64_t steps;                     // steps in that sum
-  int64_t optimizer_steps;           // optimiser steps since the last clear
-};
-
-// out (steps, N * R): the predictions in batch order; target (T, N * R).  delta (may be NULL: forward only) gets dl / dout of the SUM of the steps'
-// means.  part[step][block]: the block's sum of element losses.
-__global__ __launch_bounds__(EST_LOSS_LANES) void est_loss_kernel(const float* __restrict__ out, const float* __restrict__ target, int64_t NR, int64_t T, int64_t t0,
-                                                                  int loss_type, float* __restrict__ delta, float* __restrict__ part) {
-  __shared__ float red[EST_LOSS_LANES];
-  const int64_t s = blockIdx.y, e = (int64_t)blockIdx.x * EST_LOSS_LANES + threadIdx.x;
-  float l = 0.f;
-  if (e < NR) {
-    const int64_t t = (t0 + s) % T;
-    const float d = out[s * NR + e] - target[t * NR + e];
-    const float inv = 1.f / (float)NR, ad = fabsf(d);
-    float g;
-    if (loss_type == LG_EST_LOSS_HUBER) {                    // F.huber_loss, delta = 1
-      l = ad < 1.f ? 0.5f * d * d : ad - 0.5f;
-      g = ad < 1.f ? d : (d > 0.f ? 1.f : -1.f);
-    } else if (loss_type == LG_EST_LOSS_L1) {                // F.l1_loss: sign(0) = 0
-      l = ad;
-      g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    } else {
-      l = d * d;
-      g = 2.f * d;
-    }
-    if (delta) delta[s * NR + e] = g * inv;
-  }
-  const float sum = block_sum_256(l, red);
-  if (threadIdx.x == 0) part[(size_t)s * gridDim.x + blockIdx.x] = sum;
-}
-
-// One block.  train != 0: the steps were a group (counts an optimiser step, fills group_loss).  seq_loss (may be NULL): the update's loss vector, at
-// the offset of the group's first step.
-__global__ __launch_bounds__(256) void est_loss_finish_kernel(const float* __restrict__ part, int nblocks, int64_t nsteps, int64_t NR, float* __restrict__ step_tmp,
-                                                              float* __restrict__ group_loss, float* __restrict__ seq_loss, EstScalars* __restrict__ es, int train) {
-  for (int64_t s = threadIdx.x; s < nsteps; s += 256) {
-    float sum = 0.f;
-    for (int b = 0; b < nblocks; ++b) sum += part[(size_t)s * nblocks + b];
-    step_tmp[s] = sum / (float)NR;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double acc = es->acc;
-  for (int64_t s = 0; s < nsteps; ++s) {
-    const float v = step_tmp[s];
-    acc += (double)v;
-    group_loss[s] = v;
-    if (seq_loss) seq_loss[s] = v;
-  }
-  es->acc = acc;
-  es->steps += nsteps;
-  if (train) es->optimizer_steps += 1;
-}
-
-// mode 0: clear the update's sums; 1: write the stats
-__global__ void est_stats_kernel(EstScalars* __restrict__ es, const TrainScalars* __restrict__ sc, lg_estimator_train_stats* __restrict__ stats, int mode) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (mode == 0) { es->acc = 0.0; es->steps = 0; es->optimizer_steps = 0; return; }
-  stats->estimation = es->acc / (double)es->steps;
-  stats->optimizer_steps = (double)es->optimizer_steps;
-  stats->grad_norm = (double)sc->norm;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------ host side
-struct lg_estimator_train : TrainCore {
+struct lg_estimator_train : SeqCore {
   lg_conv_encoder* enc = nullptr; lg_mlp* combine = nullptr; lg_mlp* decoder = nullptr;
   TrainMem tm;                                 // the memory, its workspaces and carried state (lg_train_recurrent_internal.h)
-  int F = 0, P_in = 0, cat_w = 0, Fc = 0, R_out = 0, act = 0;
+  int F = 0, P_in = 0, cat_w = 0, Fc = 0, act = 0;
   int nd = 0;                                  // dense segments [0, nd): decoder, depth_encoder.10 / .12, combination_mlp.0, the memory's; then conv 1-4
   int64_t map_floats[4] = {0, 0, 0, 0};
   float* map[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -368,9 +292,6 @@ struct lg_estimator_train : TrainCore {
   float *dA = nullptr, *dB = nullptr, *dpool = nullptr, *d5 = nullptr, *d6 = nullptr, *dcomb = nullptr;
   DgradLayer dg_comb, dg_l12, dg_l10, dg_conv[4][4];       // dg_conv[l][parity class]: conv l + 1 (index 0 unused); a stride-1 layer has class 0 only (Hc == 0: no launch)
   ConvRetile* d_cretile = nullptr; int64_t cretile_big = 0;
-  int64_t seq_cap = 0;
-  float *loss_part = nullptr, *step_tmp = nullptr;
-  EstScalars* es = nullptr;
 };
 
 static TrainMem* est_mem(lg_estimator_train* p) { return p ? &p->tm : nullptr; }
@@ -420,7 +341,7 @@ static int est_check_call(lg_estimator_train* p, const float* depth, const float
 // these steps' losses, or NULL.
 static int est_steps(lg_estimator_train* p, const float* depth, const float* proprio, const float* tgt, const float* dones, int64_t T, int64_t N, int64_t first,
                      int64_t nsteps, const lg_estimator_train_hyper* h, bool train, float* seq_loss, hipStream_t st) {
-  const int64_t n = nsteps * N, NR = N * p->R_out, t0 = first % T;
+  const int64_t n = nsteps * N, t0 = first % T;
   const int hw = p->enc->H * p->enc->W;
   const bool use_dones = h->use_dones != 0;
   TrainMem* M = &p->tm;
@@ -428,7 +349,7 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
   int rc = mem_open_carry(M, N, st);
   if (rc != LG_OK) return rc;
   p->last_rows = n;
-  p->last_steps = nsteps;
+  p->last_steps = nsteps;                                    // always, and group_loss with it: after an update they are the forward-only remainder's, if there is one
   // ---- the encoder and the cat rows, one launch list per run of consecutive time indices
   for (int64_t s = 0; s < nsteps;) {
     const int64_t t = (t0 + s) % T, len = std::min(nsteps - s, T - t), at = s * N;
@@ -445,11 +366,7 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
   const TrainNet& Dn = p->net[0];
   const float* top = M->layer[M->ML - 1].hnew;
   train_launch_forward(p, top, top, nullptr, n, st);
-  const int nblocks = (int)((NR + EST_LOSS_LANES - 1) / EST_LOSS_LANES);
-  hipLaunchKernelGGL(est_loss_kernel, dim3(nblocks, (unsigned)nsteps), dim3(EST_LOSS_LANES), 0, st, (const float*)Dn.a[Dn.L], tgt, NR, T, t0, h->loss_type,
-                     train ? Dn.d[Dn.L - 1] : (float*)nullptr, p->loss_part);
-  hipLaunchKernelGGL(est_loss_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)p->loss_part, nblocks, nsteps, NR, p->step_tmp, p->group_loss, seq_loss, p->es,
-                     train ? 1 : 0);
+  seq_launch_loss(p, Dn.a[Dn.L], tgt, N, T, t0, nsteps, h->loss_type, train ? Dn.d[Dn.L - 1] : (float*)nullptr, p->group_loss, seq_loss, train ? 1 : 0, st);
   if (train) {
     // ---- the decoder backwards and dL/d(its input); then backwards through time: layer 0 propagates into the combination layer's output
     train_launch_backward(p, n, st);
@@ -480,12 +397,7 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
   }
   // ---- the running state: the memory after the last step
   if ((rc = mem_keep_running(M, W, st)) != LG_OK) return rc;
-  if (use_dones) {
-    const float* dl = dones + ((t0 + nsteps - 1) % T) * N;
-    const int64_t lstride = M->max_rows * M->H;
-    hipLaunchKernelGGL(est_mask_rows_kernel, dim3((unsigned)((N * M->H + 255) / 256)), dim3(256), 0, st, M->cur_h, dl, N, M->H, lstride, M->ML);
-    if (M->cur_c) hipLaunchKernelGGL(est_mask_rows_kernel, dim3((unsigned)((N * M->H + 255) / 256)), dim3(256), 0, st, M->cur_c, dl, N, M->H, lstride, M->ML);
-  }
+  if (use_dones) seq_launch_mask_rows(M->cur_h, M->cur_c, dones + ((t0 + nsteps - 1) % T) * N, N, M->H, M->max_rows * M->H, M->ML, st);
   POLICY_TRY(hipGetLastError());
   return LG_OK;
 }
@@ -558,7 +470,6 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   lg_estimator_train* p = new lg_estimator_train();
   p->enc = enc; p->combine = combine; p->decoder = decoder; p->device = enc->device; p->max_rows = max_rows;
   p->F = F; p->cat_w = cat_w; p->P_in = cat_w - F; p->Fc = Fc; p->act = enc->act;
-  p->R_out = decoder->h.dims[decoder->h.L];
   p->retile_own = est_retile;
   TrainMem* M = &p->tm;
   bool ok = true;
@@ -659,15 +570,10 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
       dgrad(p->dg_conv[l][cls], C.Hin, C.Win, C.Cin, C.Hout, C.Wout, C.Cout, kConvShape[l][2], C.stride, C.pad, conv_bw[l], cls);
     }
   }
-  // ---- losses
-  auto zalloc = [&](size_t bytes) -> void* { void* d = ok ? train_alloc(p, bytes, true) : nullptr; if (!d) ok = false; return d; };
-  p->loss_part = (float*)zalloc(((size_t)max_rows * p->R_out / EST_LOSS_LANES + (size_t)max_rows + 1) * sizeof(float));
-  p->step_tmp = (float*)zalloc(R * sizeof(float));
-  p->group_loss = (float*)zalloc(R * sizeof(float));
-  p->seq_cap = 1024;
-  p->seq_loss = (float*)zalloc((size_t)p->seq_cap * sizeof(float));
-  p->es = (EstScalars*)zalloc(sizeof(EstScalars));
-  p->d_cretile = (ConvRetile*)zalloc(sizeof(ConvRetile) * 4);
+  // ---- losses (the row index stays out: only the first convolution's weight gradient reads rows by time index, and it computes them itself)
+  ok = ok && seq_alloc(p, max_rows, decoder->h.dims[decoder->h.L], false);
+  p->d_cretile = ok ? (ConvRetile*)train_alloc(p, sizeof(ConvRetile) * 4, true) : nullptr;
+  ok = ok && p->d_cretile;
   ok = ok && mem_upload_retile(p, M);
   const float* const* ws[1] = {wtab};
   const float* const* bs[1] = {btab};
@@ -683,11 +589,9 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
 int lg_estimator_train_group(lg_estimator_train* p, const float* depth, const float* proprio, const float* tgt, const float* dones, int64_t T, int64_t N,
                              int64_t first_step, int64_t num_steps, int32_t train, const lg_estimator_train_hyper* hyper, void* stream) {
   POLICY_ENTRY;
-  const int rc = est_check_call(p, depth, proprio, tgt, dones, T, N, hyper);
+  int rc = est_check_call(p, depth, proprio, tgt, dones, T, N, hyper);
   if (rc != LG_OK) return rc;
-  if (num_steps < 1 || first_step < 0) return lg_policy_fail(LG_ERR_INVALID, "num_steps < 1 or first_step < 0");
-  if (num_steps > EST_MAX_STEPS) return lg_policy_fail(LG_ERR_INVALID, "num_steps > 65535");
-  if (N > p->max_rows || num_steps > p->max_rows / N) return lg_policy_fail(LG_ERR_INVALID, "num_steps * N > max_rows of the trainer");
+  if ((rc = seq_check_group(p, N, first_step, num_steps)) != LG_OK) return rc;
   DeviceScope ds_(p->device);
   return est_steps(p, depth, proprio, tgt, dones, T, N, first_step, num_steps, hyper, train != 0, nullptr, (hipStream_t)stream);
 }
@@ -697,33 +601,8 @@ int lg_estimator_train_update(lg_estimator_train* p, const float* depth, const f
   POLICY_ENTRY;
   const int rc = est_check_call(p, depth, proprio, tgt, dones, T, N, hyper);
   if (rc != LG_OK) return rc;
-  if (E < 1 || G < 1) return lg_policy_fail(LG_ERR_INVALID, "num_learning_epochs < 1 or gradient_length < 1");
-  if (G > EST_MAX_STEPS) return lg_policy_fail(LG_ERR_INVALID, "gradient_length > 65535");
-  if (N > p->max_rows || G > p->max_rows / N) return lg_policy_fail(LG_ERR_INVALID, "gradient_length * N > max_rows of the trainer");
-  DeviceScope ds_(p->device);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t total = (int64_t)E * T;
-  if (total > p->seq_cap) {                                  // (the old vector stays with the trainer: kernels in flight may still write it)
-    float* grown = (float*)train_alloc(p, (size_t)total * sizeof(float), true);
-    if (!grown) return LG_ERR_HIP;
-    p->seq_loss = grown; p->seq_cap = total;
-  }
-  p->last_update_steps = total;
-  hipLaunchKernelGGL(est_stats_kernel, dim3(1), dim3(1), 0, st, p->es, (const TrainScalars*)p->sc, stats, 0);
-  int64_t k = 0;
-  for (; total - k >= G; k += G) {
-    const int r2 = est_steps(p, depth, proprio, tgt, dones, T, N, k, G, hyper, true, p->seq_loss + k, st);
-    if (r2 != LG_OK) return r2;
-  }
-  if (k < total) {
-    const int r2 = est_steps(p, depth, proprio, tgt, dones, T, N, k, total - k, hyper, false, p->seq_loss + k, st);
-    if (r2 != LG_OK) return r2;
-  }
-  const int r3 = mem_keep_carry(&p->tm, st);
-  if (r3 != LG_OK) return r3;
-  if (stats) hipLaunchKernelGGL(est_stats_kernel, dim3(1), dim3(1), 0, st, p->es, (const TrainScalars*)p->sc, stats, 1);
-  POLICY_TRY(hipGetLastError());
-  return LG_OK;
+  return seq_update(p, T, N, E, G, [&](int64_t first, int64_t nsteps, bool train, float* seq_loss, hipStream_t st) {
+    return est_steps(p, depth, proprio, tgt, dones, T, N, first, nsteps, hyper, train, seq_loss, st); }, &p->tm, stats, nullptr, stream);
 }
 
 int64_t lg_estimator_train_parameter_count(lg_estimator_train* p) {
@@ -743,13 +622,7 @@ int lg_estimator_train_gradients(lg_estimator_train* p, float* g, float* norm, f
 
 int lg_estimator_train_forward_outputs(lg_estimator_train* p, float* predictions, void* stream) {
   POLICY_ENTRY;
-  if (!p || !predictions) return lg_policy_fail(LG_ERR_INVALID, "null trainer or buffer");
-  if (p->last_rows <= 0) return lg_policy_fail(LG_ERR_INVALID, "no group has run yet");
-  DeviceScope ds_(p->device);
-  POLICY_TRY(hipStreamSynchronize((hipStream_t)stream));
-  const TrainNet& S = p->net[0];
-  POLICY_TRY(hipMemcpy(predictions, S.a[S.L], (size_t)p->last_rows * p->R_out * sizeof(float), hipMemcpyDeviceToHost));
-  return LG_OK;
+  return seq_forward_outputs(p, predictions, stream);
 }
 
 int lg_estimator_train_step_losses(lg_estimator_train* p, float* losses, int64_t count, void* stream) {

@@ -10,14 +10,14 @@ import numpy as np
 import torch
 
 from extended_legged_gym_amd import abi
-from .policy import NativeStudentTeacherRecurrent, _ptr
+from .policy import NativeStudentTeacherRecurrent
 from .ppo import _sequential_layers
-from .trainer import _NativeTrainer
+from .trainer import _NativeSequenceTrainer
 
 _MEMORY_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
 
-class NativeRecurrentDistillation(_NativeTrainer):
+class NativeRecurrentDistillation(_NativeSequenceTrainer):
     """rsl_rl's `Distillation` for a `NativeStudentTeacherRecurrent`, with its names and defaults.  `state_dict`: the `StudentTeacherRecurrent`
     state dict `policy`'s student was built from (`student.*`, `memory_s.rnn.*`, and whatever else it holds); `student.*` and `memory_s.*` seed the
     fp32 master parameters.  After `update`, the same `policy` object acts with the new student and memory; nothing is rebuilt.  As the reference
@@ -26,6 +26,8 @@ class NativeRecurrentDistillation(_NativeTrainer):
     _destroy = "lg_distill_rtrain_destroy"
     _prefix = "lg_distill_rtrain_"
     _declare = staticmethod(abi.declare_distill_rtrain)
+    _hyper_type, _losses, _loss_name = abi.lg_distill_train_hyper, abi.DISTILL_LOSSES, "behavior"
+    _norm_names = ("grad_norm", "memory_grad_norm")          # over `student.*`, the one the clip uses; over `memory_s.*`
     _carry_on_device = True          # the carry calls take device tensors: the state never visits the host
 
     def __init__(self, policy, state_dict, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse",
@@ -57,7 +59,7 @@ class NativeRecurrentDistillation(_NativeTrainer):
         self._rest = {k: v.detach().clone() for k, v in state_dict.items() if k not in trained}          # teacher.*, memory_t.*, std: never written
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self.num_updates = 0
-        self._group_steps = self._last_steps = self._last_rows = 0
+        self._out_w = policy.num_actions
         self.optimizer_steps = self.grad_norm = self.memory_grad_norm = None
         if max_rows is not None:
             self._create(int(max_rows))
@@ -73,9 +75,6 @@ class NativeRecurrentDistillation(_NativeTrainer):
                                          *[plist([m[j] for m in self._memory]) for j in range(4)])
         return self._fn("create")(self.policy.memory_s.handle, self.policy.student.handle, C.byref(q), self.learning_rate, max_rows)
 
-    def _hyper(self):
-        return abi.lg_distill_train_hyper(abi.DISTILL_LOSSES[self.loss_type], float(self.max_grad_norm) if self.max_grad_norm else 0.0)
-
     def _rows(self, rows):
         """The (T, N, .) observations, targets and dones of a `collect_distillation` dict, contiguous fp32 on the device (its `hidden_states` entry
         is not read, as in the reference)."""
@@ -86,54 +85,23 @@ class NativeRecurrentDistillation(_NativeTrainer):
         dones = rows["dones"].to(device=self.device, dtype=torch.float32).contiguous().view(T, N)
         return obs, tgt, dones, T, N
 
-    # ---- training
-    def group(self, rows, first_step, num_steps, train=True):
-        """One optimiser step on the sum of the losses of `num_steps` consecutive steps; step s reads time index (first_step + s) mod T.  A step
-        with time index 0 enters with the carried state, the first step otherwise with the state the last step run left.  `train=False`: forward
-        and losses only (the remainder of an update).  The policy's live memories are not touched."""
-        obs, tgt, dones, T, N = self._rows(rows)
-        self._ensure(max(int(num_steps), 1) * N)
-        hyper = self._hyper()
-        self._call("group", _ptr(obs), _ptr(tgt), _ptr(dones), T, N, int(first_step), int(num_steps), 1 if train else 0, C.byref(hyper))
-        self._group_steps, self._last_rows = int(num_steps), int(num_steps) * N
-
+    # ---- training (`group`, `gradients` and `forward_outputs` are `_NativeSequenceTrainer`'s, `group` leaving the policy's live memories alone; the
+    # checkpoint and carry methods `_NativeTrainer`'s; `state_dict()` is a `StudentTeacherRecurrent` state dict: `student.*` and `memory_s.*` as
+    # trained, everything else as given; the carried state stays on the device)
     def update(self, rows):
-        """`Distillation.update` on the dict `collect_distillation` returns: the loss dict {"behavior": mean over the E * T steps}.  The number of
-        optimiser steps and the last gradient norms arrive with the same device-to-host copy (`optimizer_steps`; `grad_norm` over `student.*`, the
-        one the clip uses; `memory_grad_norm` over `memory_s.*`).  Afterwards the student memory's live state is the carry and the teacher
-        memory's is forgotten (`policy.reset(hidden_states=(s, None))` at the head of the reference's last epoch)."""
-        self.num_updates += 1
-        obs, tgt, dones, T, N = self._rows(rows)
-        self._ensure(self.gradient_length * N)
-        hyper = self._hyper()
-        self._call("update", _ptr(obs), _ptr(tgt), _ptr(dones), T, N, self.num_learning_epochs, self.gradient_length, C.byref(hyper), _ptr(self._stats))
-        st = self._stats.cpu().tolist()
-        self._last_steps = self.num_learning_epochs * T
+        """`Distillation.update` on the dict `collect_distillation` returns: the loss dict {"behavior": mean over the E * T steps}, with
+        `optimizer_steps`, `grad_norm` and `memory_grad_norm`.  Afterwards the student memory's live state is the carry and the teacher memory's
+        is forgotten (`policy.reset(hidden_states=(s, None))` at the head of the reference's last epoch)."""
+        out = super().update(rows)
+        self.policy.reset(hidden_states=(self.get_hidden_states(), None))
+        return out
+
+    def _after_update(self, N):
+        """csrc/lg_distill_train_recurrent.hip, rdistill_steps: `if (train || !seq_loss) p->last_steps = nsteps;` -- the update's forward-only
+        remainder (it has a seq_loss) leaves the last group's; `last_rows` is the last pass's either way."""
         rem = self._last_steps % self.gradient_length
         self._group_steps = self.gradient_length if self._last_steps >= self.gradient_length else rem
         self._last_rows = (rem if rem else self.gradient_length) * N
-        self.optimizer_steps = int(st[1])
-        if self.optimizer_steps:
-            self.grad_norm, self.memory_grad_norm = st[2], st[3]
-        self.policy.reset(hidden_states=(self.get_hidden_states(), None))
-        return {"behavior": st[0]}
-
-    # ---- what the device holds (the checkpoint and carry methods are `_NativeTrainer`'s; `state_dict()` is a `StudentTeacherRecurrent` state dict:
-    # `student.*` and `memory_s.*` as trained, everything else as given; the carried state stays on the device)
-    def gradients(self):
-        """The last group's gradients before the clip (dict in the state dict's names), the two norms (over `student.*`, over `memory_s.*`), and
-        its per-step losses."""
-        self._need_handle()
-        g, norms, losses = np.empty(self.num_parameters, np.float32), np.zeros(2, np.float32), np.empty(self._group_steps, np.float32)
-        self._call("gradients", g.ctypes.data, norms.ctypes.data, losses.ctypes.data, losses.size)
-        return self._split(g), (float(norms[0]), float(norms[1])), [float(x) for x in losses]
-
-    def forward_outputs(self):
-        """The student's outputs (rows, A) of the last group's (or remainder's) forward pass, step-major."""
-        self._need_handle()
-        out = np.empty((self._last_rows, self.policy.num_actions), np.float32)
-        self._call("forward_outputs", out.ctypes.data)
-        return torch.from_numpy(out)
 
     def load_teacher(self, state_dict):
         """Swaps the teacher (`policy.load_teacher`: `actor.*` of a PPO checkpoint or `teacher.*`) in the policy's image and in the `teacher.*`

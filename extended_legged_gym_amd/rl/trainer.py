@@ -159,3 +159,60 @@ class _NativeTrainer(_NativeHandle):
         assert all(tuple(p.shape) == (L, N, H) for p in parts)
         self._ensure(N)
         self._call("set_carry", _ptr(parts[0]), _ptr(parts[1]) if len(parts) > 1 else None, N)
+
+
+class _NativeSequenceTrainer(_NativeTrainer):
+    """The owners of the three trainers that run a (T, N) sequence in groups of `gradient_length` steps (csrc/lg_train_sequence.hip).  A subclass
+    supplies `_rows(rows)` -> (the tensors its entry points take, in order, ..., T, N), the names below, and `_after_update(N)`: what the library's
+    `last_steps` and `last_rows` are after its `update`."""
+    _hyper_type = _losses = None          # the header's hyper-parameter struct and its loss-type numbers
+    _loss_name = None                     # the key of the loss dict `update` returns
+    _norm_names = ("grad_norm",)          # the attributes that take stats[2:], and the norms `gradients` returns
+    _norm_needs_step = True               # False: the norm attributes are written after an update without an optimiser step too
+    _group_has_train = True               # the header's group call takes `train`
+    _group_steps = _last_steps = _last_rows = 0          # steps of the last group / of the last update, rows of the last forward pass
+
+    def _hyper(self, *more):
+        return self._hyper_type(self._losses[self.loss_type], float(self.max_grad_norm) if self.max_grad_norm else 0.0, *more)
+
+    def group(self, rows, first_step, num_steps, train=True):
+        """One optimiser step on the sum of the losses of `num_steps` consecutive steps; step s reads time index (first_step + s) mod T.  With a
+        memory, a step with time index 0 enters with the carried state, the first step otherwise with the state the last step run left.
+        `train=False`: forward and losses only (the remainder of an update)."""
+        *tensors, T, N = self._rows(rows)
+        self._ensure(max(int(num_steps), 1) * N)
+        hyper = self._hyper()
+        self._call("group", *map(_ptr, tensors), T, N, int(first_step), int(num_steps), *([1 if train else 0] if self._group_has_train else []), C.byref(hyper))
+        self._group_steps, self._last_rows = int(num_steps), int(num_steps) * N
+
+    def update(self, rows):
+        """The reference's `update` on the dict the collector returns: the loss dict {`_loss_name`: mean over the E * T steps}.  The number of
+        optimiser steps and the last gradient norm(s) arrive with the same device-to-host copy."""
+        self.num_updates += 1
+        *tensors, T, N = self._rows(rows)
+        self._ensure(self.gradient_length * N)
+        hyper = self._hyper()
+        self._call("update", *map(_ptr, tensors), T, N, self.num_learning_epochs, self.gradient_length, C.byref(hyper), _ptr(self._stats))
+        st = self._stats.cpu().tolist()
+        self._last_steps = self.num_learning_epochs * T
+        self._after_update(N)
+        self.optimizer_steps = int(st[1])
+        if self.optimizer_steps or not self._norm_needs_step:
+            for name, value in zip(self._norm_names, st[2:]):
+                setattr(self, name, value)
+        return {self._loss_name: st[0]}
+
+    def gradients(self):
+        """The last group's gradients before the clip (dict in the state dict's names), the norm (a tuple where the trainer keeps more than one),
+        and its per-step losses."""
+        self._need_handle()
+        g, norms, losses = np.empty(self.num_parameters, np.float32), np.zeros(len(self._norm_names), np.float32), np.empty(self._group_steps, np.float32)
+        self._call("gradients", g.ctypes.data, norms.ctypes.data, losses.ctypes.data, losses.size)
+        return self._split(g), float(norms[0]) if norms.size == 1 else tuple(float(x) for x in norms), [float(x) for x in losses]
+
+    def forward_outputs(self, rows=None):
+        """The outputs (rows, `_out_w`) of the last group's (or remainder's) forward pass, step-major."""
+        self._need_handle()
+        out = np.empty((self._last_rows if rows is None else rows, self._out_w), np.float32)
+        self._call("forward_outputs", out.ctypes.data)
+        return torch.from_numpy(out)

@@ -20,7 +20,7 @@ CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
 LIB = os.path.join(CSRC, "liblgstep.so")
 HEADER = os.path.join(ROOT, "include", "lgdistill_recurrent.h")
 LDS_SHARED = 80 * 1024
-KERNELS = ("rdistill_norm_kernel", "rdistill_adam_kernel", "rdistill_mask_rows_kernel", "rdistill_stats_kernel")
+KERNELS = ("rdistill_norm_kernel", "rdistill_adam_kernel")
 
 
 def _msg(lib):

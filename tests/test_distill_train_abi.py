@@ -19,7 +19,7 @@ CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
 LIB = os.path.join(CSRC, "liblgstep.so")
 HEADER = os.path.join(ROOT, "include", "lgdistill.h")
 LDS_SHARED = 80 * 1024
-KERNELS = ("distill_rows_kernel", "distill_loss_kernel", "distill_loss_finish_kernel", "distill_stats_kernel")
+KERNELS = ("seq_rows_kernel", "seq_loss_kernel", "seq_loss_finish_kernel", "seq_stats_kernel", "seq_mask_rows_kernel")
 
 
 def _msg(lib):
@@ -104,10 +104,11 @@ def test_python_refusals_that_need_no_gpu():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_distill_kernels_do_not_spill_and_fit_the_lds(tmp_path):
-    """The route of tests/test_train_abi.py on csrc/lg_distill_train.hip."""
-    obj, fat, co = (str(tmp_path / n) for n in ("lg_distill_train.o", "fat.bin", "k.co"))
+    """The route of tests/test_train_abi.py on csrc/lg_train_sequence.hip, where the kernels of the feed-forward trainer (which has none of its own) and the
+    shared ones of the recurrent student's and the estimator's live."""
+    obj, fat, co = (str(tmp_path / n) for n in ("lg_train_sequence.o", "fat.bin", "k.co"))
     subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize", "-c", "-o", obj,
-                    os.path.join(CSRC, "lg_distill_train.hip")], check=True, capture_output=True)
+                    os.path.join(CSRC, "lg_train_sequence.hip")], check=True, capture_output=True)
     subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
     subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
                     "--unbundle"], check=True, capture_output=True)
