@@ -11,6 +11,11 @@ from extended_legged_gym_amd import abi
 from .policy import _check, _lib, _ptr
 
 
+def empty(device, *shape):
+    """An uninitialised float32 tensor: every row of a collection is written before it is read."""
+    return torch.empty(*shape, device=device, dtype=torch.float32)
+
+
 def _advance(env, policy, T):
     """What a collection of T steps leaves behind on the host side: T sampling calls drawn, T env steps counted."""
     policy._call += T
@@ -42,14 +47,12 @@ def collect_rollout(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_adva
     return out
 
 
-def rollout_rows(T, N, O, A, device, compute_returns=True):
+def rollout_rows(T, N, O, A, dev, compute_returns=True):
     """The (T, N, .) tensors of one PPO collection (`observations` O wide) and the `abi.lg_rollout` over them."""
-    def z(*shape):
-        return torch.empty(*shape, device=device, dtype=torch.float32)
-    out = dict(observations=z(T, N, O), actions=z(T, N, A), rewards=z(T, N, 1), dones=z(T, N, 1), values=z(T, N, 1),
-               actions_log_prob=z(T, N, 1), mu=z(T, N, A), sigma=z(T, N, A), last_values=z(N, 1))
+    out = dict(observations=empty(dev, T, N, O), actions=empty(dev, T, N, A), rewards=empty(dev, T, N, 1), dones=empty(dev, T, N, 1), values=empty(dev, T, N, 1),
+               actions_log_prob=empty(dev, T, N, 1), mu=empty(dev, T, N, A), sigma=empty(dev, T, N, A), last_values=empty(dev, N, 1))
     if compute_returns:
-        out.update(returns=z(T, N, 1), advantages=z(T, N, 1))
+        out.update(returns=empty(dev, T, N, 1), advantages=empty(dev, T, N, 1))
     return out, abi.lg_rollout(**{k: v.data_ptr() for k, v in out.items()})
 
 
@@ -99,6 +102,30 @@ class EpisodeTracker:
         self.lenbuffer.extend(both[1].tolist())
 
 
+def _one_mode(obs_normalizer, privileged_obs_normalizer):
+    """The `training` flag of a call with up to two normalisers: one mode for both handles (the reference keeps the second in training mode
+    with the first, `on_policy_runner.py:736-738`), the only one's when there is one, 0 without any."""
+    norms = [n for n in (obs_normalizer, privileged_obs_normalizer) if n is not None]
+    if len(norms) == 2 and bool(norms[0].training) != bool(norms[1].training):
+        raise ValueError("obs_normalizer and privileged_obs_normalizer are in different modes")
+    return int(bool(norms[0].training)) if norms else 0
+
+
+def _episode_hook(hooks, env, episode_tracker, T, N, dev):
+    """Points `hooks.episode` at an `abi.lg_runner_episode` over fresh `raw_rewards` (T, N, 1), `episode_extras` (T, K), `ep_return` /
+    `ep_length` (T, N, 1) and the tracker's live sums, and returns the four tensors by name.  No tracker: nothing."""
+    if episode_tracker is None:
+        return {}
+    extra = dict(raw_rewards=empty(dev, T, N, 1), episode_extras=empty(dev, T, env.core.t["extras_episode"].numel()), ep_return=empty(dev, T, N, 1),
+                 ep_length=empty(dev, T, N, 1))
+    assert episode_tracker.cur_reward_sum.shape == (N,) and episode_tracker.cur_reward_sum.device == extra["raw_rewards"].device
+    hooks.episode = C.pointer(abi.lg_runner_episode(raw_rewards=extra["raw_rewards"].data_ptr(), extras=extra["episode_extras"].data_ptr(),
+                                                    cur_reward_sum=episode_tracker.cur_reward_sum.data_ptr(),
+                                                    cur_episode_length=episode_tracker.cur_episode_length.data_ptr(),
+                                                    ep_return=extra["ep_return"].data_ptr(), ep_length=extra["ep_length"].data_ptr()))
+    return extra
+
+
 def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_advantage=True, compute_returns=True, obs_normalizer=None,
                             episode_tracker=None, privileged_obs_normalizer=None, noise_uniforms=None, actor_columns=None):
     """`collect_rollout` through `lg_runner_collect` (include/lgrunner.h), with the runner's two device pieces between the launches of the one
@@ -133,37 +160,21 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
         O = policy.memory_a.input_size if rec else policy.actor.dims[0]
         if actor_columns is not None and (hist is not None or int(actor_columns) != O):
             raise ValueError(f"actor_columns = {actor_columns}: the actor reads {O} columns" + (", and the env has an observation history" if hist is not None else ""))
-
-    def z(*shape):
-        return torch.empty(*shape, device=dev, dtype=torch.float32)
     out, rows = rollout_rows(T, N, O, A, dev, compute_returns)
-    hooks = abi.lg_runner_hooks(normalizer=obs_normalizer.handle if obs_normalizer is not None else None,
-                                training=int(obs_normalizer.training) if obs_normalizer is not None else 0)
     if obs_normalizer is not None and obs_normalizer.num_features != O:
         raise ValueError(f"the normaliser holds {obs_normalizer.num_features} columns, the env's observations {O}")
-    extra = {}
-    if episode_tracker is not None:
-        K = env.core.t["extras_episode"].numel()
-        assert episode_tracker.cur_reward_sum.shape == (N,) and episode_tracker.cur_reward_sum.device == out["dones"].device
-        extra = dict(raw_rewards=z(T, N, 1), episode_extras=z(T, K), ep_return=z(T, N, 1), ep_length=z(T, N, 1))
-        episode = abi.lg_runner_episode(raw_rewards=extra["raw_rewards"].data_ptr(), extras=extra["episode_extras"].data_ptr(),
-                                        cur_reward_sum=episode_tracker.cur_reward_sum.data_ptr(), cur_episode_length=episode_tracker.cur_episode_length.data_ptr(),
-                                        ep_return=extra["ep_return"].data_ptr(), ep_length=extra["ep_length"].data_ptr())
-        hooks.episode = C.pointer(episode)
+    hooks = abi.lg_runner_hooks(normalizer=obs_normalizer.handle if obs_normalizer is not None else None,
+                                training=_one_mode(obs_normalizer, privileged_obs_normalizer))
+    extra = _episode_hook(hooks, env, episode_tracker, T, N, dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     head = (_ptr(policy.std), policy.seed, policy._call + 1, T, float(gamma), float(lam), int(bool(normalize_advantage)), C.byref(rows))
     call, name, tail, last, keep = lib.lg_runner_collect, "lg_runner_collect", (), None, []
     if privileged:          # the second stream: its rows, the actor's layer and the critic's normaliser ride in one more struct
-        crit = privileged_obs_normalizer
-        if crit is not None:          # (its width is the library's to check, with every other width of the call)
-            if not hooks.normalizer:
-                hooks.training = int(crit.training)          # (one mode for both handles: the critic's when it is the only one)
-            elif bool(crit.training) != bool(hooks.training):
-                raise ValueError("obs_normalizer and privileged_obs_normalizer are in different modes")
-        out["privileged_observations"] = z(T, N, O_c)
+        crit = privileged_obs_normalizer          # (its width is the library's to check, with every other width of the call)
+        out["privileged_observations"] = empty(dev, T, N, O_c)
         layer = None
         if hist is not None:
-            last = z(N, O)
+            last = empty(dev, N, O)
             layer, keep = _history_layer(env, policy, hist, T, N, noise_uniforms)
         elif noise_uniforms is not None:
             raise ValueError("noise_uniforms needs an env with an observation history")
@@ -257,12 +268,9 @@ def _collect_distillation(env, policy, num_steps, noise_uniforms, hooks=None):
     rec = getattr(policy, "is_recurrent", False)
     T, N, Ot, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
     Os = policy.memory_s.input_size if rec else policy.student.dims[0]
-
-    def z(*shape):
-        return torch.empty(*shape, device=dev, dtype=torch.float32)
-    out = dict(observations=z(T, N, Os), privileged_observations=z(T, N, Ot), actions=z(T, N, A), privileged_actions=z(T, N, A), rewards=z(T, N, 1),
-               dones=z(T, N, 1))
-    last = z(N, Os)
+    out = dict(observations=empty(dev, T, N, Os), privileged_observations=empty(dev, T, N, Ot), actions=empty(dev, T, N, A),
+               privileged_actions=empty(dev, T, N, A), rewards=empty(dev, T, N, 1), dones=empty(dev, T, N, 1))
+    last = empty(dev, N, Os)
     rows = abi.lg_distill_rollout(last_observations=last.data_ptr(), **{k: v.data_ptr() for k, v in out.items()})
     hist = getattr(env, "obs_history", None)
     layer, keep = None, []
@@ -308,25 +316,11 @@ def collect_distillation_tracked(env, policy, num_steps, obs_normalizer=None, pr
     episode_tracker (`EpisodeTracker`): adds `raw_rewards` (T, N, 1) (equal to `rewards`: distillation stores the env's reward as it is),
     `episode_extras` (T, K), and `ep_return` / `ep_length` (T, N, 1), defined where `dones > 0`, as `collect_rollout_tracked` returns them; the
     tracker's live sums advance in place."""
-    dev = policy.device
     T, N = int(num_steps), env.core.t["obs_buf"].shape[0]
-    norms = [n for n in (obs_normalizer, privileged_obs_normalizer) if n is not None]
-    if len(norms) == 2 and bool(norms[0].training) != bool(norms[1].training):
-        raise ValueError("obs_normalizer and privileged_obs_normalizer are in different modes")
     hooks = abi.lg_runner_distill(student_normalizer=obs_normalizer.handle if obs_normalizer is not None else None,
                                   teacher_normalizer=privileged_obs_normalizer.handle if privileged_obs_normalizer is not None else None,
-                                  training=int(bool(norms[0].training)) if norms else 0)
-    extra = {}
-    if episode_tracker is not None:
-        def z(*shape):
-            return torch.empty(*shape, device=dev, dtype=torch.float32)
-        K = env.core.t["extras_episode"].numel()
-        assert episode_tracker.cur_reward_sum.shape == (N,) and episode_tracker.cur_reward_sum.device == policy.std.device
-        extra = dict(raw_rewards=z(T, N, 1), episode_extras=z(T, K), ep_return=z(T, N, 1), ep_length=z(T, N, 1))
-        episode = abi.lg_runner_episode(raw_rewards=extra["raw_rewards"].data_ptr(), extras=extra["episode_extras"].data_ptr(),
-                                        cur_reward_sum=episode_tracker.cur_reward_sum.data_ptr(), cur_episode_length=episode_tracker.cur_episode_length.data_ptr(),
-                                        ep_return=extra["ep_return"].data_ptr(), ep_length=extra["ep_length"].data_ptr())
-        hooks.episode = C.pointer(episode)
+                                  training=_one_mode(obs_normalizer, privileged_obs_normalizer))
+    extra = _episode_hook(hooks, env, episode_tracker, T, N, policy.device)
     out = _collect_distillation(env, policy, T, noise_uniforms, hooks)
     out.update(extra)
     return out

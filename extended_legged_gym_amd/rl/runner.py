@@ -11,7 +11,9 @@ Refused by name (`NotImplementedError`): `Distillation` (`rl.NativeDistillationR
 Privileged critic observations (`env.num_privileged_obs` with `get_privileged_observations()` returning that tensor; `on_policy_runner.py:161-215`):
 the critic's first layer / `memory_c` is `num_privileged_obs` wide, there are two normalisers, the rollout holds `privileged_observations`, and the
 collection is the one-call two-stream collector (`lg_runner_collect_privileged`) for an env the library can run whole (`collects_privileged_natively`),
-the host loop for any other."""
+the host loop for any other.
+
+`NativeRunner` is the base of this runner and of `NativeDistillationRunner`: the loop, the host collection skeleton and the checkpoint path."""
 import json
 import os
 import statistics
@@ -19,7 +21,7 @@ import time
 
 import torch
 
-from .collector import EpisodeTracker, collect_rollout_tracked, rollout_rows
+from .collector import EpisodeTracker, collect_rollout_tracked, empty, rollout_rows
 from .normalizer import STATE_KEYS, NativeEmpiricalNormalization
 from .storage import compute_returns
 
@@ -73,6 +75,21 @@ def policy_noise_std_type(policy_class_name, policy_cfg):
     return "scalar" if policy_class_name == "ActorCriticRecurrent" else policy_cfg.get("noise_std_type", "scalar")
 
 
+def checked_activation(policy_cfg):
+    activation = policy_cfg.get("activation", "elu")
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"Unknown activation: {activation}")
+    return activation
+
+
+def seeded_state_dict(seed, module_class, *args):
+    """The `state_dict()` of `module_class(*args)`, its initial weights drawn under `seed` without disturbing the global generator."""
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(int(seed))
+        module = module_class(*args)
+    return {k: v.detach().clone() for k, v in module.state_dict().items()}
+
+
 def initial_state_dict(policy_class_name, num_obs, num_actions, policy_cfg, seed, num_critic_obs=None):
     """The `state_dict()` of a freshly initialised `ActorCritic` / `ActorCriticRecurrent` (torch's default `nn.Linear` / `nn.LSTM` / `nn.GRU`
     initialisation, drawn under `seed` without disturbing the global generator): keys `std` / `log_std`, `actor.N.*`, `critic.N.*`,
@@ -80,19 +97,14 @@ def initial_state_dict(policy_class_name, num_obs, num_actions, policy_cfg, seed
     (`num_privileged_obs`); None or `num_obs`: the same draws, the same bits as without it."""
     if policy_class_name not in ("ActorCritic", "ActorCriticRecurrent"):
         raise NotImplementedError(f"policy_class_name {policy_class_name}: the native runner builds ActorCritic and ActorCriticRecurrent")
-    activation = policy_cfg.get("activation", "elu")
-    if activation not in ACTIVATIONS:
-        raise ValueError(f"Unknown activation: {activation}")
+    activation = checked_activation(policy_cfg)
     rnn = None
     if policy_class_name == "ActorCriticRecurrent":
         rnn = dict(rnn_type=str(policy_cfg.get("rnn_type", "lstm")).lower(), rnn_hidden_size=int(policy_cfg.get("rnn_hidden_size", 256)),
                    rnn_num_layers=int(policy_cfg.get("rnn_num_layers", 1)))
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(int(seed))
-        module = _ActorCritic(num_obs, num_actions, policy_cfg.get("actor_hidden_dims", [256, 256, 256]), policy_cfg.get("critic_hidden_dims", [256, 256, 256]),
-                              activation, float(policy_cfg.get("init_noise_std", 1.0)), policy_noise_std_type(policy_class_name, policy_cfg), rnn,
-                              None if num_critic_obs is None else int(num_critic_obs))
-    return {k: v.detach().clone() for k, v in module.state_dict().items()}
+    return seeded_state_dict(seed, _ActorCritic, num_obs, num_actions, policy_cfg.get("actor_hidden_dims", [256, 256, 256]),
+                             policy_cfg.get("critic_hidden_dims", [256, 256, 256]), activation, float(policy_cfg.get("init_noise_std", 1.0)),
+                             policy_noise_std_type(policy_class_name, policy_cfg), rnn, None if num_critic_obs is None else int(num_critic_obs))
 
 
 # ---------------------------------------------------------------------------------------------------------------- checkpoint layout (no GPU)
@@ -113,30 +125,40 @@ def _adam_group(learning_rate, count):
     return group
 
 
-def adam_state_dict(optimizer_state):
-    """`NativePPO.optimizer_state()` (dicts `exp_avg`, `exp_avg_sq`, `parameters` by name, `step`, `learning_rate`) -> what
-    `torch.optim.Adam(policy.parameters(), lr).state_dict()` holds: parameter i of `parameter_order`, per parameter `step` (float32 scalar),
-    `exp_avg`, `exp_avg_sq`; an optimiser that has not stepped holds no state."""
-    names = parameter_order(optimizer_state["exp_avg"].keys())
+def to_adam_state_dict(optimizer_state, names, order, is_trained):
+    """A trainer's `optimizer_state()` (dicts `exp_avg`, `exp_avg_sq`, `parameters` over the trained names, `step`, `learning_rate`) and the names
+    of the whole state dict -> what `torch.optim.Adam(policy.parameters(), lr).state_dict()` holds: one group over ALL parameters in `order`,
+    and state entries (`step` a float32 scalar, `exp_avg`, `exp_avg_sq`) only for the `is_trained` ones, which are the only ones torch's lazy
+    state initialisation ever reaches; an optimiser that has not stepped holds no state."""
+    names = order(names)
+    trained = [n for n in names if is_trained(n)]
+    if sorted(trained) != sorted(optimizer_state["exp_avg"].keys()):
+        raise KeyError(f"the optimiser's tensors {sorted(optimizer_state['exp_avg'].keys())} are not the trained ones {sorted(trained)}")
     state = {}
     if int(optimizer_state["step"]) > 0:
         for i, n in enumerate(names):
-            state[i] = {"step": torch.tensor(float(optimizer_state["step"]), dtype=torch.float32),
-                        "exp_avg": optimizer_state["exp_avg"][n].detach().cpu().clone(), "exp_avg_sq": optimizer_state["exp_avg_sq"][n].detach().cpu().clone()}
+            if is_trained(n):
+                state[i] = {"step": torch.tensor(float(optimizer_state["step"]), dtype=torch.float32),
+                            "exp_avg": optimizer_state["exp_avg"][n].detach().cpu().clone(), "exp_avg_sq": optimizer_state["exp_avg_sq"][n].detach().cpu().clone()}
     return {"state": state, "param_groups": [_adam_group(optimizer_state["learning_rate"], len(names))]}
 
 
-def native_optimizer_state(model_state_dict, adam):
-    """The inverse: a checkpoint's `model_state_dict` and `optimizer_state_dict` -> the dict `NativePPO.load_optimizer_state` takes."""
-    names = parameter_order(model_state_dict.keys())
+def from_adam_state_dict(model_state_dict, adam, order, is_trained):
+    """The inverse: a checkpoint's `model_state_dict` and `optimizer_state_dict` -> the dict a trainer's `load_optimizer_state` takes, over the
+    trained names.  An untrained parameter must hold no moments (only distillation has any: the teacher and `std`)."""
+    names = order(model_state_dict.keys())
     group = adam["param_groups"][0]
     if len(adam["param_groups"]) != 1 or list(group["params"]) != list(range(len(names))):
         raise ValueError("optimizer_state_dict: expected one parameter group over the policy's parameters in order")
-    params = {n: model_state_dict[n].detach().cpu() for n in names}
     state, steps = adam["state"], set()
-    avg, sq = {}, {}
+    params, avg, sq = {}, {}, {}
     for i, n in enumerate(names):
         entry = state.get(i)
+        if not is_trained(n):
+            if entry is not None:
+                raise ValueError(f"optimizer_state_dict: parameter {i} ({n}) holds moments, but distillation never trains it")
+            continue
+        params[n] = model_state_dict[n].detach().cpu()
         if entry is None:
             avg[n], sq[n] = torch.zeros_like(params[n]), torch.zeros_like(params[n])
             steps.add(0)
@@ -148,6 +170,20 @@ def native_optimizer_state(model_state_dict, adam):
     if len(steps) != 1:
         raise ValueError(f"optimizer_state_dict: the parameters have different step counts {sorted(steps)}")
     return dict(parameters=params, exp_avg=avg, exp_avg_sq=sq, step=steps.pop(), learning_rate=float(group["lr"]))
+
+
+def _every_name(name):
+    return True
+
+
+def adam_state_dict(optimizer_state):
+    """`NativePPO.optimizer_state()` -> `torch.optim.Adam(policy.parameters(), lr).state_dict()`: parameter i of `parameter_order`, all trained."""
+    return to_adam_state_dict(optimizer_state, optimizer_state["exp_avg"].keys(), parameter_order, _every_name)
+
+
+def native_optimizer_state(model_state_dict, adam):
+    """The inverse: a checkpoint's `model_state_dict` and `optimizer_state_dict` -> the dict `NativePPO.load_optimizer_state` takes."""
+    return from_adam_state_dict(model_state_dict, adam, parameter_order, _every_name)
 
 
 # ---------------------------------------------------------------------------------------------------------------- logging
@@ -201,12 +237,185 @@ def steps_outside_the_library(env):
     return hasattr(env, "_after_native") or getattr(type(env), "step", None) is not LeggedRobot.step
 
 
-# ---------------------------------------------------------------------------------------------------------------- the runner
-class RunnerLogging:
-    """What the native runners share around their loops (`NativeOnPolicyRunner`, `NativeDistillationRunner`): the writer, the per-iteration `log`
-    (`on_policy_runner.py:488-660`) and the `Episode/*` means.  A runner provides `env`, `alg`, `num_steps_per_env`, `writer`, `log_dir`,
-    `disable_logs`, `tot_timesteps`, `tot_time`, `layered` and `_host_episode`."""
+# ---------------------------------------------------------------------------------------------------------------- the runners
+def _clone_state(hidden_states):
+    """A copy of a memory's live state: `(h, c)` for an LSTM, `h` for a GRU."""
+    return tuple(h.clone() for h in hidden_states) if isinstance(hidden_states, tuple) else hidden_states.clone()
 
+
+class NativeRunner:
+    """What the native runners share (`NativeOnPolicyRunner`, `NativeDistillationRunner`): the split of the train config, the normalisers and
+    counters, the modes, `learn` (`on_policy_runner.py:347-486`), the host collection loop (`:395-431`), `save`, the writer, the per-iteration
+    `log` (`:488-660`) and the `Episode/*` means.  A runner supplies
+      `_normalizers()`        one handle (or None) per observation stream: one stream, or the policy's and the critic's / teacher's;
+      `_before_learn()`       what must hold before `learn` opens anything (default: nothing);
+      `_parameter_order`, `_adam_state_dict(model)`        the checkpoint layout `save` writes;
+      `_collect_one_call(tracker)`        the collection as one call into the library;
+      `_host_rows`, `_host_act`, `_host_reward`, `_host_finish`        the algorithm's part of the host loop (see `_collect_host`);
+      `load`."""
+
+    def _configure(self, env, train_cfg, log_dir, device, algorithm, policy):
+        """The three sections of `train_cfg` as dicts of this runner; returns the algorithm's and the policy's class name (`class_name` in the
+        section, else `runner.*_class_name`, else the defaults given)."""
+        self.cfg, self.alg_cfg, self.policy_cfg = dict(train_cfg["runner"]), dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
+        self.env, self.device, self.log_dir = env, torch.device(device), log_dir
+        self.seed = int(train_cfg.get("seed", 1))
+        return (self.alg_cfg.pop("class_name", self.cfg.get("algorithm_class_name", algorithm)),
+                self.policy_cfg.pop("class_name", self.cfg.get("policy_class_name", policy)))
+
+    def _start(self, widths, layered):
+        """One normaliser per width with `empirical_normalization` (a single one serves both attributes), the counters, the env's first reset."""
+        self.num_steps_per_env, self.save_interval = int(self.cfg["num_steps_per_env"]), int(self.cfg["save_interval"])
+        self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
+        norms = [NativeEmpiricalNormalization([w], until=int(1.0e8), device=str(self.device)) for w in widths] if self.empirical_normalization else [None]
+        self.obs_normalizer, self.privileged_obs_normalizer = norms[0], norms[-1]
+        self.layered = layered
+        self.writer, self.disable_logs = None, False
+        self.tot_timesteps, self.tot_time, self.current_learning_iteration = 0, 0.0, 0
+        self._host_obs, self._host_priv, self._host_episode = None, None, None
+        self.env.reset()
+
+    # ---- modes (`:729-754`)
+    def _handles(self):
+        return [norm for norm in self._normalizers() if norm is not None]
+
+    def train_mode(self):
+        for norm in self._handles():
+            norm.train()
+
+    def eval_mode(self):
+        for norm in self._handles():
+            norm.eval()
+
+    def forget_carried(self):
+        """The next collection starts from the env's raw rows: the normalisers' carried rows and the host loop's are dropped."""
+        for norm in self._handles():
+            norm.forget_carried()
+        self._host_obs = self._host_priv = None
+
+    # ---- collection
+    def _collect(self, tracker):
+        """One collection of `num_steps_per_env` steps: the dict of the runner's tracked one-call collector, from that call or from the host loop."""
+        return self._collect_host(tracker, self.num_steps_per_env) if self.layered else self._collect_one_call(tracker)
+
+    def _second_row(self, obs, second=None):
+        """`on_policy_runner.py:403-412`: the step's second value, else the getter, else the observations."""
+        if second is None:
+            second = self.env.get_privileged_observations() if hasattr(self.env, "get_privileged_observations") else None
+        return (obs if second is None else second).to(self.device)
+
+    def _collect_host(self, tracker, T):
+        """The same dict from a host loop over `env.step`, for env classes whose step is more than the native one.  The runner's part:
+        `_host_rows(T, N, obs, priv)` allocates the algorithm's (T, N, .) rows, `_host_act(d, t, obs, priv)` runs the policy on row t, stores
+        what it gives and returns the actions, `_host_reward(d, t, rew, infos)` writes `rewards[t]`, `_host_finish(d, last)` adds what the
+        algorithm computes behind the loop from the last row of the critic's stream.  With one stream `priv` is None and the step's second
+        value is not read."""
+        env, policy, dev = self.env, self.alg.policy, self.device
+        norms = self._normalizers()
+        two = len(norms) == 2
+        norm, pnorm = norms[0], norms[1] if two else None
+        obs = self._host_obs if self._host_obs is not None else env.get_observations().to(dev)          # (the first rows pass no normaliser: :364-366)
+        priv = None
+        if two:
+            priv = self._host_priv if self._host_priv is not None else self._second_row(obs)
+        N, ex = env.num_envs, env.core.t["extras_episode"]
+        d = self._host_rows(T, N, obs, priv)
+        d.update(raw_rewards=empty(dev, T, N, 1), episode_extras=empty(dev, T, ex.numel()))
+        self._host_episode = []
+        for t in range(T):
+            d["observations"][t] = obs
+            if two:
+                d["privileged_observations"][t] = priv
+            obs, second, rew, dones, infos = env.step(self._host_act(d, t, obs, priv))
+            obs = obs.to(dev)
+            if two:
+                priv = self._second_row(obs, second)
+                if norm is not None and pnorm is not None:
+                    obs, priv = norm.step_pair(pnorm, obs, priv)
+                else:
+                    obs = norm(obs) if norm is not None else obs
+                    priv = pnorm(priv) if pnorm is not None else priv.clone()          # (the env's own buffer: the next step overwrites it)
+            elif norm is not None:
+                obs = norm(obs)
+            d["raw_rewards"][t, :, 0] = rew
+            self._host_reward(d, t, rew, infos)
+            d["dones"][t, :, 0] = (dones != 0).float()
+            d["episode_extras"][t] = ex
+            # infos["episode"] of this step, for the entries that are not views of extras_episode (a layer's own means): on_policy_runner.py:511-512
+            self._host_episode.append({k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in infos.get("episode", {}).items()
+                                       if not _view_index(v, ex)[0]})
+            policy.reset(dones)
+        self._host_obs, self._host_priv = obs.clone(), priv.clone() if two else None
+        self._host_finish(d, priv if two else obs)
+        ep_return, ep_length = tracker.track(d["raw_rewards"], d["dones"])
+        d["ep_return"], d["ep_length"] = ep_return.reshape(T, N, 1), ep_length.reshape(T, N, 1)
+        return d
+
+    def _host_finish(self, d, last):
+        pass
+
+    # ---- the loop (`:347-486`)
+    def _before_learn(self):
+        pass
+
+    def learn(self, num_learning_iterations, init_at_random_ep_len=False):
+        env = self.env
+        self._before_learn()
+        self._open_writer()
+        if init_at_random_ep_len:
+            env.episode_length_buf[:] = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
+        self.forget_carried()
+        self.train_mode()
+        tracker = EpisodeTracker(env.num_envs, self.device)
+        start_iter = self.current_learning_iteration
+        tot_iter = start_iter + int(num_learning_iterations)
+        for it in range(start_iter, tot_iter):
+            start = time.time()
+            rollout = self._collect(tracker)
+            tracker.extend(rollout["dones"], rollout["ep_return"], rollout["ep_length"])          # (the one device-to-host copy of the collection)
+            stop = time.time()
+            collection_time, start = stop - start, stop
+            loss_dict = self.alg.update(rollout)
+            stop = time.time()
+            learn_time = stop - start
+            self.current_learning_iteration = it
+            if self.log_dir is not None and not self.disable_logs:
+                self.log(dict(it=it, tot_iter=tot_iter, start_iter=start_iter, num_learning_iterations=int(num_learning_iterations), collection_time=collection_time,
+                              learn_time=learn_time, loss_dict=loss_dict, rewbuffer=tracker.rewbuffer, lenbuffer=tracker.lenbuffer,
+                              episode=self._episode_means(rollout)))
+                if it % self.save_interval == 0:
+                    self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
+            if self.cfg.get("multi_stage_rewards", False) and len(tracker.rewbuffer) > 0 and env.update_reward_scales(statistics.mean(tracker.rewbuffer)):
+                print("Updated reward scales to ", env.reward_scales_stage)
+                tracker.rewbuffer.clear()
+                tracker.cur_reward_sum.zero_()
+        if self.log_dir is not None and not self.disable_logs:
+            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+            if hasattr(self.writer, "flush"):
+                self.writer.flush()
+
+    # ---- checkpoints (`:662-684`) and the policy handed to `play` (`:717-727`)
+    def model_state_dict(self):
+        sd = self.alg.state_dict()
+        return {n: sd[n] for n in self._parameter_order(sd.keys())}
+
+    def save(self, path, infos=None):
+        model = self.model_state_dict()
+        saved = {"model_state_dict": model, "optimizer_state_dict": self._adam_state_dict(model), "iter": self.current_learning_iteration, "infos": infos}
+        if self.empirical_normalization:
+            saved["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            saved["privileged_obs_norm_state_dict"] = self.privileged_obs_normalizer.state_dict()
+        torch.save(saved, path)
+
+    def get_inference_policy(self, device=None):
+        self.eval_mode()
+        policy = self.alg.policy.act_inference
+        if self.empirical_normalization:
+            norm = self.obs_normalizer
+            return lambda x: policy(norm(x))
+        return policy
+
+    # ---- logging
     def _open_writer(self):
         if self.log_dir is not None and self.writer is None and not self.disable_logs:
             self.writer = _make_writer(self.log_dir)
@@ -276,12 +485,12 @@ class RunnerLogging:
         print(log_string)
 
 
-class NativeOnPolicyRunner(RunnerLogging):
+class NativeOnPolicyRunner(NativeRunner):
+    _parameter_order = staticmethod(parameter_order)          # `ActorCritic(Recurrent).parameters()`
+
     def __init__(self, env, train_cfg, log_dir=None, device="cuda:0"):
         from . import NativeActorCritic, NativeActorCriticRecurrent, NativePPO, NativeRecurrentPPO, NativeSymmetricPPO
-        self.cfg, self.alg_cfg, self.policy_cfg = dict(train_cfg["runner"]), dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
-        self.env, self.device, self.log_dir = env, torch.device(device), log_dir
-        alg_name = self.alg_cfg.pop("class_name", self.cfg.get("algorithm_class_name", "PPO"))
+        alg_name, policy_name = self._configure(env, train_cfg, log_dir, device, "PPO", "ActorCritic")
         if alg_name == "Distillation":
             raise NotImplementedError("Distillation is not run by the native runner: tools/train_distill.py drives rl.NativeDistillation, and rl.NativeDistillationRunner runs it")
         if alg_name != "PPO":
@@ -289,7 +498,6 @@ class NativeOnPolicyRunner(RunnerLogging):
         for name in REFUSED_ALGORITHM_OPTIONS:
             if self.alg_cfg.get(name):
                 raise NotImplementedError(f"{name} is not built in the native runner")
-        policy_name = self.policy_cfg.pop("class_name", self.cfg.get("policy_class_name", "ActorCritic"))
         if policy_name not in ("ActorCritic", "ActorCriticRecurrent"):
             raise NotImplementedError(f"policy_class_name {policy_name}: the native runner builds ActorCritic and ActorCriticRecurrent")
         num_obs, num_priv = env.num_obs, getattr(env, "num_privileged_obs", None)
@@ -305,7 +513,6 @@ class NativeOnPolicyRunner(RunnerLogging):
         symmetry_cfg = self.alg_cfg.get("symmetry_cfg")
         if symmetry_cfg and recurrent:
             raise NotImplementedError("symmetry_cfg with ActorCriticRecurrent is not built in the native update (rl.NativeSymmetricPPO is feed-forward)")
-        self.seed = int(train_cfg.get("seed", 1))
         self.noise_std_type = policy_noise_std_type(policy_name, self.policy_cfg)
         sd = initial_state_dict(policy_name, num_obs, env.num_actions, self.policy_cfg, self.seed, num_critic_obs=num_critic_obs)
         activation = self.policy_cfg.get("activation", "elu")
@@ -320,157 +527,53 @@ class NativeOnPolicyRunner(RunnerLogging):
         else:
             self.alg = (NativeRecurrentPPO if recurrent else NativePPO)(policy, sd, **kw)
         self.gamma, self.lam = float(self.alg_cfg.get("gamma", 0.998)), float(self.alg_cfg.get("lam", 0.95))
-        self.num_steps_per_env, self.save_interval = int(self.cfg["num_steps_per_env"]), int(self.cfg["save_interval"])
-        self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
-        self.obs_normalizer = NativeEmpiricalNormalization([num_obs], until=int(1.0e8), device=str(self.device)) if self.empirical_normalization else None
-        self.privileged_obs_normalizer = self.obs_normalizer          # without privileged observations one handle serves actor and critic
-        if self.privileged and self.empirical_normalization:
-            self.privileged_obs_normalizer = NativeEmpiricalNormalization([num_critic_obs], until=int(1.0e8), device=str(self.device))
         # env classes with host work around the native step: the collection loop runs on the host.  With privileged observations the rule is the
-        # env class's own declaration: the one-call two-stream collector, or the host loop
-        self.layered = not collects_privileged_natively(env) if self.privileged else steps_outside_the_library(env)
-        self.writer, self.disable_logs = None, False
-        self.tot_timesteps, self.tot_time, self.current_learning_iteration = 0, 0.0, 0
-        self._host_obs, self._host_priv, self._host_episode = None, None, None
-        self.env.reset()
+        # env class's own declaration: the one-call two-stream collector, or the host loop.  Without them one handle serves actor and critic
+        self._start([num_obs, num_critic_obs] if self.privileged else [num_obs],
+                    layered=not collects_privileged_natively(env) if self.privileged else steps_outside_the_library(env))
 
-    # ---- modes (`:729-754`)
     def _normalizers(self):
-        """The actor's handle and, where the critic has its own, the critic's."""
-        both = (self.obs_normalizer, self.privileged_obs_normalizer if self.privileged else None)
-        return [n for n in both if n is not None]
+        """The actor's handle and, where the critic has its own stream, the critic's."""
+        return (self.obs_normalizer, self.privileged_obs_normalizer) if self.privileged else (self.obs_normalizer,)
 
-    def train_mode(self):
-        for norm in self._normalizers():
-            norm.train()
+    # ---- collection: `PPO.act` / `process_env_step` / `compute_returns` (`ppo.py:147-192`)
+    def _collect_one_call(self, tracker):
+        return collect_rollout_tracked(self.env, self.alg.policy, self.num_steps_per_env, gamma=self.gamma, lam=self.lam, obs_normalizer=self.obs_normalizer,
+                                       episode_tracker=tracker, privileged_obs_normalizer=self.privileged_obs_normalizer if self.privileged else None)
 
-    def eval_mode(self):
-        for norm in self._normalizers():
-            norm.eval()
-
-    def forget_carried(self):
-        for norm in self._normalizers():
-            norm.forget_carried()
-
-    # ---- collection
-    def _collect(self, tracker):
-        """One collection of `num_steps_per_env` steps: the rollout dict of `collect_rollout_tracked`."""
-        T = self.num_steps_per_env
-        if not self.layered:
-            return collect_rollout_tracked(self.env, self.alg.policy, T, gamma=self.gamma, lam=self.lam, obs_normalizer=self.obs_normalizer, episode_tracker=tracker,
-                                           privileged_obs_normalizer=self.privileged_obs_normalizer if self.privileged else None)
-        return self._collect_host(tracker, T)
-
-    def _collect_host(self, tracker, T):
-        """The same dict from a host loop, for env classes whose step is more than the native one."""
-        env, policy, norm = self.env, self.alg.policy, self.obs_normalizer
-        pnorm = self.privileged_obs_normalizer if self.privileged else None
-        obs = self._host_obs if self._host_obs is not None else env.get_observations().to(self.device)
-        priv = None
-        if self.privileged:          # (the first rows of learn() pass no normaliser: on_policy_runner.py:364-366)
-            priv = self._host_priv if self._host_priv is not None else env.get_privileged_observations().to(self.device)
-        N, O, A, dev = env.num_envs, obs.shape[1], env.num_actions, self.device
-        ex = env.core.t["extras_episode"]
-
-        def z(*shape):
-            return torch.empty(*shape, device=dev, dtype=torch.float32)
-        d = rollout_rows(T, N, O, A, dev, compute_returns=False)[0]          # (last_values, returns and advantages are assigned below)
-        d.update(raw_rewards=z(T, N, 1), episode_extras=z(T, ex.numel()))
-        if self.privileged:
-            d["privileged_observations"] = z(T, N, priv.shape[1])
-        hid, self._host_episode = [[], []], []
-        for t in range(T):
-            if policy.is_recurrent:
-                for k, m in enumerate((policy.memory_a, policy.memory_c)):
-                    m.ensure_state(N)
-                    hs = m.hidden_states
-                    hid[k].append(tuple(h.clone() for h in hs) if isinstance(hs, tuple) else hs.clone())
-            actions, values, logp, mu, sigma = policy.act_and_evaluate(obs, priv)
-            d["observations"][t], d["actions"][t], d["values"][t], d["actions_log_prob"][t, :, 0], d["mu"][t], d["sigma"][t] = obs, actions, values, logp, mu, sigma
-            if self.privileged:
-                d["privileged_observations"][t] = priv
-            obs, priv, rew, dones, infos = env.step(actions)
-            obs = obs.to(dev)
-            if self.privileged:          # on_policy_runner.py:403-412: the step's second value, else the getter, else the observations
-                if priv is None:
-                    priv = env.get_privileged_observations()
-                priv = (obs if priv is None else priv).to(dev)
-                if norm is not None and pnorm is not None:
-                    obs, priv = norm.step_pair(pnorm, obs, priv)
-                else:
-                    obs = norm(obs) if norm is not None else obs
-                    priv = pnorm(priv) if pnorm is not None else priv.clone()          # (the env's own buffer: the next step overwrites it)
-            elif norm is not None:
-                obs = norm(obs)
-            time_outs = infos["time_outs"].to(dev, torch.float32) if "time_outs" in infos else torch.zeros(N, device=dev)
-            d["raw_rewards"][t, :, 0] = rew
-            d["rewards"][t, :, 0] = rew + self.gamma * values[:, 0] * time_outs
-            d["dones"][t, :, 0] = (dones != 0).float()
-            d["episode_extras"][t] = ex
-            # infos["episode"] of this step, for the entries that are not views of extras_episode (a layer's own means): on_policy_runner.py:511-512
-            self._host_episode.append({k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in infos.get("episode", {}).items()
-                                       if not _view_index(v, ex)[0]})
-            policy.reset(dones)
-        self._host_obs = obs.clone()
-        self._host_priv = priv.clone() if self.privileged else None
-        d["last_values"] = policy.evaluate(priv if self.privileged else obs).clone()
-        d["returns"], d["advantages"] = compute_returns(d["rewards"], d["dones"], d["values"], d["last_values"], self.gamma, self.lam)
-        ep_return, ep_length = tracker.track(d["raw_rewards"], d["dones"])
-        d["ep_return"], d["ep_length"] = ep_return.reshape(T, N, 1), ep_length.reshape(T, N, 1)
-        if policy.is_recurrent:
-            for key, rows in (("hidden_states_a", hid[0]), ("hidden_states_c", hid[1])):
-                d[key] = tuple(torch.stack([r[j] for r in rows]) for j in range(2)) if isinstance(rows[0], tuple) else torch.stack(rows)
+    def _host_rows(self, T, N, obs, priv):
+        d = rollout_rows(T, N, obs.shape[1], self.env.num_actions, self.device, compute_returns=False)[0]          # (`_host_finish` assigns the rest)
+        if priv is not None:
+            d["privileged_observations"] = empty(self.device, T, N, priv.shape[1])
+        if self.alg.policy.is_recurrent:
+            d["hidden_states_a"], d["hidden_states_c"] = [], []
         return d
 
-    # ---- the loop (`:347-486`)
-    def learn(self, num_learning_iterations, init_at_random_ep_len=False):
-        env = self.env
-        self._open_writer()
-        if init_at_random_ep_len:
-            env.episode_length_buf[:] = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
-        self.forget_carried()
-        self._host_obs = self._host_priv = None
-        self.train_mode()
-        tracker = EpisodeTracker(env.num_envs, self.device)
-        start_iter = self.current_learning_iteration
-        tot_iter = start_iter + int(num_learning_iterations)
-        for it in range(start_iter, tot_iter):
-            start = time.time()
-            rollout = self._collect(tracker)
-            tracker.extend(rollout["dones"], rollout["ep_return"], rollout["ep_length"])          # (the one device-to-host copy of the collection)
-            stop = time.time()
-            collection_time, start = stop - start, stop
-            loss_dict = self.alg.update(rollout)
-            stop = time.time()
-            learn_time = stop - start
-            self.current_learning_iteration = it
-            if self.log_dir is not None and not self.disable_logs:
-                self.log(dict(it=it, tot_iter=tot_iter, start_iter=start_iter, num_learning_iterations=int(num_learning_iterations), collection_time=collection_time,
-                              learn_time=learn_time, loss_dict=loss_dict, rewbuffer=tracker.rewbuffer, lenbuffer=tracker.lenbuffer,
-                              episode=self._episode_means(rollout)))
-                if it % self.save_interval == 0:
-                    self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
-            if self.cfg.get("multi_stage_rewards", False) and len(tracker.rewbuffer) > 0 and env.update_reward_scales(statistics.mean(tracker.rewbuffer)):
-                print("Updated reward scales to ", env.reward_scales_stage)
-                tracker.rewbuffer.clear()
-                tracker.cur_reward_sum.zero_()
-        if self.log_dir is not None and not self.disable_logs:
-            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
-            if hasattr(self.writer, "flush"):
-                self.writer.flush()
+    def _host_act(self, d, t, obs, priv):          # `PPO.act` (`ppo.py:147-159`)
+        policy = self.alg.policy
+        if policy.is_recurrent:          # the state of each memory BEFORE step t's act (`ppo.py:148-149`)
+            for key, m in (("hidden_states_a", policy.memory_a), ("hidden_states_c", policy.memory_c)):
+                m.ensure_state(obs.shape[0])
+                d[key].append(_clone_state(m.hidden_states))
+        actions, values, logp, mu, sigma = policy.act_and_evaluate(obs, priv)
+        d["actions"][t], d["values"][t], d["actions_log_prob"][t, :, 0], d["mu"][t], d["sigma"][t] = actions, values, logp, mu, sigma
+        return actions
+
+    def _host_reward(self, d, t, rew, infos):          # the time-out bootstrap of `process_env_step` (`ppo.py:179-183`)
+        time_outs = infos["time_outs"].to(self.device, torch.float32) if "time_outs" in infos else torch.zeros(rew.shape[0], device=self.device)
+        d["rewards"][t, :, 0] = rew + self.gamma * d["values"][t, :, 0] * time_outs
+
+    def _host_finish(self, d, last):          # `PPO.compute_returns` (`ppo.py:190-192`)
+        d["last_values"] = self.alg.policy.evaluate(last).clone()
+        d["returns"], d["advantages"] = compute_returns(d["rewards"], d["dones"], d["values"], d["last_values"], self.gamma, self.lam)
+        if self.alg.policy.is_recurrent:          # (T, L, N, H) per memory, `(h, c)` for an LSTM: `RolloutStorage._save_hidden_states`
+            for key in ("hidden_states_a", "hidden_states_c"):
+                rows = d[key]
+                d[key] = tuple(torch.stack([r[j] for r in rows]) for j in range(2)) if isinstance(rows[0], tuple) else torch.stack(rows)
 
     # ---- checkpoints (`:662-715`)
-    def model_state_dict(self):
-        sd = self.alg.state_dict()
-        return {n: sd[n] for n in parameter_order(sd.keys())}
-
-    def save(self, path, infos=None):
-        saved = {"model_state_dict": self.model_state_dict(), "optimizer_state_dict": adam_state_dict(self.alg.optimizer_state()),
-                 "iter": self.current_learning_iteration, "infos": infos}
-        if self.empirical_normalization:
-            saved["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
-            saved["privileged_obs_norm_state_dict"] = self.privileged_obs_normalizer.state_dict()
-        torch.save(saved, path)
+    def _adam_state_dict(self, model):
+        return adam_state_dict(self.alg.optimizer_state())
 
     def load(self, path, load_optimizer=True):
         loaded = torch.load(path, map_location="cpu", weights_only=False)
@@ -498,11 +601,3 @@ class NativeOnPolicyRunner(RunnerLogging):
             self.alg.load_state_dict(model)
         self.current_learning_iteration = loaded["iter"]
         return loaded.get("infos")
-
-    def get_inference_policy(self, device=None):
-        self.eval_mode()
-        policy = self.alg.policy.act_inference
-        if self.empirical_normalization:
-            norm = self.obs_normalizer
-            return lambda x: policy(norm(x))
-        return policy
