@@ -749,3 +749,60 @@ def declare_runner_distill(lib):
 
 
 RUNNER_DISTILL_SYMBOLS = ["lg_runner_collect_distillation", "lg_runner_collect_distillation_recurrent"]
+
+
+class lg_sensor_raycaster(C.Structure):
+    """include/lgsensors.h: the ray caster's parts of a sensor rig (device pointers to the Python object's own tensors)."""
+    _fields_ = [("ray_origins", C.c_void_p), ("ray_dirs", C.c_void_p), ("num_rays", i32), ("max_distance", f32), ("attach_yaw_only", i32),
+                ("ray_hits", C.c_void_p), ("hits_found", C.c_void_p), ("raycast_distances", C.c_void_p), ("distance_stride", i32)]
+
+
+class lg_sensor_camera(C.Structure):
+    """include/lgsensors.h: the depth camera's parts of a sensor rig."""
+    _fields_ = [("params", lg_depth_params), ("ray_dirs", C.c_void_p), ("camera_pos", C.c_void_p), ("camera_rot", C.c_void_p),
+                ("depth_buffer", C.c_void_p), ("update_interval", i32), ("counter", C.c_int64)]
+
+
+class lg_estimation_out(C.Structure):
+    """include/lgsensors.h: device pointers to the (T, n, .) rows of one estimation collection."""
+    _fields_ = [(k, C.c_void_p) for k in ("depth_images", "proprio_data", "raycast_targets", "dones", "predictions")]
+
+
+class lg_estimation_nets(C.Structure):
+    """include/lgsensors.h: the four stages of `lg_estimator_step` and the memory's live state."""
+    _fields_ = [(k, C.c_void_p) for k in ("encoder", "combine", "memory", "decoder", "h", "c")]
+
+
+SENSOR_STRUCTS = {"lg_sensor_raycaster": lg_sensor_raycaster, "lg_sensor_camera": lg_sensor_camera, "lg_estimation_out": lg_estimation_out,
+                  "lg_estimation_nets": lg_estimation_nets}
+
+
+def declare_sensors(lib):
+    """Prototypes of the sensors inside the one-call collectors (include/lgsensors.h), same library."""
+    vp, i64, u64 = C.c_void_p, C.c_int64, C.c_uint64
+    lib.lg_post_physics_transition.argtypes = [vp, vp, vp, f32, vp, vp, vp]
+    lib.lg_post_physics_transition.restype = C.c_int
+    lib.lg_extra_obs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(vp)]
+    lib.lg_extra_obs_info.restype = C.c_int
+    lib.lg_sensor_rig_create.argtypes = [vp, vp, C.POINTER(lg_sensor_raycaster), C.POINTER(lg_sensor_camera)]
+    lib.lg_sensor_rig_create.restype = vp
+    lib.lg_sensor_rig_destroy.argtypes = [vp]
+    lib.lg_sensor_rig_destroy.restype = None
+    lib.lg_sensor_rig_counter.argtypes = [vp]
+    lib.lg_sensor_rig_counter.restype = i64
+    lib.lg_sensor_rig_set_counter.argtypes = [vp, i64]
+    lib.lg_sensor_rig_set_counter.restype = C.c_int
+    lib.lg_sensor_step_transition.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp]
+    lib.lg_sensor_step_transition.restype = C.c_int
+    lib.lg_runner_collect_sensors.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, f32, f32, i32, C.POINTER(lg_rollout), C.POINTER(lg_rollout_hidden),
+                                              vp, vp, vp, vp, C.POINTER(lg_runner_hooks), vp]
+    lib.lg_runner_collect_sensors.restype = C.c_int
+    lib.lg_estimation_rows.argtypes = [vp, i32, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]
+    lib.lg_estimation_rows.restype = C.c_int
+    lib.lg_collect_estimation.argtypes = [vp, vp, vp, i32, C.POINTER(lg_estimation_out), C.POINTER(lg_estimation_nets), vp]
+    lib.lg_collect_estimation.restype = C.c_int
+    return lib
+
+
+SENSOR_SYMBOLS = ["lg_post_physics_transition", "lg_extra_obs_info", "lg_sensor_rig_create", "lg_sensor_rig_destroy", "lg_sensor_rig_counter",
+                  "lg_sensor_rig_set_counter", "lg_sensor_step_transition", "lg_runner_collect_sensors", "lg_estimation_rows", "lg_collect_estimation"]

@@ -44,6 +44,9 @@
   X(int, lg_compute_torques, (lg_ctx * c, const float* actions, void* stream), (c, actions, stream))                                                  \
   X(int, lg_simulate, (lg_ctx * c, void* stream), (c, stream))                                                                                        \
   X(int, lg_post_physics_step, (lg_ctx * c, void* stream), (c, stream))                                                                               \
+  X(int, lg_post_physics_transition, (lg_ctx * c, float* next_obs, const float* values, float gamma, float* rewards, float* dones, void* stream),     \
+    (c, next_obs, values, gamma, rewards, dones, stream))                                                                                             \
+  X(int, lg_extra_obs_info, (lg_ctx * c, int32_t* num_extra_obs, const float** bound), (c, num_extra_obs, bound))                                     \
   X(int, lg_reset_idx, (lg_ctx * c, const int32_t* env_ids, int32_t n, int32_t update_curriculum, void* stream), (c, env_ids, n, update_curriculum, stream)) \
   X(int, lg_set_state_indexed, (lg_ctx * c, const float* root_states, const float* dof_state, const int32_t* env_ids, int32_t n, void* stream),       \
     (c, root_states, dof_state, env_ids, n, stream))                                                                                                  \
@@ -78,6 +81,8 @@
 #define lg_compute_torques LG_ENTRY(lg_compute_torques)
 #define lg_simulate LG_ENTRY(lg_simulate)
 #define lg_post_physics_step LG_ENTRY(lg_post_physics_step)
+#define lg_post_physics_transition LG_ENTRY(lg_post_physics_transition)
+#define lg_extra_obs_info LG_ENTRY(lg_extra_obs_info)
 #define lg_reset_idx LG_ENTRY(lg_reset_idx)
 #define lg_set_state_indexed LG_ENTRY(lg_set_state_indexed)
 #define lg_gather_step_rows LG_ENTRY(lg_gather_step_rows)

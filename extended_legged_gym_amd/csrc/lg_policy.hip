@@ -927,6 +927,8 @@ int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn*
   if (rc != LG_OK) return rc;
   const CollectHooks hk = hooks ? *hooks : CollectHooks();
   const bool two = hk.privileged_observations != nullptr;
+  if (hk.sensors && two) return lg_policy_fail(LG_ERR_UNSUPPORTED, "a sensor rig together with privileged observations (two streams) is not built");
+  if (hk.sensors && lg_policy_sensor_env(hk.sensors) != env) return lg_policy_fail(LG_ERR_INVALID, "the sensor rig is attached to another env context");
   const int A = actor->h.dims[actor->h.L];
   const int64_t Oa = mem_a ? mem_a->input : actor->h.dims[0];
   if ((!two && Oa != Oc) || (mem_a ? mem_c->input : critic->h.dims[0]) != Oc || critic->h.dims[critic->h.L] != 1 || A != Aenv)
@@ -979,8 +981,12 @@ int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn*
     const bool more = t + 1 < T;
     // the critic's next row; after the last step into its normaliser's carried row (none: the env's own row serves)
     float* next_c = more ? crit_rows + (t + 1) * sp : carried_c;
-    rc = lg_step_transition(env, act_t, next_c, out->values + (size_t)t * n, gamma, out->rewards + (size_t)t * n, dones_t, stream);
-    if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
+    if (hk.sensors) {
+      if ((rc = lg_policy_sensor_step(hk.sensors, act_t, next_c, out->values + (size_t)t * n, gamma, out->rewards + (size_t)t * n, dones_t, stream)) != LG_OK) return rc;
+    } else {
+      rc = lg_step_transition(env, act_t, next_c, out->values + (size_t)t * n, gamma, out->rewards + (size_t)t * n, dones_t, stream);
+      if (rc != LG_OK) return lg_policy_fail(rc, std::string("lg_step_transition failed: ") + lg_last_error(env));
+    }
     // two streams: the actor's next row; after the last step the un-normalised row goes to last_observations and its normalised copy to the carried row
     float *norm_out_a = nullptr, *next_a = nullptr;
     if (two) {

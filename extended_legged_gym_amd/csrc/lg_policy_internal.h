@@ -41,7 +41,13 @@ void lg_rnn_widths(const lg_rnn* m, int* type, int* input, int* hidden, int* dev
 //               serves that row.  history, normalizer_c and last_observations are not read.
 //   two streams (privileged_observations set): the critic reads the env's row (stored there, O_c wide, `normalizer_c`), the actor the history
 //               layer's row or a column prefix of the env's raw row (out->observations, O_a wide, `normalizer`); a carried row each.
+//   sensors     (one stream only) the env's step is lg_sensor_step_transition on this rig (include/lgsensors.h, lg_sensors.hip) in the place of
+//               lg_step_transition: the ray caster between the step's two halves, the depth camera behind it.  Nothing else in the loop moves.
 struct lg_obsnorm;
+struct lg_sensor_rig;
+// the rig's step behind its checks, and the context it is attached to (lg_sensors.hip)
+int lg_policy_sensor_step(lg_sensor_rig* rig, const float* actions, float* next_obs, const float* values, float gamma, float* rewards, float* dones, void* stream);
+lg_ctx* lg_policy_sensor_env(lg_sensor_rig* rig);
 struct CollectHooks {
   lg_obsnorm* normalizer = nullptr;             // the actor's: every new row of its stream passes lg_obsnorm_step before it is stored and read; the row
                                                 // after the last step is the handle's carried row, row 0 of the next collection
@@ -52,6 +58,7 @@ struct CollectHooks {
   const lg_obs_history* history = nullptr;      // the actor's layer (two streams); NULL: the actor reads a column prefix of the env's row
   float* privileged_observations = nullptr;     // (T, n, O_c): selects the two-stream mode
   float* last_observations = nullptr;           // (n, O_a) or NULL: the actor's un-normalised row after the last step (two streams)
+  lg_sensor_rig* sensors = nullptr;             // the env's sensor rig (one stream); NULL: the step is lg_step_transition
 };
 int lg_policy_collect_rollout(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call,
                               int32_t T, float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a,

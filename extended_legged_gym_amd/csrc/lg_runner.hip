@@ -213,10 +213,11 @@ int lg_runner_episode_track(const float* rewards, const float* dones, int32_t T,
 // episode bookkeeping follows it on the same stream.  The message prefix is the caller's: each entry point opens its own POLICY_ENTRY.
 int lg_runner_collect_both(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
                            float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a, float* c_a, float* h_c,
-                           float* c_c, const lg_runner_hooks* hooks, const lg_runner_privileged* priv, void* stream) {
+                           float* c_c, const lg_runner_hooks* hooks, const lg_runner_privileged* priv, lg_sensor_rig* sensors, void* stream) {
   if (!env || !actor || !critic || !std || !out || T <= 0) return lg_policy_fail(LG_ERR_INVALID, "null argument or T < 1");
   if ((mem_a != nullptr) != (mem_c != nullptr) || (mem_a && !hid)) return lg_policy_fail(LG_ERR_INVALID, "a recurrent policy needs both memories and the hidden-state rows");
   CollectHooks ch;
+  ch.sensors = sensors;
   const lg_runner_episode* ep = hooks ? hooks->episode : nullptr;
   if (hooks) { ch.normalizer = hooks->normalizer; ch.update = hooks->training != 0; }
   if (priv) {
@@ -241,5 +242,5 @@ extern "C" int lg_runner_collect(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_r
                                  float* h_c, float* c_c, const lg_runner_hooks* hooks, void* stream) {
   POLICY_ENTRY;
   return lg_runner_collect_both(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c, hooks, nullptr,
-                                stream);
+                                nullptr, stream);
 }

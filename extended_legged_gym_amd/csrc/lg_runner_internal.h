@@ -143,7 +143,9 @@ LG_DEV void obsnorm_apply_body(int bx, int by, const float* x, int64_t n, int64_
 // the checks every call over rows makes (lg_runner.hip): NULL handle, rows, stride, row count
 int obsnorm_rows_ok(const lg_obsnorm* h, const float* x, int64_t n, int64_t row_stride);
 
-// the body of lg_runner_collect (priv NULL) and of lg_runner_collect_privileged, behind their POLICY_ENTRY (lg_runner.hip)
+// the body of lg_runner_collect (priv and sensors NULL), of lg_runner_collect_privileged and of lg_runner_collect_sensors (a rig: lg_sensors.hip), behind
+// their POLICY_ENTRY (lg_runner.hip)
+struct lg_sensor_rig;
 int lg_runner_collect_both(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_rnn* mem_c, lg_mlp* critic, const float* std, uint64_t seed, uint64_t first_call, int32_t T,
                            float gamma, float lam, int32_t normalize_advantage, const lg_rollout* out, const lg_rollout_hidden* hid, float* h_a, float* c_a, float* h_c,
-                           float* c_c, const lg_runner_hooks* hooks, const lg_runner_privileged* priv, void* stream);
+                           float* c_c, const lg_runner_hooks* hooks, const lg_runner_privileged* priv, lg_sensor_rig* sensors, void* stream);

@@ -100,7 +100,7 @@ int lg_runner_collect_privileged(lg_ctx* env, lg_rnn* mem_a, lg_mlp* actor, lg_r
   POLICY_ENTRY;
   if (!priv || !priv->privileged_observations) return lg_policy_fail(LG_ERR_INVALID, "null privileged struct or null privileged_observations rows");
   return lg_runner_collect_both(env, mem_a, actor, mem_c, critic, std, seed, first_call, T, gamma, lam, normalize_advantage, out, hid, h_a, c_a, h_c, c_c, hooks, priv,
-                                stream);
+                                nullptr, stream);
 }
 
 }  // extern "C"

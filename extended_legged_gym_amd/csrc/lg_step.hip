@@ -3246,6 +3246,23 @@ int lg_post_physics_step(lg_ctx* c, void* stream) {
   return launch_post(c, (hipStream_t)stream, nullptr, nullptr, c->h.N, 0);
 }
 
+// The second half of lg_step_transition (include/lgsensors.h): lg_post_physics_step whose kernel also fills one transition of a rollout storage.  Pairs
+// with lg_step_physics, for a step with sensor launches between the two halves (lg_sensor_step_transition, lg_sensors.hip).
+int lg_post_physics_transition(lg_ctx* c, float* next_observations, const float* values, float gamma, float* rewards, float* dones, void* stream) {
+  if (!c) return LG_ERR_INVALID;
+  DeviceScope ds_(c->device);
+  if (!rewards || !dones) { c->err = "lg_post_physics_transition: null row"; return LG_ERR_INVALID; }
+  return launch_post(c, (hipStream_t)stream, nullptr, nullptr, c->h.N, 0, nullptr, 0, PostSink{next_observations, values, rewards, dones, gamma});
+}
+
+// the width of the extra-observation block and the buffer lg_set_extra_obs bound (NULL: none)
+int lg_extra_obs_info(lg_ctx* c, int32_t* num_extra_obs, const float** bound) {
+  if (!c) return LG_ERR_INVALID;
+  if (num_extra_obs) *num_extra_obs = c->h.cfg.num_extra_obs;
+  if (bound) *bound = (const float*)c->h.extra_obs;
+  return LG_OK;
+}
+
 int lg_reset_idx(lg_ctx* c, const int32_t* env_ids, int32_t n, int32_t update_curriculum, void* stream) {
   if (!c) return LG_ERR_INVALID;
   DeviceScope ds_(c->device);

@@ -27,3 +27,4 @@ from .estimator_distillation import NativeEstimatorDistillation          # noqa:
 from .normalizer import NativeEmpiricalNormalization          # noqa: F401
 from .runner import NativeOnPolicyRunner          # noqa: F401
 from .distillation_runner import NativeDistillationRunner          # noqa: F401
+from .sensors import SensorRig          # noqa: F401

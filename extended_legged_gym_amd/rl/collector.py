@@ -127,7 +127,7 @@ def _episode_hook(hooks, env, episode_tracker, T, N, dev):
 
 
 def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normalize_advantage=True, compute_returns=True, obs_normalizer=None,
-                            episode_tracker=None, privileged_obs_normalizer=None, noise_uniforms=None, actor_columns=None):
+                            episode_tracker=None, privileged_obs_normalizer=None, noise_uniforms=None, actor_columns=None, sensors=None):
     """`collect_rollout` through `lg_runner_collect` (include/lgrunner.h), with the runner's two device pieces between the launches of the one
     call.  Same dict; both hooks None: the same rows, bit for bit.
     obs_normalizer (`NativeEmpiricalNormalization`): every new observation row is normalised in place (and counted when the normaliser is in
@@ -145,13 +145,24 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
     also `privileged_observations` (T, N, O_c), `values` are the critic's on the privileged rows.  `obs_normalizer` is the ACTOR's,
     `privileged_obs_normalizer` the critic's: each with its own carried row.  The history is stepped in place by the library and `env.obs_buf` is
     left as the actor's un-normalised row after the last step, as `collect_distillation` does; noise follows `env.add_noise`, and `noise_uniforms`
-    (T, N, H * W) replaces the Philox draws.  For every other env the three arguments must stay None and the call is the one above."""
+    (T, N, H * W) replaces the Philox draws.  For every other env the three arguments must stay None and the call is the one above.
+
+    SENSORS (`lg_runner_collect_sensors`, include/lgsensors.h): `sensors`, a `SensorRig` of this env (`rl/sensors.py`), for an env whose step
+    drives the ray caster and the depth camera (`LeggedRobotRayCast`, `LeggedRobotDepth`): every step of the call is the library's sensor step,
+    the rows are those of a host loop over `env.step`, and the env's sensors and counters are left as that loop leaves them.  One stream only."""
     from .normalizer import _runner_lib
     lib = _runner_lib()
+    if sensors is not None:
+        from .sensors import _sensor_lib
+        lib = _sensor_lib()
+        if sensors.env is not env:
+            raise ValueError("sensors: the rig belongs to another env")
     dev = policy.device
     T, N, O, A = int(num_steps), env.core.t["obs_buf"].shape[0], env.core.t["obs_buf"].shape[1], policy.num_actions
     hist = getattr(env, "obs_history", None)
     privileged = hist is not None or actor_columns is not None
+    if privileged and sensors is not None:
+        raise ValueError("sensors: a sensor rig together with privileged observations (an observation history, actor_columns) is not built")
     if not privileged and (privileged_obs_normalizer is not None or noise_uniforms is not None):
         raise ValueError("privileged_obs_normalizer / noise_uniforms need an env with an observation history, or actor_columns")
     O_c = O
@@ -181,15 +192,23 @@ def collect_rollout_tracked(env, policy, num_steps, gamma=0.99, lam=0.95, normal
         priv = abi.lg_runner_privileged(history=C.pointer(layer) if layer is not None else None, critic_normalizer=crit.handle if crit is not None else None,
                                         privileged_observations=out["privileged_observations"].data_ptr(), last_observations=last.data_ptr() if last is not None else None)
         call, name, tail = lib.lg_runner_collect_privileged, "lg_runner_collect_privileged", (C.byref(priv),)
+    first = env.core.ctx
+    if sensors is not None:          # the rig in the place of the context it is attached to
+        call, name, first = lib.lg_runner_collect_sensors, "lg_runner_collect_sensors", sensors.handle
+        sensors.begin()
     if not getattr(policy, "is_recurrent", False):
-        rc = call(env.core.ctx, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None, C.byref(hooks), *tail, stream)
+        rc = call(first, None, policy.actor.handle, None, policy.critic.handle, *head, None, None, None, None, None, C.byref(hooks), *tail, stream)
     else:
         mems, hidden, state, stacks = _hidden_rows(policy, T, N)
-        rc = call(env.core.ctx, mems[0], policy.actor.handle, mems[1], policy.critic.handle, *head, C.byref(hidden), *state, C.byref(hooks), *tail, stream)
+        rc = call(first, mems[0], policy.actor.handle, mems[1], policy.critic.handle, *head, C.byref(hidden), *state, C.byref(hooks), *tail, stream)
         out.update(stacks)
     _check(rc, name)
     del keep
-    _advance(env, policy, T)
+    if sensors is not None:
+        policy._call += T
+        sensors.finish(T)
+    else:
+        _advance(env, policy, T)
     if last is not None:
         env.obs_buf = last
     out.update(extra)
@@ -337,7 +356,7 @@ def estimation_row(env):
     return depth, torch.cat([env.base_lin_vel, env.base_ang_vel], dim=-1), env._get_raycast_distances(normalize=False)
 
 
-def collect_estimation(env, policy, num_steps, estimator=None):
+def collect_estimation(env, policy, num_steps, estimator=None, one_call=False, actions=None):
     """The data-collection loop of `TerrainEstimatorRunner.learn` (`rsl_rl/runners/terrain_estimator_runner.py:392-438`) over an env that carries
     the depth camera and the ray caster.  Per step t: the camera's latest frame, `cat[base_lin_vel, base_ang_vel]` and the un-normalised ray
     distances are copied into row t of preallocated (T, N, .) tensors (what `EstimatorRolloutStorage.add_transitions` keeps,
@@ -348,8 +367,19 @@ def collect_estimation(env, policy, num_steps, estimator=None):
 
     Returns a dict: depth_images (T, N, h, w), proprio_data (T, N, 6), raycast_targets (T, N, R), dones (T, N).  With `estimator`
     (a `NativeTerrainEstimator`) it is also stepped on every row and reset on `dones[t]` after the step (`distillation.py:275`): the evaluation
-    loop of `play` (`:637-730`), adding predictions (T, N, R) and the per-step `mse` / `mae` (T) it prints (`:666-670`)."""
+    loop of `play` (`:637-730`), adding predictions (T, N, R) and the per-step `mse` / `mae` (T) it prints (`:666-670`).
+
+    `actions` (T, N, A), with `policy=None`: the env is stepped with `actions[t]` instead of a draw.
+    `one_call=True`: the same loop as ONE call into the library (`lg_collect_estimation`, include/lgsensors.h) on the env's `SensorRig`
+    (`rl/sensors.py`; built on first use, `ValueError` where the rig refuses the env).  `policy` must be a native feed-forward policy exposing its
+    actor (`policy.actor`, a `NativeMLP`: it reads the env's raw row, or its first columns when it is narrower), or None together with `actions`.
+    The same dict, bit for bit, except `raycast_targets`' relation to `torch.norm`: the kernel takes torch's order of fp32 roundings, which holds
+    as long as torch keeps it.  `mse` / `mae` are the two expressions above on the returned rows."""
     T = int(num_steps)
+    if one_call:
+        return _collect_estimation_one_call(env, policy, T, estimator, actions)
+    if actions is not None and policy is not None:
+        raise ValueError("collect_estimation: give a policy or actions, not both")
     depth, proprio, target = estimation_row(env)
     N, dev = depth.shape[0], depth.device
     out = dict(depth_images=torch.empty(T, N, *depth.shape[1:], device=dev), proprio_data=torch.empty(T, N, proprio.shape[1], device=dev),
@@ -367,12 +397,58 @@ def collect_estimation(env, policy, num_steps, estimator=None):
             out["predictions"][t].copy_(pred)
             out["mse"][t] = torch.mean((pred - target) ** 2)
             out["mae"][t] = torch.mean(torch.abs(pred - target))
-        if policy is None:
-            actions = torch.randn(N, env.num_actions, device=env.device) * 0.5
+        if actions is not None:
+            step_actions = actions[t]
+        elif policy is None:
+            step_actions = torch.randn(N, env.num_actions, device=env.device) * 0.5
         else:
-            actions = policy.act_inference(env.obs_buf)
-        dones = env.step(actions)[3]
+            step_actions = policy.act_inference(env.obs_buf)
+        dones = env.step(step_actions)[3]
         out["dones"][t].copy_(dones)
         if estimator is not None:
             estimator.reset(dones)
+    return out
+
+
+def _collect_estimation_one_call(env, policy, T, estimator, actions):
+    """`collect_estimation(one_call=True)`: the checks the host can make, the rows, the one call, the rig's bookkeeping, `mse` / `mae`."""
+    from .sensors import SensorRig, _sensor_lib
+    if (policy is None) == (actions is None):
+        raise ValueError("collect_estimation(one_call=True): exactly one of policy and actions must be given"
+                         + (" (no policy: the actions come pre-drawn, (T, N, A))" if policy is None else ""))
+    actor = None
+    if policy is not None:
+        actor = getattr(policy, "actor", None)
+        if getattr(policy, "is_recurrent", False) or getattr(actor, "handle", None) is None or not hasattr(actor, "dims"):
+            raise ValueError("collect_estimation(one_call=True): policy must be a native feed-forward policy exposing its actor (policy.actor, a NativeMLP)")
+    rig = SensorRig.from_env(env, camera=True)
+    if not (rig.has_rays and rig.has_camera):
+        raise ValueError("collect_estimation(one_call=True): the env's rig must carry both the ray caster and the depth camera")
+    lib = _sensor_lib()
+    depth = env.get_depth_images()
+    N, dev, R = depth.shape[0], depth.device, env.ray_caster.num_rays
+    if actions is not None:
+        actions = actions.to(dev, torch.float32).contiguous()
+        if actions.shape != (T, N, env.num_actions):
+            raise ValueError(f"actions of shape {tuple(actions.shape)}, expected {(T, N, env.num_actions)}")
+    out = dict(depth_images=torch.empty(T, N, *depth.shape[2:], device=dev), proprio_data=torch.empty(T, N, 6, device=dev),
+               raycast_targets=torch.empty(T, N, R, device=dev), dones=torch.empty(T, N, device=dev))
+    nets = None
+    if estimator is not None:
+        out["predictions"] = torch.empty(T, N, estimator.num_raycast_outputs, device=dev)
+        estimator.memory.ensure_state(N)
+        h, c = estimator.memory._ptrs()
+        nets = abi.lg_estimation_nets(encoder=estimator.encoder.handle, combine=estimator.combine.handle, memory=estimator.memory.handle,
+                                      decoder=estimator.decoder.handle, h=h, c=c)
+    rows = abi.lg_estimation_out(**{k: out[k].data_ptr() for k in ("depth_images", "proprio_data", "raycast_targets", "dones", "predictions") if k in out})
+    rig.begin()
+    _check(lib.lg_collect_estimation(rig.handle, actor.handle if actor is not None else None, _ptr(actions), T, C.byref(rows),
+                                     C.byref(nets) if nets is not None else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lg_collect_estimation")
+    rig.finish(T)
+    if estimator is not None:
+        out.update(mse=torch.empty(T, device=dev), mae=torch.empty(T, device=dev))
+        for t in range(T):
+            pred, target = out["predictions"][t], out["raycast_targets"][t]
+            out["mse"][t] = torch.mean((pred - target) ** 2)
+            out["mae"][t] = torch.mean(torch.abs(pred - target))
     return out

@@ -237,6 +237,17 @@ def steps_outside_the_library(env):
     return hasattr(env, "_after_native") or getattr(type(env), "step", None) is not LeggedRobot.step
 
 
+SENSOR_COLLECTION_MODES = ("host", "native")
+
+
+def sensor_collection_mode(runner_cfg):
+    """`runner.sensor_collection`: "host" when the key is absent; ValueError for anything but "host" / "native".  No device needed."""
+    mode = runner_cfg.get("sensor_collection", "host")
+    if mode not in SENSOR_COLLECTION_MODES:
+        raise ValueError(f"runner.sensor_collection = {mode!r}: must be one of {SENSOR_COLLECTION_MODES}")
+    return mode
+
+
 # ---------------------------------------------------------------------------------------------------------------- the runners
 def _clone_state(hidden_states):
     """A copy of a memory's live state: `(h, c)` for an LSTM, `h` for a GRU."""
@@ -529,8 +540,15 @@ class NativeOnPolicyRunner(NativeRunner):
         self.gamma, self.lam = float(self.alg_cfg.get("gamma", 0.998)), float(self.alg_cfg.get("lam", 0.95))
         # env classes with host work around the native step: the collection loop runs on the host.  With privileged observations the rule is the
         # env class's own declaration: the one-call two-stream collector, or the host loop.  Without them one handle serves actor and critic
-        self._start([num_obs, num_critic_obs] if self.privileged else [num_obs],
-                    layered=not collects_privileged_natively(env) if self.privileged else steps_outside_the_library(env))
+        # `runner.sensor_collection`: "host" (the default) keeps the envs that drive sensors around the step on the host loop; "native" attaches
+        # the env's `SensorRig` and collects through `lg_runner_collect_sensors`, or raises the rig's refusal
+        self.sensor_collection = sensor_collection_mode(self.cfg)
+        self.sensors = None
+        if self.sensor_collection == "native":
+            from .sensors import SensorRig
+            self.sensors = SensorRig.from_env(env)
+        layered = not collects_privileged_natively(env) if self.privileged else steps_outside_the_library(env)
+        self._start([num_obs, num_critic_obs] if self.privileged else [num_obs], layered=layered and self.sensors is None)
 
     def _normalizers(self):
         """The actor's handle and, where the critic has its own stream, the critic's."""
@@ -539,7 +557,8 @@ class NativeOnPolicyRunner(NativeRunner):
     # ---- collection: `PPO.act` / `process_env_step` / `compute_returns` (`ppo.py:147-192`)
     def _collect_one_call(self, tracker):
         return collect_rollout_tracked(self.env, self.alg.policy, self.num_steps_per_env, gamma=self.gamma, lam=self.lam, obs_normalizer=self.obs_normalizer,
-                                       episode_tracker=tracker, privileged_obs_normalizer=self.privileged_obs_normalizer if self.privileged else None)
+                                       episode_tracker=tracker, privileged_obs_normalizer=self.privileged_obs_normalizer if self.privileged else None,
+                                       sensors=self.sensors)
 
     def _host_rows(self, T, N, obs, priv):
         d = rollout_rows(T, N, obs.shape[1], self.env.num_actions, self.device, compute_returns=False)[0]          # (`_host_finish` assigns the rest)

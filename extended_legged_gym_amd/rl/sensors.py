@@ -1,0 +1,140 @@
+"""`SensorRig`: the ray caster and the depth camera of a `LeggedRobotRayCast` / `LeggedRobotDepth` env attached to its context as the library's
+`lg_sensor_rig` (include/lgsensors.h), so that the one-call collectors drive them between the launches of an env step instead of `env.step`
+from Python.  The rig owns no sensor memory: `env.raycast_distances`, `env.ray_caster.data.ray_hits` and `env.get_depth_images()` are the
+buffers it writes, and `finish(T)` leaves the env's host-side bookkeeping as T calls of `env.step` would."""
+import ctypes as C
+
+import torch
+
+from extended_legged_gym_amd import abi
+from .policy import _NativeHandle, _lib, _ptr
+
+
+def _sensor_lib():
+    lib = _lib()
+    if not getattr(lib, "_sensors_declared", False):
+        from .normalizer import _runner_lib
+        _runner_lib()
+        abi.declare_sensors(lib)
+        lib._sensors_declared = True
+    return lib
+
+
+def refusal(env, camera=None):
+    """Why `SensorRig.from_env(env, camera)` cannot serve this env, or None.  No device work, nothing stepped."""
+    from extended_legged_gym_amd.envs.base.legged_robot_depthcam import LeggedRobotDepth
+    from extended_legged_gym_amd.envs.base.legged_robot_raycast import LeggedRobotRayCast
+    name = type(env).__name__
+    if getattr(env, "num_privileged_obs", None) is not None or getattr(env, "privileged_obs_buf", None) is not None:
+        return f"{name} has privileged observations: the sensor rig serves the one-stream collectors only"
+    if hasattr(env, "_after_native"):
+        return f"{name} runs a device layer behind the native step (_after_native), which the sensor step does not launch"
+    if getattr(type(env), "step", None) not in (LeggedRobotRayCast.step, LeggedRobotDepth.step):
+        return f"{name}.step is not LeggedRobotRayCast.step or LeggedRobotDepth.step: the env has no sensor the rig could drive, or host work of its own around the step"
+    rays, cam = getattr(env, "ray_caster", None), getattr(env, "depth_camera", None)
+    kind = getattr(getattr(env.cfg, "depth", None), "camera_type", None)
+    if camera and (cam is None or kind != "Warp"):
+        return f"camera_type {kind!r}: the rig drives the ray-cast camera, camera_type 'Warp'"
+    if cam is not None and kind == "Warp" and camera is not False:
+        if getattr(env.cfg.depth, "dis_noise", 0.0) != 0:
+            return f"depth.dis_noise = {env.cfg.depth.dis_noise}: the host draws that noise with torch.rand on every step, the sensor step has no noise"
+        if int(env.cfg.depth.update_interval) < 1:
+            return f"depth.update_interval = {env.cfg.depth.update_interval}: must be at least 1"
+    else:
+        cam = None
+    if rays is None and cam is None:
+        return f"{name} has neither the ray caster (raycaster.enable_raycast) nor the ray-cast depth camera (depth.camera_type 'Warp') enabled"
+    if rays is not None and rays.cfg.update_period > 0:
+        return f"the ray caster has update_period = {rays.cfg.update_period} > 0: the sensor step casts every env on every step"
+    return None
+
+
+class SensorRig(_NativeHandle):
+    _destroy = "lg_sensor_rig_destroy"
+
+    def __init__(self, env, camera=None):
+        why = refusal(env, camera)
+        if why is not None:
+            raise ValueError("SensorRig: " + why)
+        self._open(env.device, "sensor")
+        self.lib = _sensor_lib()
+        self.env = env
+        rays = env.ray_caster
+        cam = env.depth_camera if (env.depth_camera is not None and env.cfg.depth.camera_type == "Warp" and camera is not False) else None
+        meshes = ([next(iter(rays.meshes.values()))] if rays is not None else []) + ([cam.meshes["terrain"]] if cam is not None else [])
+        if any(m is not meshes[0] for m in meshes):
+            raise ValueError("SensorRig: the ray caster and the depth camera cast against different meshes")
+        self.mesh = meshes[0]
+        rs, cs = None, None
+        if rays is not None:
+            d = rays.raycast_distances
+            rs = abi.lg_sensor_raycaster(ray_origins=rays._pattern_origins.data_ptr(), ray_dirs=rays._pattern_dirs.data_ptr(), num_rays=rays.num_rays,
+                                         max_distance=float(rays.cfg.max_distance), attach_yaw_only=int(bool(rays.cfg.attach_yaw_only)),
+                                         ray_hits=rays._data.ray_hits.data_ptr(), hits_found=rays._hits_found_u8.data_ptr(), raycast_distances=d.data_ptr(),
+                                         distance_stride=int(d.stride(0)))
+        if cam is not None:
+            cs = abi.lg_sensor_camera(params=cam._params, ray_dirs=cam._pattern_dirs.data_ptr(), camera_pos=cam.camera_pos.data_ptr(),
+                                      camera_rot=cam.camera_rot.data_ptr(), depth_buffer=cam.depth_buffer.data_ptr(),
+                                      update_interval=int(env.cfg.depth.update_interval), counter=int(env.depth_update_counter))
+        self.has_rays, self.has_camera = rays is not None, cam is not None
+        self._key = self._buffers(env, camera)
+        self._camera_arg = camera
+        self._created(self.lib.lg_sensor_rig_create(env.core.ctx, self.mesh.handle, C.byref(rs) if rs is not None else None, C.byref(cs) if cs is not None else None),
+                      "lg_sensor_rig_create")
+
+    @staticmethod
+    def _buffers(env, camera):
+        """What a cached rig was built over: the context and the sensors' tensors."""
+        rays, cam = getattr(env, "ray_caster", None), getattr(env, "depth_camera", None)
+        key = [env.core.ctx, camera]
+        if rays is not None:
+            key += [rays._data.ray_hits.data_ptr(), rays.raycast_distances.data_ptr(), int(rays.raycast_distances.stride(0))]
+        if cam is not None and hasattr(cam, "camera_pos"):
+            key += [cam.depth_buffer.data_ptr(), cam.camera_pos.data_ptr(), int(env.cfg.depth.update_interval)]
+        return key
+
+    @classmethod
+    def from_env(cls, env, camera=None):
+        """The rig of `env`: its ray caster, its depth camera, or both -- whatever it has enabled.  camera=True asks for the camera (the
+        estimation collection needs both), camera=False leaves it out.  The rig is kept on the env and reused while the sensors' tensors stay
+        the ones it was built over.  ValueError, naming the reason: privileged observations; an `_after_native` layer; an env class whose `step`
+        is not `LeggedRobotRayCast.step` / `LeggedRobotDepth.step`; no sensor enabled; `depth.dis_noise != 0`; a camera asked for with
+        `camera_type` other than "Warp"; a ray caster with `update_period > 0`."""
+        cached = getattr(env, "_sensor_rig", None)
+        if cached is not None and getattr(cached, "handle", None) and cached._camera_arg == camera and cached._key == cls._buffers(env, camera) and refusal(env, camera) is None:
+            return cached
+        rig = cls(env, camera)
+        env._sensor_rig = rig
+        return rig
+
+    # ---- around a collecting call
+    def begin(self):
+        """The camera's phase is the env's counter, whoever stepped the env since the last call."""
+        if self.has_camera:
+            self._check(self.lib.lg_sensor_rig_set_counter(self.handle, int(self.env.depth_update_counter)), "lg_sensor_rig_set_counter")
+
+    def finish(self, T):
+        """The env's host bookkeeping after T sensor steps, as T calls of `env.step` leave it."""
+        env, T = self.env, int(T)
+        env.common_step_counter += T
+        if self.has_camera:
+            env.depth_update_counter = int(self.lib.lg_sensor_rig_counter(self.handle))
+        elif getattr(env, "depth_camera", None) is not None:
+            env.depth_update_counter += T
+        rays = env.ray_caster
+        if self.has_rays:
+            for _ in range(T):          # (T float32 additions of dt, the sum `update_from_root_states` builds)
+                rays._timestamp += env.dt
+            rays._timestamp_last_update[:] = rays._timestamp
+            rays._is_outdated[:] = False
+            rays._data.pos, rays._data.rot = env.root_states[:, 0:3], env.root_states[:, 3:7]
+
+    def step_transition(self, actions, rewards, dones, next_observations=None, values=None, gamma=0.0):
+        """`lg_sensor_step_transition`: one `env.step` with the transition rows of `lg_step_transition`, then `finish(1)`.  actions (N, A),
+        rewards / dones (N) float32 written in place; next_observations (N, O) and values (N) optional."""
+        for x in (actions, rewards, dones, next_observations, values):
+            assert x is None or (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous())
+        self.begin()
+        self._check(self.lib.lg_sensor_step_transition(self.handle, _ptr(actions), _ptr(next_observations), _ptr(values), float(gamma), _ptr(rewards), _ptr(dones),
+                                                       self._stream()), "lg_sensor_step_transition")
+        self.finish(1)

@@ -131,6 +131,9 @@ def get_args(argv=None):
     p.add_argument("--num_threads", type=int, default=0)
     p.add_argument("--runner", type=str, choices=("rsl_rl", "native"), default="rsl_rl",
                    help="rsl_rl: the external package's OnPolicyRunner; native: rl.NativeOnPolicyRunner (collection and PPO update on the library's kernels)")
+    p.add_argument("--sensor_collection", type=str, choices=("host", "native"), default=None,
+                   help="--runner native on an env with the ray caster / depth camera: host (the default) collects through env.step, native through the "
+                        "library's sensor step (rl.SensorRig, runner.sensor_collection of the train config)")
     p.add_argument("--teacher_model_path", type=str,
                    help="distillation tasks: the checkpoint of the teacher's PPO run (or of a distillation run), runner.teacher_model_path of the train config")
     args = p.parse_args(argv)

@@ -72,7 +72,10 @@ class TaskRegistry():
             log_dir = None
         else:
             log_dir = os.path.join(log_root, datetime.now().strftime('%b%d_%H-%M-%S') + '_' + train_cfg.runner.run_name)
-        runner = OnPolicyRunner(env, class_to_dict(train_cfg), log_dir, device=args.rl_device)
+        cfg_dict = class_to_dict(train_cfg)
+        if native and getattr(args, "sensor_collection", None) is not None:          # `--sensor_collection host|native` (rl.NativeOnPolicyRunner)
+            cfg_dict["runner"]["sensor_collection"] = args.sensor_collection
+        runner = OnPolicyRunner(env, cfg_dict, log_dir, device=args.rl_device)
         if train_cfg.runner.resume:
             resume_path = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
             print(f"Loading model from: {resume_path}")

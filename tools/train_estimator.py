@@ -9,8 +9,9 @@ counterpart of the reference's `legged_gym/scripts/terrain_est_train.py` (`Terra
   a gradient step every `gradient_length` chunks, the memory carried across chunks and detached after each gradient step, in eager PyTorch
   (`--update torch`, the default); `--update native` runs the same update on the device through `rl.NativeEstimatorDistillation`
   (include/lgestimator_train.h).
-* collection: `collect_estimation` (`extended_legged_gym_amd/rl/collector.py`) on `elspider_air_rough_raycast`; `--python-loop` collects the
-  same rows with a plain loop over `env.step` (the checker).
+* collection: `collect_estimation` (`extended_legged_gym_amd/rl/collector.py`) on `elspider_air_rough_raycast`, as its host loop (`--collect host`,
+  the default) or as one call into the library (`--collect one-call`); `--python-loop` collects the same rows with a plain loop over `env.step`
+  (the checker).
 
     python tools/train_estimator.py --iters 50 --envs 1024 [--policy walk_policy.pt] [--out run.json] [--update native]
 """
@@ -206,15 +207,25 @@ def collect_python_loop(env, policy, num_steps):
 
 
 def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr=1e-3, gradient_length=15, out=None, log=print, small_terrain=False, update_device=None,
-          eval_precision="fp32", update="torch"):
+          eval_precision="fp32", update="torch", collect="host"):
     """update_device: where the torch update runs (default: the env's device).  "cpu" makes the update reproducible bit for bit -- the GPU's
     convolution backward is not -- which is what a comparison of two collections needs.  eval_precision: the encoder mode ("fp32" | "bf16") of the
     native estimator that plays the trained module over the closing evaluation steps; training itself is fp32.  update: "torch" (`estimator_update`
     on a `TerrainEstimatorTorch`) or "native" (`rl.NativeEstimatorDistillation`: the update on the device, the weights trained in place in an fp32
-    `NativeTerrainEstimator`; update_device does not apply)."""
+    `NativeTerrainEstimator`; update_device does not apply).  collect: "host" (`collect_estimation`'s loop over `env.step`) or "one-call" (the
+    same rows through `lg_collect_estimation`, include/lgsensors.h; without a policy the 0.5 * randn actions are drawn before the call, step by
+    step, so both ways consume the generator alike)."""
     from extended_legged_gym_amd.rl import NativeActorCritic, NativeEstimatorDistillation, NativeTerrainEstimator, collect_estimation
     if update not in ("torch", "native"):
         raise ValueError(f"update {update!r}: must be torch or native")
+    if collect not in ("host", "one-call"):
+        raise ValueError(f"collect {collect!r}: must be host or one-call")
+
+    def collect_rows(estimator=None):
+        if collect == "host":
+            return collect_estimation(env, policy, steps, estimator=estimator)
+        drawn = None if policy is not None else torch.stack([torch.randn(env.num_envs, env.num_actions, device=env.device) * 0.5 for _ in range(steps)])
+        return collect_estimation(env, policy, steps, estimator=estimator, one_call=True, actions=drawn)
     torch.manual_seed(seed)
     env = make_env(envs, seed, small_terrain=small_terrain)
     policy = None
@@ -234,7 +245,7 @@ def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr
         alg = NativeEstimatorDistillation(trained, start, gradient_length=gradient_length, learning_rate=lr)
     for it in range(iters):
         with torch.inference_mode():
-            rows = collect_python_loop(env, policy, steps) if python_loop else collect_estimation(env, policy, steps)
+            rows = collect_python_loop(env, policy, steps) if python_loop else collect_rows()
         if alg is not None:
             loss = alg.update(rows)["estimation"]
         else:
@@ -250,7 +261,7 @@ def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr
         state = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     native = NativeTerrainEstimator(state, shape, 6, device=str(env.device), encoder_precision=eval_precision)          # the file below is one it loads
     with torch.inference_mode():
-        ev = collect_estimation(env, policy, steps, estimator=native)
+        ev = collect_rows(native)
     log(f"native estimator ({eval_precision} encoder) over {steps} fresh steps: mse {ev['mse'].mean().item():.6f}  mae {ev['mae'].mean().item():.6f}")
     if out:
         with open(out, "w") as f:
@@ -274,8 +285,10 @@ def main(argv=None):
     ap.add_argument("--small-terrain", action="store_true", help="2 x 3 terrain tiles (quick runs)")
     ap.add_argument("--eval-precision", choices=("fp32", "bf16"), default="fp32", help="encoder mode of the native estimator that plays the trained module at the end")
     ap.add_argument("--update", choices=("torch", "native"), default="torch", help="where the gradient steps run: eager torch, or the library's kernels (rl.NativeEstimatorDistillation)")
+    ap.add_argument("--collect", choices=("host", "one-call"), default="host", help="collect_estimation as the host loop over env.step, or as one call into the library (lg_collect_estimation)")
     a = ap.parse_args(argv)
-    train(a.iters, a.envs, a.steps, a.seed, a.policy, a.python_loop, out=a.out, small_terrain=a.small_terrain, eval_precision=a.eval_precision, update=a.update)
+    train(a.iters, a.envs, a.steps, a.seed, a.policy, a.python_loop, out=a.out, small_terrain=a.small_terrain, eval_precision=a.eval_precision, update=a.update,
+          collect=a.collect)
 
 
 if __name__ == "__main__":
