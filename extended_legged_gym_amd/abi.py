@@ -292,6 +292,12 @@ def declare_policy_wide(lib):
     """Prototype of include/lgpolicy_wide.h: `lg_mlp_create` for an input row of up to MLP_MAX_INPUT columns."""
     lib.lg_mlp_create_wide.argtypes = [i32, C.POINTER(i32), C.POINTER(C.POINTER(f32)), C.POINTER(C.POINTER(f32)), i32, C.c_int]
     lib.lg_mlp_create_wide.restype = C.c_void_p
+    # include/lgpolicy_wide_memory.h: `lg_rnn_create` for an input row of up to RNN_MAX_INPUT columns, and the host tiling of its two images
+    fpp = C.POINTER(C.POINTER(f32))
+    lib.lg_rnn_create_wide.argtypes = [i32, i32, i32, i32, fpp, fpp, fpp, fpp, C.c_int]
+    lib.lg_rnn_create_wide.restype = C.c_void_p
+    lib.lg_rnn_tile_weights_wide.argtypes = [i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lg_rnn_tile_weights_wide.restype = C.c_int64
     return lib
 
 
@@ -660,6 +666,9 @@ ENCODER_MAX_SIDE, ENCODER_MIN_SIDE, ENCODER_MAX_OUT = 128, 8, 512          # lim
 MLP_MAX_WIDTH = 512          # widest layer of an lg_mlp, inputs included: MLP_MAXW of csrc/lg_policy.hip, held to it by tests/test_estimator_abi.py
 MLP_MAX_INPUT = 2048         # widest input row of lg_mlp_create_wide: LG_MLP_MAX_INPUT of include/lgpolicy_wide.h (the other widths stay within MLP_MAX_WIDTH)
 POLICY_WIDE_SYMBOLS = ["lg_mlp_create_wide"]
+RNN_MAX_WIDTH = 512          # widest input of lg_rnn_create, and the hidden width's bound
+RNN_MAX_INPUT = 2048         # widest input row of lg_rnn_create_wide: LG_RNN_MAX_INPUT of include/lgpolicy_wide_memory.h
+POLICY_WIDE_MEMORY_SYMBOLS = ["lg_rnn_create_wide", "lg_rnn_tile_weights_wide"]
 RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2, "lrelu": 3, "selu": 4}
 

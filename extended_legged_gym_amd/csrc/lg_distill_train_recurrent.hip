@@ -161,6 +161,11 @@ lg_distill_rtrain* lg_distill_rtrain_create(lg_rnn* mem, lg_mlp* student, const 
                                            std::to_string(MLP_MAXW) + " columns");
     return nullptr;
   }
+  if (mem->wide) {
+    lg_policy_fail(LG_ERR_UNSUPPORTED, "the memory is a wide one (lg_rnn_create_wide, " + std::to_string(mem->input) + " inputs): this trainer takes memories of at most " +
+                                           std::to_string(RNN_XMAX) + " inputs (lg_ppo_recurrent_create trains a wide memory)");
+    return nullptr;
+  }
   if (student->h.dims[0] != mem->hidden) { lg_policy_fail(LG_ERR_INVALID, "the MLP's input width is not the memory's hidden width"); return nullptr; }
   if (student->device != mem->device) { lg_policy_fail(LG_ERR_INVALID, "the memory and the network live on different devices"); return nullptr; }
   const int ML = mem->num_layers, Ls = student->h.L, H = mem->hidden;

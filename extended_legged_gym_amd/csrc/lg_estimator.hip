@@ -540,6 +540,7 @@ int lg_estimator_step(lg_conv_encoder* e, lg_mlp* combine, lg_rnn* mem, lg_mlp* 
   lg_rnn_widths(mem, &rtype, &rin, &rhid, &rdev);
   lg_mlp_widths(decoder, &dl, &din, &dout, &ddev);
   if (cin > MLP_MAXW) return lg_policy_fail(LG_ERR_UNSUPPORTED, "combine takes " + std::to_string(cin) + " inputs: the estimator's stages are at most " + std::to_string(MLP_MAXW) + " wide (a handle of lg_mlp_create_wide is refused)");
+  if (mem->wide) return lg_policy_fail(LG_ERR_UNSUPPORTED, "the memory is a wide one (lg_rnn_create_wide, " + std::to_string(rin) + " inputs): the estimator's memory takes at most " + std::to_string(RNN_XMAX) + " inputs");
   const int P = cin - e->out_dim;
   if (cl != 1 || P < 0 || cout != rin || din != rhid)
     return lg_policy_fail(LG_ERR_INVALID, "stage widths do not chain (combine: one layer of encoder out_dim + proprio inputs; its outputs = the memory's input; decoder input = the memory's hidden width)");

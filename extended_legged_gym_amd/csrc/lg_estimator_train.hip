@@ -452,6 +452,11 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   if (max_rows < 1) { lg_policy_fail(LG_ERR_INVALID, "max_rows < 1"); return nullptr; }
   if (!(learning_rate > 0.0)) { lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0"); return nullptr; }
   if (enc->prec != LG_PREC_F32) { lg_policy_fail(LG_ERR_UNSUPPORTED, "a bf16 encoder cannot be trained: train fp32, then build a bf16 estimator from the parameters"); return nullptr; }
+  if (mem->wide) {
+    lg_policy_fail(LG_ERR_UNSUPPORTED, "the memory is a wide one (lg_rnn_create_wide, " + std::to_string(mem->input) + " inputs): the estimator's memory takes at most " +
+                                           std::to_string(RNN_XMAX) + " inputs");
+    return nullptr;
+  }
   const int F = enc->out_dim, cat_w = combine->h.dims[0], Fc = combine->h.dims[combine->h.L], H = mem->hidden, ML = mem->num_layers;
   if (combine->h.L != 1 || cat_w < F || Fc != mem->input || decoder->h.dims[0] != H) {
     lg_policy_fail(LG_ERR_INVALID, "stage widths do not chain (combine: one layer of encoder out_dim + proprio inputs; its outputs = the memory's input; decoder input = the memory's hidden width)");

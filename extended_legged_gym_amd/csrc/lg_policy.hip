@@ -25,6 +25,7 @@
 #include "lg_device.h"
 #include "lg_policy_internal.h"
 #include "lg_rnn_tile.h"
+#include "lg_switches.h"
 #include "../../include/lgpolicy.h"
 #include "../../include/lgrunner.h"
 #include "../../include/lgrunner_privileged.h"
@@ -530,6 +531,90 @@ __global__ __launch_bounds__(MLP_THREADS) void rnn_layer_kernel(RnnStepArgs S0, 
   if (S.L.gru) rnn_tile<true, false>(S, none, row0, n, img); else rnn_tile<false, false>(S, none, row0, n, img);
 }
 
+// ---- a wide memory (lgpolicy_wide.h: lg_rnn_create_wide): layer 0 as projection + seeded step.
+// The one-launch tile cannot take more than RNN_XMAX inputs: it keeps the whole row [x ; h] of 32 rows resident (128 KB at 512 + 512; 320 KB at
+// 2048 + 512, a workgroup has 160), and it cannot slab x either, because a wave walks its chunks one after another under the resident row -- slabs would
+// need the accumulators of ALL chunks of the wave alive at once (8 chunks x 8 tiles x 4 registers).  So the x part is cut off the chain: here the
+// chunks lie on blockIdx.y, a wave owns ONE chunk of 16 hidden units and keeps its G gate accumulators of both row halves in registers while the row
+// passes through LDS in slabs of RNN_XMAX columns.  Every output is one k-ascending chain from zero over blocks of 16 inputs, the chain the narrow tile
+// walks before it reaches h, stored unrounded; rnn_tile<.., SEED> picks it up.  64 KB of LDS: two workgroups per CU.
+template <int G>
+LG_DEV void rnn_xproj_tile(const RnnXprojArgs& P, int64_t row0, int64_t n, float* img) {
+  const RnnLayerDev& R = P.L;
+  const int tid = threadIdx.x, lane = tid & 63, c = blockIdx.y * (MLP_THREADS / 64) + (tid >> 6);
+  const int I = R.I, Hp = 16 * R.nch;
+  const float* __restrict__ x = P.x;
+  const int64_t* __restrict__ gather = P.idx;
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) { acc[g][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[g][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  const float4* ap = reinterpret_cast<const float4*>(img) + (lane & 15) * 4 + (lane >> 4);
+  for (int k0 = 0; k0 < R.Ip; k0 += RNN_XMAX) {
+    const int Kp = R.Ip - k0 < RNN_XMAX ? R.Ip - k0 : RNN_XMAX;       // a multiple of 16
+    if (k0) lds_barrier();                                             // every wave has read the slab before
+    for (int base = 0; base < MLP_ROWS * Kp; base += 8 * MLP_THREADS) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int e = base + u * MLP_THREADS + tid, r = e / Kp, k = e - r * Kp;
+        const int64_t row = row0 + r;
+        float val = 0.f;
+        if (e < MLP_ROWS * Kp && row < n && k0 + k < I) val = x[(gather ? gather[row] : row) * I + k0 + k];
+        v[u] = val;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int e = base + u * MLP_THREADS + tid, r = e / Kp, k = e - r * Kp;
+        if (e < MLP_ROWS * Kp) img[IMG(r, k)] = v[u];
+      }
+    }
+    lds_barrier();
+    if (c < R.nch) {
+      const int kb0 = k0 >> 4;
+      const float4* wc = reinterpret_cast<const float4*>(R.w) + ((size_t)c * (R.nbx + 1) + kb0) * G * 64 + lane;
+      rnn_blocks<G, 2>(acc, wc, ap, 0, Kp >> 4, R.nbx - kb0);
+    }
+  }
+  if (c >= R.nch) return;
+  float* __restrict__ y = P.y;
+  const int col = c * 16 + (lane & 15);
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t row = row0 + 4 * (lane >> 4) + i + 16 * hf;
+        if (row < n) y[(row * G + g) * Hp + col] = acc[g][hf][i];
+      }
+}
+
+// blockIdx.y: eight chunks of 16 hidden units; blockIdx.z picks the memory
+__global__ __launch_bounds__(MLP_THREADS) void rnn_wide_xproj_kernel(RnnXprojArgs P0, RnnXprojArgs P1, int64_t n) {
+  __shared__ __attribute__((aligned(16))) float img[MLP_ROWS * RNN_XMAX];
+  const RnnXprojArgs& P = blockIdx.z == 0 ? P0 : P1;
+  if ((int)blockIdx.y * (MLP_THREADS / 64) >= P.L.nch) return;        // the narrower memory of a pair: the whole workgroup leaves
+  const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
+  if (P.L.gru) rnn_xproj_tile<3>(P, row0, n, img); else rnn_xproj_tile<4>(P, row0, n, img);
+}
+
+void rnn_launch_xproj(const RnnXprojArgs* a, const RnnXprojArgs* b, int64_t n, hipStream_t st) {
+  const int nch = b && b->L.nch > a->L.nch ? b->L.nch : a->L.nch, per = MLP_THREADS / 64;
+  hipLaunchKernelGGL(rnn_wide_xproj_kernel, dim3((unsigned)((n + MLP_ROWS - 1) / MLP_ROWS), (nch + per - 1) / per, b ? 2 : 1), dim3(MLP_THREADS), 0, st, *a, b ? *b : *a, n);
+}
+
+// layer 0 of a wide memory after its projection y: the tile with SEED; the image holds h alone (32 rows x 512 floats = 64 KB).  Both memories' operands
+// in ONE kernel argument indexed by blockIdx.y: the operands of the memory that is not this workgroup's are never loaded
+struct RnnWidePair { RnnStepArgs S[2]; const float* y[2]; };
+__global__ __launch_bounds__(MLP_THREADS) void rnn_wide_layer_kernel(RnnWidePair P, int64_t n) {
+  __shared__ __attribute__((aligned(16))) float img[MLP_ROWS * RNN_XMAX];
+  const RnnStepArgs& S = P.S[blockIdx.y];
+  const float* __restrict__ y = P.y[blockIdx.y];
+  const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
+  const RnnSaveArgs none{};
+  if (S.L.gru) rnn_tile<true, false, true>(S, none, row0, n, img, y); else rnn_tile<false, false, true>(S, none, row0, n, img, y);
+}
+
 // Memory.reset(dones) (memory.py:45-51): hidden_state[..., dones == 1, :] = 0 on every layer
 __global__ __launch_bounds__(256) void rnn_reset_rows_kernel(float* __restrict__ h, float* __restrict__ c, const float* __restrict__ dones, int64_t n, int H, int L) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -545,8 +630,8 @@ static size_t rnn_tiled_count(int G, int I, int H) {
   const int Ip = (I + 15) & ~15, nb = (Ip + ((H + 15) & ~15)) / 16, nch = (H + 15) / 16;
   return (size_t)nch * (nb + 1) * G * 64 * 4;
 }
-static void rnn_tile_weights(int G, int I, int H, const float* w_ih, const float* w_hh, float* tiled) {
-  const int Ip = (I + 15) & ~15, nb = (Ip + ((H + 15) & ~15)) / 16, nch = (H + 15) / 16;
+void rnn_tile_weights_at(int G, int I, int Ip, int nb, int H, const float* w_ih, const float* w_hh, float* tiled) {
+  const int nch = (H + 15) / 16;
   for (int c = 0; c < nch; ++c)
     for (int b = 0; b <= nb; ++b)
       for (int g = 0; g < G; ++g)
@@ -561,6 +646,13 @@ static void rnn_tile_weights(int G, int I, int H, const float* w_ih, const float
             tiled[((((size_t)c * (nb + 1) + b) * G + g) * 64 + ln) * 4 + s] = v;
           }
 }
+static void rnn_tile_weights(int G, int I, int H, const float* w_ih, const float* w_hh, float* tiled) {
+  const int Ip = (I + 15) & ~15;
+  rnn_tile_weights_at(G, I, Ip, (Ip + ((H + 15) & ~15)) / 16, H, w_ih, w_hh, tiled);
+}
+// the two images of a wide layer 0: the projection's (w_ih alone, nbx + 1 blocks per chunk) and the seeded tile's (w_hh alone, nch + 1 blocks)
+static size_t rnn_tiled_count_x(int G, int I, int H) { return (size_t)((H + 15) / 16) * (((I + 15) >> 4) + 1) * G * 64 * 4; }
+static size_t rnn_tiled_count_h(int G, int H) { return (size_t)((H + 15) / 16) * ((H + 15) / 16 + 1) * G * 64 * 4; }
 
 static int rnn_check(const lg_rnn* m, const float* h, const float* c, int64_t n) {
   if (!m || !h || n < 0) return lg_policy_fail(LG_ERR_INVALID, "null memory or hidden state, or n < 0");
@@ -580,11 +672,50 @@ static RnnStepArgs rnn_args(const lg_rnn* m, int l, const float* x, int64_t n, f
   return a;
 }
 
+// the projection workspace of a wide memory for n rows: allocated at the first step, regrown when n grows (the old buffer is released only after the
+// stream it was last used on has drained), never shrunk
+static int rnn_wide_workspace(lg_rnn* m, int64_t n, hipStream_t st) {
+  if (n > m->y_rows) {
+    if (m->y) { POLICY_TRY(hipStreamSynchronize(m->y_stream)); (void)hipFree(m->y); m->y = nullptr; m->y_rows = 0; }
+    const int G = m->type == LG_RNN_GRU ? 3 : 4;
+    POLICY_TRY(hipMalloc((void**)&m->y, (size_t)n * G * 16 * m->xproj.nch * sizeof(float)));
+    m->y_rows = n;
+  }
+  m->y_stream = st;
+  return LG_OK;
+}
+
 // layers of one memory (b null), or of two memories of equal depth side by side
 static int rnn_step_pair(lg_rnn* a, const float* xa, float* ha, float* ca, float* outa, lg_rnn* b, const float* xb, float* hb, float* cb, float* outb,
                          int64_t n, const float* reset, hipStream_t st) {
   const unsigned tiles = (unsigned)((n + MLP_ROWS - 1) / MLP_ROWS);
-  for (int l = 0; l < a->num_layers; ++l) {
+  const bool any_wide = a->wide || (b && b->wide);
+  if (any_wide) {
+    // layer 0 of a wide memory: projection, then the seeded tile; two wide memories side by side, a mixed pair one memory after the other
+    int rc = a->wide ? rnn_wide_workspace(a, n, st) : LG_OK;
+    if (rc == LG_OK && b && b->wide) rc = rnn_wide_workspace(b, n, st);
+    if (rc != LG_OK) return rc;
+    const RnnStepArgs s0 = rnn_args(a, 0, xa, n, ha, ca, reset, outa);
+    const RnnStepArgs s1 = b ? rnn_args(b, 0, xb, n, hb, cb, reset, outb) : s0;
+    const RnnXprojArgs p0{a->xproj, xa, nullptr, a->y}, p1{b ? b->xproj : a->xproj, xb, nullptr, b ? b->y : nullptr};
+    if (b && a->wide && b->wide) {
+      rnn_launch_xproj(&p0, &p1, n, st);
+      hipLaunchKernelGGL(rnn_wide_layer_kernel, dim3(tiles, 2), dim3(MLP_THREADS), 0, st, RnnWidePair{{s0, s1}, {a->y, b->y}}, n);
+    } else {
+      lg_rnn* mem[2] = {a, b};
+      const RnnStepArgs* ss[2] = {&s0, &s1};
+      const RnnXprojArgs* pp[2] = {&p0, &p1};
+      for (int k = 0; k < (b ? 2 : 1); ++k) {
+        if (mem[k]->wide) {
+          rnn_launch_xproj(pp[k], nullptr, n, st);
+          hipLaunchKernelGGL(rnn_wide_layer_kernel, dim3(tiles, 1), dim3(MLP_THREADS), 0, st, RnnWidePair{{*ss[k], *ss[k]}, {mem[k]->y, mem[k]->y}}, n);
+        } else {
+          hipLaunchKernelGGL(rnn_layer_kernel, dim3(tiles, 1), dim3(MLP_THREADS), 0, st, *ss[k], *ss[k], n);
+        }
+      }
+    }
+  }
+  for (int l = any_wide ? 1 : 0; l < a->num_layers; ++l) {
     const RnnStepArgs s0 = rnn_args(a, l, xa, n, ha, ca, reset, outa);
     const RnnStepArgs s1 = b ? rnn_args(b, l, xb, n, hb, cb, reset, outb) : s0;
     hipLaunchKernelGGL(rnn_layer_kernel, dim3(tiles, b ? 2 : 1), dim3(MLP_THREADS), 0, st, s0, s1, n);
@@ -641,15 +772,16 @@ void lg_rnn_destroy(lg_rnn* m) {
   if (!m) return;
   DeviceScope ds_(m->device);
   for (void* p : m->allocs) (void)hipFree(p);
+  if (m->y) (void)hipFree(m->y);
   delete m;
 }
 
-lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t hidden, const float* const* w_ih, const float* const* w_hh,
-                      const float* const* b_ih, const float* const* b_hh, int device_id) {
-  POLICY_ENTRY;
+// the body of lg_rnn_create (max_input 512) and lg_rnn_create_wide (LG_RNN_MAX_INPUT).  wide: layer 0 takes the projection + seeded-tile path
+static lg_rnn* rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t hidden, const float* const* w_ih, const float* const* w_hh,
+                          const float* const* b_ih, const float* const* b_hh, int device_id, int max_input, bool wide) {
   if (type != LG_RNN_LSTM && type != LG_RNN_GRU) { lg_policy_fail(LG_ERR_INVALID, "unknown memory type (lstm | gru)"); return nullptr; }
   if (num_layers < 1 || num_layers > RNN_MAX_LAYERS) { lg_policy_fail(LG_ERR_INVALID, "number of layers out of range (1..4)"); return nullptr; }
-  if (input < 1 || input > 512) { lg_policy_fail(LG_ERR_INVALID, "input width out of range (1..512)"); return nullptr; }
+  if (input < 1 || input > max_input) { lg_policy_fail(LG_ERR_INVALID, "input width out of range (1.." + std::to_string(max_input) + ")"); return nullptr; }
   if (hidden < 1 || hidden > 512) { lg_policy_fail(LG_ERR_INVALID, "hidden width out of range (1..512)"); return nullptr; }
   if (!w_ih || !w_hh || !b_ih || !b_hh) { lg_policy_fail(LG_ERR_INVALID, "null weight list"); return nullptr; }
   for (int l = 0; l < num_layers; ++l)
@@ -658,14 +790,27 @@ lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t h
   DeviceScope ds_(device_id);
   if (!ds_.ok) { lg_policy_fail(LG_ERR_INVALID, "bad device"); return nullptr; }
   lg_rnn* m = new lg_rnn();
-  m->type = type; m->num_layers = num_layers; m->input = input; m->hidden = hidden; m->device = device_id;
+  m->type = type; m->num_layers = num_layers; m->input = input; m->hidden = hidden; m->device = device_id; m->wide = wide;
   const int G = type == LG_RNN_GRU ? 3 : 4, H = hidden;
   for (int l = 0; l < num_layers; ++l) {
     const int I = l == 0 ? input : hidden, Ip = (I + 15) & ~15, nch = (H + 15) / 16, Hp = 16 * nch;
     RnnLayerDev& R = m->layer[l];
     R.gru = type == LG_RNN_GRU; R.I = I; R.H = H; R.Ip = Ip; R.nbx = Ip / 16; R.nb = (Ip + Hp) / 16; R.nch = nch;
-    std::vector<float> tw(rnn_tiled_count(G, I, H)), tb((size_t)4 * Hp, 0.f);
-    rnn_tile_weights(G, I, H, w_ih[l], w_hh[l], tw.data());
+    std::vector<float> tw, tb((size_t)4 * Hp, 0.f);
+    if (wide && l == 0) {
+      RnnLayerDev& X = m->xproj;
+      X = R; X.b = nullptr;
+      std::vector<float> tx(rnn_tiled_count_x(G, I, H));
+      rnn_tile_weights_at(G, I, RNN_NO_HH, X.nbx, H, w_ih[l], nullptr, tx.data());
+      X.w = (const float*)lg_policy_upload(tx.data(), tx.size() * 4, m->allocs);
+      if (!X.w) { lg_rnn_destroy(m); return nullptr; }
+      R.I = 0; R.Ip = 0; R.nbx = 0; R.nb = nch;                 // the seeded tile's image: h alone
+      tw.resize(rnn_tiled_count_h(G, H));
+      rnn_tile_weights_at(G, 0, 0, nch, H, nullptr, w_hh[l], tw.data());
+    } else {
+      tw.resize(rnn_tiled_count(G, I, H));
+      rnn_tile_weights(G, I, H, w_ih[l], w_hh[l], tw.data());
+    }
     for (int u = 0; u < H; ++u) {
       if (type == LG_RNN_LSTM) {
         for (int g = 0; g < 4; ++g) tb[(size_t)g * Hp + u] = b_ih[l][g * H + u] + b_hh[l][g * H + u];
@@ -681,6 +826,43 @@ lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t h
     if (!R.b) { lg_rnn_destroy(m); return nullptr; }
   }
   return m;
+}
+
+lg_rnn* lg_rnn_create(int32_t type, int32_t num_layers, int32_t input, int32_t hidden, const float* const* w_ih, const float* const* w_hh,
+                      const float* const* b_ih, const float* const* b_hh, int device_id) {
+  POLICY_ENTRY;
+  return rnn_create(type, num_layers, input, hidden, w_ih, w_hh, b_ih, b_hh, device_id, RNN_XMAX, false);
+}
+
+lg_rnn* lg_rnn_create_wide(int32_t type, int32_t num_layers, int32_t input, int32_t hidden, const float* const* w_ih, const float* const* w_hh,
+                           const float* const* b_ih, const float* const* b_hh, int device_id) {
+  POLICY_ENTRY;
+  // diagnostic (lgpolicy_wide_memory.h, lg_switches.h): LG_RNN_FORCE_WIDE=1 sends a narrow memory through the wide kernels too, to compare their bits
+  // with lg_rnn_create's
+  int force = 0;
+  std::string bad;
+  if (!lg_switch_flag("LG_RNN_FORCE_WIDE", force, bad)) { lg_policy_fail(LG_ERR_INVALID, bad); return nullptr; }
+  const bool wide = input > RNN_XMAX || force == 1;
+  return rnn_create(type, num_layers, input, hidden, w_ih, w_hh, b_ih, b_hh, device_id, LG_RNN_MAX_INPUT, wide);
+}
+
+int64_t lg_rnn_tile_weights_wide(int32_t type, int32_t input, int32_t hidden, const float* w_ih, const float* w_hh, float* tiled_x, float* tiled_h,
+                                 int64_t* count_h) {
+  POLICY_ENTRY;
+  if (type != LG_RNN_LSTM && type != LG_RNN_GRU) return lg_policy_fail(LG_ERR_INVALID, "unknown memory type (lstm | gru)");
+  if (input < 1 || input > LG_RNN_MAX_INPUT) return lg_policy_fail(LG_ERR_INVALID, "input width out of range (1.." + std::to_string(LG_RNN_MAX_INPUT) + ")");
+  if (hidden < 1 || hidden > 512) return lg_policy_fail(LG_ERR_INVALID, "hidden width out of range (1..512)");
+  const int G = type == LG_RNN_GRU ? 3 : 4;
+  if (tiled_x) {
+    if (!w_ih) return lg_policy_fail(LG_ERR_INVALID, "null weight");
+    rnn_tile_weights_at(G, input, RNN_NO_HH, (input + 15) >> 4, hidden, w_ih, nullptr, tiled_x);
+  }
+  if (tiled_h) {
+    if (!w_hh) return lg_policy_fail(LG_ERR_INVALID, "null weight");
+    rnn_tile_weights_at(G, 0, 0, (hidden + 15) / 16, hidden, nullptr, w_hh, tiled_h);
+  }
+  if (count_h) *count_h = (int64_t)rnn_tiled_count_h(G, hidden);
+  return (int64_t)rnn_tiled_count_x(G, input, hidden);
 }
 
 int lg_rnn_step(lg_rnn* m, const float* x, int64_t n, float* h, float* c, const float* reset, float* out, void* stream) {

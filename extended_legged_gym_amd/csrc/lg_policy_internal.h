@@ -147,4 +147,20 @@ struct lg_rnn {
   int type = 0, num_layers = 0, input = 0, hidden = 0, device = 0;
   RnnLayerDev layer[RNN_MAX_LAYERS];
   std::vector<void*> allocs;
+  // a wide memory (lg_rnn_create_wide, more than RNN_XMAX inputs): layer 0 is two launches.  rnn_wide_xproj_kernel walks the x part of the chain
+  // over `xproj` (w: [chunk][nbx + 1 blocks][gate][lane][4], the last block zero; I, Ip, nbx, nch, H as usual; b unused) into y, and the seeded tile
+  // (lg_rnn_tile.h, SEED) goes on over layer[0], which then describes the h part alone: I = Ip = nbx = 0, nb = nch.
+  bool wide = false;
+  RnnLayerDev xproj{};
+  float* y = nullptr;                // (y_rows, G * 16 nch): the projection of the last step, owned; grows with n, never shrinks
+  int64_t y_rows = 0;
+  hipStream_t y_stream = nullptr;    // the stream y was last used on: drained before y is released
 };
+#define RNN_XMAX 512         // widest input of the one-launch layer (RNN_KMAX - 512); a slab of the projection's staged row
+// The x part of a wide layer 0 for rows [0, n): y[(row * G + g) * Hp + u] = sum_k x[src(row)][k] w_ih[g H + u][k], ONE k-ascending chain per output over
+// blocks of 16 inputs (the order rnn_blocks walks the x part of the narrow layer), src(row) = idx ? idx[row] : row.  b NULL: one memory.
+struct RnnXprojArgs { RnnLayerDev L; const float* x; const int64_t* idx; float* y; };
+void rnn_launch_xproj(const RnnXprojArgs* a, const RnnXprojArgs* b, int64_t n, hipStream_t st);
+// [chunk][nb + 1 blocks][gate][lane][4] of Wcat[:, 0 .. I) = w_ih, Wcat[:, Ip .. Ip + H) = w_hh (either may be absent: I = 0, or Ip past the last block)
+void rnn_tile_weights_at(int G, int I, int Ip, int nb, int H, const float* w_ih, const float* w_hh, float* tiled);
+#define RNN_NO_HH (1 << 30)  // the Ip of an image without a hidden part

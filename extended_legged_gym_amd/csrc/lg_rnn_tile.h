@@ -1,7 +1,10 @@
 // lg_rnn_tile.h — the device tile of one LSTM / GRU layer step, shared by the inference kernel (lg_policy.hip: rnn_layer_kernel) and the
 // training forward (lg_train_recurrent.hip).  One compile-time switch, SAVE, separates them: the k-chain, its order and the gate epilogue are
 // the same code, so the training forward computes lg_rnn_step's values bit for bit, and the SAVE = false instance is the inference kernel as
-// it was.
+// it was.  A third switch, SEED, is layer 0 of a wide memory (lg_rnn_create_wide): the x part of the chain was walked by rnn_wide_xproj_kernel
+// and left unrounded in fp32 (`seed`, (n, G * 16 nch)); the accumulators start from it and the chain goes on over the h blocks, so the sum is the
+// narrow chain cut at the x / h boundary.  The layer descriptor of such a layer has I = Ip = nbx = 0: the image holds h alone.  The SEED = false
+// instances never read `seed` and are the kernels as they were.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -81,8 +84,8 @@ LG_DEV void rnn_blocks(f32x4 (&acc)[4][2], const float4* __restrict__ wc, const 
   }
 }
 
-template <bool GRU, bool SAVE>
-LG_DEV void rnn_tile(const RnnStepArgs& S, const RnnSaveArgs& V, int64_t row0, int64_t n, float* img) {
+template <bool GRU, bool SAVE, bool SEED = false>
+LG_DEV void rnn_tile(const RnnStepArgs& S, const RnnSaveArgs& V, int64_t row0, int64_t n, float* img, const float* __restrict__ seed = nullptr) {
   const RnnLayerDev& R = S.L;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int I = R.I, H = R.H, Ip = R.Ip, Kp = R.nb * 16;
@@ -119,6 +122,17 @@ LG_DEV void rnn_tile(const RnnStepArgs& S, const RnnSaveArgs& V, int64_t row0, i
     f32x4 acc[4][2];
 #pragma unroll
     for (int g = 0; g < 4; ++g) { acc[g][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[g][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    if constexpr (SEED) {                                      // slots 0 .. G - 1 from the projection; a GRU's slot 3 (the hidden side of n) from zero
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int64_t row = row0 + 4 * (lane >> 4) + i + 16 * hf;
+            if (row < n) acc[g][hf][i] = seed[(row * G + g) * Hp + c * 16 + (lane & 15)];
+          }
+    }
     const float4* wc = reinterpret_cast<const float4*>(R.w) + (size_t)c * (R.nb + 1) * G * 64 + lane;
     if (GRU) {
       rnn_blocks<G, 2>(acc, wc, ap, 0, R.nbx, R.nb);

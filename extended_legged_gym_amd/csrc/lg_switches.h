@@ -29,6 +29,7 @@ static const LgSwitch lg_switch_table[] = {
   {"LG_SDF_ORDER",    "0 | 1",                     "1",    "every SDF query",  "0: one env's bodies side by side in a workgroup instead of one body of several envs"},
   {"LG_SDF_BLOCK",    "64 | 128 | 256",            "128",  "every SDF query",  "threads per workgroup of sdf_bodies_kernel"},
   {"LG_RAY_SKIP",     "0 | 1 | 2 | 9",             "1",    "every depth render", "0: rays walk from the camera; 2: also the coarse walk over blocks; 9: timing probe, every ray misses"},
+  {"LG_RNN_FORCE_WIDE", "0 | 1",                   "0",    "lg_rnn_create_wide", "1: a memory of 512 inputs or fewer takes the wide kernels too (projection + seeded step): a test hook for their bits"},
 };
 
 static inline bool lg_switch_refuse(const char* name, const char* value, std::string& err) {

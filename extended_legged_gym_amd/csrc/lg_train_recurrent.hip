@@ -40,6 +40,17 @@ __global__ __launch_bounds__(MLP_THREADS) void rnn_train_forward_kernel(RnnTrain
   if (S.L.gru) rnn_tile<true, true>(S, V, row0, n, img); else rnn_tile<false, true>(S, V, row0, n, img);
 }
 
+// layer 0 of a wide memory (lg_rnn_create_wide): the tile with SAVE and SEED on the projection rows y of this step (rnn_wide_xproj_kernel ran over all
+// T * count rows of the mini-batch before the first step: the projection does not depend on the state).  The image holds h alone: 64 KB.
+__global__ __launch_bounds__(MLP_THREADS) void rnn_wide_train_forward_kernel(RnnTrainPair P, const float* __restrict__ y0, const float* __restrict__ y1, int64_t n) {
+  __shared__ __attribute__((aligned(16))) float img[MLP_ROWS * RNN_XMAX];
+  const RnnStepArgs& S = P.S[blockIdx.y];
+  const RnnSaveArgs& V = P.V[blockIdx.y];
+  const float* __restrict__ y = blockIdx.y == 0 ? y0 : y1;
+  const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
+  if (S.L.gru) rnn_tile<true, true, true>(S, V, row0, n, img, y); else rnn_tile<false, true, true>(S, V, row0, n, img, y);
+}
+
 // one 16-column chunk over nblk blocks of 16 inputs: both row halves, k ascending (chunk_chain of lg_train.hip)
 LG_DEV void rec_chain(const float4* __restrict__ wc, const float4* ap, int nblk, f32x4& acc0, f32x4& acc1) {
   for (int kb = 0; kb < nblk; ++kb) {
@@ -169,7 +180,8 @@ __global__ __launch_bounds__(MLP_THREADS) void rnn_backward_kernel(RnnBackPair P
   if (B.gru) rnn_back_tile<true>(B, row0, n, img); else rnn_back_tile<false>(B, row0, n, img);
 }
 
-// element e of the tiled weights (rnn_tile_weights of lg_policy.hip, the same index arithmetic), then of the bias rows
+// element e of the tiled weights (rnn_tile_weights_at of lg_policy.hip, the same index arithmetic), then of the bias rows.  A wide layer 0 has two
+// entries: the projection image (Ip = RNN_NO_HH: no hidden part; b NULL: no bias rows) and the seeded tile's (I = Ip = 0: h alone, and the bias rows)
 __global__ __launch_bounds__(256) void rnn_retile_kernel(const RnnRetile* __restrict__ tab, const float* __restrict__ theta) {
   const RnnRetile R = tab[blockIdx.y];
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -187,7 +199,7 @@ __global__ __launch_bounds__(256) void rnn_retile_kernel(const RnnRetile* __rest
       else if (k >= R.Ip && k < R.Ip + H) v = theta[R.whh + (int64_t)(g * H + u) * H + (k - R.Ip)];
     }
     R.w[e] = v;
-  } else if (e < wcount + 4 * Hp) {
+  } else if (e < wcount + 4 * Hp && R.b) {
     const int j = (int)(e - wcount), g = j / Hp, u = j - g * Hp;
     float v = 0.f;
     if (u < H) {
@@ -212,6 +224,7 @@ struct RecMem {
   lg_rnn* m = nullptr;
   int G = 0, L = 0, I = 0, H = 0;
   MemLayer layer[RNN_MAX_LAYERS];
+  float* y = nullptr;                // a wide memory: layer 0's projection of the mini-batch, (max_rows, G * H padded to 16)
 };
 
 struct lg_ppo_recurrent : TrainCore {
@@ -251,6 +264,12 @@ static int rec_step(lg_ppo_recurrent* p, const lg_ppo_rows* r, const lg_rollout_
   const float* hs[2] = {hid->h_a, hid->h_c};
   const float* cs[2] = {hid->c_a, hid->c_c};
   hipLaunchKernelGGL(rec_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p->idx, n, mb, N, env0);
+  // ---- a wide memory's input projection: all T * mb rows at once
+  const bool wide[2] = {p->mem[0].m->wide, p->mem[1].m->wide};
+  RnnXprojArgs X[2];
+  for (int k = 0; k < 2; ++k) X[k] = RnnXprojArgs{p->mem[k].m->xproj, xs[k], p->idx, p->mem[k].y};
+  if (wide[0] && wide[1]) rnn_launch_xproj(&X[0], &X[1], n, st);
+  else for (int k = 0; k < 2; ++k) if (wide[k]) rnn_launch_xproj(&X[k], nullptr, n, st);
   // ---- forward through time
   for (int t = 0; t < T; ++t)
     for (int l = 0; l < L; ++l) {
@@ -271,7 +290,22 @@ static int rec_step(lg_ppo_recurrent* p, const lg_ppo_rows* r, const lg_rollout_
         V[k].hin = Y.hin + at; V[k].hnew = Y.hnew + at;
         V[k].cin = M.G == 4 ? Y.cin + at : nullptr; V[k].cnew = M.G == 4 ? Y.cnew + at : nullptr;
       }
-      hipLaunchKernelGGL(rnn_train_forward_kernel, dim3(tiles, 2), dim3(MLP_THREADS), 0, st, P, mb);
+      if (l > 0 || !(wide[0] || wide[1])) {
+        hipLaunchKernelGGL(rnn_train_forward_kernel, dim3(tiles, 2), dim3(MLP_THREADS), 0, st, P, mb);
+        continue;
+      }
+      const float* yt[2];
+      for (int k = 0; k < 2; ++k) yt[k] = wide[k] ? p->mem[k].y + (size_t)t * mb * p->mem[k].G * 16 * p->mem[k].m->xproj.nch : nullptr;
+      if (wide[0] && wide[1]) {
+        hipLaunchKernelGGL(rnn_wide_train_forward_kernel, dim3(tiles, 2), dim3(MLP_THREADS), 0, st, P, yt[0], yt[1], mb);
+      } else {                                               // a mixed pair: one memory after the other
+        for (int k = 0; k < 2; ++k) {
+          RnnTrainPair One{};
+          One.S[0] = P.S[k]; One.V[0] = P.V[k];
+          if (wide[k]) hipLaunchKernelGGL(rnn_wide_train_forward_kernel, dim3(tiles, 1), dim3(MLP_THREADS), 0, st, One, yt[k], yt[k], mb);
+          else hipLaunchKernelGGL(rnn_train_forward_kernel, dim3(tiles, 1), dim3(MLP_THREADS), 0, st, One, mb);
+        }
+      }
     }
   // ---- the MLPs on the memories' outputs, time-major; the losses; the MLPs' backward and dL/d(their input)
   train_launch_forward(p, p->mem[0].layer[L - 1].hnew, p->mem[1].layer[L - 1].hnew, nullptr, n, st);
@@ -407,6 +441,7 @@ lg_ppo_recurrent* lg_ppo_recurrent_create(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* 
       train_core_add_seg(p, k, LG_MLP_MAX_LAYERS + 2 * l, K, I, Y.Dih, l == 0 ? nullptr : M.layer[l - 1].hnew, nullptr, nullptr, 0, Y.wtx, nbk, &ok);
       train_core_add_seg(p, k, LG_MLP_MAX_LAYERS + 2 * l + 1, K, H, Y.Dhh, Y.hin, nullptr, nullptr, 0, Y.wth, nbk, &ok);
     }
+    if (mems[k]->wide) M.y = alloc(R * M.G * 16 * ((H + 15) / 16), false);
     float* bw0 = alloc((size_t)Nn.bnch[0] * (Nn.bkpad[0] / 16) * 256, true);
     Nn.bw[0] = bw0; S0.bw = bw0; S0.Ain = M.layer[M.L - 1].hnew;
   }
@@ -425,6 +460,14 @@ lg_ppo_recurrent* lg_ppo_recurrent_create(lg_rnn* mem_a, lg_mlp* actor, lg_rnn* 
       retile.push_back(rt);
       const int64_t cnt = (int64_t)D.nch * (D.nb + 1) * rt.G * 256 + 4 * 16 * D.nch;
       if (cnt > p->retile_big) p->retile_big = cnt;
+      if (l == 0 && p->mem[k].m->wide) {
+        const RnnLayerDev& Xd = p->mem[k].m->xproj;
+        RnnRetile rx = rt;
+        rx.w = const_cast<float*>(Xd.w); rx.b = nullptr; rx.I = Xd.I; rx.Ip = RNN_NO_HH; rx.nb = Xd.nbx;
+        retile.push_back(rx);
+        const int64_t cx = (int64_t)Xd.nch * (Xd.nbx + 1) * rx.G * 256;
+        if (cx > p->retile_big) p->retile_big = cx;
+      }
     }
   p->nretile = (int)retile.size();
   p->loss_part = alloc(train_ppo_loss_floats(max_rows), true);

@@ -229,7 +229,9 @@ class NativeMemory(_NativeHandle):
                 f"layer {l}: shapes do not belong to an nn.{rnn_type.upper()} of hidden size {H}"
         fp = C.POINTER(C.c_float)
         lists = [(fp * len(arrs))(*[layer[j].ctypes.data_as(fp) for layer in arrs]) for j in range(4)]
-        self._created(self.lib.lg_rnn_create(abi.RNN_TYPES[rnn_type], self.num_layers, self.input_size, H, *lists, index), "lg_rnn_create")
+        # an input row wider than the one-launch layer holds (an observation that carries a sensor) takes the entry point with the projection in front
+        create = "lg_rnn_create_wide" if self.input_size > abi.RNN_MAX_WIDTH else "lg_rnn_create"
+        self._created(getattr(self.lib, create)(abi.RNN_TYPES[rnn_type], self.num_layers, self.input_size, H, *lists, index), create)
         self.h = self.c = None
 
     @classmethod

@@ -148,7 +148,12 @@ class NativeRecurrentPPO(NativePPO):
         self._need_handle()
         mem = self.policy.memory_a if memory == 0 else self.policy.memory_c
         G, H = (4 if mem.rnn_type == "lstm" else 3), mem.hidden_size
-        count = int(self.lib.lg_rnn_tile_weights(abi.RNN_TYPES[mem.rnn_type], mem.input_size if layer == 0 else H, H, None, None, None))
+        if layer == 0 and mem.input_size > abi.RNN_MAX_WIDTH:          # a wide memory: the seeded step's image (weight_hh alone; lgpolicy_wide_memory.h)
+            size = C.c_int64(0)
+            self.lib.lg_rnn_tile_weights_wide(abi.RNN_TYPES[mem.rnn_type], mem.input_size, H, None, None, None, None, C.byref(size))
+            count = size.value
+        else:
+            count = int(self.lib.lg_rnn_tile_weights(abi.RNN_TYPES[mem.rnn_type], mem.input_size if layer == 0 else H, H, None, None, None))
         w, b = np.empty(count, np.float32), np.empty(4 * 16 * ((H + 15) // 16), np.float32)
         self._call("get_images", memory, layer, w.ctypes.data, b.ctypes.data)
         return w, b
