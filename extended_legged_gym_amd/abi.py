@@ -1,9 +1,14 @@
-"""ctypes mirror of `include/lgstep.h` (the C ABI of the env-step library).
+"""ctypes mirror of the headers under `include/` (the C ABI of the env-step library).
 
-Only declarations live here: struct layouts, enum values and function prototypes.  `tests/test_abi.py` parses the
-header and checks every enum value and struct size against this file so the two cannot drift apart.
+Only declarations live here: struct layouts, enum values and function prototypes, one `declare_*` function per unit, and at the
+end the table of units (`UNITS`) with `declare(lib, *units)`, the one way to set prototypes on a library.  `tests/test_abi_units.py`
+parses every header and checks names, exports and struct layouts against this file, `tests/test_abi.py` the enum values, so the
+two cannot drift apart.
 """
+import collections
 import ctypes as C
+import functools
+import types
 
 LG_ABI_VERSION = 5
 LG_MAX_LEGS, LG_JOINTS_PER_LEG, LG_MAX_JOINTS_PER_LEG = 6, 3, 6
@@ -21,7 +26,6 @@ LG_MESH_PLANE, LG_MESH_HEIGHTFIELD, LG_MESH_TRIMESH = 0, 1, 2
 LG_RNG_PHILOX, LG_RNG_INJECT = 0, 1
 LG_SOLVER_PGS, LG_SOLVER_TGS = 0, 1
 LG_FRICTION_CONE, LG_FRICTION_PYRAMID = 0, 1
-
 
 
 def rand_slots(num_dof=12):
@@ -378,7 +382,6 @@ def declare_policy(lib):
     return lib
 
 
-
 class lg_ppo_rows(C.Structure):
     """include/lgtrain.h: device pointers to the flattened (R, .) rows of a rollout."""
     _fields_ = [(k, C.c_void_p) for k in ("observations", "critic_observations", "actions", "values", "returns", "advantages", "actions_log_prob",
@@ -480,11 +483,6 @@ def declare_train_symmetry(lib):
     return lib
 
 
-SYMMETRY_TRAIN_SYMBOLS = ["lg_ppo_sym_create", "lg_ppo_sym_destroy", "lg_ppo_sym_minibatch", "lg_ppo_sym_update", "lg_ppo_sym_parameter_count",
-                          "lg_ppo_sym_gradients", "lg_ppo_sym_forward_outputs", "lg_ppo_sym_get_parameters", "lg_ppo_sym_get_state", "lg_ppo_sym_set_state",
-                          "lg_ppo_sym_set_learning_rate"]
-
-
 class lg_ppo_recurrent_params(C.Structure):
     """include/lgtrain_recurrent.h: HOST parameters of an ActorCriticRecurrent in torch's layout, and the shapes they were taken from."""
     _fields_ = ([(k, i32) for k in ("rnn_type", "num_layers", "input_a", "hidden_a", "input_c", "hidden_c")] +
@@ -513,12 +511,6 @@ def declare_train_recurrent(lib):
     lib.lg_ppo_recurrent_get_images.restype = C.c_int
     _declare_trainer_group(lib, "lg_ppo_recurrent", workspace=True)
     return lib
-
-
-TRAIN_RECURRENT_SYMBOLS = ["lg_ppo_recurrent_create", "lg_ppo_recurrent_destroy", "lg_ppo_recurrent_minibatch", "lg_ppo_recurrent_update",
-                           "lg_ppo_recurrent_parameter_count", "lg_ppo_recurrent_workspace_bytes", "lg_ppo_recurrent_gradients",
-                           "lg_ppo_recurrent_forward_outputs", "lg_ppo_recurrent_get_parameters", "lg_ppo_recurrent_get_state",
-                           "lg_ppo_recurrent_set_state", "lg_ppo_recurrent_set_learning_rate", "lg_ppo_recurrent_get_images"]
 
 
 class lg_distill_train_hyper(C.Structure):
@@ -551,10 +543,6 @@ def declare_distill_train(lib):
     return lib
 
 
-DISTILL_TRAIN_SYMBOLS = ["lg_distill_train_create", "lg_distill_train_destroy", "lg_distill_train_group", "lg_distill_train_update",
-                         "lg_distill_train_parameter_count", "lg_distill_train_gradients", "lg_distill_train_forward_outputs",
-                         "lg_distill_train_step_losses", "lg_distill_train_get_parameters", "lg_distill_train_get_state",
-                         "lg_distill_train_set_state", "lg_distill_train_set_learning_rate"]
 DISTILL_LOSSES = {"mse": 0, "huber": 1}          # enum lg_distill_loss
 
 
@@ -588,14 +576,6 @@ def declare_distill_rtrain(lib):
     lib.lg_distill_rtrain_forward_outputs.restype = C.c_int
     _declare_trainer_group(lib, "lg_distill_rtrain", carry=True, workspace=True, step_losses=True)
     return lib
-
-
-DISTILL_RTRAIN_SYMBOLS = ["lg_distill_rtrain_create", "lg_distill_rtrain_destroy", "lg_distill_rtrain_group", "lg_distill_rtrain_update",
-                          "lg_distill_rtrain_parameter_count", "lg_distill_rtrain_student_parameter_count", "lg_distill_rtrain_workspace_bytes",
-                          "lg_distill_rtrain_gradients", "lg_distill_rtrain_forward_outputs", "lg_distill_rtrain_step_losses",
-                          "lg_distill_rtrain_get_carry", "lg_distill_rtrain_set_carry", "lg_distill_rtrain_reset_carry",
-                          "lg_distill_rtrain_get_parameters", "lg_distill_rtrain_get_state", "lg_distill_rtrain_set_state",
-                          "lg_distill_rtrain_set_learning_rate"]
 
 
 class lg_estimator_train_hyper(C.Structure):
@@ -637,46 +617,20 @@ def declare_estimator_train(lib):
     return lib
 
 
-ESTIMATOR_TRAIN_SYMBOLS = ["lg_estimator_train_create", "lg_estimator_train_destroy", "lg_estimator_train_group", "lg_estimator_train_update",
-                           "lg_estimator_train_parameter_count", "lg_estimator_train_workspace_bytes", "lg_estimator_train_wgrad_slab_rows",
-                           "lg_estimator_train_gradients", "lg_estimator_train_forward_outputs", "lg_estimator_train_step_losses",
-                           "lg_estimator_train_get_carry", "lg_estimator_train_set_carry", "lg_estimator_train_reset_carry",
-                           "lg_estimator_train_get_parameters", "lg_estimator_train_get_state", "lg_estimator_train_set_state",
-                           "lg_estimator_train_set_learning_rate"]
 ESTIMATOR_LOSSES = {"mse": 0, "huber": 1, "l1": 2}          # enum lg_estimator_loss
 
-TRAIN_SYMBOLS = ["lg_ppo_create", "lg_ppo_destroy", "lg_ppo_minibatch", "lg_ppo_update", "lg_ppo_parameter_count", "lg_ppo_gradients",
-                 "lg_ppo_forward_outputs", "lg_ppo_get_parameters", "lg_ppo_get_state", "lg_ppo_set_state", "lg_ppo_set_learning_rate", "lg_ppo_wgrad_slab_rows"]
 NOISE_STD_TYPES = {"scalar": 0, "log": 1}          # enum lg_noise_std_type
 LR_SCHEDULES = {"fixed": 0, "adaptive": 1}          # enum lg_lr_schedule
 
-POLICY_SYMBOLS = ["lg_mlp_create", "lg_mlp_destroy", "lg_mlp_last_error", "lg_mlp_forward", "lg_policy_act", "lg_compute_returns",
-                  "lg_collect_rollout", "lg_plan_from_nodes", "lg_mppi_update", "lg_mppi_sample_plans", "lg_planner_diffuse",
-                  "lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",
-                  "lg_collect_rollout_recurrent", "lg_obs_history_step", "lg_distill_act", "lg_distill_act_recurrent", "lg_collect_distillation",
-                  "lg_collect_distillation_recurrent", "lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights",
-                  "lg_conv_encoder_forward", "lg_mlp_set_output_activation", "lg_estimator_step", "lg_conv_encoder_stage_shape",
-                  "lg_conv_encoder_forward_stages", "lg_conv_encoder_create_precision", "lg_conv_encoder_precision"]
-ESTIMATOR_SYMBOLS = ["lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights", "lg_conv_encoder_forward",
-                     "lg_mlp_set_output_activation", "lg_estimator_step", "lg_conv_encoder_stage_shape", "lg_conv_encoder_forward_stages"]
-ESTIMATOR_BF16_SYMBOLS = ["lg_conv_encoder_create_precision", "lg_conv_encoder_precision", "lg_conv_tile_weights_bf16"]
 LG_PREC_F32, LG_PREC_BF16 = 0, 1          # the encoder's precision modes (include/lgpolicy.h)
 ENCODER_PRECISIONS = {"fp32": LG_PREC_F32, "bf16": LG_PREC_BF16}
 ENCODER_MAX_SIDE, ENCODER_MIN_SIDE, ENCODER_MAX_OUT = 128, 8, 512          # limits of lg_conv_encoder_create
 MLP_MAX_WIDTH = 512          # widest layer of an lg_mlp, inputs included: MLP_MAXW of csrc/lg_policy.hip, held to it by tests/test_estimator_abi.py
 MLP_MAX_INPUT = 2048         # widest input row of lg_mlp_create_wide: LG_MLP_MAX_INPUT of include/lgpolicy_wide.h (the other widths stay within MLP_MAX_WIDTH)
-POLICY_WIDE_SYMBOLS = ["lg_mlp_create_wide"]
 RNN_MAX_WIDTH = 512          # widest input of lg_rnn_create, and the hidden width's bound
 RNN_MAX_INPUT = 2048         # widest input row of lg_rnn_create_wide: LG_RNN_MAX_INPUT of include/lgpolicy_wide_memory.h
-POLICY_WIDE_MEMORY_SYMBOLS = ["lg_rnn_create_wide", "lg_rnn_tile_weights_wide"]
 RNN_TYPES = {"lstm": 0, "gru": 1}          # enum lg_rnn_type
 ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2, "lrelu": 3, "selu": 4}
-
-PRODUCT_SYMBOLS = ["lg_abi_sizes", "lg_arena_bytes", "lg_create", "lg_get_tensor", "lg_step", "lg_step_physics", "lg_step_subset", "lg_step_transition", "lg_sync_main_to_rollout", "lg_rollout_batch", "lg_compute_torques",
-                   "lg_simulate", "lg_post_physics_step", "lg_reset_idx", "lg_profile_begin", "lg_profile_end", "lg_last_error",
-                   "lg_destroy", "lg_set_extra_obs", "lg_mesh_create", "lg_mesh_destroy", "lg_mesh_info", "lg_mesh_ray_lattice", "lg_mesh_contact_lattice", "lg_mesh_last_error",
-                   "lg_raycast_mesh", "lg_mesh_query_sdf", "lg_raycaster_update", "lg_depth_camera_update",
-                   "lg_terrain_generate", "lg_heightfield_to_trimesh", "lg_pose_layer_step", "lg_set_reward_terms", "lg_set_async_gait", "lg_set_lattice_capsules", "lg_step_subset_physics", "lg_post_physics_subset", "lg_raycaster_update_subset", "lg_sdf_bodies_update", "lg_set_state_indexed", "lg_gather_step_rows", "lg_step_subset_rows", "lg_step_rollout", "lg_set_extra_termination", "lg_foottrack_stray", "lg_foottrack_layer_step"]
 
 
 class lg_runner_episode(C.Structure):
@@ -716,10 +670,6 @@ def declare_runner(lib):
     return lib
 
 
-RUNNER_SYMBOLS = ["lg_obsnorm_create", "lg_obsnorm_destroy", "lg_obsnorm_get_state", "lg_obsnorm_set_state", "lg_obsnorm_step", "lg_obsnorm_inverse",
-                  "lg_obsnorm_carried", "lg_obsnorm_forget_carried", "lg_runner_collect", "lg_runner_episode_track"]
-
-
 class lg_runner_privileged(C.Structure):
     """include/lgrunner_privileged.h: what lg_runner_collect_privileged takes beyond lg_runner_collect."""
     _fields_ = [("history", C.POINTER(lg_obs_history)), ("critic_normalizer", C.c_void_p), ("privileged_observations", C.c_void_p),
@@ -737,9 +687,6 @@ def declare_runner_privileged(lib):
     return lib
 
 
-RUNNER_PRIVILEGED_SYMBOLS = ["lg_obsnorm_step_pair", "lg_runner_collect_privileged"]
-
-
 class lg_runner_distill(C.Structure):
     """include/lgrunner_distill.h: the hooks of lg_runner_collect_distillation(_recurrent)."""
     _fields_ = [("student_normalizer", C.c_void_p), ("teacher_normalizer", C.c_void_p), ("training", i32), ("episode", C.POINTER(lg_runner_episode))]
@@ -755,9 +702,6 @@ def declare_runner_distill(lib):
         [vp] * 8 + [C.POINTER(lg_runner_distill), vp]
     lib.lg_runner_collect_distillation_recurrent.restype = C.c_int
     return lib
-
-
-RUNNER_DISTILL_SYMBOLS = ["lg_runner_collect_distillation", "lg_runner_collect_distillation_recurrent"]
 
 
 class lg_sensor_raycaster(C.Structure):
@@ -780,10 +724,6 @@ class lg_estimation_out(C.Structure):
 class lg_estimation_nets(C.Structure):
     """include/lgsensors.h: the four stages of `lg_estimator_step` and the memory's live state."""
     _fields_ = [(k, C.c_void_p) for k in ("encoder", "combine", "memory", "decoder", "h", "c")]
-
-
-SENSOR_STRUCTS = {"lg_sensor_raycaster": lg_sensor_raycaster, "lg_sensor_camera": lg_sensor_camera, "lg_estimation_out": lg_estimation_out,
-                  "lg_estimation_nets": lg_estimation_nets}
 
 
 def declare_sensors(lib):
@@ -813,5 +753,65 @@ def declare_sensors(lib):
     return lib
 
 
-SENSOR_SYMBOLS = ["lg_post_physics_transition", "lg_extra_obs_info", "lg_sensor_rig_create", "lg_sensor_rig_destroy", "lg_sensor_rig_counter",
-                  "lg_sensor_rig_set_counter", "lg_sensor_step_transition", "lg_runner_collect_sensors", "lg_estimation_rows", "lg_collect_estimation"]
+# ---------------------------------------------------------------------------------------------------------------------------------- the units
+Unit = collections.namedtuple("Unit", "declare headers")
+
+# One row per `declare_*` function: the headers under include/ whose prototypes it mirrors.  Everything else about a unit is derived: its symbols
+# are what the function sets (`symbols`), its structs are the `typedef struct lg_...` names of its headers, found here by name.  A new header
+# costs its `declare_x`, a row here and the refusal table of its test file; tests/test_abi_units.py holds every row to the same checks.
+UNITS = {
+    "product": Unit(declare_product, ("lgstep.h",)),
+    "policy": Unit(declare_policy, ("lgpolicy.h",)),
+    "policy_wide": Unit(declare_policy_wide, ("lgpolicy_wide.h", "lgpolicy_wide_memory.h")),
+    "train": Unit(declare_train, ("lgtrain.h",)),
+    "train_symmetry": Unit(declare_train_symmetry, ("lgtrain_symmetry.h",)),
+    "train_recurrent": Unit(declare_train_recurrent, ("lgtrain_recurrent.h",)),
+    "distill_train": Unit(declare_distill_train, ("lgdistill.h",)),
+    "distill_rtrain": Unit(declare_distill_rtrain, ("lgdistill_recurrent.h",)),
+    "estimator_train": Unit(declare_estimator_train, ("lgestimator_train.h",)),
+    "runner": Unit(declare_runner, ("lgrunner.h",)),
+    "runner_privileged": Unit(declare_runner_privileged, ("lgrunner_privileged.h",)),
+    "runner_distill": Unit(declare_runner_distill, ("lgrunner_distill.h",)),
+    "sensors": Unit(declare_sensors, ("lgsensors.h",)),
+}
+
+
+class _Recorder:
+    """Stands in for the library: keeps every function a `declare_*` touches, with the prototype it is given."""
+
+    def __init__(self):
+        self.functions = {}
+
+    def __getattr__(self, name):
+        return self.functions.setdefault(name, types.SimpleNamespace(argtypes=None, restype=C.c_int))
+
+
+@functools.lru_cache(maxsize=None)
+def _recorded(declare):
+    rec = _Recorder()
+    declare(rec)
+    return rec.functions
+
+
+def prototypes(unit):
+    """name -> (argtypes, restype) record of every function the unit's `declare_*` sets, in the order it sets them.  No library needed.  (Kept per
+    declare function, not per unit name: whoever replaces a row of `UNITS` gets that row's own record.)"""
+    return _recorded(UNITS[unit].declare)
+
+
+def symbols(unit):
+    """The entry points of a unit: what its `declare_*` declares."""
+    return list(prototypes(unit))
+
+
+def declare(lib, *units):
+    """Sets the prototypes of the named units on `lib`, each at most once per library object; every unit: `declare(lib, *UNITS)`."""
+    done = lib.__dict__.setdefault("_lg_units", set())
+    for unit in units:
+        if unit not in done:
+            UNITS[unit].declare(lib)
+            done.add(unit)
+    return lib
+
+
+PRODUCT_SYMBOLS, POLICY_SYMBOLS, TRAIN_SYMBOLS = symbols("product"), symbols("policy"), symbols("train")

@@ -19,7 +19,7 @@ class NativeDistillation(_NativeSequenceTrainer):
     object acts with the new student; nothing is rebuilt."""
     _destroy = "lg_distill_train_destroy"
     _prefix = "lg_distill_train_"
-    _declare = staticmethod(abi.declare_distill_train)
+    _unit = "distill_train"
     _hyper_type, _losses, _loss_name = abi.lg_distill_train_hyper, abi.DISTILL_LOSSES, "behavior"
     _norm_needs_step = False
     _group_has_train = False

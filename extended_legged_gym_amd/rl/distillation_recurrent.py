@@ -25,7 +25,7 @@ class NativeRecurrentDistillation(_NativeSequenceTrainer):
     the next update's epochs start from) and forgets the teacher memory's."""
     _destroy = "lg_distill_rtrain_destroy"
     _prefix = "lg_distill_rtrain_"
-    _declare = staticmethod(abi.declare_distill_rtrain)
+    _unit = "distill_rtrain"
     _hyper_type, _losses, _loss_name = abi.lg_distill_train_hyper, abi.DISTILL_LOSSES, "behavior"
     _norm_names = ("grad_norm", "memory_grad_norm")          # over `student.*`, the one the clip uses; over `memory_s.*`
     _carry_on_device = True          # the carry calls take device tensors: the state never visits the host

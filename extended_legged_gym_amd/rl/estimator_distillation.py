@@ -14,7 +14,7 @@ from .trainer import _NativeSequenceTrainer, _declared
 
 
 def _estimator_train_lib():
-    return _declared(abi.declare_estimator_train)
+    return _declared("estimator_train")
 
 
 class NativeEstimatorDistillation(_NativeSequenceTrainer):
@@ -24,7 +24,7 @@ class NativeEstimatorDistillation(_NativeSequenceTrainer):
     (`get_hidden_states` / `set_hidden_states`)."""
     _destroy = "lg_estimator_train_destroy"
     _prefix = "lg_estimator_train_"
-    _declare = staticmethod(abi.declare_estimator_train)
+    _unit = "estimator_train"
     _hyper_type, _losses, _loss_name = abi.lg_estimator_train_hyper, abi.ESTIMATOR_LOSSES, "estimation"
     _norm_names = ("last_grad_norm",)
 

@@ -7,18 +7,12 @@ import ctypes as C
 import numpy as np
 import torch
 
-from extended_legged_gym_amd import abi
-from .policy import _NativeHandle, _lib, _ptr
+from extended_legged_gym_amd.native import load_library
+from .policy import _NativeHandle, _ptr
 
 
 def _runner_lib():
-    lib = _lib()
-    if not getattr(lib, "_runner_declared", False):
-        abi.declare_runner(lib)
-        abi.declare_runner_privileged(lib)
-        abi.declare_runner_distill(lib)
-        lib._runner_declared = True
-    return lib
+    return load_library("policy", "policy_wide", "runner", "runner_privileged", "runner_distill")
 
 
 STATE_KEYS = ("_mean", "_var", "_std", "count")

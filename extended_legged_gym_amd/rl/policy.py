@@ -17,12 +17,7 @@ from extended_legged_gym_amd.native import load_library
 
 
 def _lib():
-    lib = load_library()
-    if not getattr(lib, "_policy_declared", False):
-        abi.declare_policy(lib)
-        abi.declare_policy_wide(lib)
-        lib._policy_declared = True
-    return lib
+    return load_library("policy", "policy_wide")
 
 
 LOG_SQRT_2PI = 0.9189385332046727          # log sqrt(2 pi) of Normal.log_prob and Normal.entropy

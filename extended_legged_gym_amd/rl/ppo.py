@@ -13,7 +13,7 @@ from .trainer import _NativeTrainer, _declared
 
 
 def _train_lib():
-    return _declared(abi.declare_train)
+    return _declared("train")
 
 
 def _sequential_layers(state_dict, prefix):
@@ -28,7 +28,7 @@ class NativePPO(_NativeTrainer):
     the new weights; nothing is rebuilt."""
     _destroy = "lg_ppo_destroy"
     _prefix = "lg_ppo_"          # the entry points of include/lgtrain.h
-    _declare = staticmethod(abi.declare_train)
+    _unit = "train"
 
     def __init__(self, policy, state_dict, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, schedule="fixed", desired_kl=0.01, max_grad_norm=1.0, use_clipped_value_loss=True, max_rows=None,

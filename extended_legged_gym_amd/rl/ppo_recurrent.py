@@ -21,7 +21,7 @@ class NativeRecurrentPPO(NativePPO):
     the fp32 masters.  After `update`, the same `policy` object acts with the new weights; nothing is rebuilt."""
     _destroy = "lg_ppo_recurrent_destroy"
     _prefix = "lg_ppo_recurrent_"
-    _declare = staticmethod(abi.declare_train_recurrent)
+    _unit = "train_recurrent"
 
     def __init__(self, policy, state_dict, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, schedule="fixed", desired_kl=0.01, max_grad_norm=1.0, use_clipped_value_loss=True, max_rows=None,

@@ -20,7 +20,7 @@ class NativeSymmetricPPO(NativePPO):
     `"module:function"`), `_env` (passed to the function while it is probed)."""
     _destroy = "lg_ppo_sym_destroy"
     _prefix = "lg_ppo_sym_"
-    _declare = staticmethod(abi.declare_train_symmetry)
+    _unit = "train_symmetry"
 
     def __init__(self, policy, state_dict, symmetry_cfg=None, **kw):
         if not symmetry_cfg:

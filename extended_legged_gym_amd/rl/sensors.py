@@ -7,17 +7,12 @@ import ctypes as C
 import torch
 
 from extended_legged_gym_amd import abi
-from .policy import _NativeHandle, _lib, _ptr
+from extended_legged_gym_amd.native import load_library
+from .policy import _NativeHandle, _ptr
 
 
 def _sensor_lib():
-    lib = _lib()
-    if not getattr(lib, "_sensors_declared", False):
-        from .normalizer import _runner_lib
-        _runner_lib()
-        abi.declare_sensors(lib)
-        lib._sensors_declared = True
-    return lib
+    return load_library("policy", "policy_wide", "runner", "runner_privileged", "runner_distill", "sensors")
 
 
 def refusal(env, camera=None):

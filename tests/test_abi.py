@@ -1,14 +1,14 @@
-"""The C-ABI library loads without a GPU, exports every symbol include/lgstep.h declares, and agrees with the ctypes
-mirror (extended_legged_gym_amd/abi.py) on enum values and struct sizes.  No compute calls here."""
+"""The C-ABI library loads without a GPU and agrees with the ctypes mirror (extended_legged_gym_amd/abi.py) on the enum values of
+include/lgstep.h and on the struct sizes it reports itself; names, exports and struct layouts of every header: tests/test_abi_units.py.
+No compute calls here."""
 import ctypes
 import os
 import re
 
 from extended_legged_gym_amd import abi
+from tests.abi_checks import ROOT, header_names, library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "lgstep.h")).read()
-LIB = os.path.join(ROOT, "extended_legged_gym_amd", "csrc", "liblgstep.so")
 
 
 def parse_enum(name):
@@ -57,12 +57,10 @@ def test_enums_match_the_header():
 
 
 def test_library_exports_every_declared_symbol_and_struct_sizes_agree():
-    declared = sorted(set(re.findall(r"\b(lg_[a-z_]+)\s*\(", HEADER)))
-    assert sorted(abi.PRODUCT_SYMBOLS) == declared
-    lib = ctypes.CDLL(LIB)
-    for sym in declared:
+    assert sorted(abi.PRODUCT_SYMBOLS) == header_names("lgstep.h")
+    lib = library("product")
+    for sym in abi.PRODUCT_SYMBOLS:
         assert hasattr(lib, sym), sym
-    abi.declare_product(lib)
     sizes = (ctypes.c_int32 * 4)()
     lib.lg_abi_sizes(sizes)
     assert list(sizes) == [abi.LG_ABI_VERSION, ctypes.sizeof(abi.lg_config), ctypes.sizeof(abi.lg_robot_model),
@@ -71,12 +69,10 @@ def test_library_exports_every_declared_symbol_and_struct_sizes_agree():
 
 def test_policy_header_symbols_are_exported():
     hdr = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
-    declared = sorted(set(re.findall(r"\b(lg_[a-z_]+)\s*\(", hdr)))
-    assert sorted(abi.POLICY_SYMBOLS) == declared
-    lib = ctypes.CDLL(LIB)
-    for sym in declared:
+    assert sorted(abi.POLICY_SYMBOLS) == header_names("lgpolicy.h") and "lg_conv_tile_weights_bf16" in abi.POLICY_SYMBOLS
+    lib = library("policy")
+    for sym in abi.POLICY_SYMBOLS:
         assert hasattr(lib, sym), sym
-    abi.declare_policy(lib)
     body = re.search(r"enum\s+lg_activation\s*\{(.*?)\};", hdr, re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     vals = {k.strip(): int(v) for k, v in (item.split("=") for item in body.split(",") if "=" in item)}
@@ -92,21 +88,3 @@ def test_product_has_no_path_through_the_oracle():
                 txt = open(os.path.join(dirpath, f)).read()
                 for needle in ("import oracle", "from oracle", "liblg_oracle", "lgo_", "oracle_lib", "lg_oracle"):
                     assert needle not in txt, f"{f} reaches into the oracle ({needle})"
-
-
-def test_layer_parameter_structs_mirror_the_header(tmp_path):
-    """The ctypes mirrors of the device layers' parameter blocks (`lg_pose_params`, `lg_foottrack_params`, `lg_foottrack_state`: passed by value into kernels)
-    against `sizeof` / `offsetof` as the C compiler lays the header's structs out."""
-    import ctypes as C
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lgstep.h"\nint main(void) {\n'
-                   '  printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(lg_pose_params), sizeof(lg_foottrack_params), sizeof(lg_foottrack_state),\n'
-                   '         offsetof(lg_foottrack_params, scales), offsetof(lg_foottrack_params, feet_indices), offsetof(lg_foottrack_state, fw_timer));\n  return 0;\n}\n')
-    exe = tmp_path / "sizes"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = [C.sizeof(abi.lg_pose_params), C.sizeof(abi.lg_foottrack_params), C.sizeof(abi.lg_foottrack_state),
-            abi.lg_foottrack_params.scales.offset, abi.lg_foottrack_params.feet_indices.offset, abi.lg_foottrack_state.fw_timer.offset]
-    assert got == want

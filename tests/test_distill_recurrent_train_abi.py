@@ -1,76 +1,38 @@
-"""CPU side of the recurrent student's native distillation update (include/lgdistill_recurrent.h): the header names, the library's exports and the
-ctypes mirror agree and are disjoint from the other headers' lists; the struct layouts match a C compiler's; one refused call per entry point leaves
-a message that starts with that entry point's name; the Python layer's refusals (loss type with the reference's text, multi_gpu_cfg, a policy that is
-not a `NativeStudentTeacherRecurrent`) need no GPU, and `NativeDistillation` keeps refusing a recurrent policy; the new kernels' code-object metadata
-(cross-compiled for gfx950) shows no spills, no scratch, and LDS within the 80 KB tests/test_train_abi.py allows a workgroup that shares its compute
-unit (none of the new kernels is a 512-lane tile kernel).  No GPU needed."""
+"""CPU side of the recurrent student's native distillation update (include/lgdistill_recurrent.h); names, exports, declarations and struct
+layouts: tests/test_abi_units.py.  Here: the prefix, which the other trainers' headers leave alone, and the stats fields; one refused call per
+entry point leaves a message that starts with that entry point's name; the Python layer's refusals (loss type with the reference's text,
+multi_gpu_cfg, a policy that is not a `NativeStudentTeacherRecurrent`) need no GPU, and `NativeDistillation` keeps refusing a recurrent policy;
+the kernels' code-object metadata (cross-compiled for gfx950) shows no spills, no scratch, and LDS within the 80 KB tests/test_train_abi.py
+allows a workgroup that shares its compute unit (none of them is a 512-lane tile kernel).  No GPU needed."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from extended_legged_gym_amd import abi
-from tests.test_policy_recurrent_abi import HIPCC, LLVM
+from tests.abi_checks import HIPCC, check_no_spill_no_scratch, check_refusals, header_source, kernel_metadata, library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
-LIB = os.path.join(CSRC, "liblgstep.so")
-HEADER = os.path.join(ROOT, "include", "lgdistill_recurrent.h")
 LDS_SHARED = 80 * 1024
 KERNELS = ("rdistill_norm_kernel", "rdistill_adam_kernel")
 
 
-def _msg(lib):
-    return (lib.lg_mlp_last_error(None) or b"").decode()
-
-
 def test_header_exports_and_declarations_agree():
-    names = sorted(set(re.findall(r"\b(lg_[a-z_]+)\(", open(HEADER).read())))
-    assert names == sorted(abi.DISTILL_RTRAIN_SYMBOLS), (names, abi.DISTILL_RTRAIN_SYMBOLS)
-    for other in (abi.TRAIN_SYMBOLS, abi.POLICY_SYMBOLS, abi.DISTILL_TRAIN_SYMBOLS, abi.TRAIN_RECURRENT_SYMBOLS, abi.ESTIMATOR_SYMBOLS, abi.ESTIMATOR_BF16_SYMBOLS,
-                  abi.ESTIMATOR_TRAIN_SYMBOLS, abi.PRODUCT_SYMBOLS):
-        assert not set(names) & set(other)
-    assert all(n.startswith("lg_distill_rtrain_") for n in names)
-    plain = abi.declare_estimator_train(abi.declare_distill_train(abi.declare_train(abi.declare_policy(C.CDLL(LIB)))))
-    for sym in names:
-        assert hasattr(plain, sym), sym
-        assert getattr(plain, sym).argtypes is None, f"another declare function declares {sym}"
-    lib = abi.declare_distill_rtrain(C.CDLL(LIB))
-    for sym in names:
-        assert getattr(lib, sym).argtypes is not None, sym
+    assert all(n.startswith("lg_distill_rtrain_") for n in abi.symbols("distill_rtrain"))
     for other in ("lgpolicy.h", "lgtrain.h", "lgdistill.h", "lgtrain_recurrent.h", "lgestimator_train.h"):
-        assert not re.search(r"lg_distill_rtrain_[a-z_]+\(", open(os.path.join(ROOT, "include", other)).read()), other
-    assert "lgdistill_recurrent.h" in open(os.path.join(ROOT, "include", "lgdistill.h")).read()
+        assert not re.search(r"lg_distill_rtrain_[a-z_]+\(", header_source(other)), other
+    assert "lgdistill_recurrent.h" in header_source("lgdistill.h")
     from extended_legged_gym_amd import rl
     assert hasattr(rl, "NativeRecurrentDistillation")
 
 
-def test_struct_layouts_match_the_c_compiler(tmp_path):
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang") or os.path.join(LLVM, "clang")
-    structs = {"lg_distill_rtrain_params": abi.lg_distill_rtrain_params, "lg_distill_rtrain_stats": abi.lg_distill_rtrain_stats,
-               "lg_distill_train_hyper": abi.lg_distill_train_hyper}
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "lgdistill_recurrent.h"', "int main(void) {"]
-    for name, cls in structs.items():
-        lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
-        for field, _ in cls._fields_:
-            lines.append(f'  printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
-    lines += ["  return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True, capture_output=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-    for name, cls in structs.items():
-        assert int(got[name]) == C.sizeof(cls), name
-        for field, _ in cls._fields_:
-            assert int(got[f"{name}.{field}"]) == getattr(cls, field).offset, (name, field)
+def test_struct_layouts_match_the_c_compiler():
+    """(The layouts: tests/test_abi_units.py.)  The stats the Python layer reads by position."""
     assert [f for f, _ in abi.lg_distill_rtrain_stats._fields_] == ["behavior", "optimizer_steps", "grad_norm", "memory_grad_norm"]
 
 
 def test_one_refusal_per_entry_point_names_it():
-    lib = abi.declare_distill_rtrain(abi.declare_policy(C.CDLL(LIB)))
+    lib = library("policy", "distill_rtrain")
     p = 0x1000          # never read: the NULL handle is refused first
     hyper = abi.lg_distill_train_hyper(0, 1.0)
     calls = {
@@ -91,11 +53,8 @@ def test_one_refusal_per_entry_point_names_it():
         "lg_distill_rtrain_set_state": lambda: lib.lg_distill_rtrain_set_state(None, p, p, p, 0, 1e-3, None),
         "lg_distill_rtrain_set_learning_rate": lambda: lib.lg_distill_rtrain_set_learning_rate(None, 1e-3, None),
     }
-    assert set(calls) | {"lg_distill_rtrain_destroy"} == set(abi.DISTILL_RTRAIN_SYMBOLS)          # destroy cannot fail (NULL is a no-op)
-    for name, call in calls.items():
-        rc = call()
-        assert (rc is None or rc == 0) if name == "lg_distill_rtrain_create" else rc == abi.LG_ERR_INVALID, (name, rc)
-        assert _msg(lib).startswith(name + ": "), (name, _msg(lib))
+    # destroy cannot fail (NULL is a no-op)
+    check_refusals("distill_rtrain", lib, calls, quiet={"lg_distill_rtrain_destroy"}, returns_handle={"lg_distill_rtrain_create"})
     lib.lg_distill_rtrain_destroy(None)
 
 
@@ -115,31 +74,7 @@ def test_python_refusals_that_need_no_gpu():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_recurrent_distillation_kernels_do_not_spill_and_fit_the_lds(tmp_path):
-    """The route of tests/test_train_abi.py on csrc/lg_distill_train_recurrent.hip."""
-    obj, fat, co = (str(tmp_path / n) for n in ("lg_distill_train_recurrent.o", "fat.bin", "k.co"))
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize", "-c", "-o", obj,
-                    os.path.join(CSRC, "lg_distill_train_recurrent.hip")], check=True, capture_output=True)
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
-    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
-                    "--unbundle"], check=True, capture_output=True)
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    blocks, cur = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
-            cur = {}
-        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
-        if m and cur is not None:
-            if m.group(1) == "name":
-                blocks[m.group(2)] = cur
-            elif m.group(2).isdigit():
-                cur[m.group(1)] = int(m.group(2))
+def test_recurrent_distillation_kernels_do_not_spill_and_fit_the_lds():
+    blocks = kernel_metadata("lg_distill_train_recurrent.hip")
     assert len(blocks) == len(KERNELS), sorted(blocks)          # every kernel of the translation unit is held to the bounds
-    for part in KERNELS:
-        hit = [v for k, v in blocks.items() if part in k]
-        assert len(hit) == 1, (part, sorted(blocks))
-        r = hit[0]
-        print(part, r)
-        assert r.get("vgpr_spill_count", 0) == 0 and r.get("sgpr_spill_count", 0) == 0 and r["private_segment_fixed_size"] == 0, (part, r)
-        assert r["group_segment_fixed_size"] <= LDS_SHARED, (part, r)
+    check_no_spill_no_scratch(blocks, KERNELS, LDS_SHARED)

@@ -4,7 +4,6 @@ formula; the rounding helper against torch's cast; and the power of the interval
 fault of tests/test_encoder_reference_power.py, applied to the bf16-operand float64 reference, must leave the acceptance interval of its own
 stage in at least one entry.  No kernel runs here and no GPU is needed."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -12,16 +11,16 @@ import pytest
 import torch
 
 from extended_legged_gym_amd import abi
+from tests.abi_checks import header_source, last_error, library
 from tests.bf16_encoder_rule import R, bf16_operand_pair, outside, rne_bf16_bits, stage_reference
+from tests.test_estimator_abi import NEW as FP32_ESTIMATOR
 from tests.test_encoder_reference_power import CASES, SHAPES, camera_input, faults, model_pair, run_stage, wide_input
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "extended_legged_gym_amd", "csrc", "liblgstep.so")
 NEW = ["lg_conv_encoder_create_precision", "lg_conv_encoder_precision", "lg_conv_tile_weights_bf16"]
 
 
 def _lib():
-    return abi.declare_policy(C.CDLL(LIB))
+    return library("policy")
 
 
 # ------------------------------------------------------------------------------------------------------------ 4. rounding
@@ -46,18 +45,17 @@ def test_numpy_rounding_agrees_with_torchs_cast():
 
 # ------------------------------------------------------------------------------------------------------------ 1. ABI
 def test_bf16_symbols_are_in_the_header_exported_and_declared():
-    header = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
-    lib = C.CDLL(LIB)
+    header = header_source("lgpolicy.h")
+    lib = _lib()
     for sym in NEW:
         assert re.search(r"\b%s\(" % sym, header), sym
-        assert sym in abi.ESTIMATOR_BF16_SYMBOLS and sym not in abi.ESTIMATOR_SYMBOLS and hasattr(lib, sym), sym
+        assert sym in abi.POLICY_SYMBOLS and sym not in FP32_ESTIMATOR and hasattr(lib, sym), sym
     assert re.search(r"#define LG_PREC_F32 0\b", header) and re.search(r"#define LG_PREC_BF16 1\b", header)
     assert (abi.LG_PREC_F32, abi.LG_PREC_BF16) == (0, 1)
-    abi.declare_policy(lib)
     for sym in NEW:
         assert getattr(lib, sym).argtypes, sym
     assert lib.lg_conv_encoder_precision(None) == abi.LG_ERR_INVALID
-    assert "lg_conv_encoder_precision" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert "lg_conv_encoder_precision" in last_error(lib)
 
 
 def test_an_unknown_precision_is_refused_without_a_device():
@@ -73,10 +71,10 @@ def test_an_unknown_precision_is_refused_without_a_device():
     lists = (fp * 6)(*[np.zeros(4, np.float32).ctypes.data_as(fp) for _ in range(6)])
     for bad in (2, -1, 7):
         assert not lib.lg_conv_encoder_create_precision(28, 56, 64, 0, lists, lists, 0, bad)
-        assert "precision" in (lib.lg_mlp_last_error(None) or b"").decode()
+        assert "precision" in last_error(lib)
     for prec in (abi.LG_PREC_F32, abi.LG_PREC_BF16):          # a known precision: the refusals of lg_conv_encoder_create
         assert not lib.lg_conv_encoder_create_precision(129, 56, 64, 0, lists, lists, 0, prec)
-        assert "image size" in (lib.lg_mlp_last_error(None) or b"").decode()
+        assert "image size" in last_error(lib)
 
 
 # ------------------------------------------------------------------------------------------------------------ 2. the weight tiles

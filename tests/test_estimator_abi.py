@@ -5,33 +5,28 @@ gfx950): no spills, no scratch, LDS within one workgroup's share of a compute un
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from extended_legged_gym_amd import abi
-from tests.test_policy_recurrent_abi import HIPCC, LLVM
+from tests.abi_checks import HIPCC, check_no_spill_no_scratch, header_source, kernel, kernel_metadata, last_error, library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
-LIB = os.path.join(CSRC, "liblgstep.so")
 NEW = ["lg_conv_encoder_create", "lg_conv_encoder_destroy", "lg_conv_tile_weights", "lg_conv_encoder_forward", "lg_mlp_set_output_activation",
        "lg_estimator_step", "lg_conv_encoder_stage_shape", "lg_conv_encoder_forward_stages"]
 
 
 def _lib():
-    return abi.declare_policy(C.CDLL(LIB))
+    return library("policy")
 
 
 def test_new_symbols_are_in_the_header_exported_and_declared():
-    header = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
-    lib = C.CDLL(LIB)
+    header = header_source("lgpolicy.h")
+    lib = _lib()
     for sym in NEW:
         assert re.search(r"\b%s\(" % sym, header), sym
-        assert sym in abi.ESTIMATOR_SYMBOLS and hasattr(lib, sym), sym
+        assert sym in abi.POLICY_SYMBOLS and hasattr(lib, sym), sym
     assert "terrain_estimator.py:80-109" in header and "terrain_estimator.py:162-198" in header
-    abi.declare_policy(lib)
     for sym in NEW:
         assert getattr(lib, sym).argtypes, sym
     from extended_legged_gym_amd import rl
@@ -84,59 +79,38 @@ def test_refusals_that_need_no_device():
     for args, word in (((129, 56, 64, 0), "image size"), ((28, 7, 64, 0), "image size"), ((28, 56, 513, 0), "out_dim"), ((28, 56, 0, 0), "out_dim"),
                        ((28, 56, 64, 3), "activation")):
         assert not lib.lg_conv_encoder_create(*args, lists, lists, 0), args
-        msg = (lib.lg_mlp_last_error(None) or b"").decode()
+        msg = last_error(lib)
         assert "lg_conv_encoder_create" in msg and word in msg, (args, msg)
     assert not lib.lg_conv_encoder_create(28, 56, 64, 0, None, lists, 0)
-    assert "null" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert "null" in last_error(lib)
     p = 0x1000
     assert lib.lg_conv_encoder_forward(None, p, 1568, 4, p, None) == abi.LG_ERR_INVALID
-    assert "lg_conv_encoder_forward" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert "lg_conv_encoder_forward" in last_error(lib)
     for stages in (1, 7, 0, 8):
         assert lib.lg_conv_encoder_forward_stages(None, p, 1568, 4, stages, p, None) == abi.LG_ERR_INVALID
-        assert "lg_conv_encoder_forward_stages" in (lib.lg_mlp_last_error(None) or b"").decode()
+        assert "lg_conv_encoder_forward_stages" in last_error(lib)
     assert lib.lg_conv_encoder_stage_shape(None, 1, None, None, None) == abi.LG_ERR_INVALID
-    assert "lg_conv_encoder_stage_shape" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert "lg_conv_encoder_stage_shape" in last_error(lib)
     assert lib.lg_estimator_step(None, None, None, None, p, 1568, p, 4, p, None, None, p, None) == abi.LG_ERR_INVALID
-    assert "lg_estimator_step" in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert "lg_estimator_step" in last_error(lib)
     assert lib.lg_mlp_set_output_activation(None, 1) == abi.LG_ERR_INVALID
     # abi.MLP_MAX_WIDTH, which parse_estimator_state holds the combination layer to, is the library's own limit: one more is refused for its width
     w, b = np.zeros((4, abi.MLP_MAX_WIDTH + 1), np.float32), np.zeros(4, np.float32)
     one = lambda a: (fp * 1)(a.ctypes.data_as(fp))          # noqa: E731
     assert not lib.lg_mlp_create(1, (C.c_int32 * 2)(abi.MLP_MAX_WIDTH + 1, 4), one(w), one(b), 0, 0)
-    assert "layer width out of range (1..%d)" % abi.MLP_MAX_WIDTH in (lib.lg_mlp_last_error(None) or b"").decode()
+    assert "layer width out of range (1..%d)" % abi.MLP_MAX_WIDTH in last_error(lib)
     mlp = lib.lg_mlp_create(1, (C.c_int32 * 2)(abi.MLP_MAX_WIDTH, 4), one(w[:, :-1].copy()), one(b), 0, 0)
-    assert mlp or "layer width" not in (lib.lg_mlp_last_error(None) or b"").decode()          # without a device it fails later, for that reason
+    assert mlp or "layer width" not in last_error(lib)          # without a device it fails later, for that reason
     if mlp:
         lib.lg_mlp_destroy(mlp)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_estimator_kernels_do_not_spill_and_fit_the_lds(tmp_path):
-    """The route of tests/test_kernel_resources.py on csrc/lg_estimator.hip.  LDS bar: 160 KB per compute unit; the conv kernel is meant to run
-    several workgroups per compute unit (two waves per SIMD at least), so one workgroup may take at most half of it."""
-    obj, fat, co = (str(tmp_path / n) for n in ("lg_estimator.o", "fat.bin", "k.co"))
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize", "-c", "-o", obj,
-                    os.path.join(CSRC, "lg_estimator.hip")], check=True, capture_output=True)
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
-    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
-                    "--unbundle"], check=True, capture_output=True)
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    blocks, cur = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
-            cur = {}
-        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
-        if m and cur is not None:
-            if m.group(1) == "name":
-                blocks[m.group(2)] = cur
-            elif m.group(2).isdigit():
-                cur[m.group(1)] = int(m.group(2))
-    for part in ("conv_gemm_kernel", "pool_flatten_kernel", "cat_columns_kernel"):
-        hit = [v for k, v in blocks.items() if part in k]
-        assert len(hit) == 1, (part, sorted(blocks))
-        r = hit[0]
-        print(part, r)
-        assert r.get("vgpr_spill_count", 0) == 0 and r.get("sgpr_spill_count", 0) == 0 and r["private_segment_fixed_size"] == 0, (part, r)
-        assert r["group_segment_fixed_size"] <= 80 * 1024, (part, r)
-        assert r["vgpr_count"] <= 128, (part, r)          # 256 lanes x 128 registers: two workgroups' waves per SIMD
+def test_estimator_kernels_do_not_spill_and_fit_the_lds():
+    """csrc/lg_estimator.hip.  LDS bar: 160 KB per compute unit; the conv kernel is meant to run several workgroups per compute unit (two waves per
+    SIMD at least), so one workgroup may take at most half of it."""
+    blocks = kernel_metadata("lg_estimator.hip")
+    kernels = ("conv_gemm_kernel", "pool_flatten_kernel", "cat_columns_kernel")
+    check_no_spill_no_scratch(blocks, kernels, 80 * 1024)
+    for part in kernels:
+        assert kernel(blocks, part)["vgpr_count"] <= 128, part          # 256 lanes x 128 registers: two workgroups' waves per SIMD

@@ -4,17 +4,11 @@ nearly all of it in the single-wave fallback paths inlined next to the hot code;
 (`physics_kernel<0, TMESH, HELPERS>`), and this test keeps it that way."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-
-
-CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
-LLVM = "/opt/rocm/lib/llvm/bin"
+from tests.abi_checks import CSRC, HIPCC, LLVM, ROOT, object_metadata
 
 
 def _from_built_object(obj):
@@ -25,27 +19,10 @@ def _from_built_object(obj):
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h") or f == "lg_step.hip"] + [os.path.join(ROOT, "include", "lgstep.h")]      # (what lg_step.hip includes)
     if os.path.getmtime(obj) < max(os.path.getmtime(f) for f in srcs):
         return None
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
-        if subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat]).returncode != 0:
-            return None
-        if subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
-                           "--unbundle"], capture_output=True).returncode != 0:
-            return None
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout
-    blocks, cur = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
-            cur = {}
-        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
-        if m and cur is not None:
-            k, v = m.group(1), m.group(2)
-            if k == "name":
-                blocks[v] = cur
-            elif v.isdigit():
-                cur[k] = int(v)
+    try:
+        blocks = object_metadata(obj)
+    except (subprocess.CalledProcessError, OSError):
+        return None
     out = {}
     for name, r in blocks.items():
         if "vgpr_count" in r:

@@ -71,31 +71,12 @@ PRE_EXISTING = os.path.join(ROOT, "tests", "golden", "physics_kernel_resources_m
 
 def _sgpr_counts(legs):
     """.sgpr_count of every kernel in the code object of csrc/lg_step<legs>.o when that object is current (test_kernel_resources._from_built_object's rule)."""
-    import re
-    import subprocess
-    import tempfile
-    from tests.test_kernel_resources import CSRC, LLVM, _from_built_object
+    from tests.abi_checks import CSRC, object_metadata
+    from tests.test_kernel_resources import _from_built_object
     obj = os.path.join(CSRC, f"lg_step{legs}.o")
     if _from_built_object(obj) is None:
         return {}
-    with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
-        subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
-                        "--unbundle"], capture_output=True, check=True)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout
-    blocks, cur = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
-            cur = {}
-        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
-        if m and cur is not None:
-            if m.group(1) == "name":
-                blocks[m.group(2)] = cur
-            elif m.group(1) == "sgpr_count":
-                cur["sgpr_count"] = int(m.group(2))
-    return {k: r["sgpr_count"] for k, r in blocks.items() if "sgpr_count" in r}
+    return {k: r["sgpr_count"] for k, r in object_metadata(obj).items() if "sgpr_count" in r}
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")

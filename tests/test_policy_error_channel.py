@@ -1,20 +1,18 @@
 """The one error channel of include/lgpolicy.h: every entry point that returns a status or a handle leaves, when it refuses a call, a message in
 `lg_mlp_last_error` that begins with the name of the entry point the caller called -- the same message whether the query gets a handle or NULL.
 
-CPU half (ctypes, no device): one refused call per entry point, enumerated from `abi.declare_policy`'s own declarations so that a new entry point
-cannot be left out.  GPU half: the refusals that need live handles (widths that do not chain, an LSTM without its cell state, more than 32 actions),
+CPU half (ctypes, no device): one refused call per entry point, enumerated from what `abi.declare_policy` declares (`abi.prototypes`) so that a new
+entry point cannot be left out.  GPU half: the refusals that need live handles (widths that do not chain, an LSTM without its cell state, more than 32 actions),
 through the acts and through the collectors, each followed by a valid call on the same handles."""
 import ctypes as C
-import os
 import types
 
 import numpy as np
 import pytest
 
 from extended_legged_gym_amd import abi
+from tests.abi_checks import library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "extended_legged_gym_amd", "csrc", "liblgstep.so")
 P = 0x1000                # a non-NULL pointer that is never dereferenced: every call below is refused before anything is read
 
 # The exclusions, by name: functions that return nothing, the pure size queries of the host re-tilings (a negative count is their whole error
@@ -58,16 +56,8 @@ REFUSED = {
 
 
 def _declared():
-    """name -> restype of everything `abi.declare_policy` declares, read off a recorder in place of the library."""
-    class Recorder:
-        def __init__(self):
-            self.fns = {}
-
-        def __getattr__(self, name):
-            return self.fns.setdefault(name, types.SimpleNamespace(argtypes=None, restype=C.c_int))
-    rec = Recorder()
-    abi.declare_policy(rec)
-    return {k: v.restype for k, v in rec.fns.items()}
+    """name -> restype of everything `abi.declare_policy` declares."""
+    return {k: v.restype for k, v in abi.prototypes("policy").items()}
 
 
 def _message(lib, handle=None):
@@ -87,7 +77,7 @@ def test_the_enumeration_leaves_out_nothing():
 
 @pytest.mark.parametrize("name", sorted(REFUSED))
 def test_a_refused_call_names_its_entry_point(name):
-    lib = abi.declare_policy(C.CDLL(LIB))
+    lib = library("policy")
     REFUSED["lg_obs_history_step" if name != "lg_obs_history_step" else "lg_mlp_forward"](lib)          # some other entry point's message is in the channel
     rc = REFUSED[name](lib)
     if _declared()[name] is C.c_void_p:

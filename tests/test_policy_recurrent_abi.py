@@ -4,35 +4,29 @@ size a gfx950 workgroup can have, and the host re-tiling of the `[x ; h]` weight
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from extended_legged_gym_amd import abi
+from tests.abi_checks import HIPCC, header_source, kernel_metadata, last_error, library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
-LIB = os.path.join(CSRC, "liblgstep.so")
-HIPCC = "/opt/rocm/bin/hipcc"
-LLVM = "/opt/rocm/lib/llvm/bin"
 NEW = ["lg_rnn_create", "lg_rnn_destroy", "lg_rnn_tile_weights", "lg_rnn_step", "lg_rnn_reset_rows", "lg_policy_act_recurrent",
        "lg_collect_rollout_recurrent"]
 
 
 def _lib():
-    return abi.declare_policy(C.CDLL(LIB))
+    return library("policy")
 
 
 def test_new_symbols_are_exported_and_declared():
-    lib = C.CDLL(LIB)
+    lib = _lib()
     for sym in NEW:
         assert sym in abi.POLICY_SYMBOLS and hasattr(lib, sym), sym
-    abi.declare_policy(lib)
     for sym in NEW:
         assert getattr(lib, sym).argtypes, sym
     assert C.sizeof(abi.lg_rollout_hidden) == 4 * C.sizeof(C.c_void_p)
-    hdr = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
+    hdr = header_source("lgpolicy.h")
     body = re.search(r"enum\s+lg_rnn_type\s*\{(.*?)\};", hdr, re.S).group(1)
     vals = {k.strip(): int(v) for k, v in (item.split("=") for item in body.split(",") if "=" in item)}
     assert {k[len("LG_RNN_"):].lower(): v for k, v in vals.items()} == abi.RNN_TYPES
@@ -46,36 +40,12 @@ def test_create_refuses_out_of_range_shapes_with_a_message():
     for args, word in (((0, 1, 48, 513), "hidden"), ((0, 0, 48, 64), "layers"), ((0, 5, 48, 64), "layers"), ((7, 1, 48, 64), "type"),
                        ((1, 1, 513, 64), "input"), ((1, 1, 0, 64), "input")):
         assert not lib.lg_rnn_create(*args, *lists, 0), args
-        msg = (lib.lg_mlp_last_error(None) or b"").decode()
-        assert word in msg, (args, msg)
-
-
-def _kernel_metadata(tmp_path):
-    """Metadata notes of the gfx950 code object of csrc/lg_policy.hip, compiled with the Makefile's flags (the route of tests/test_kernel_resources.py)."""
-    obj, fat, co = (str(tmp_path / n) for n in ("lg_policy.o", "fat.bin", "k.co"))
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize", "-c", "-o", obj,
-                    os.path.join(CSRC, "lg_policy.hip")], check=True, capture_output=True)
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
-    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
-                    "--unbundle"], check=True, capture_output=True)
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    blocks, cur = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
-            cur = {}
-        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
-        if m and cur is not None:
-            if m.group(1) == "name":
-                blocks[m.group(2)] = cur
-            elif m.group(2).isdigit():
-                cur[m.group(1)] = int(m.group(2))
-    return blocks
+        assert word in last_error(lib), (args, last_error(lib))
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_memory_kernels_use_no_scratch_and_fit_the_lds(tmp_path):
-    blocks = _kernel_metadata(tmp_path)
+def test_memory_kernels_use_no_scratch_and_fit_the_lds():
+    blocks = kernel_metadata("lg_policy.hip")
     new = {k: v for k, v in blocks.items() if "rnn_" in k}
     assert any("rnn_layer_kernel" in k for k in new) and any("rnn_reset_rows_kernel" in k for k in new), sorted(blocks)
     for name, r in new.items():

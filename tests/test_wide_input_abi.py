@@ -4,28 +4,23 @@ act and training-forward kernels report no scratch, no spills and no more LDS th
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from extended_legged_gym_amd import abi
+from tests.abi_checks import HIPCC, header_source, kernel, kernel_metadata, last_error, library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "extended_legged_gym_amd", "csrc")
-LIB = os.path.join(CSRC, "liblgstep.so")
-HIPCC = "/opt/rocm/bin/hipcc"
-LLVM = "/opt/rocm/lib/llvm/bin"
+WIDE = ["lg_mlp_create_wide"]          # what include/lgpolicy_wide.h itself declares (the memory's two: tests/test_wide_recurrent_abi.py)
 
 
 def _lib():
-    return abi.declare_policy_wide(abi.declare_policy(C.CDLL(LIB)))
+    return library("policy", "policy_wide")
 
 
 def test_header_abi_and_library_agree():
-    hdr = open(os.path.join(ROOT, "include", "lgpolicy_wide.h")).read()
-    narrow_hdr = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
-    assert sorted(set(re.findall(r"\b(lg_[a-z_]+)\s*\(", hdr)) - set(abi.POLICY_SYMBOLS)) == sorted(abi.POLICY_WIDE_SYMBOLS) == ["lg_mlp_create_wide"]
+    hdr, narrow_hdr = header_source("lgpolicy_wide.h"), header_source("lgpolicy.h")
+    assert sorted(set(re.findall(r"\b(lg_[a-z0-9_]+)\s*\(", hdr)) - set(abi.POLICY_SYMBOLS)) == WIDE and set(WIDE) < set(abi.symbols("policy_wide"))
     assert int(re.search(r"#define\s+LG_MLP_MAX_INPUT\s+(\d+)", hdr).group(1)) == abi.MLP_MAX_INPUT == 2048
     assert abi.MLP_MAX_WIDTH == 512 and abi.MLP_MAX_INPUT % abi.MLP_MAX_WIDTH == 0
     proto = re.search(r"lg_mlp\*\s+lg_mlp_create_wide\(([^)]*)\)", hdr).group(1)
@@ -42,7 +37,7 @@ def _create(lib, name, dims):
     w = np.zeros(max(1, max(dims)) ** 2, np.float32)
     ptrs = (fp * L)(*[w.ctypes.data_as(fp)] * L)
     handle = getattr(lib, name)(L, (C.c_int32 * (L + 1))(*dims), ptrs, ptrs, abi.ACTIVATIONS["elu"], 0)
-    return handle, (lib.lg_mlp_last_error(None) or b"").decode()
+    return handle, last_error(lib)
 
 
 @pytest.mark.parametrize("dims,words", [([2049, 16], ("input", "2049", "2048")), ([600, 513, 4], ("hidden", "513", "512")), ([600, 64, 513], ("output", "513", "512")),
@@ -61,41 +56,16 @@ def test_the_narrow_entry_point_keeps_its_limit_and_message():
         assert not handle and msg == "lg_mlp_create: layer width out of range (1..512)", (dims, msg)
 
 
-def _metadata(tmp_path, source):
-    """Metadata notes of the gfx950 code object of a csrc file, compiled with the Makefile's flags (the route of tests/test_policy_recurrent_abi.py)."""
-    obj, fat, co = (str(tmp_path / (source + n)) for n in (".o", ".fat", ".co"))
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize", "-c", "-o", obj,
-                    os.path.join(CSRC, source)], check=True, capture_output=True)
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
-    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}",
-                    "--unbundle"], check=True, capture_output=True)
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    blocks, cur = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith("- .agpr_count:") or line.startswith("- .args:"):
-            cur = {}
-        m = re.match(r"-?\s*\.(\w+):\s+(\S+)$", line)
-        if m and cur is not None:
-            if m.group(1) == "name":
-                blocks[m.group(2)] = cur
-            elif m.group(2).isdigit():
-                cur[m.group(1)] = int(m.group(2))
-    return blocks
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("source,kernels", [("lg_policy.hip", (("mlp_forward_kernel", "mlp_wide_forward_kernel"), ("policy_act_kernel", "policy_wide_act_kernel"),
                                                               ("distill_act_kernel", "distill_wide_act_kernel"))),
                                             ("lg_train.hip", (("ppo_forward_kernel", "ppo_wide_forward_kernel"),))])
-def test_wide_instances_use_no_scratch_no_spills_and_no_more_lds(tmp_path, source, kernels):
-    blocks = _metadata(tmp_path, source)
-    for kernel, wide_kernel in kernels:          # (the wide names do not contain the narrow ones: the existing metadata tests find a kernel by substring)
-        narrow = [v for k, v in blocks.items() if kernel in k]
-        wide = [v for k, v in blocks.items() if wide_kernel in k]
-        assert len(narrow) == 1 and len(wide) == 1, (kernel, sorted(blocks))
-        print(kernel, "narrow", narrow[0], "wide", wide[0])
-        for r in (narrow[0], wide[0]):
-            assert r["private_segment_fixed_size"] == 0 and r.get("vgpr_spill_count", 0) == 0 and r.get("sgpr_spill_count", 0) == 0, (kernel, r)
-        assert wide[0]["group_segment_fixed_size"] <= narrow[0]["group_segment_fixed_size"], (kernel, wide[0], narrow[0])
-        assert wide[0]["vgpr_count"] <= 256, (kernel, wide[0])          # two waves per SIMD
+def test_wide_instances_use_no_scratch_no_spills_and_no_more_lds(source, kernels):
+    blocks = kernel_metadata(source)
+    for name, wide_name in kernels:          # (the wide names do not contain the narrow ones: the existing metadata tests find a kernel by substring)
+        narrow, wide = kernel(blocks, name), kernel(blocks, wide_name)
+        print(name, "narrow", narrow, "wide", wide)
+        for r in (narrow, wide):
+            assert r["private_segment_fixed_size"] == 0 and r.get("vgpr_spill_count", 0) == 0 and r.get("sgpr_spill_count", 0) == 0, (name, r)
+        assert wide["group_segment_fixed_size"] <= narrow["group_segment_fixed_size"], (name, wide, narrow)
+        assert wide["vgpr_count"] <= 256, (name, wide)          # two waves per SIMD

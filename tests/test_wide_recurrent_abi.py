@@ -11,27 +11,30 @@ import numpy as np
 import pytest
 
 from extended_legged_gym_amd import abi
-from tests.test_wide_input_abi import HIPCC, LIB, ROOT, _metadata
+from tests.abi_checks import HIPCC, header_source, kernel_metadata, last_error, library
+
+WIDE_MEMORY = ["lg_rnn_create_wide", "lg_rnn_tile_weights_wide"]          # what include/lgpolicy_wide_memory.h declares
 
 
 def _lib():
-    return abi.declare_policy_wide(abi.declare_policy(C.CDLL(LIB)))
+    return library("policy", "policy_wide")
 
 
 def test_header_abi_and_library_agree():
-    hdr = open(os.path.join(ROOT, "include", "lgpolicy_wide_memory.h")).read()
-    wide_hdr = open(os.path.join(ROOT, "include", "lgpolicy_wide.h")).read()
-    narrow_hdr = open(os.path.join(ROOT, "include", "lgpolicy.h")).read()
+    hdr, wide_hdr, narrow_hdr = header_source("lgpolicy_wide_memory.h"), header_source("lgpolicy_wide.h"), header_source("lgpolicy.h")
     assert '#include "lgpolicy_wide_memory.h"' in wide_hdr                  # one include gives both wide create functions
-    declared = set(re.findall(r"\b(lg_[a-z_]+)\s*\(", hdr)) - set(abi.POLICY_SYMBOLS)
-    assert sorted(declared) == sorted(abi.POLICY_WIDE_MEMORY_SYMBOLS) == ["lg_rnn_create_wide", "lg_rnn_tile_weights_wide"]
+    declared = set(re.findall(r"\b(lg_[a-z0-9_]+)\s*\(", hdr)) - set(abi.POLICY_SYMBOLS)
+    assert sorted(declared) == WIDE_MEMORY and set(WIDE_MEMORY) < set(abi.symbols("policy_wide"))
+    # lgpolicy_wide.h keeps to one symbol of its own: the unit is that one and the memory's two
+    own = set(re.findall(r"\b(lg_[a-z0-9_]+)\s*\(", wide_hdr)) - set(abi.POLICY_SYMBOLS)
+    assert own == {"lg_mlp_create_wide"} and sorted(own | declared) == sorted(abi.symbols("policy_wide"))
     assert int(re.search(r"#define\s+LG_RNN_MAX_INPUT\s+(\d+)", hdr).group(1)) == abi.RNN_MAX_INPUT == 2048
     assert abi.RNN_MAX_WIDTH == 512 and abi.RNN_MAX_INPUT % abi.RNN_MAX_WIDTH == 0
     proto = re.search(r"lg_rnn\*\s+lg_rnn_create_wide\(([^)]*)\)", hdr).group(1)
     narrow = re.search(r"lg_rnn\*\s+lg_rnn_create\(([^)]*)\)", narrow_hdr).group(1)
     assert re.sub(r"\s+", " ", proto) == re.sub(r"\s+", " ", narrow)          # the arguments of lg_rnn_create
     lib = _lib()
-    for sym in abi.POLICY_WIDE_MEMORY_SYMBOLS:
+    for sym in WIDE_MEMORY:
         assert hasattr(lib, sym) and getattr(lib, sym).argtypes, sym
     assert lib.lg_rnn_create_wide.argtypes == lib.lg_rnn_create.argtypes and lib.lg_rnn_create_wide.restype is C.c_void_p
 
@@ -47,7 +50,7 @@ def _lists(null=False):
 def test_refusals_name_the_entry_point_and_the_width(args, words):
     lib = _lib()
     assert not lib.lg_rnn_create_wide(*args, *_lists(), 0), args
-    msg = (lib.lg_mlp_last_error(None) or b"").decode()
+    msg = last_error(lib)
     assert msg.startswith("lg_rnn_create_wide: "), msg
     for word in words:
         assert word in msg, (args, msg)
@@ -56,7 +59,7 @@ def test_refusals_name_the_entry_point_and_the_width(args, words):
 def test_null_lists_are_refused():
     lib = _lib()
     assert not lib.lg_rnn_create_wide(0, 1, 578, 64, *_lists(null=True), 0)
-    msg = (lib.lg_mlp_last_error(None) or b"").decode()
+    msg = last_error(lib)
     assert msg.startswith("lg_rnn_create_wide: ") and "null" in msg, msg
 
 
@@ -64,7 +67,7 @@ def test_the_diagnostic_switch_is_checked(monkeypatch):
     lib = _lib()
     monkeypatch.setenv("LG_RNN_FORCE_WIDE", "yes")
     assert not lib.lg_rnn_create_wide(0, 1, 578, 64, *_lists(), 0)
-    msg = (lib.lg_mlp_last_error(None) or b"").decode()
+    msg = last_error(lib)
     assert msg.startswith("lg_rnn_create_wide: ") and "LG_RNN_FORCE_WIDE" in msg and "yes" in msg, msg
 
 
@@ -72,7 +75,7 @@ def test_the_narrow_entry_point_keeps_its_limit_and_message():
     lib = _lib()
     for I in (513, 578, 2048):
         assert not lib.lg_rnn_create(1, 1, I, 64, *_lists(), 0)
-        msg = (lib.lg_mlp_last_error(None) or b"").decode()
+        msg = last_error(lib)
         assert msg == "lg_rnn_create: input width out of range (1..512)", (I, msg)
     assert lib.lg_rnn_tile_weights(0, 513, 64, None, None, None) < 0          # the one-image tiling stays at 512 too
 
@@ -108,15 +111,15 @@ def test_wide_weight_tiling_round_trips(rnn_type, I, H):
         rest[:, :H, :K] = 0
         assert not rest.any() and np.isfinite(tiled).all()
     assert lib.lg_rnn_tile_weights_wide(t, 2049, H, None, None, None, None, None) < 0
-    assert (lib.lg_mlp_last_error(None) or b"").decode().startswith("lg_rnn_tile_weights_wide: ")
+    assert last_error(lib).startswith("lg_rnn_tile_weights_wide: ")
     assert lib.lg_rnn_tile_weights_wide(t, I, 513, None, None, None, None, None) < 0 and lib.lg_rnn_tile_weights_wide(5, I, H, None, None, None, None, None) < 0
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("source,new,kept", [("lg_policy.hip", ("rnn_wide_xproj_kernel", "rnn_wide_layer_kernel"), "rnn_layer_kernel"),
                                              ("lg_train_recurrent.hip", ("rnn_wide_train_forward_kernel",), "rnn_train_forward_kernel")])
-def test_wide_memory_kernels_use_no_scratch_no_spills_and_fit_the_lds(tmp_path, source, new, kept):
-    blocks = _metadata(tmp_path, source)
+def test_wide_memory_kernels_use_no_scratch_no_spills_and_fit_the_lds(source, new, kept):
+    blocks = kernel_metadata(source)
     rnn = {k: v for k, v in blocks.items() if "rnn_" in k}
     for name in new + (kept,):
         assert len([k for k in rnn if name in k]) == 1, (name, sorted(blocks))          # (no new name contains an old one)

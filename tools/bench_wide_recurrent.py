@@ -37,18 +37,18 @@ ROWS, WIDE, NARROW, H, A, MLP = 4096, 578, 235, 512, 18, [512, 256, 128]
 def library(path):
     """The rl objects created inside bind to the library at `path` (each keeps the library it was created with)."""
     from extended_legged_gym_amd import abi, native
-    keep = (native._lib, native.LIB_PATH, abi.declare_policy_wide)
+    keep = (native._lib, native.LIB_PATH, abi.UNITS["policy_wide"])
 
     def tolerant(lib):          # the parent's library has no wide-memory entry points
         try:
-            return keep[2](lib)
+            return keep[2].declare(lib)
         except AttributeError:
             return lib
-    native._lib, native.LIB_PATH, abi.declare_policy_wide = None, path, tolerant
+    native._lib, native.LIB_PATH, abi.UNITS["policy_wide"] = None, path, keep[2]._replace(declare=tolerant)
     try:
         yield
     finally:
-        native._lib, native.LIB_PATH, abi.declare_policy_wide = keep
+        native._lib, native.LIB_PATH, abi.UNITS["policy_wide"] = keep
 
 
 def spread(xs):
