@@ -301,13 +301,15 @@ def state_parts(state):
 # ---- the cases of tests/test_hip_distill_recurrent_update.py
 def group_cases(slab_rows, rnn):
     """Per memory type: nothing a multiple of 16; exact tiles with a single step; G * N a few rows past one weight-gradient slab; a non-zero carry
-    with dones at the group's first, middle and last step (the group starts at time index 0, so it enters with the carry)."""
+    with dones at the group's first, middle and last step (the group starts at time index 0, so it enters with the carry); hidden 344, where the
+    backward tile takes two passes over the gate derivative's columns (K = 4 x 344 = 1376 for the LSTM, 3 x 344 = 1032 for the GRU)."""
     salt = 0 if rnn == "lstm" else 50
     return [
         Case(f"{rnn}_h40_n7_g3", rnn=rnn, salt=salt + 1),
         Case(f"{rnn}_h16_n16_g1", S=16, H=16, layers=1, mlp=(16,), A=16, N=16, G=1, rnn=rnn, loss="mse", salt=salt + 2),
         Case(f"{rnn}_h40_slab_g7", N=-(-(slab_rows + 3) // 7), G=7, rnn=rnn, salt=salt + 3),
         Case(f"{rnn}_h40_n7_g3_carry_dones", rnn=rnn, salt=salt + 4, dones_at={0: None, 1: None, 2: None}),
+        Case(f"{rnn}_h344_n7_g3", H=344, rnn=rnn, salt=salt + 5),
     ]
 
 

@@ -83,7 +83,7 @@ def _trained(sd):
 
 # ------------------------------------------------------------------------------------------------------------ 1. one group against float64
 @pytest.mark.parametrize("rnn", RNNS)
-@pytest.mark.parametrize("index", range(4), ids=["h40_n7_g3", "h16_n16_g1", "h40_slab_g7", "carry_dones"])
+@pytest.mark.parametrize("index", range(5), ids=["h40_n7_g3", "h16_n16_g1", "h40_slab_g7", "carry_dones", "h344_n7_g3"])
 def test_group_gradients_against_float64(index, rnn):
     """Every tensor's gradient before the clip, both norms and each step loss within the bar; the trainer's forward outputs bit-equal to
     `policy.act_inference` stepped over the same rows from the same state with `policy.reset(dones[t])` after each step.  The single-step case and

@@ -8,6 +8,16 @@ Shapes, the smallest at which each part can go wrong:
   R3  LSTM, 2 layers, hidden 64, T = 7, 75 envs: 525 rows = two full weight-gradient slabs and a ragged third
   R4  LSTM, 1 layer, hidden 512, obs 235, MLP [512, 256, 128], T = 3, 33 envs: the widest row, the LDS limit, two passes over D (4 x 512 columns)
   R5  T = 1 (101 envs); and R5b a mini-batch that is not the first slice (env0 = 37 of N = 2 x 37 + 5, GRU, 1 layer)
+The backward tile (`rows_times_tiled`) walks the K = G H columns of the gate derivative D in passes of 1024; later passes add into dh_prev / dx, and a
+GRU's z dh term and the zeroing of rows that entered from a saved state run in the last pass alone:
+  R6  GRU, 1 layer, hidden 344: K = 1032, a GRU's two-pass backward, second pass of 8 columns
+  R7  GRU, 2 layers, hidden 512: K = 1536, the whole n gate in pass two; dx of layer 1 across the edge
+  R8  LSTM, 1 layer, hidden 257: K = 1028, second pass of 4 columns, not a whole 16-block
+  R9  LSTM, 2 layers, hidden 260: K = 1040, second pass of one block, two layers
+  R10 GRU, 1 layer, hidden 342, T = 4, 37 envs: K = 1026, second pass of 2 columns
+  R11 LSTM, 1 layer, hidden 136, critic obs 33: 9 chunks, one ragged pass
+  R12 GRU, 3 layers, hidden 9, obs 5 / critic obs 1, MLP [16]: H < 16, depth 3, a critic row of one column
+tests/test_rnn_sweep_power.py shows on R6 - R10, without a GPU, that this bar sees a pass that is dropped, a pass that overwrites, and a lost z dh.
 dones: `ppo_recurrent_reference.dones_pattern`, the issue's pattern scaled to the shape."""
 import numpy as np
 import pytest
@@ -27,7 +37,16 @@ SHAPES = {          # rnn_type, layers, hidden, obs, critic obs, MLP, T, N, env0
     "R4": ("lstm", 1, 512, 235, 235, [512, 256, 128], 3, 33, 0, 33, "std"),
     "R5": ("lstm", 1, 40, 20, 24, [32, 16], 1, 101, 0, 101, "std"),
     "R5b": ("gru", 1, 40, 20, 24, [32, 16], 5, 79, 37, 37, "log_std"),
+    "R6": ("gru", 1, 344, 20, 24, [32, 16], 3, 33, 0, 33, "std"),
+    "R7": ("gru", 2, 512, 48, 48, [64, 32], 3, 33, 0, 33, "std"),
+    "R8": ("lstm", 1, 257, 20, 24, [32, 16], 3, 33, 0, 33, "std"),
+    "R9": ("lstm", 2, 260, 17, 16, [32, 16], 3, 33, 0, 33, "std"),
+    "R10": ("gru", 1, 342, 20, 24, [32, 16], 4, 37, 0, 37, "std"),
+    "R11": ("lstm", 1, 136, 16, 33, [32, 16], 4, 37, 0, 37, "std"),
+    "R12": ("gru", 3, 9, 5, 1, [16], 4, 37, 0, 37, "std"),
 }
+PASS_EDGE_SHAPES = ("R6", "R7", "R8", "R9", "R10")          # K > 1024: tests/test_rnn_sweep_power.py plants the backward's faults on these
+SWEEP_SHAPES = PASS_EDGE_SHAPES + ("R11", "R12")          # the memory sweep's cases: their figures go to rnn_sweep.json (tests/test_hip_rnn_sweep.py)
 _CACHE = {}
 
 
@@ -56,7 +75,9 @@ def _build(sd, rnn_type, std_type, **kw):
     return policy, NativeRecurrentPPO(policy, sd, **kw)
 
 
-GRAD_CASES = [("R1", True), ("R1", False), ("R2", True), ("R2", False), ("R3", True), ("R4", True), ("R4", False), ("R5", True), ("R5b", True), ("R5b", False)]
+GRAD_CASES = [("R1", True), ("R1", False), ("R2", True), ("R2", False), ("R3", True), ("R4", True), ("R4", False), ("R5", True), ("R5b", True), ("R5b", False),
+              ("R6", True), ("R7", True), ("R7", False), ("R8", True), ("R9", True), ("R10", True), ("R10", False), ("R11", True), ("R12", True)]
+FIGURES = {}          # shape -> the worst e / e32 and e / bar over its gradient tensors (tests/test_hip_rnn_sweep.py writes those of R6 - R12 out)
 
 
 @pytest.mark.parametrize("shape,clipped", GRAD_CASES)
@@ -75,7 +96,10 @@ def test_gradients_losses_and_norm_against_float64(shape, clipped):
     assert set(g) == set(g64)
     ok = True
     for k in g64:
-        ok &= _within(f"{shape} {k}", _err(g[k], g64[k]), _err(g32[k], g64[k]))
+        e, e32 = _err(g[k], g64[k]), _err(g32[k], g64[k])
+        ok &= _within(f"{shape} {k}", e, e32)
+        fig = FIGURES.setdefault(shape, dict(e_over_e32=0.0, e_over_bar=0.0))
+        fig.update(e_over_e32=max(fig["e_over_e32"], e / max(e32, 1e-300)), e_over_bar=max(fig["e_over_bar"], e / max(8.0 * e32, 2e-5)))
     ok &= _within(f"{shape} norm", abs(norm - float(n64)) / float(n64), abs(float(n32) - float(n64)) / float(n64))
     for k in ("surrogate", "value_function", "entropy", "kl"):
         ok &= _within(f"{shape} {k}", abs(means[k] - float(m64[k])) / abs(float(m64[k])), abs(float(m32[k]) - float(m64[k])) / abs(float(m64[k])))
