@@ -753,8 +753,33 @@ def declare_sensors(lib):
     return lib
 
 
+class lg_estimation_driver(C.Structure):
+    """include/lgrunner_estimator.h: who moves the robot during an estimation collection; the four last members exist to be refused by name."""
+    _fields_ = [("actions", C.c_void_p), ("actor", C.c_void_p), ("memory", C.c_void_p), ("h", C.c_void_p), ("c", C.c_void_p), ("normalizer", C.c_void_p),
+                ("normalizer_training", i32), ("critic", C.c_void_p), ("std", C.c_void_p), ("privileged_observations", C.c_void_p)]
+
+
+class lg_estimation_stats(C.Structure):
+    """include/lgrunner_estimator.h: the per-step means, the four per-ray rows and the kernel's workspace."""
+    _fields_ = [(k, C.c_void_p) for k in ("mse", "mae", "ray_sq_error", "ray_abs_error", "ray_bias", "ray_max_error", "workspace")] + \
+        [("workspace_floats", C.c_int64)]
+
+
+def declare_runner_estimator(lib):
+    """Prototypes of the terrain-estimator runner's device side (include/lgrunner_estimator.h), same library."""
+    vp, i64 = C.c_void_p, C.c_int64
+    lib.lg_estimation_errors_workspace.argtypes = [i64, i32]
+    lib.lg_estimation_errors_workspace.restype = i64
+    lib.lg_estimation_errors.argtypes = [vp, vp, i32, i64, i32, C.POINTER(lg_estimation_stats), vp]
+    lib.lg_estimation_errors.restype = C.c_int
+    lib.lg_runner_collect_estimation.argtypes = [vp, C.POINTER(lg_estimation_driver), i32, C.POINTER(lg_estimation_out), C.POINTER(lg_estimation_nets),
+                                                 C.POINTER(lg_estimation_stats), vp]
+    lib.lg_runner_collect_estimation.restype = C.c_int
+    return lib
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------- the units
-Unit = collections.namedtuple("Unit", "declare headers")
+Unit =collections.namedtuple("Unit", "declare headers")
 
 # One row per `declare_*` function: the headers under include/ whose prototypes it mirrors.  Everything else about a unit is derived: its symbols
 # are what the function sets (`symbols`), its structs are the `typedef struct lg_...` names of its headers, found here by name.  A new header
@@ -773,6 +798,7 @@ UNITS = {
     "runner_privileged": Unit(declare_runner_privileged, ("lgrunner_privileged.h",)),
     "runner_distill": Unit(declare_runner_distill, ("lgrunner_distill.h",)),
     "sensors": Unit(declare_sensors, ("lgsensors.h",)),
+    "runner_estimator": Unit(declare_runner_estimator, ("lgrunner_estimator.h",)),
 }
 
 

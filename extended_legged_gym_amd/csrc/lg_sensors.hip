@@ -15,6 +15,7 @@
 #include "lg_estimator_internal.h"
 #include "lg_policy_internal.h"
 #include "lg_runner_internal.h"
+#include "lg_runner_estimator_internal.h"
 #include "../../include/lgpolicy.h"
 #include "../../include/lgrunner.h"
 #include "../../include/lgsensors.h"
@@ -158,6 +159,129 @@ int lg_policy_sensor_step(lg_sensor_rig* rig, const float* actions, float* next_
 }
 lg_ctx* lg_policy_sensor_env(lg_sensor_rig* rig) { return rig->env; }
 
+// The estimation collection loop behind lg_collect_estimation (a driver of actions or a bare actor, no stats) and lg_runner_collect_estimation
+// (include/lgrunner_estimator.h): lg_runner_estimator_internal.h.  The policy's input row x is the env's raw row, its column prefix (a strided copy
+// into scratch) when the policy is narrower, and the normaliser's output (scratch) when there is one.
+int lg_estimation_collect(lg_sensor_rig* rig, const lg_estimation_driver* drv, int32_t T, const lg_estimation_out* out, const lg_estimation_nets* est,
+                          const lg_estimation_stats* stats, void* stream) {
+  if (!rig) return lg_policy_fail(LG_ERR_INVALID, "null sensor rig");
+  if (!rig->has_rays || !rig->has_camera) return lg_policy_fail(LG_ERR_INVALID, "the rig must carry both the ray caster and the depth camera");
+  if (T < 1) return lg_policy_fail(LG_ERR_INVALID, "T < 1");
+  lg_mlp* actor = drv->actor; const float* actions = drv->actions;
+  lg_rnn* mem = drv->memory; lg_obsnorm* norm = drv->normalizer;
+  if ((actor != nullptr) == (actions != nullptr)) return lg_policy_fail(LG_ERR_INVALID, "exactly one of actor and actions must be given");
+  if (!actor && (mem || norm)) return lg_policy_fail(LG_ERR_INVALID, "a memory or a normaliser needs the actor behind it: pre-drawn actions pass neither");
+  if (!out || !out->depth_images || !out->proprio_data || !out->raycast_targets || !out->dones) return lg_policy_fail(LG_ERR_INVALID, "null output row");
+  void* p; int64_t shp[4], ashp[4]; int32_t nd, dt;
+  lg_ctx* env = rig->env;
+  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's observation rows: ") + lg_last_error(env));
+  const float* env_obs = (const float*)p; const int64_t n = rig->n, O = shp[1];
+  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's action rows: ") + lg_last_error(env));
+  const int64_t A = ashp[1];
+  if (lg_get_tensor(env, LG_T_BASE_LIN_VEL, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's base_lin_vel: ") + lg_last_error(env));
+  const float* lin = (const float*)p;
+  if (lg_get_tensor(env, LG_T_BASE_ANG_VEL, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's base_ang_vel: ") + lg_last_error(env));
+  const float* ang = (const float*)p;
+  int64_t in_w = 0, mem_top = 0;
+  if (actor) {
+    int al, ain, aout, adev;
+    lg_mlp_widths(actor, &al, &ain, &aout, &adev);
+    if (adev != rig->device) return lg_policy_fail(LG_ERR_INVALID, "the actor is on another device than the env context");
+    if (aout != A) return lg_policy_fail(LG_ERR_INVALID, "the actor ends in " + std::to_string(aout) + " actions, the env takes " + std::to_string(A));
+    in_w = ain;
+    if (mem) {
+      int rtype, rin, rhid, rdev;
+      lg_rnn_widths(mem, &rtype, &rin, &rhid, &rdev);
+      if (rdev != rig->device) return lg_policy_fail(LG_ERR_INVALID, "the policy's memory is on another device than the env context");
+      if (!drv->h || (rtype == LG_RNN_LSTM && !drv->c)) return lg_policy_fail(LG_ERR_INVALID, "the policy's memory needs its state (h, and c for an LSTM)");
+      if (ain != rhid) return lg_policy_fail(LG_ERR_INVALID, "the actor reads " + std::to_string(ain) + " columns, the policy's memory has " + std::to_string(rhid) + " hidden units");
+      in_w = rin;
+      mem_top = (int64_t)(mem->num_layers - 1) * n * rhid;
+    }
+    if (in_w > O)
+      return lg_policy_fail(LG_ERR_INVALID, std::string(mem ? "the policy's memory" : "the actor") + " reads " + std::to_string(in_w) + " columns, the env's observation row has " + std::to_string(O));
+    if (norm) {
+      if (norm->device != rig->device) return lg_policy_fail(LG_ERR_INVALID, "the normaliser is on another device than the env context");
+      if (norm->O != in_w) return lg_policy_fail(LG_ERR_INVALID, "the normaliser has " + std::to_string(norm->O) + " columns, the policy reads " + std::to_string(in_w));
+    }
+  }
+  const lg_depth_params& dp = rig->cam.params;
+  const int64_t hw = (int64_t)dp.resized_width * dp.resized_height;
+  const int R = rig->rays.num_rays;
+  int64_t Rp = 0;
+  if (est) {
+    if (!est->encoder || !est->combine || !est->memory || !est->decoder || !est->h) return lg_policy_fail(LG_ERR_INVALID, "null estimator stage or memory state");
+    if (!out->predictions) return lg_policy_fail(LG_ERR_INVALID, "null output row (predictions)");
+    if (est->encoder->H != dp.resized_height || est->encoder->W != dp.resized_width)
+      return lg_policy_fail(LG_ERR_INVALID, "the encoder takes " + std::to_string(est->encoder->H) + " x " + std::to_string(est->encoder->W) + " images, the camera's frames are " +
+                                                std::to_string(dp.resized_height) + " x " + std::to_string(dp.resized_width));
+    int cl, cin, cout, cdev, dl, din, dout, ddev, rtype, rin, rhid, rdev;
+    lg_mlp_widths(est->combine, &cl, &cin, &cout, &cdev);
+    lg_mlp_widths(est->decoder, &dl, &din, &dout, &ddev);
+    lg_rnn_widths(est->memory, &rtype, &rin, &rhid, &rdev);
+    if (cin - est->encoder->out_dim != 6) return lg_policy_fail(LG_ERR_INVALID, "the estimator's combination layer does not read the six base velocities behind the features");
+    if (rtype == LG_RNN_LSTM && !est->c) return lg_policy_fail(LG_ERR_INVALID, "an LSTM needs its cell state");
+    Rp = dout;
+  }
+  if (stats) {
+    if (!est) return lg_policy_fail(LG_ERR_INVALID, "error figures need an estimator: stats without nets");
+    if (Rp != R) return lg_policy_fail(LG_ERR_INVALID, "the estimator predicts " + std::to_string(Rp) + " distances, the ray caster has " + std::to_string(R) + " rays");
+    const int rc = lg_estimation_stats_ok(stats, n, R);
+    if (rc != LG_OK) return rc;
+  }
+  DeviceScope ds_(rig->device);
+  hipStream_t st = (hipStream_t)stream;
+  // scratch: [reward row n | the policy's input row n x in_w (a column prefix, or the normaliser's output) | its actions n x A]
+  const bool prefix = actor && in_w < O;
+  const bool own_row = prefix || norm;
+  const size_t need = (size_t)n + (own_row ? (size_t)n * in_w : 0) + (actor ? (size_t)n * A : 0);
+  if (need > rig->scratch_floats) {
+    if (rig->scratch) { POLICY_TRY(hipStreamSynchronize(st)); (void)hipFree(rig->scratch); rig->scratch = nullptr; rig->scratch_floats = 0; }
+    POLICY_TRY(hipMalloc((void**)&rig->scratch, need * sizeof(float)));
+    rig->scratch_floats = need;
+  }
+  float* rew_row = rig->scratch;
+  float* own = rig->scratch + n;
+  float* act_row = own + (own_row ? (size_t)n * in_w : 0);
+  int rc;
+  for (int t = 0; t < T; ++t) {
+    float* depth_t = out->depth_images + (size_t)t * n * hw;
+    float* proprio_t = out->proprio_data + (size_t)t * n * 6;
+    float* targets_t = out->raycast_targets + (size_t)t * n * R;
+    float* dones_t = out->dones + (size_t)t * n;
+    rc = estimation_rows_launch(rig->cam.depth_buffer, dp.buffer_len, hw, lin, ang, rig->rays.ray_hits, rig->root_states, n, R, depth_t, proprio_t, targets_t, st);
+    if (rc != LG_OK) return rc;
+    if (est) {
+      float* pred_t = out->predictions + (size_t)t * n * Rp;
+      rc = lg_estimator_step(est->encoder, est->combine, est->memory, est->decoder, depth_t, hw, proprio_t, n, est->h, est->c, nullptr, pred_t, stream);
+      if (rc != LG_OK) return rc;
+      if (stats && (rc = lg_estimation_errors_launch(pred_t, targets_t, n, R, stats, stats->mse + t, stats->mae + t, t == 0, st)) != LG_OK) return rc;
+    }
+    const float* act_t = actions ? actions + (size_t)t * n * A : act_row;
+    if (actor) {
+      const float* x = env_obs;
+      if (prefix) {
+        POLICY_TRY(hipMemcpy2DAsync(own, (size_t)in_w * 4, env_obs, (size_t)O * 4, (size_t)in_w * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
+        x = own;
+      }
+      if (norm) {
+        if ((rc = lg_obsnorm_step(norm, x, n, in_w, 0, own, stream)) != LG_OK) return rc;
+        x = own;
+      }
+      if (mem) {
+        if ((rc = lg_rnn_step(mem, x, n, drv->h, drv->c, nullptr, nullptr, stream)) != LG_OK) return rc;
+        x = drv->h + mem_top;
+      }
+      if ((rc = lg_mlp_forward(actor, x, n, act_row, stream)) != LG_OK) return rc;
+    }
+    if ((rc = sensor_step(rig, act_t, nullptr, nullptr, 0.f, rew_row, dones_t, stream)) != LG_OK) return rc;
+    if (est && (rc = lg_rnn_reset_rows(est->memory, est->h, est->c, dones_t, n, stream)) != LG_OK) return rc;
+    if (mem && (rc = lg_rnn_reset_rows(mem, drv->h, drv->c, dones_t, n, stream)) != LG_OK) return rc;
+  }
+  POLICY_TRY(hipGetLastError());
+  return LG_OK;
+}
+
 extern "C" {
 
 lg_sensor_rig* lg_sensor_rig_create(lg_ctx* env, lg_mesh* mesh, const lg_sensor_raycaster* rays, const lg_sensor_camera* cam) {
@@ -246,88 +370,9 @@ int lg_estimation_rows(const float* depth_buffer, int32_t buffer_len, int64_t hw
 int lg_collect_estimation(lg_sensor_rig* rig, lg_mlp* actor, const float* actions, int32_t T, const lg_estimation_out* out, const lg_estimation_nets* est,
                           void* stream) {
   POLICY_ENTRY;
-  if (!rig) return lg_policy_fail(LG_ERR_INVALID, "null sensor rig");
-  if (!rig->has_rays || !rig->has_camera) return lg_policy_fail(LG_ERR_INVALID, "the rig must carry both the ray caster and the depth camera");
-  if (T < 1) return lg_policy_fail(LG_ERR_INVALID, "T < 1");
-  if ((actor != nullptr) == (actions != nullptr)) return lg_policy_fail(LG_ERR_INVALID, "exactly one of actor and actions must be given");
-  if (!out || !out->depth_images || !out->proprio_data || !out->raycast_targets || !out->dones) return lg_policy_fail(LG_ERR_INVALID, "null output row");
-  void* p; int64_t shp[4], ashp[4]; int32_t nd, dt;
-  lg_ctx* env = rig->env;
-  if (lg_get_tensor(env, LG_T_OBS_BUF, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's observation rows: ") + lg_last_error(env));
-  const float* env_obs = (const float*)p; const int64_t n = rig->n, O = shp[1];
-  if (lg_get_tensor(env, LG_T_ACTIONS, &p, ashp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's action rows: ") + lg_last_error(env));
-  const int64_t A = ashp[1];
-  if (lg_get_tensor(env, LG_T_BASE_LIN_VEL, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's base_lin_vel: ") + lg_last_error(env));
-  const float* lin = (const float*)p;
-  if (lg_get_tensor(env, LG_T_BASE_ANG_VEL, &p, shp, &nd, &dt) != LG_OK) return lg_policy_fail(LG_ERR_INVALID, std::string("the env's base_ang_vel: ") + lg_last_error(env));
-  const float* ang = (const float*)p;
-  int64_t in_w = 0;
-  if (actor) {
-    int al, ain, aout, adev;
-    lg_mlp_widths(actor, &al, &ain, &aout, &adev);
-    if (adev != rig->device) return lg_policy_fail(LG_ERR_INVALID, "the actor is on another device than the env context");
-    if (aout != A) return lg_policy_fail(LG_ERR_INVALID, "the actor ends in " + std::to_string(aout) + " actions, the env takes " + std::to_string(A));
-    if (ain > O) return lg_policy_fail(LG_ERR_INVALID, "the actor reads " + std::to_string(ain) + " columns, the env's observation row has " + std::to_string(O));
-    in_w = ain;
-  }
-  const lg_depth_params& dp = rig->cam.params;
-  const int64_t hw = (int64_t)dp.resized_width * dp.resized_height;
-  const int R = rig->rays.num_rays;
-  int64_t Rp = 0;
-  if (est) {
-    if (!est->encoder || !est->combine || !est->memory || !est->decoder || !est->h) return lg_policy_fail(LG_ERR_INVALID, "null estimator stage or memory state");
-    if (!out->predictions) return lg_policy_fail(LG_ERR_INVALID, "null output row (predictions)");
-    if (est->encoder->H != dp.resized_height || est->encoder->W != dp.resized_width)
-      return lg_policy_fail(LG_ERR_INVALID, "the encoder takes " + std::to_string(est->encoder->H) + " x " + std::to_string(est->encoder->W) + " images, the camera's frames are " +
-                                                std::to_string(dp.resized_height) + " x " + std::to_string(dp.resized_width));
-    int cl, cin, cout, cdev, dl, din, dout, ddev, rtype, rin, rhid, rdev;
-    lg_mlp_widths(est->combine, &cl, &cin, &cout, &cdev);
-    lg_mlp_widths(est->decoder, &dl, &din, &dout, &ddev);
-    lg_rnn_widths(est->memory, &rtype, &rin, &rhid, &rdev);
-    if (cin - est->encoder->out_dim != 6) return lg_policy_fail(LG_ERR_INVALID, "the estimator's combination layer does not read the six base velocities behind the features");
-    if (rtype == LG_RNN_LSTM && !est->c) return lg_policy_fail(LG_ERR_INVALID, "an LSTM needs its cell state");
-    Rp = dout;
-  }
-  DeviceScope ds_(rig->device);
-  hipStream_t st = (hipStream_t)stream;
-  // scratch: [reward row n | the actor's column prefix n x in_w (only when narrower than the row) | its actions n x A]
-  const bool prefix = actor && in_w < O;
-  const size_t need = (size_t)n + (prefix ? (size_t)n * in_w : 0) + (actor ? (size_t)n * A : 0);
-  if (need > rig->scratch_floats) {
-    if (rig->scratch) { POLICY_TRY(hipStreamSynchronize(st)); (void)hipFree(rig->scratch); rig->scratch = nullptr; rig->scratch_floats = 0; }
-    POLICY_TRY(hipMalloc((void**)&rig->scratch, need * sizeof(float)));
-    rig->scratch_floats = need;
-  }
-  float* rew_row = rig->scratch;
-  float* prefix_row = rig->scratch + n;
-  float* act_row = prefix_row + (prefix ? (size_t)n * in_w : 0);
-  int rc;
-  for (int t = 0; t < T; ++t) {
-    float* depth_t = out->depth_images + (size_t)t * n * hw;
-    float* proprio_t = out->proprio_data + (size_t)t * n * 6;
-    float* dones_t = out->dones + (size_t)t * n;
-    rc = estimation_rows_launch(rig->cam.depth_buffer, dp.buffer_len, hw, lin, ang, rig->rays.ray_hits, rig->root_states, n, R, depth_t, proprio_t,
-                                out->raycast_targets + (size_t)t * n * R, st);
-    if (rc != LG_OK) return rc;
-    if (est) {
-      rc = lg_estimator_step(est->encoder, est->combine, est->memory, est->decoder, depth_t, hw, proprio_t, n, est->h, est->c, nullptr,
-                             out->predictions + (size_t)t * n * Rp, stream);
-      if (rc != LG_OK) return rc;
-    }
-    const float* act_t = actions ? actions + (size_t)t * n * A : act_row;
-    if (actor) {
-      const float* x = env_obs;
-      if (prefix) {
-        POLICY_TRY(hipMemcpy2DAsync(prefix_row, (size_t)in_w * 4, env_obs, (size_t)O * 4, (size_t)in_w * 4, (size_t)n, hipMemcpyDeviceToDevice, st));
-        x = prefix_row;
-      }
-      if ((rc = lg_mlp_forward(actor, x, n, act_row, stream)) != LG_OK) return rc;
-    }
-    if ((rc = sensor_step(rig, act_t, nullptr, nullptr, 0.f, rew_row, dones_t, stream)) != LG_OK) return rc;
-    if (est && (rc = lg_rnn_reset_rows(est->memory, est->h, est->c, dones_t, n, stream)) != LG_OK) return rc;
-  }
-  POLICY_TRY(hipGetLastError());
-  return LG_OK;
+  lg_estimation_driver drv{};
+  drv.actions = actions; drv.actor = actor;
+  return lg_estimation_collect(rig, &drv, T, out, est, nullptr, stream);
 }
 
 }  // extern "C"

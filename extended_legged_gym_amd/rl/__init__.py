@@ -10,7 +10,9 @@ recurrent student: truncated BPTT through its memory, include/lgdistill_recurren
 `collect_rollout_tracked` / `EpisodeTracker` (the collection with the normaliser and the episode bookkeeping between its launches, include/lgrunner.h;
 with privileged critic observations -- two observation streams, two normalisers, `NativeEmpiricalNormalization.step_pair` --
 include/lgrunner_privileged.h); `NativeDistillationRunner` (the same surface for `Distillation`: the teacher from the PPO runner's checkpoint, two
-normalisers) over `collect_distillation_tracked` (include/lgrunner_distill.h)."""
+normalisers) over `collect_distillation_tracked` (include/lgrunner_distill.h); `NativeTerrainEstimatorRunner` (rsl_rl's `TerrainEstimatorRunner` surface:
+`learn`, `play`, the reference's checkpoints) over `collect_estimation_driven` -- the estimation collection with the pretrained policy as its driver --
+and `estimation_errors` (include/lgrunner_estimator.h); `TerrainEstimatorTorch`, the torch restatement that seeds it."""
 from .policy import (NativeActorCritic, NativeActorCriticRecurrent, NativeMemory, NativeMLP,          # noqa: F401
                      NativeStudentTeacher, NativeStudentTeacherRecurrent)
 from .storage import compute_returns                      # noqa: F401
@@ -28,3 +30,5 @@ from .normalizer import NativeEmpiricalNormalization          # noqa: F401
 from .runner import NativeOnPolicyRunner          # noqa: F401
 from .distillation_runner import NativeDistillationRunner          # noqa: F401
 from .sensors import SensorRig          # noqa: F401
+from .estimator_torch import TerrainEstimatorTorch          # noqa: F401
+from .estimator_runner import NativeTerrainEstimatorRunner, collect_estimation_driven, estimation_errors          # noqa: F401

@@ -363,7 +363,8 @@ def collect_estimation(env, policy, num_steps, estimator=None, one_call=False, a
     `algorithms/distillation.py:398-407`), the env is stepped with `policy.act_inference(env.obs_buf)` (a native policy; `policy=None`:
     `0.5 * randn`, as `:427`), and `dones[t]` = the step's `reset_buf`.  The reference's storage never fills its `dones` (they stay zero, so its
     update never resets the memory at an episode boundary); the REAL ones are returned here.  A host loop over `env.step`: the sensors are driven
-    from the env classes.
+    from the env classes.  A policy with a `reset` method (a recurrent one: its memory) is reset on every step's dones, as the one call of
+    `collect_estimation_driven` (`rl/estimator_runner.py`) resets it.
 
     Returns a dict: depth_images (T, N, h, w), proprio_data (T, N, 6), raycast_targets (T, N, R), dones (T, N).  With `estimator`
     (a `NativeTerrainEstimator`) it is also stepped on every row and reset on `dones[t]` after the step (`distillation.py:275`): the evaluation
@@ -407,6 +408,8 @@ def collect_estimation(env, policy, num_steps, estimator=None, one_call=False, a
         out["dones"][t].copy_(dones)
         if estimator is not None:
             estimator.reset(dones)
+        if hasattr(policy, "reset"):          # a recurrent policy's memory (`Memory.reset(dones)`); nothing for a feed-forward one
+            policy.reset(dones)
     return out
 
 
