@@ -617,7 +617,26 @@ def declare_estimator_train(lib):
     return lib
 
 
+def declare_estimator_train_bf16(lib):
+    """Prototypes of the bf16-encoder trainer's own entry points (include/lgestimator_train_bf16.h), same library; the handle it creates takes every
+    call of `declare_estimator_train`."""
+    vp, i64 = C.c_void_p, C.c_int64
+    lib.lg_estimator_bf16train_create.argtypes = [vp, vp, vp, vp, C.POINTER(lg_estimator_train_params), C.c_double, i64]
+    lib.lg_estimator_bf16train_create.restype = vp
+    lib.lg_estimator_bf16train_wgrad_slab_rows.argtypes = []
+    lib.lg_estimator_bf16train_wgrad_slab_rows.restype = i32
+    lib.lg_estimator_bf16train_saved_stage.argtypes = [vp, i32, vp, i64, vp]
+    lib.lg_estimator_bf16train_saved_stage.restype = C.c_int
+    lib.lg_estimator_bf16train_backward_stage.argtypes = [vp, i32, vp, i64, vp, vp, vp]
+    lib.lg_estimator_bf16train_backward_stage.restype = C.c_int
+    return lib
+
+
 ESTIMATOR_LOSSES = {"mse": 0, "huber": 1, "l1": 2}          # enum lg_estimator_loss
+# enum lg_estimator_bf16_stage
+ESTIMATOR_BF16_STAGES = {"pool_backward": 0, "dgrad_conv4": 1, "dgrad_conv3": 2, "dgrad_conv2": 3, "wgrad_conv4": 4, "wgrad_conv3": 5, "wgrad_conv2": 6, "wgrad_conv1": 7,
+                         "linear2": 8, "linear1": 9}
+ENCODER_TRAININGS = ("fp32", "bf16")          # NativeEstimatorDistillation(encoder_training=...)
 
 NOISE_STD_TYPES = {"scalar": 0, "log": 1}          # enum lg_noise_std_type
 LR_SCHEDULES = {"fixed": 0, "adaptive": 1}          # enum lg_lr_schedule
@@ -794,6 +813,7 @@ UNITS = {
     "distill_train": Unit(declare_distill_train, ("lgdistill.h",)),
     "distill_rtrain": Unit(declare_distill_rtrain, ("lgdistill_recurrent.h",)),
     "estimator_train": Unit(declare_estimator_train, ("lgestimator_train.h",)),
+    "estimator_train_bf16": Unit(declare_estimator_train_bf16, ("lgestimator_train_bf16.h",)),
     "runner": Unit(declare_runner, ("lgrunner.h",)),
     "runner_privileged": Unit(declare_runner_privileged, ("lgrunner_privileged.h",)),
     "runner_distill": Unit(declare_runner_distill, ("lgrunner_distill.h",)),

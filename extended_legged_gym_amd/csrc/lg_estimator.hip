@@ -583,6 +583,22 @@ int enc_forward_saved(lg_conv_encoder* e, const float* depth, int64_t depth_stri
   return LG_OK;
 }
 
+// The same for an LG_PREC_BF16 encoder: the launch list of enc_forward's bf16 branch onto the caller's maps, so the features are those of
+// lg_conv_encoder_forward / lg_estimator_step bit for bit.  maps[0 .. 5] hold bf16, maps[6] the fp32 features.
+int enc_forward_saved_bf16(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, void* const* maps, const int64_t* strides, hipStream_t st) {
+  const void* in = depth; int64_t in_stride = depth_stride;
+  for (int k = 1; k <= ENC_LAYERS + 1; ++k) {
+    if (k == 5) hipLaunchKernelGGL(enc_bf16_pool_kernel, dim3((unsigned)((n * 1024 + 255) / 256)), dim3(256), 0, st, (const __bf16*)in, n, e->Hp, e->Wp, 64, (__bf16*)maps[k - 1]);
+    else {
+      const int rc = enc_launch_bf16(e->layer[k < 5 ? k - 1 : k - 2], k, in, in_stride, n, maps[k - 1], strides[k - 1], st);
+      if (rc != LG_OK) return rc;
+    }
+    in = maps[k - 1]; in_stride = strides[k - 1];
+  }
+  POLICY_TRY(hipGetLastError());
+  return LG_OK;
+}
+
 void enc_launch_cat(const float* proprio, int64_t n, int P, float* dst, int stride, int col0, hipStream_t st) {
   hipLaunchKernelGGL(cat_columns_kernel, dim3((unsigned)((n * P + 255) / 256)), dim3(256), 0, st, proprio, n, P, dst, stride, col0);
 }

@@ -43,5 +43,8 @@ static const int kConvShape[4][5] = {{1, 32, 5, 2, 2}, {32, 64, 3, 2, 1}, {64, 1
 // stage k = 1..7 (conv 1-4, pool + flatten, linear 1, linear 2) of the fp32 encoder on n images, written to maps[k - 1] with rows strides[k - 1] floats
 // apart (conv maps (env, y, x, channel)); the kernels and grids of lg_conv_encoder_forward
 int enc_forward_saved(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, float* const* maps, const int64_t* strides, hipStream_t st);
+// the same stages of an LG_PREC_BF16 encoder: maps[0 .. 5] bf16 (strides in elements), maps[6] the fp32 features; the kernels and grids of its
+// lg_conv_encoder_forward
+int enc_forward_saved_bf16(lg_conv_encoder* e, const float* depth, int64_t depth_stride, int64_t n, void* const* maps, const int64_t* strides, hipStream_t st);
 // columns [col0, col0 + P) of the (n, stride) rows = proprio (n, P)
 void enc_launch_cat(const float* proprio, int64_t n, int P, float* dst, int stride, int col0, hipStream_t st);

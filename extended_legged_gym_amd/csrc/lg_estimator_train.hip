@@ -23,6 +23,8 @@
 //   est_act_delta_kernel      d *= act'(y) for the combination layer, whose weight gradient needs its pre-activation delta as rows.
 //   est_conv_retile_kernel    the masters -> the forward images of conv 1-4 (lg_conv_tile_weights' layout, bit for bit) with their bias rows, and the
 //                             transposed images of conv 2-4.
+// A trainer of an LG_PREC_BF16 encoder (lg_estimator_bf16train_create) is the same object: its steps take the encoder's forward, the pooling / convolution
+// backward and the retile from lg_estimator_train_bf16.hip (lg_estimator_train_internal.h) and everything else from here.
 // No atomics: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -34,31 +36,9 @@
 
 #include "lg_device.h"
 #include "lg_policy_internal.h"
-#include "lg_estimator_internal.h"
-#include "lg_train_internal.h"
-#include "lg_train_recurrent_internal.h"
-#include "lg_train_sequence_internal.h"
-#include "../../include/lgestimator_train.h"
+#include "lg_estimator_train_internal.h"
 
 #define EST_WGRAD_SLAB 8192         // rows (env, output pixel) per slab of a convolution's weight gradient
-#define EST_DENSE_EXTRA 3           // depth_encoder.10, depth_encoder.12, combination_mlp.0
-
-LG_DEV float est_act_grad(float y, int act) {
-  switch (act) {
-    case LG_ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case LG_ACT_TANH: return 1.f - y * y;
-    default: return y > 0.f ? 1.f : y + 1.f;                // ELU
-  }
-}
-
-struct DgradLayer {
-  int Hin, Win, Cin, Hout, Wout, Cout, sh, pad, act;       // sh = stride - 1 (stride 1 | 2): t is a multiple of the stride iff (t & sh) == 0, t / stride = t >> sh
-  int py, px, Hc, Wc;                                       // the rows of this launch: input pixels (py + (sh + 1) cy, px + (sh + 1) cx), cy < Hc, cx < Wc
-  int nkb, nkb_w;                                           // this launch's K rounded up to 64, / 16; k-blocks per chunk of the weight image
-  const float* wt;                                          // [16-column chunk of ci][k / 16][lane][4], k = (ky, kx, co) over ALL taps
-  const int32_t* ktab;                                      // [16 nkb]: (ky << 26) | (kx << 22) | co of this launch's k, -1 beyond its K
-  const int32_t* wblk;                                      // [nkb]: the k-block of the weight image that holds this launch's k-block
-};
 
 __global__ __launch_bounds__(CONV_THREADS) void est_dgrad_kernel(DgradLayer L, const float* __restrict__ D, int64_t d_estride, int64_t n, const float* __restrict__ ysrc,
                                                                   int64_t y_estride, float* __restrict__ out, int64_t out_estride) {
@@ -281,30 +261,18 @@ __global__ __launch_bounds__(256) void est_conv_retile_kernel(const ConvRetile* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host side
-struct lg_estimator_train : SeqCore {
-  lg_conv_encoder* enc = nullptr; lg_mlp* combine = nullptr; lg_mlp* decoder = nullptr;
-  TrainMem tm;                                 // the memory, its workspaces and carried state (lg_train_recurrent_internal.h)
-  int F = 0, P_in = 0, cat_w = 0, Fc = 0, act = 0;
-  int nd = 0;                                  // dense segments [0, nd): decoder, depth_encoder.10 / .12, combination_mlp.0, the memory's; then conv 1-4
-  int64_t map_floats[4] = {0, 0, 0, 0};
-  float* map[4] = {nullptr, nullptr, nullptr, nullptr};
-  float *pool = nullptr, *y5 = nullptr, *cat = nullptr, *comb = nullptr;
-  float *dA = nullptr, *dB = nullptr, *dpool = nullptr, *d5 = nullptr, *d6 = nullptr, *dcomb = nullptr;
-  DgradLayer dg_comb, dg_l12, dg_l10, dg_conv[4][4];       // dg_conv[l][parity class]: conv l + 1 (index 0 unused); a stride-1 layer has class 0 only (Hc == 0: no launch)
-  ConvRetile* d_cretile = nullptr; int64_t cretile_big = 0;
-};
-
 static TrainMem* est_mem(lg_estimator_train* p) { return p ? &p->tm : nullptr; }
 
 // the masters -> the convolutions' and the memory's images (the dense layers' are the Adam kernel's / train_core_retile's)
 static int est_retile(TrainCore* c, hipStream_t st) {
   lg_estimator_train* p = static_cast<lg_estimator_train*>(c);
-  hipLaunchKernelGGL(est_conv_retile_kernel, dim3((unsigned)((p->cretile_big + 255) / 256), 4), dim3(256), 0, st, (const ConvRetile*)p->d_cretile, (const float*)p->theta);
+  if (p->b16) est16_retile(p, st);
+  else hipLaunchKernelGGL(est_conv_retile_kernel, dim3((unsigned)((p->cretile_big + 255) / 256), 4), dim3(256), 0, st, (const ConvRetile*)p->d_cretile, (const float*)p->theta);
   return mem_retile(&p->tm, p->theta, st);
 }
 
-static void est_launch_dgrad(const DgradLayer& L, const float* D, int64_t d_estride, int64_t n, const float* ysrc, int64_t y_estride, float* out, int64_t out_estride,
-                             hipStream_t st) {
+void est_launch_dgrad(const DgradLayer& L, const float* D, int64_t d_estride, int64_t n, const float* ysrc, int64_t y_estride, float* out, int64_t out_estride,
+                      hipStream_t st) {
   if (L.Hc < 1 || L.Wc < 1) return;
   const int64_t tiles = (n * L.Hc * L.Wc + CONV_ROWS - 1) / CONV_ROWS;
   hipLaunchKernelGGL(est_dgrad_kernel, dim3((unsigned)tiles, (unsigned)((L.Cin + CONV_COLS - 1) / CONV_COLS)), dim3(CONV_THREADS), 0, st, L, D, d_estride, n, ysrc, y_estride,
@@ -324,6 +292,30 @@ static int est_launch_conv_wgrad(lg_estimator_train* p, int l, const float* D, c
   const int tiles = ((C.Cout + 31) / 32) * ((W.K + 1 + 63) / 64);
   hipLaunchKernelGGL(est_conv_wgrad_kernel, dim3((unsigned)((tiles + 3) / 4), (unsigned)nslabs), dim3(256), 0, st, W, (uint32_t)M);
   return nslabs;
+}
+
+// stages 1-7 of the fp32 encoder on rows [at, at + n) of the group: the saved maps, the features into the cat rows
+static int est_forward_fp32(lg_estimator_train* p, const float* depth, int64_t depth_stride, int64_t n, int64_t at, hipStream_t st) {
+  float* maps[7] = {p->map[0] + at * p->map_floats[0], p->map[1] + at * p->map_floats[1], p->map[2] + at * p->map_floats[2], p->map[3] + at * p->map_floats[3],
+                    p->pool + at * 1024, p->y5 + at * 128, p->cat + at * p->cat_w};
+  const int64_t strides[7] = {p->map_floats[0], p->map_floats[1], p->map_floats[2], p->map_floats[3], 1024, 128, p->cat_w};
+  return enc_forward_saved(p->enc, depth, depth_stride, n, maps, strides, st);
+}
+
+// from dpool: the pooling and conv 4 .. conv 1 backwards, each convolution's weight gradient as soon as its delta stands (two delta buffers ping-pong);
+// cslabs[l]: the slabs of conv l + 1's weight gradient.  The sibling of est16_backward.
+static void est_backward_fp32(lg_estimator_train* p, const float* depth, int64_t n, int64_t N, int64_t T, int64_t t0, int* cslabs, hipStream_t st) {
+  const ConvLayerDev* C = p->enc->layer;
+  const int hw = p->enc->H * p->enc->W;
+  hipLaunchKernelGGL(est_pool_backward_kernel, dim3((unsigned)((n * p->map_floats[3] + 255) / 256)), dim3(256), 0, st, (const float*)p->dpool, (const float*)p->map[3], n,
+                     C[3].Hout, C[3].Wout, 64, p->act, p->dB);
+  cslabs[3] = est_launch_conv_wgrad(p, 3, p->dB, p->map[2], p->map_floats[2], n, N, 0, 0, st);
+  for (int k = 0; k < 4; ++k) est_launch_dgrad(p->dg_conv[3][k], p->dB, p->map_floats[3], n, p->map[2], p->map_floats[2], p->dA, p->map_floats[2], st);
+  cslabs[2] = est_launch_conv_wgrad(p, 2, p->dA, p->map[1], p->map_floats[1], n, N, 0, 0, st);
+  for (int k = 0; k < 4; ++k) est_launch_dgrad(p->dg_conv[2][k], p->dA, p->map_floats[2], n, p->map[1], p->map_floats[1], p->dB, p->map_floats[1], st);
+  cslabs[1] = est_launch_conv_wgrad(p, 1, p->dB, p->map[0], p->map_floats[0], n, N, 0, 0, st);
+  for (int k = 0; k < 4; ++k) est_launch_dgrad(p->dg_conv[1][k], p->dB, p->map_floats[1], n, p->map[0], p->map_floats[0], p->dA, p->map_floats[0], st);
+  cslabs[0] = est_launch_conv_wgrad(p, 0, p->dA, depth, hw, n, N, T, t0, st);
 }
 
 static int est_check_call(lg_estimator_train* p, const float* depth, const float* proprio, const float* tgt, const float* dones, int64_t T, int64_t N,
@@ -349,14 +341,12 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
   int rc = mem_open_carry(M, N, st);
   if (rc != LG_OK) return rc;
   p->last_rows = n;
+  if (p->b16) { p->last_depth = depth; p->last_N = N; p->last_T = T; p->last_t0 = t0; }          // lg_estimator_bf16train_backward_stage reads them
   p->last_steps = nsteps;                                    // always, and group_loss with it: after an update they are the forward-only remainder's, if there is one
   // ---- the encoder and the cat rows, one launch list per run of consecutive time indices
   for (int64_t s = 0; s < nsteps;) {
     const int64_t t = (t0 + s) % T, len = std::min(nsteps - s, T - t), at = s * N;
-    float* maps[7] = {p->map[0] + at * p->map_floats[0], p->map[1] + at * p->map_floats[1], p->map[2] + at * p->map_floats[2], p->map[3] + at * p->map_floats[3],
-                      p->pool + at * 1024, p->y5 + at * 128, p->cat + at * p->cat_w};
-    const int64_t strides[7] = {p->map_floats[0], p->map_floats[1], p->map_floats[2], p->map_floats[3], 1024, 128, p->cat_w};
-    if ((rc = enc_forward_saved(p->enc, depth + t * N * hw, hw, len * N, maps, strides, st)) != LG_OK) return rc;
+    if ((rc = p->b16 ? est16_forward(p, depth + t * N * hw, hw, len * N, at, st) : est_forward_fp32(p, depth + t * N * hw, hw, len * N, at, st)) != LG_OK) return rc;
     if (p->P_in > 0) enc_launch_cat(proprio + t * N * p->P_in, len * N, p->P_in, p->cat + at * p->cat_w, p->cat_w, p->F, st);
     s += len;
   }
@@ -377,17 +367,9 @@ static int est_steps(lg_estimator_train* p, const float* depth, const float* pro
     est_launch_dgrad(p->dg_comb, p->dcomb, p->Fc, n, p->cat, p->cat_w, p->d6, p->F, st);
     est_launch_dgrad(p->dg_l12, p->d6, p->F, n, p->y5, 128, p->d5, 128, st);
     est_launch_dgrad(p->dg_l10, p->d5, 128, n, nullptr, 0, p->dpool, 1024, st);
-    const ConvLayerDev* C = p->enc->layer;
-    hipLaunchKernelGGL(est_pool_backward_kernel, dim3((unsigned)((n * p->map_floats[3] + 255) / 256)), dim3(256), 0, st, (const float*)p->dpool, (const float*)p->map[3], n,
-                       C[3].Hout, C[3].Wout, 64, p->act, p->dB);
     int cslabs[4];
-    cslabs[3] = est_launch_conv_wgrad(p, 3, p->dB, p->map[2], p->map_floats[2], n, N, 0, 0, st);
-    for (int k = 0; k < 4; ++k) est_launch_dgrad(p->dg_conv[3][k], p->dB, p->map_floats[3], n, p->map[2], p->map_floats[2], p->dA, p->map_floats[2], st);
-    cslabs[2] = est_launch_conv_wgrad(p, 2, p->dA, p->map[1], p->map_floats[1], n, N, 0, 0, st);
-    for (int k = 0; k < 4; ++k) est_launch_dgrad(p->dg_conv[2][k], p->dA, p->map_floats[2], n, p->map[1], p->map_floats[1], p->dB, p->map_floats[1], st);
-    cslabs[1] = est_launch_conv_wgrad(p, 1, p->dB, p->map[0], p->map_floats[0], n, N, 0, 0, st);
-    for (int k = 0; k < 4; ++k) est_launch_dgrad(p->dg_conv[1][k], p->dB, p->map_floats[1], n, p->map[0], p->map_floats[0], p->dA, p->map_floats[0], st);
-    cslabs[0] = est_launch_conv_wgrad(p, 0, p->dA, depth, hw, n, N, T, t0, st);
+    if (p->b16) est16_backward(p, depth, n, N, T, t0, cslabs, st);
+    else est_backward_fp32(p, depth, n, N, T, t0, cslabs, st);
     // ---- the dense weight gradients in one slab pass, every reduction, the norm, Adam, the images
     train_launch_wgrad_range(p, 0, p->nd, nullptr, nullptr, nullptr, n, st);
     train_launch_reduce_range(p, 0, p->nd, (int)((n + WGRAD_SLAB - 1) / WGRAD_SLAB), st);
@@ -438,6 +420,7 @@ void lg_estimator_train_destroy(lg_estimator_train* p) {
   if (!p) return;
   DeviceScope ds_(p->device);
   (void)hipDeviceSynchronize();
+  est16_free(p);
   train_core_free(p);
   delete p;
 }
@@ -445,13 +428,23 @@ void lg_estimator_train_destroy(lg_estimator_train* p) {
 lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* combine, lg_rnn* mem, lg_mlp* decoder, const lg_estimator_train_params* q, double learning_rate,
                                               int64_t max_rows) {
   POLICY_ENTRY;
+  if (enc && enc->prec != LG_PREC_F32) {
+    lg_policy_fail(LG_ERR_UNSUPPORTED, "a bf16 encoder cannot be trained by this entry: lg_estimator_bf16train_create trains it, or train fp32, then build a bf16 estimator from the parameters");
+    return nullptr;
+  }
+  return est_train_create(enc, combine, mem, decoder, q, learning_rate, max_rows, false);
+}
+
+}  // extern "C"
+
+lg_estimator_train* est_train_create(lg_conv_encoder* enc, lg_mlp* combine, lg_rnn* mem, lg_mlp* decoder, const lg_estimator_train_params* q, double learning_rate,
+                                     int64_t max_rows, bool bf16) {
   if (!enc || !combine || !mem || !decoder) { lg_policy_fail(LG_ERR_INVALID, "null encoder, combination layer, memory or decoder"); return nullptr; }
   if (!q) { lg_policy_fail(LG_ERR_INVALID, "null parameters"); return nullptr; }
   if (!q->encoder_weights || !q->encoder_biases || !q->combine_weight || !q->combine_bias || !q->memory_w_ih || !q->memory_w_hh || !q->memory_b_ih || !q->memory_b_hh ||
       !q->decoder_weights || !q->decoder_biases) { lg_policy_fail(LG_ERR_INVALID, "null parameter list"); return nullptr; }
   if (max_rows < 1) { lg_policy_fail(LG_ERR_INVALID, "max_rows < 1"); return nullptr; }
   if (!(learning_rate > 0.0)) { lg_policy_fail(LG_ERR_INVALID, "learning rate <= 0"); return nullptr; }
-  if (enc->prec != LG_PREC_F32) { lg_policy_fail(LG_ERR_UNSUPPORTED, "a bf16 encoder cannot be trained: train fp32, then build a bf16 estimator from the parameters"); return nullptr; }
   if (mem->wide) {
     lg_policy_fail(LG_ERR_UNSUPPORTED, "the memory is a wide one (lg_rnn_create_wide, " + std::to_string(mem->input) + " inputs): the estimator's memory takes at most " +
                                            std::to_string(RNN_XMAX) + " inputs");
@@ -481,9 +474,9 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   auto alloc = [&](size_t floats, bool zero) -> float* { float* d = ok ? (float*)train_alloc(p, floats * sizeof(float), zero) : nullptr; if (!d) ok = false; return d; };
   const size_t R = (size_t)max_rows;
   // ---- workspaces
-  for (int l = 0; l < 4; ++l) { p->map_floats[l] = (int64_t)enc->layer[l].Hout * enc->layer[l].Wout * enc->layer[l].Cout; p->map[l] = alloc(R * p->map_floats[l], false); }
+  for (int l = 0; l < 4; ++l) { p->map_floats[l] = (int64_t)enc->layer[l].Hout * enc->layer[l].Wout * enc->layer[l].Cout; if (!bf16) p->map[l] = alloc(R * p->map_floats[l], false); }
   p->pool = alloc(R * 1024, false); p->y5 = alloc(R * 128, false); p->cat = alloc(R * cat_w, false); p->comb = alloc(R * Fc, false);
-  p->dA = alloc(R * std::max(p->map_floats[0], p->map_floats[2]), false); p->dB = alloc(R * std::max(p->map_floats[1], p->map_floats[3]), false);
+  if (!bf16) { p->dA = alloc(R * std::max(p->map_floats[0], p->map_floats[2]), false); p->dB = alloc(R * std::max(p->map_floats[1], p->map_floats[3]), false); }
   p->dpool = alloc(R * 1024, false); p->d5 = alloc(R * 128, false); p->d6 = alloc(R * F, false); p->dcomb = alloc(R * Fc, false);
   ok = ok && mem_alloc(p, M, mem);
   const int K = M->Gates * H, nbk = (K + 15) / 16;
@@ -501,9 +494,14 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   auto transposed = [&](int dO, int dI) -> float* { return alloc((size_t)(((dI + 63) & ~63) / 16) * (((dO + 63) & ~63) / 16) * 256, true); };
   const ConvLayerDev& L10 = enc->layer[4]; const ConvLayerDev& L12 = enc->layer[5];
   float* bw10 = transposed(128, 1024); float* bw12 = transposed(F, 128); float* bwc = transposed(Fc, cat_w);
-  const int seg_l10 = p->nseg;
-  dense_seg(ID_L10, 128, 1024, p->d5, p->pool, const_cast<float*>(L10.w), const_cast<float*>(L10.b), L10.nkb, bw10, 128 / 16);
-  dense_seg(ID_L12, F, 128, p->d6, p->y5, const_cast<float*>(L12.w), const_cast<float*>(L12.b), L12.nkb, bw12, ((F + 63) & ~63) / 16);
+  const int seg_l10 = p->seg_l10 = p->nseg;
+  if (bf16) {          // Adam writes no image of the two linear layers: est16_retile rounds the masters into the bf16 forward images and the fp32 transposed ones
+    dense_seg(ID_L10, 128, 1024, p->d5, p->pool, nullptr, nullptr, 0, nullptr, 0);
+    dense_seg(ID_L12, F, 128, p->d6, p->y5, nullptr, nullptr, 0, nullptr, 0);
+  } else {
+    dense_seg(ID_L10, 128, 1024, p->d5, p->pool, const_cast<float*>(L10.w), const_cast<float*>(L10.b), L10.nkb, bw10, 128 / 16);
+    dense_seg(ID_L12, F, 128, p->d6, p->y5, const_cast<float*>(L12.w), const_cast<float*>(L12.b), L12.nkb, bw12, ((F + 63) & ~63) / 16);
+  }
   dense_seg(ID_COMB, Fc, cat_w, p->dcomb, p->cat, const_cast<float*>(combine->h.w[0]), const_cast<float*>(combine->h.b[0]), combine->h.kpad[0] / 16, bwc, ((Fc + 63) & ~63) / 16);
   wtab[ID_L10] = q->encoder_weights[4]; btab[ID_L10] = q->encoder_biases[4];
   wtab[ID_L12] = q->encoder_weights[5]; btab[ID_L12] = q->encoder_biases[5];
@@ -528,7 +526,7 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   for (int l = 0; l < 4 && ok; ++l) {          // the partials are est_conv_wgrad_kernel's; Adam writes no image (fw, fb, bw NULL): est_conv_retile_kernel does
     const ConvLayerDev& C = enc->layer[l];
     const int kh = kConvShape[l][2], dI = C.Cin * kh * kh;
-    const int64_t cslabs = (max_rows * C.Hout * C.Wout + EST_WGRAD_SLAB - 1) / EST_WGRAD_SLAB;
+    const int64_t slab = bf16 ? est16_slab_rows() : EST_WGRAD_SLAB, cslabs = (max_rows * C.Hout * C.Wout + slab - 1) / slab;
     TrainSeg& S = p->seg[p->nseg++];
     S.net = 0; S.layer = ID_CONV + l; S.dO = C.Cout; S.dI = dI; S.f_nb = 0; S.b_nb = 0; S.woff = 0; S.boff = 0; S.D = nullptr; S.Ain = nullptr;
     S.partial = alloc((size_t)cslabs * C.Cout * (dI + 1), false);
@@ -536,7 +534,7 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
     const int64_t cnt = (int64_t)C.Cout * (dI + 1);
     if (cnt > p->big) p->big = cnt;
     wtab[ID_CONV + l] = q->encoder_weights[l]; btab[ID_CONV + l] = q->encoder_biases[l];
-    if (l > 0) conv_bw[l] = alloc((size_t)(((C.Cin + 63) & ~63) / 16) * (((kh * kh * C.Cout + 63) & ~63) / 16) * 256, true);
+    if (l > 0 && !bf16) conv_bw[l] = alloc((size_t)(((C.Cin + 63) & ~63) / 16) * (((kh * kh * C.Cout + 63) & ~63) / 16) * 256, true);
   }
   // ---- the flat order: the module's state_dict()
   auto place = [&](TrainSeg& S) { S.woff = off; off += (int64_t)S.dO * S.dI; S.boff = off; off += S.dO; };
@@ -568,7 +566,7 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   dgrad(p->dg_comb, 1, 1, F, 1, 1, Fc, 1, 1, 0, bwc, 0);          // only the first F inputs of the cat rows are propagated: the proprio columns are data
   dgrad(p->dg_l12, 1, 1, 128, 1, 1, F, 1, 1, 0, bw12, 0);
   dgrad(p->dg_l10, 1, 1, 1024, 1, 1, 128, 1, 1, 0, bw10, 0);
-  for (int l = 1; l < 4; ++l) {
+  for (int l = 1; l < 4 && !bf16; ++l) {
     const ConvLayerDev& C = enc->layer[l];
     for (int cls = 0; cls < 4; ++cls) {
       if (C.stride == 1 && cls > 0) { p->dg_conv[l][cls] = DgradLayer{}; continue; }          // Hc = 0: never launched
@@ -580,6 +578,7 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   p->d_cretile = ok ? (ConvRetile*)train_alloc(p, sizeof(ConvRetile) * 4, true) : nullptr;
   ok = ok && p->d_cretile;
   ok = ok && mem_upload_retile(p, M);
+  ok = ok && (!bf16 || est16_setup(p, bw10, bw12));
   const float* const* ws[1] = {wtab};
   const float* const* bs[1] = {btab};
   if (!ok || train_core_finish(p, off, ws, bs, nullptr, learning_rate) != LG_OK ||
@@ -590,6 +589,8 @@ lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* enc, lg_mlp* comb
   }
   return p;
 }
+
+extern "C" {
 
 int lg_estimator_train_group(lg_estimator_train* p, const float* depth, const float* proprio, const float* tgt, const float* dones, int64_t T, int64_t N,
                              int64_t first_step, int64_t num_steps, int32_t train, const lg_estimator_train_hyper* hyper, void* stream) {

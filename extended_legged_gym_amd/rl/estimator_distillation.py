@@ -21,7 +21,12 @@ class NativeEstimatorDistillation(_NativeSequenceTrainer):
     """rsl_rl's `EstimatorDistillation` for a `NativeTerrainEstimator`, with its names and defaults.  `state_dict`: the `TerrainEstimator` state
     dict `estimator` was built from; it seeds the fp32 master parameters.  After `update`, the same `estimator` object predicts with the new
     weights; nothing is rebuilt, and its live inference state is not touched: the trainer owns the state it carries from update to update
-    (`get_hidden_states` / `set_hidden_states`)."""
+    (`get_hidden_states` / `set_hidden_states`).
+
+    `encoder_training="bf16"` (opt-in) trains an estimator built with `encoder_precision="bf16"`, natively (include/lgestimator_train_bf16.h): the update
+    differentiates the function that estimator computes, with fp32 master weights and fp32 Adam, bf16 saved maps and map-shaped deltas, and bf16
+    matrix-core kernels for the convolutions' data and weight gradients.  `state_dict()` returns the fp32 masters; the estimator's bf16 images are
+    rounded from them after every optimiser step and after `load_state_dict`."""
     _destroy = "lg_estimator_train_destroy"
     _prefix = "lg_estimator_train_"
     _unit = "estimator_train"
@@ -29,17 +34,26 @@ class NativeEstimatorDistillation(_NativeSequenceTrainer):
     _norm_names = ("last_grad_norm",)
 
     def __init__(self, estimator, state_dict, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse",
-                 use_dones=False, multi_gpu_cfg=None, max_rows=None):
+                 use_dones=False, multi_gpu_cfg=None, max_rows=None, encoder_training="fp32"):
         if loss_type not in abi.ESTIMATOR_LOSSES:
             raise ValueError(f"Unknown loss type: {loss_type}. Supported types are: mse, huber, l1")
         if multi_gpu_cfg:
             raise NotImplementedError("multi_gpu_cfg is not built in the native update")
-        if getattr(estimator, "precision", "fp32") != "fp32":
-            raise NotImplementedError("an estimator with encoder_precision=\"bf16\" is not trained by the native update: train an fp32 estimator, then build a "
-                                      "bf16 one from state_dict()")
+        if encoder_training not in abi.ENCODER_TRAININGS:
+            raise ValueError(f"Unknown encoder_training: {encoder_training}. Supported values are: fp32, bf16")
+        precision = getattr(estimator, "precision", "fp32")
+        if encoder_training == "fp32" and precision != "fp32":
+            raise NotImplementedError("an estimator with encoder_precision=\"bf16\" is not trained by the fp32 update: pass encoder_training=\"bf16\" to train it "
+                                      "natively, or train an fp32 estimator, then build a bf16 one from state_dict()")
+        if encoder_training == "bf16" and precision != "bf16":
+            raise ValueError("encoder_training=\"bf16\" trains an estimator built with encoder_precision=\"bf16\", and this one's encoder is "
+                             f"{precision}: build the estimator with encoder_precision=\"bf16\", or pass encoder_training=\"fp32\"")
         if not isinstance(estimator, NativeTerrainEstimator):
             raise TypeError("NativeEstimatorDistillation trains a NativeTerrainEstimator")
         self._open_trainer(estimator.device)
+        self.encoder_training = encoder_training
+        if encoder_training == "bf16":
+            abi.declare(self.lib, "estimator_train_bf16")
         self.estimator = estimator
         self.num_learning_epochs, self.gradient_length = int(num_learning_epochs), int(gradient_length)
         self.learning_rate, self.max_grad_norm, self.loss_type, self.use_dones = float(learning_rate), max_grad_norm, loss_type, bool(use_dones)
@@ -78,7 +92,8 @@ class NativeEstimatorDistillation(_NativeSequenceTrainer):
             plist([m[0] for m in spec["memory"]]), plist([m[1] for m in spec["memory"]]), plist([m[2] for m in spec["memory"]]), plist([m[3] for m in spec["memory"]]),
             plist([w for w, _ in spec["decoder"]]), plist([b for _, b in spec["decoder"]]))
         est = self.estimator
-        return self._fn("create")(est.encoder.handle, est.combine.handle, est.memory.handle, est.decoder.handle, C.byref(q), self.learning_rate, max_rows)
+        create = self.lib.lg_estimator_bf16train_create if self.encoder_training == "bf16" else self._fn("create")
+        return create(est.encoder.handle, est.combine.handle, est.memory.handle, est.decoder.handle, C.byref(q), self.learning_rate, max_rows)
 
     def _hyper(self):
         return super()._hyper(int(self.use_dones))
@@ -98,6 +113,29 @@ class NativeEstimatorDistillation(_NativeSequenceTrainer):
         if self.use_dones:
             dones = rows["dones"].to(device=self.device, dtype=torch.float32).contiguous().view(T, N)
         return depth, prop, tgt, dones, T, N
+
+    # ---- the bf16 trainer's stage calls (tests/test_hip_estimator_bf16_stages.py)
+    def saved_stage(self, k):
+        """Stage k = 1..6 of the last group call's saved forward rows, expanded exactly to fp32: maps (rows, y, x, channel), else (rows, width)."""
+        enc, rows = self.estimator.encoder, self._last_rows
+        count, (h, w, c) = enc.stage_shape(k)
+        out = torch.empty((rows, h, w, c) if k <= 4 else (rows, count), dtype=torch.float32, device=self.device)
+        self._check(self.lib.lg_estimator_bf16train_saved_stage(self.handle, k, out.data_ptr(), out.numel(), self._stream()), "lg_estimator_bf16train_saved_stage")
+        return out
+
+    def backward_stage(self, stage, delta, out_shape=None, grad_shape=None):
+        """One backward stage of the encoder (a name of `abi.ESTIMATOR_BF16_STAGES`) on the last group call's saved rows and `delta` (fp32, rows first):
+        (the output delta of `out_shape` or None, (dW of `grad_shape`, db) or None)."""
+        delta = delta.to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty(out_shape, dtype=torch.float32, device=self.device) if out_shape else None
+        grad = torch.empty(int(torch.tensor(grad_shape).prod()) + grad_shape[0], dtype=torch.float32, device=self.device) if grad_shape else None
+        self._check(self.lib.lg_estimator_bf16train_backward_stage(self.handle, abi.ESTIMATOR_BF16_STAGES[stage], delta.data_ptr(), delta.shape[0],
+                                                                   out.data_ptr() if out is not None else None, grad.data_ptr() if grad is not None else None,
+                                                                   self._stream()), "lg_estimator_bf16train_backward_stage")
+        if grad is None:
+            return out, None
+        nw = grad.numel() - grad_shape[0]
+        return out, (grad[:nw].view(grad_shape), grad[nw:])
 
     # ---- training (`group`, `update`, `gradients` and `forward_outputs` are `_NativeSequenceTrainer`'s; the checkpoint and carry methods
     # `_NativeTrainer`'s; `state_dict()` is a `TerrainEstimator` state dict as trained: `NativeTerrainEstimator`, `TerrainEstimatorTorch` and the

@@ -22,7 +22,21 @@ from .policy import _ptr
 from .runner import NativeRunner, seeded_state_dict, sensor_collection_mode, to_adam_state_dict, from_adam_state_dict
 
 ESTIMATOR_KEYS = ("encoder_output_dim", "memory_hidden_size", "memory_num_layers", "memory_type", "decoder_hidden_dims", "activation")
-ALGORITHM_KEYS = ("num_learning_epochs", "gradient_length", "learning_rate", "max_grad_norm", "loss_type", "use_dones")
+ALGORITHM_KEYS = ("num_learning_epochs", "gradient_length", "learning_rate", "max_grad_norm", "loss_type", "use_dones", "encoder_training")
+
+
+def parse_encoder_training(alg_cfg, encoder_precision):
+    """`algorithm.encoder_training` ("fp32" when absent) against `runner.encoder_precision`: bf16 training plays the estimator it trains, so the pair
+    ("bf16", "fp32") is refused."""
+    training = alg_cfg.get("encoder_training", "fp32")
+    if training not in abi.ENCODER_TRAININGS:
+        raise ValueError(f"Unknown algorithm.encoder_training: {training}. Supported values are: fp32, bf16")
+    if training == "bf16" and encoder_precision != "bf16":
+        raise ValueError("algorithm.encoder_training=\"bf16\" trains and plays the estimator with the bf16 encoder, and runner.encoder_precision is "
+                         f"\"{encoder_precision}\": set runner.encoder_precision=\"bf16\", or algorithm.encoder_training=\"fp32\"")
+    return training
+
+
 RAY_KEYS = ("ray_sq_error", "ray_abs_error", "ray_bias", "ray_max_error")
 
 
@@ -157,7 +171,9 @@ class NativeTerrainEstimatorRunner(NativeRunner):
 
     Estimator: a `NativeTerrainEstimator` (fp32) initialised from `TerrainEstimatorTorch` under `train_cfg["seed"]` (default 1), trained in place by
     `NativeEstimatorDistillation`.  `runner.encoder_precision = "bf16"` builds the estimator `play` steps, from the trained `state_dict()`, with the
-    bf16 encoder; training stays fp32.
+    bf16 encoder; training stays fp32 unless `algorithm.encoder_training = "bf16"` (default "fp32"): then the training estimator itself is built with
+    the bf16 encoder, collection predicts with it, `NativeEstimatorDistillation(encoder_training="bf16")` trains it and `play` steps that same object.
+    Checkpoints hold the fp32 masters in either mode: a run can be resumed in the other one.
 
     Pretrained policy (`:162-245`): a checkpoint of `NativeOnPolicyRunner` or rsl_rl's `OnPolicyRunner` -- `model_state_dict` of an `ActorCritic` or,
     with "Recurrent" in `runner.policy_class_name`, an `ActorCriticRecurrent` (`policy.rnn_type`, default lstm), plus `obs_norm_state_dict` when
@@ -191,6 +207,7 @@ class NativeTerrainEstimatorRunner(NativeRunner):
         from .estimator import parse_precision
         parse_precision(encoder_precision)
         self.encoder_precision = encoder_precision
+        self.encoder_training = parse_encoder_training(self.alg_cfg, encoder_precision)
         # dimensions (`:69-121`)
         self.depth_image_shape = tuple(int(v) for v in depth.shape[-2:])
         self.proprio_dim = 6
@@ -203,7 +220,8 @@ class NativeTerrainEstimatorRunner(NativeRunner):
         self.initial_state_dict = seeded_state_dict(self.seed, TerrainEstimatorTorch, self.depth_image_shape, self.proprio_dim, self.num_raycast_outputs,
                                                     *[kw.get(k, d) for k, d in (("encoder_output_dim", 64), ("memory_hidden_size", 256), ("memory_num_layers", 1),
                                                                                  ("memory_type", "gru"), ("decoder_hidden_dims", (128, 64)), ("activation", "elu"))])
-        self.estimator = NativeTerrainEstimator(self.initial_state_dict, self.depth_image_shape, self.proprio_dim, self.activation, self.memory_type, str(self.device))
+        self.estimator = NativeTerrainEstimator(self.initial_state_dict, self.depth_image_shape, self.proprio_dim, self.activation, self.memory_type, str(self.device),
+                                                encoder_precision=self.encoder_training)
         self.alg = NativeEstimatorDistillation(self.estimator, self.initial_state_dict, **{k: self.alg_cfg[k] for k in ALGORITHM_KEYS if k in self.alg_cfg})
         self.num_steps_per_env, self.save_interval = int(self.cfg["num_steps_per_env"]), int(self.cfg["save_interval"])
         self.play_block_steps = int(self.cfg.get("play_block_steps", 100))
@@ -393,8 +411,12 @@ class NativeTerrainEstimatorRunner(NativeRunner):
         return self.estimator
 
     def _estimator_for_play(self):
-        """The estimator `play` steps: its own object, built from the trained `state_dict()` in `runner.encoder_precision`, so that playing moves
-        neither the training estimator's weights nor its live state; rebuilt after an update or a load."""
+        """The estimator `play` steps.  fp32 training: its own object, built from the trained `state_dict()` in `runner.encoder_precision`, so that
+        playing moves neither the training estimator's weights nor its live state; rebuilt after an update or a load.  bf16 training: the training
+        estimator itself -- the network that is played is the one that was trained --, so `play` resets and advances its live memory state (the
+        trainer's carry is its own and does not move)."""
+        if self.encoder_training == "bf16":          # the network that is played is the one that was trained
+            return self.estimator
         key = (self.alg.num_updates, self.current_learning_iteration)
         if self._play_estimator is None or self._play_key != key:
             if self._play_estimator is not None:

@@ -35,6 +35,8 @@ NATIVE_PARAMETERS = [
     {"name": "--sensor_collection", "type": str, "choices": ["host", "native"], "default": None,
      "help": "host (the default): collect through env.step; native: the one call into the library (runner.sensor_collection)"},
     {"name": "--encoder_precision", "type": str, "choices": ["fp32", "bf16"], "default": None, "help": "encoder mode of the estimator that play steps (runner.encoder_precision)"},
+    {"name": "--encoder_training", "type": str, "choices": ["fp32", "bf16"], "default": None,
+     "help": "fp32 (the default), or bf16: train the estimator whose depth encoder runs in bf16, natively (algorithm.encoder_training; needs --encoder_precision bf16)"},
     {"name": "--policy_class_name", "type": str, "default": None, "help": "ActorCritic (the default) or ActorCriticRecurrent: the class of --pretrained_policy"},
 ]
 
@@ -103,6 +105,8 @@ def native_runner_options(train_cfg, args):
     for key in ("sensor_collection", "encoder_precision", "policy_class_name"):
         if getattr(args, key, None) is not None:
             train_cfg["runner"][key] = getattr(args, key)
+    if getattr(args, "encoder_training", None) is not None:
+        train_cfg["algorithm"]["encoder_training"] = args.encoder_training
     if getattr(args, "seed", None) is not None:
         train_cfg["seed"] = args.seed
     return train_cfg

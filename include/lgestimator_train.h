@@ -67,8 +67,8 @@ typedef struct lg_estimator_train_stats {
 
 /* A trainer over the estimator's four handles, which must outlive it.  The HOST parameters become the fp32 masters Adam updates, and the create call
  * rewrites every device image from them.  Moments, step count and carry start at zero.  max_rows: the largest G * N a group may have.  Refused: a
- * NULL handle or pointer, max_rows < 1, a learning rate that is not > 0, an encoder that is not LG_PREC_F32 (train fp32, then build a bf16 estimator
- * from the trained parameters), stages whose widths do not chain or that live on different devices. */
+ * NULL handle or pointer, max_rows < 1, a learning rate that is not > 0, an encoder that is not LG_PREC_F32 (lg_estimator_bf16train_create of
+ * lgestimator_train_bf16.h trains it; or train fp32, then build a bf16 estimator from the trained parameters), stages whose widths do not chain or that live on different devices. */
 lg_estimator_train* lg_estimator_train_create(lg_conv_encoder* encoder, lg_mlp* combine, lg_rnn* memory, lg_mlp* decoder, const lg_estimator_train_params* params,
                                               double learning_rate, int64_t max_rows);
 void lg_estimator_train_destroy(lg_estimator_train* trainer);

@@ -11,6 +11,9 @@ synchronise.
 (c) one runner iteration (`learn(1)`: collection + update) against the loop of `tools/train_estimator.py --collect one-call --update native`;
 (d) `play` throughput in env steps per second: the collection with the estimator stepped and the figures on, fp32 and bf16 encoder.
 
+(e) `--training-modes`, a run of its own: one runner iteration (`learn(1)`) with `algorithm.encoder_training` "fp32" and "bf16", two runners on two
+    envs in one process, interleaved blocks; merged into the same file under "e_runner_iteration_by_encoder_training".
+
 Writes profiles/native_runner_estimator.json.  usage: python tools/bench_runner_estimator.py [--envs 4096] [--steps 24] [--blocks 7] [--reps 3]"""
 import argparse
 import datetime
@@ -59,8 +62,35 @@ def torch_reductions(pred, tgt):
     return mse, mae
 
 
+def training_modes(a):
+    """(e): `learn(1)` of an fp32-trained and of a bf16-trained runner, interleaved."""
+    N, T = a.envs, a.steps
+    runners = {}
+    for mode in ("fp32", "bf16"):
+        cfg = create_terrain_estimator_config(get_terrain_estimator_args(["--num_steps_per_env", str(T)]))
+        cfg["runner"].update(sensor_collection="native", encoder_precision=mode)
+        cfg["algorithm"]["encoder_training"] = mode
+        runners[mode] = NativeTerrainEstimatorRunner(make_env(N, small_terrain=a.small_terrain), cfg, log_dir=None, device="cuda:0")
+        assert runners[mode].one_call
+    for r in runners.values():
+        timed(lambda: r.learn(1), 2)
+    samples = {mode: [] for mode in runners}
+    for _ in range(a.blocks):
+        for mode, r in runners.items():
+            samples[mode].append(timed(lambda: r.learn(1), a.reps))
+    res = {mode: summary(v) for mode, v in samples.items()}
+    doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    doc["e_runner_iteration_by_encoder_training"] = dict(res, envs=N, steps=T, blocks=a.blocks, reps_per_block=a.reps, small_terrain=bool(a.small_terrain),
+                                                          date=datetime.date.today().isoformat(), bf16_over_fp32_median=res["bf16"]["median_ms"] / res["fp32"]["median_ms"],
+                                                          last_losses={mode: r.losses[-1] for mode, r in runners.items()})
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print(json.dumps(doc["e_runner_iteration_by_encoder_training"], indent=1))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--training-modes", action="store_true", help="(e) only: one runner iteration with encoder_training fp32 and bf16, merged into --out")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--blocks", type=int, default=7)
@@ -70,6 +100,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_runner_estimator needs the GPU: a CPU run has no timing to give")
+    if a.training_modes:
+        return training_modes(a)
     N, T = a.envs, a.steps
     cfg = create_terrain_estimator_config(get_terrain_estimator_args(["--num_steps_per_env", str(T)]))
     cfg["runner"]["sensor_collection"] = "native"

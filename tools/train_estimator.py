@@ -134,19 +134,24 @@ def collect_python_loop(env, policy, num_steps):
 
 
 def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr=1e-3, gradient_length=15, out=None, log=print, small_terrain=False, update_device=None,
-          eval_precision="fp32", update="torch", collect="host"):
+          eval_precision=None, update="torch", collect="host", train_precision="fp32"):
     """update_device: where the torch update runs (default: the env's device).  "cpu" makes the update reproducible bit for bit -- the GPU's
     convolution backward is not -- which is what a comparison of two collections needs.  eval_precision: the encoder mode ("fp32" | "bf16") of the
-    native estimator that plays the trained module over the closing evaluation steps; training itself is fp32.  update: "torch" (`estimator_update`
+    native estimator that plays the trained module over the closing evaluation steps; None: the training precision, so that what is played is what
+    was trained.  update: "torch" (`estimator_update`
     on a `TerrainEstimatorTorch`) or "native" (`rl.NativeEstimatorDistillation`: the update on the device, the weights trained in place in an fp32
     `NativeTerrainEstimator`; update_device does not apply).  collect: "host" (`collect_estimation`'s loop over `env.step`) or "one-call" (the
     same rows through `lg_collect_estimation`, include/lgsensors.h; without a policy the 0.5 * randn actions are drawn before the call, step by
-    step, so both ways consume the generator alike)."""
+    step, so both ways consume the generator alike).  train_precision: "bf16" (with update "native") trains a `NativeTerrainEstimator` whose
+    depth encoder runs in bf16 with `NativeEstimatorDistillation(encoder_training="bf16")`."""
     from extended_legged_gym_amd.rl import NativeActorCritic, NativeEstimatorDistillation, NativeTerrainEstimator, collect_estimation
     if update not in ("torch", "native"):
         raise ValueError(f"update {update!r}: must be torch or native")
     if collect not in ("host", "one-call"):
         raise ValueError(f"collect {collect!r}: must be host or one-call")
+    if train_precision not in ("fp32", "bf16") or (train_precision == "bf16" and update != "native"):
+        raise ValueError(f"train_precision {train_precision!r}: must be fp32, or bf16 with update native")
+    eval_precision = eval_precision or train_precision
 
     def collect_rows(estimator=None):
         if collect == "host":
@@ -168,8 +173,8 @@ def train(iters, envs, steps=24, seed=1, policy_path=None, python_loop=False, lr
     trained = alg = None
     if update == "native":
         start = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-        trained = NativeTerrainEstimator(start, shape, 6, device=str(env.device))
-        alg = NativeEstimatorDistillation(trained, start, gradient_length=gradient_length, learning_rate=lr)
+        trained = NativeTerrainEstimator(start, shape, 6, device=str(env.device), encoder_precision=train_precision)
+        alg = NativeEstimatorDistillation(trained, start, gradient_length=gradient_length, learning_rate=lr, encoder_training=train_precision)
     for it in range(iters):
         with torch.inference_mode():
             rows = collect_python_loop(env, policy, steps) if python_loop else collect_rows()
@@ -210,12 +215,13 @@ def main(argv=None):
     ap.add_argument("--python-loop", action="store_true", help="collect with a plain loop over env.step (the checker of collect_estimation)")
     ap.add_argument("--out", default=None, help="write the loss curve here (JSON) and the trained module next to it (_model.pt)")
     ap.add_argument("--small-terrain", action="store_true", help="2 x 3 terrain tiles (quick runs)")
-    ap.add_argument("--eval-precision", choices=("fp32", "bf16"), default="fp32", help="encoder mode of the native estimator that plays the trained module at the end")
+    ap.add_argument("--eval-precision", choices=("fp32", "bf16"), default=None, help="encoder mode of the native estimator that plays the trained module at the end (default: --train-precision)")
     ap.add_argument("--update", choices=("torch", "native"), default="torch", help="where the gradient steps run: eager torch, or the library's kernels (rl.NativeEstimatorDistillation)")
     ap.add_argument("--collect", choices=("host", "one-call"), default="host", help="collect_estimation as the host loop over env.step, or as one call into the library (lg_collect_estimation)")
+    ap.add_argument("--train-precision", choices=("fp32", "bf16"), default="fp32", help="with --update native: bf16 trains the estimator whose depth encoder runs in bf16 (fp32 masters and Adam)")
     a = ap.parse_args(argv)
     train(a.iters, a.envs, a.steps, a.seed, a.policy, a.python_loop, out=a.out, small_terrain=a.small_terrain, eval_precision=a.eval_precision, update=a.update,
-          collect=a.collect)
+          collect=a.collect, train_precision=a.train_precision)
 
 
 if __name__ == "__main__":
